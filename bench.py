@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""bench.py -- frames/sec (+ p50/p99 latency) of the fused detector path, 640x640 batch-1, on N MI355X.
+"""bench.py -- frames/sec (+ p50/p99 latency with --full) of the fused detector path, 640x640 batch-1, on N MI355X.
 
-    python bench.py --gpus 1 --steps 2000 --warmup 200
+    python bench.py --gpus 1 --steps 2000 --warmup 200 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,8 +11,12 @@ detections left in HBM (DESIGN.md section 4 lists the launches). Weak scaling: e
 (frames shard embarrassingly); the only collective is the RCCL all-gather of the fixed-size
 detection slots, issued every GATHER_EVERY frames on a dedicated comm stream behind the events of exactly those
 frames (gather.SlotRing: double-buffered banks, inference never waits on the collective it just fed).
-value = N*K / max-over-ranks(time). A --steps block shorter than MIN_BLOCK_S is repeated and the MEDIAN block time is
-reported ("repeats" in the JSON line): a 20-frame block is 3 ms, mostly ramp.
+value = N*K / max-over-ranks(time of ONE block of exactly K steps); ms_per_step = that time / K. A short block is mostly
+ramp (20 frames = 3 ms): pick K for a block of a second or more.
+
+A plain run sets up, warms up, times the K steps, writes the last step's detections (--dump-outputs DIR) and prints the
+line. --full adds what takes runs of its own: the serial latency (inside the C ABI and through ctypes; with the gather at
+N > 1), the roofline of the dominant kernel (live per-op timing) and the CPU baseline (--no-cpu-baseline drops it).
 
 Workload = BASELINE.json configs[1]: unina-yolo-dla-m (graph A), fp16, batch 1, 640x640, NMS on GPU; synthetic
 frames (N(0,1), seeds 1234..), seeded synthetic weights (no checkpoints exist for the reference).
@@ -44,8 +48,6 @@ N_SEEDED = 16            # the first of them are the seeded host frames (seeds 1
 IN_FLIGHT = int(os.environ.get("UNINA_IN_FLIGHT", "2"))   # engine handles per GPU = frames in flight
 GATHER_EVERY = 16        # frames per RCCL all-gather of detection slots
 GATHER_BANKS = 3         # slot banks of the ring (>= 2: the gather of one bank overlaps inference into the next)
-MIN_BLOCK_S = 0.5        # a timed --steps block shorter than this is repeated (median reported)
-MAX_REPEATS = 400
 
 
 def launcher_command(n_gpus, argv, port):
@@ -82,9 +84,14 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--size", type=int, default=640)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--latency-frames", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the serial latency, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the detections of the last timed step to DIR/detections.npy (float32 [n, 6]: x1, y1, x2, y2, "
+                         "confidence, class_id; other ranks: detections_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--latency-frames", type=int, default=300, help="--full: frames of the serial latency loop")
     ap.add_argument("--precision", choices=["fp16", "fp32", "int8", "strict"], default="fp16",
                     help="fp16 = BASELINE configs[1] (headline); strict = split-fp16 operands (fp16 hi/lo pairs, 3 MFMAs per k block): "
                          "the north-star tolerance on every detection at the fp16 matrix rate; fp32 = native fp32-MFMA mode (same tolerance, 1/16 of the rate)")
@@ -94,6 +101,8 @@ def main():
                     help="A = model.py's graph (BASELINE configs); B = qat.py's topology (stride-32 stage, third FPN level)")
     ap.add_argument("--tune-cache", default=os.environ.get("UNINA_TUNE_CACHE", ""), help="tactic cache file (JSON)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -165,6 +174,7 @@ def main():
             gathered_frames[0] += bank.shape[0] * bank.shape[1]
         ring = gather.SlotRing(gather.CudaRuntime(dev), local, gathered, GATHER_EVERY, on_gathered=on_gathered)
     next_frame = [0]
+    last_slot = [None]                     # result slot of the last frame run() enqueued (what --dump-outputs writes)
 
     def infer_into(i, k, slot):
         with torch.cuda.stream(streams[k]):
@@ -173,12 +183,17 @@ def main():
     def run(n_frames):
         """n_frames frames, IN_FLIGHT of them overlapping on separate streams; N > 1: detections gathered with RCCL
         every GATHER_EVERY frames on the comm stream (gather.run_frames / SlotRing), off the inference streams' path."""
+        if n_frames < 1:
+            return
         if ring is None:
             for i in range(n_frames):
                 infer_into(i, i % IN_FLIGHT, results[i % GATHER_EVERY])
+            last_slot[0] = results[(n_frames - 1) % GATHER_EVERY]
             return
         gather.run_frames(n_frames, IN_FLIGHT, ring, infer_into, streams, start=next_frame[0])
         next_frame[0] += n_frames
+        last = next_frame[0] - 1           # SlotRing.slot: frame i -> bank (i // k) % banks, slot i % k
+        last_slot[0] = ring.local[(last // GATHER_EVERY) % GATHER_BANKS, last % GATHER_EVERY]
 
     def fence():
         if ring is not None:
@@ -202,19 +217,15 @@ def main():
         return dt
 
     run(args.warmup)
-    blocks = [timed_block()]
-    # a short block is mostly ramp (20 frames = 3 ms): repeat it until MIN_BLOCK_S of timed work, report the median.
-    # Every rank takes the same decision: blocks[0] is already the max over ranks.
-    repeats = 1 if blocks[0] >= MIN_BLOCK_S else min(MAX_REPEATS, int(np.ceil(MIN_BLOCK_S / max(blocks[0], 1e-6))))
-    for _ in range(repeats - 1):
-        blocks.append(timed_block())
-    dt = float(np.median(blocks))
+    dt = timed_block()                     # exactly --steps timed frames per rank, one block
     fps = world * args.steps / dt
     n_det = int((ring.local[0, 0, 0] if ring is not None else results[0, 0]).item())
+    if args.dump_outputs:
+        dump_detections(args.dump_outputs, last_slot[0], rank)
 
     # ---- N > 1: per-frame latency INCLUDING the gather (every rank takes part: one collective per frame) ----
     lat_gather = None
-    if world > 1:
+    if world > 1 and args.full:
         one = torch.zeros((1, slot_words), dtype=torch.int32, device=dev)
         allr = torch.zeros((world, 1, slot_words), dtype=torch.int32, device=dev)
         samples = []
@@ -228,8 +239,9 @@ def main():
                 samples.append((time.perf_counter() - a) * 1e3)
         lat_gather = np.array(samples)
 
-    line = None
-    if rank == 0:
+    dname = {"fp32": "f32", "int8": "i8", "strict": "f16x2"}.get(args.precision, "f16")
+    full = {}                              # --full: the fields after "config" in the line
+    if rank == 0 and args.full:
         # ---- per-frame latency: submit -> detections on the host, one frame at a time (no overlap) ----
         lat = []
         e0 = engines[0]
@@ -249,7 +261,6 @@ def main():
         # ---- roofline of the dominant kernel: live HIP-event timing of every op on the launch stream ----
         ops = e0.profile_ops(iters=20)
         post_ms = e0.profile_post(20, conf, 0.45, 0.1)
-        dname = {"fp32": "f32", "int8": "i8", "strict": "f16x2"}.get(args.precision, "f16")
         by_kernel = {}
         for o in ops:
             if o["ms"] <= 0.0:
@@ -304,16 +315,7 @@ def main():
         if not args.no_cpu_baseline and world == 1:      # (rank 0 at N = 1 only: at N > 1 the other ranks would wait on it)
             cpu = cpu_baseline(u, sd, S, conf, args.cpu_seconds, args.variant)
 
-        line = {
-            "metric": "frames/sec, 640x640 batch-1 (p99 latency alongside)" if S == 640 else f"frames/sec, {S}x{S} batch-1",
-            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 5), "repeats": repeats, "block_ms": {"median": round(1e3 * dt, 3), "min": round(1e3 * min(blocks), 3), "max": round(1e3 * max(blocks), 3)},
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": dname, "data": "synthetic",
-            "config": {"workload": f"unina-yolo-dla-m graph {args.variant} {args.precision}, batch=1, {S}x{S}, NMS on-GPU" + (" (BASELINE configs[1])" if args.variant == "A" and S == 640 and args.precision == "fp16" else ""),
-                       "frames_in_flight_per_gpu": IN_FLIGHT, "parallelism": f"replica x{world}, RCCL all-gather of detection slots every {GATHER_EVERY} frames on a comm stream ({GATHER_BANKS} banks)" if world > 1 else "1 GPU",
-                       "distinct_frames": n_frames,
-                       "thresholds": {"conf": conf, "iou": 0.45, "conformal_q": 0.1}, "detections_last_frame": n_det},
+        full = {
             "latency_ms": {"p50": round(float(np.percentile(lat, 50)), 4), "p99": round(float(np.percentile(lat, 99)), 4),
                            "mean": round(float(lat.mean()), 4), "frames": len(lat),
                            "mode": "serial, submit->detections on host, timed inside the C ABI (unina_serial_latency)",
@@ -322,12 +324,28 @@ def main():
             "cpu_baseline": cpu,
         }
         if lat_gather is not None:
-            line["latency_ms"]["with_gather"] = {"p50": round(float(np.percentile(lat_gather, 50)), 4), "p99": round(float(np.percentile(lat_gather, 99)), 4),
+            full["latency_ms"]["with_gather"] = {"p50": round(float(np.percentile(lat_gather, 50)), 4), "p99": round(float(np.percentile(lat_gather, 99)), 4),
                                                  "frames": len(lat_gather), "mode": "serial, submit -> frame's slot all-gathered over RCCL -> sync"}
-            line["config"]["gathered_frames"] = gathered_frames[0]
         if cpu:
-            line["gpu_over_cpu"] = round(fps / world / cpu["value"], 1)
-            line["gpu_over_one_cpu_core"] = round(fps / world / cpu["one_core"]["value"], 1)
+            full["gpu_over_cpu"] = round(fps / world / cpu["value"], 1)
+            full["gpu_over_one_cpu_core"] = round(fps / world / cpu["one_core"]["value"], 1)
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "frames/sec, 640x640 batch-1 (p99 latency alongside)" if S == 640 else f"frames/sec, {S}x{S} batch-1",
+            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt / args.steps, 5), "block_ms": round(1e3 * dt, 3),
+            "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": dname, "data": "synthetic",
+            "config": {"workload": f"unina-yolo-dla-m graph {args.variant} {args.precision}, batch=1, {S}x{S}, NMS on-GPU" + (" (BASELINE configs[1])" if args.variant == "A" and S == 640 and args.precision == "fp16" else ""),
+                       "frames_in_flight_per_gpu": IN_FLIGHT, "parallelism": f"replica x{world}, RCCL all-gather of detection slots every {GATHER_EVERY} frames on a comm stream ({GATHER_BANKS} banks)" if world > 1 else "1 GPU",
+                       "distinct_frames": n_frames,
+                       "thresholds": {"conf": conf, "iou": 0.45, "conformal_q": 0.1}, "detections_last_frame": n_det},
+            **full,
+        }
+        if world > 1:
+            line["config"]["gathered_frames"] = gathered_frames[0]
     for e in engines:
         e.close()
     if world > 1:
@@ -335,6 +353,17 @@ def main():
         dist.destroy_process_group()
     if line is not None:
         print(json.dumps(line))
+
+
+def dump_detections(out_dir, slot, rank=0):
+    """The detections a caller of the timed path receives for its last frame (the int32 result slot unina_infer_async
+    filled: count, then GpuDetection records) -> out_dir/detections.npy, float32 [n, 6] = x1, y1, x2, y2, confidence,
+    class_id in the kernel's output order (rank r > 0: detections_rank<r>.npy)."""
+    from unina_yolo_dla_amd.engine import Engine
+    det = Engine.unpack(slot)
+    arr = np.stack([det[f].astype(np.float32) for f in ("x1", "y1", "x2", "y2", "confidence", "class_id")], axis=1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "detections.npy" if rank == 0 else f"detections_rank{rank}.npy"), arr.reshape(-1, 6))
 
 
 def _kernel_key(name: str):

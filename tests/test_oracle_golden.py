@@ -100,22 +100,26 @@ def test_postprocess_cpu_header_semantics_match_reference_fixture(pkg, oracle_mo
 
 
 def test_postprocess_live_reference_header_bit_exact(pkg, oracle_mod, oracle_sd7):
-    """Where the compiled reference header is present (dev container) the restatement must agree
-    bit for bit on identical head tensors."""
-    if not oracle_mod.have_ref():
-        pytest.skip("oracle/_ref absent (reference tree not on this machine)")
+    """The restatement must agree bit for bit with the compiled reference header on identical head tensors: with the
+    header's output stored by tests/golden/make_golden_ref_post.py everywhere, and with the live header as well where
+    oracle/_ref was built (the reference tree is present)."""
     heads = _heads_640(pkg, oracle_mod, oracle_sd7)
+    gold = load_golden("ref_post_frame640_seed1234.npz")
     for conf, iou, q in [(0.5, 0.45, 0.1), (0.3, 0.2, 0.0), (0.2, 0.6, 0.25)]:
         a, na = oracle_mod.postprocess(heads, conf, iou, q, sem=oracle_mod.semantics("cpu_header"))
-        b, nb = oracle_mod.ref_postprocess(heads, conf, iou, q)
-        assert na == nb and len(a) == len(b)
-        assert np.array_equal(a["confidence"], b["confidence"])
-        # records with EQUAL confidence may be permuted: the reference's std::sort is unstable
-        # (postprocess.hpp:46-49), the oracle's order is the stable one of SURVEY App. D.
-        ka = np.lexsort((a["y2"], a["x2"], a["y1"], a["x1"], a["class_id"], -a["confidence"]))
-        kb = np.lexsort((b["y2"], b["x2"], b["y1"], b["x1"], b["class_id"], -b["confidence"]))
-        for f in ("x1", "y1", "x2", "y2", "confidence", "class_id"):
-            assert np.array_equal(a[f][ka], b[f][kb]), (conf, iou, q, f)
+        tag = f"conf{conf}_iou{iou}_q{q}"
+        refs = [("stored", gold[f"dets_{tag}"], int(gold[f"ncand_{tag}"]))]
+        if oracle_mod.have_ref():
+            refs.append(("live", *oracle_mod.ref_postprocess(heads, conf, iou, q)))
+        for src, b, nb in refs:
+            assert na == nb and len(a) == len(b), (src, conf, iou, q)
+            assert np.array_equal(a["confidence"], b["confidence"]), (src, conf, iou, q)
+            # records with EQUAL confidence may be permuted: the reference's std::sort is unstable
+            # (postprocess.hpp:46-49), the oracle's order is the stable one of SURVEY App. D.
+            ka = np.lexsort((a["y2"], a["x2"], a["y1"], a["x1"], a["class_id"], -a["confidence"]))
+            kb = np.lexsort((b["y2"], b["x2"], b["y1"], b["x1"], b["class_id"], -b["confidence"]))
+            for f in ("x1", "y1", "x2", "y2", "confidence", "class_id"):
+                assert np.array_equal(a[f][ka], b[f][kb]), (src, conf, iou, q, f)
 
 
 def test_postprocess_engine_semantics_properties(pkg, oracle_mod, oracle_sd7):

@@ -13,7 +13,7 @@ run() {  # name, seconds, command...
 }
 [ -n "${SKIP_TESTS:-}" ] || run tests 420 python -m pytest tests -m gpu -q --timeout 300 ${PYTEST_ARGS:-}
 [ -n "${SKIP_TESTS:-}" ] || run smoke 120 python -c 'import __graft_entry__ as g; g.smoke()'
-run bench 300 python bench.py --gpus 1 --tune-cache /tmp/tune.json ${BENCH_ARGS:-}
+run bench 300 python bench.py --gpus 1 --full --tune-cache /tmp/tune.json ${BENCH_ARGS:-}
 if [ -n "${PROFILE:-}" ]; then
   export TMPDIR=/tmp; cd /tmp
   rm -rf "$REPO/gpurun_out/prof"

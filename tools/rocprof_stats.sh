@@ -11,7 +11,7 @@ export TMPDIR=/tmp; cd /tmp
 for PREC in fp16 strict serial; do
   unset UNINA_IN_FLIGHT
   if [ $PREC = serial ]; then export UNINA_IN_FLIGHT=1; PREC=fp16; TAG=fp16_serial; else TAG=$PREC; fi
-  ARGS="--precision $PREC --no-cpu-baseline --latency-frames 20 --tune-cache /tmp/tune_$PREC.json"
+  ARGS="--precision $PREC --full --no-cpu-baseline --latency-frames 20 --tune-cache /tmp/tune_$PREC.json"
   python3 "$REPO/bench.py" --steps 50 --warmup 10 $ARGS > /dev/null 2>&1     # tactic cache: no tuning launches in the traced run
   rm -rf "$REPO/gpurun_out/stats_$TAG"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/gpurun_out/stats_$TAG" -o stats -- \
