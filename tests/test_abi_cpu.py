@@ -69,6 +69,25 @@ def test_load_errors_are_loud_not_fatal(lib, tmp_path):
     lib.unina_unload_engine(None)                                                            # NULL is a no-op
 
 
+@pytest.mark.parametrize("nc,rc", [(0, 6), (16384, 6), (3, 2), (5, 2)])   # UNINA_ERR_UNSUPPORTED / UNINA_ERR_FORMAT
+def test_load_rejects_bad_class_counts(pkg, sd7, lib, tmp_path, nc, rc):
+    """The header's num_classes must be 1..16383 (the two-launch NMS carries a class id in 14 bits) and equal the channel
+    count of the cls output buffers (the decode reads that many planes). Checked before any HIP call, so without a GPU."""
+    from unina_yolo_dla_amd import export
+    path = tmp_path / "a.une"
+    export.export_engine(sd7, str(path), pkg.graph.Graph(in_h=64, in_w=64))   # 4 classes
+    raw = bytearray(path.read_bytes())
+    f = list(export._HDR.unpack_from(raw))
+    assert f[6] == 4
+    f[6] = nc
+    raw[:export._HDR.size] = export._HDR.pack(*f)
+    path.write_bytes(bytes(raw))
+    h = C.c_void_p()
+    assert lib.unina_load_engine(str(path).encode(), 0, C.byref(h)) == rc
+    assert lib.unina_last_error(None) and b"num_classes" in lib.unina_last_error(None)
+    assert not h.value
+
+
 def test_engine_wrapper_refuses_without_gpu(pkg, sd7, tmp_path):
     import torch
     if torch.cuda.is_available():

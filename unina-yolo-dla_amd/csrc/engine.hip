@@ -1381,6 +1381,12 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
     if (e->out_buf[i] < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks a head output buffer");
   }
   if (e->images_buf < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks the images input buffer");
+  // the decode reads num_classes planes of every cls buffer; the two-launch NMS carries a class id in 14 bits
+  if (e->h.num_classes == 0 || e->h.num_classes > (uint32_t)kMaxNumClasses)
+    return bail(UNINA_ERR_UNSUPPORTED, "num_classes must be 1..16383");
+  for (int i = 0; i < 3; ++i)
+    if (e->bufs[e->out_buf[2 * i]].d.c != e->h.num_classes)
+      return bail(UNINA_ERR_FORMAT, "header num_classes differs from the channel count of a cls output buffer");
 
   // convs: a LANE-order twin of every slice's weight blocks (kernels.h weight_block_to_lane_order) for the kernels that take
   // weights straight into registers (conv3x3_regq / conv3x3_ws / the decode launch's output convs); the file's order stays

@@ -324,7 +324,7 @@ struct PostParams {
   // the greedy scan in rank order (one wave per class residue) and writes the compacted output. Same results as mode 0.
   int mode;                  // 0: everything in one launch (one workgroup gathers, sorts, scans); 2: the two-launch form
   float4* ws_box;            // [MAX_DETECTIONS] boxes of the (selected) candidates, by list position
-  float2* ws_cc;             // [MAX_DETECTIONS] (confidence, class | enumeration index << 8)
+  float2* ws_cc;             // [MAX_DETECTIONS] (confidence, class | enumeration index << 14)
   unsigned int* ticket2;     // arrival counter of launch 2 (zero at rest)
   int* ws_total;             // candidates in the list (zero at rest: launch 2's last arriver resets it)
   int* ws_hist;              // [4096] histogram of the candidates' confidences, bin = floor(conf * 4096) (zero at rest)
@@ -349,6 +349,7 @@ size_t post_workspace_bytes();
 void post_bind_workspace(PostParams* p, void* ws);   // ws: post_workspace_bytes() of device memory, zeroed once
 bool post_plan_blocks(PostParams* p);                // mode 2: fills bstart / cpb from gw, gh, h1; false if the grid would exceed 1024 workgroups
 constexpr int kPostBlock = 1024;
+constexpr int kMaxNumClasses = 16383;                // class ids the two-launch form's 14-bit class field holds (unina_load_engine checks)
 constexpr int kPost2Block = 256;                     // threads per workgroup of the mode-2 kernels (= candidate segment size)
 int post_num_blocks(const int gw[3], const int gh[3]);
 hipError_t post_init();   // per device: raise the dynamic-LDS limit of the post-process kernels

@@ -658,10 +658,15 @@ __device__ __forceinline__ int conf_bin(float c) {
   const int b = (int)(c * (float)kBins);
   return b > kBins - 1 ? kBins - 1 : b;
 }
-// (class id | enumeration index << 8) travels in the second float of a candidate's (confidence, class) pair
-__device__ __forceinline__ float pack_ce(int class_id, int eidx) { return __int_as_float((class_id & 0xFF) | (eidx << 8)); }
-__device__ __forceinline__ int ce_class(float y) { return (int)(signed char)(__float_as_int(y) & 0xFF); }
-__device__ __forceinline__ unsigned ce_eidx(float y) { return (unsigned)__float_as_int(y) >> 8; }
+// (class id | enumeration index << kClassBits) travels in the second float of a candidate's (confidence, class) pair. The
+// enumeration index is below kListCap = 2^18 (post_plan_blocks), which leaves 14 bits for the class; the all-ones field
+// is the padding dummy's class -1, so num_classes <= kClassMask = kMaxNumClasses (checked by unina_load_engine)
+constexpr int kClassBits = 14;
+constexpr int kClassMask = (1 << kClassBits) - 1;
+static_assert(kClassMask == kMaxNumClasses, "the all-ones class field is the dummy's -1");
+__device__ __forceinline__ float pack_ce(int class_id, int eidx) { return __int_as_float((class_id & kClassMask) | (eidx << kClassBits)); }
+__device__ __forceinline__ int ce_class(float y) { return (int)((unsigned)__float_as_int(y) << (32 - kClassBits)) >> (32 - kClassBits); }
+__device__ __forceinline__ unsigned ce_eidx(float y) { return (unsigned)__float_as_int(y) >> kClassBits; }
 
 }  // namespace
 
@@ -1011,7 +1016,7 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
       // the pair test of `suppresses` (same arithmetic; the IoU is symmetric bit for bit), once for both orientations
       const float ix1 = fmaxf(a.x, bb.x), iy1 = fmaxf(a.y, bb.y);
       const float ix2 = fminf(a.z, bb.z), iy2 = fminf(a.w, bb.w);
-      bool over = gi != gj && ((__float_as_int(bc.y) ^ __float_as_int(ac.y)) & 0xFF) == 0 && !(ix1 >= ix2 || iy1 >= iy2);
+      bool over = gi != gj && ((__float_as_int(bc.y) ^ __float_as_int(ac.y)) & kClassMask) == 0 && !(ix1 >= ix2 || iy1 >= iy2);
       if (over) {
         const float inter = (ix2 - ix1) * (iy2 - iy1);
         const float area_b = (bb.z - bb.x) * (bb.w - bb.y);
@@ -1209,6 +1214,7 @@ int post_num_blocks(const int gw[3], const int gh[3]) {
 }
 
 constexpr size_t kListCap = 256 * 1024;   // candidates the compact list can hold (= cells of the largest supported frame: 1024 workgroups x 256)
+static_assert(kListCap == (size_t)1 << (32 - kClassBits), "an enumeration index must fit the bits above the class in pack_ce");
 size_t post_workspace_bytes() {
   return sizeof(float4) * kMaxDet + sizeof(float2) * kMaxDet + 256 + sizeof(int) * kBins + sizeof(uint2) * kListCap +
          sizeof(int) * kMaxDet + sizeof(unsigned long long) * ((size_t)kMaxDet * kWords + kWords);
