@@ -192,8 +192,9 @@ int unina_autotune(unina_engine_t *e, int iters, hipStream_t stream);
  * unina_fusion_groups: number of blocks currently running fused (0 when off / none recognised). */
 int unina_set_fusion(unina_engine_t *e, int enable);
 int unina_fusion_groups(const unina_engine_t *e);
-/* Load-time analysis alone, no device needed: number of C3k2 blocks of the engine file that would run fused
- * (negative = -error code). */
+/* Load-time analysis alone, no device needed: runs exactly the host-side checks and fusion matchers of
+ * unina_load_engine on the engine file and returns the number of fused groups it finds (C3k2 blocks, heads, conv
+ * pairs), or -code where unina_load_engine would fail with that code before touching the device. */
 int unina_debug_fusable_groups(const char *path);
 
 /* Copies an internal activation buffer to the host as fp32 NCHW ([C,H,W]) -- parity tests only.

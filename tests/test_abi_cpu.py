@@ -88,6 +88,28 @@ def test_load_rejects_bad_class_counts(pkg, sd7, lib, tmp_path, nc, rc):
     assert not h.value
 
 
+def test_weight_range_past_blob_is_rejected_at_load(pkg, sd7, lib, tmp_path):
+    """A conv whose 16-aligned weight offset lies inside the blob but whose weights run past its end: the loader rejects
+    the file before any HIP call, and the load-time hook (the loader's host side) with the same code, before a fusion
+    matcher packs those weights."""
+    from unina_yolo_dla_amd import export
+    path = tmp_path / "a.une"
+    export.export_engine(sd7, str(path), pkg.graph.Graph(in_h=64, in_w=64))
+    raw = bytearray(path.read_bytes())
+    f = export._HDR.unpack_from(raw)
+    n_buf, n_ops, blob_bytes = f[7], f[8], f[13]
+    op0 = export._HDR.size + 64 * n_buf
+    kinds = [struct.unpack_from("<I", raw, op0 + 256 * i)[0] for i in range(n_ops)]
+    w_off_at = op0 + 256 * kinds.index(export.OP_CONV) + export._OP_HEAD.size + 24   # seg[0].w_off of the first conv
+    struct.pack_into("<Q", raw, w_off_at, (blob_bytes - 16) & ~15)
+    path.write_bytes(bytes(raw))
+    h = C.c_void_p()
+    assert lib.unina_load_engine(str(path).encode(), 0, C.byref(h)) == 2                      # UNINA_ERR_FORMAT
+    assert b"weight offset outside blob" in lib.unina_last_error(None)
+    assert not h.value
+    assert lib.unina_debug_fusable_groups(str(path).encode()) == -2
+
+
 def test_engine_wrapper_refuses_without_gpu(pkg, sd7, tmp_path):
     import torch
     if torch.cuda.is_available():
@@ -137,7 +159,8 @@ def test_export_embeds_narrow_widths(pkg):
 def test_c3k2_groups_are_recognised_at_load(lib, pkg, sd7, tmp_path):
     """Load-time block fusion (csrc/c3k2_fused.hip, head_fused.hip): the structural matcher finds the seven C3k2 blocks
     of graph (A) (model.py:76-110) and the P2 DetectionHead (model.py:274-303; the only head whose weights a workgroup
-    can stream) in the exporter's op table, one block fewer in the lite_p2 variant, none in an fp32 engine file."""
+    can stream) in the exporter's op table, one block fewer in the lite_p2 variant, none in an fp32 engine file, the blocks
+    and the conv pair in a STRICT one (the count the loader reports: tests/test_gpu_strict.py)."""
     from unina_yolo_dla_amd import export
     g = pkg.graph.Graph(in_h=64, in_w=64)
     path = str(tmp_path / "a.une")
@@ -145,6 +168,8 @@ def test_c3k2_groups_are_recognised_at_load(lib, pkg, sd7, tmp_path):
     assert lib.unina_debug_fusable_groups(path.encode()) == 9      # 7 C3k2 blocks + P2 head + the sppf.cv2 -> lateral_p3 pair
     export.export_engine(sd7, path, g, precision=export.FP32)
     assert lib.unina_debug_fusable_groups(path.encode()) == 0
+    export.export_engine(sd7, path, g, precision=export.STRICT)
+    assert lib.unina_debug_fusable_groups(path.encode()) == 8      # split fp16: 7 C3k2 blocks + the pair (no head kernel)
     gl = pkg.graph.Graph(in_h=64, in_w=64, lite_p2=True)
     export.export_engine(pkg.synth.make_state_dict(7, gl), path, gl)
     assert lib.unina_debug_fusable_groups(path.encode()) == 8

@@ -72,15 +72,17 @@ def test_strict_every_buffer_vs_oracle(pkg, sd7, oracle_mod, oracle_sd7, torch_c
 
 
 @pytest.mark.parametrize("size", [64, 96, 640])
-def test_strict_fused_equals_per_op_within_fp32_noise(pkg, sd7, torch_cuda, size):
+def test_strict_fused_equals_per_op_within_fp32_noise(pkg, sd7, torch_cuda, size, tmp_path):
     """The frame as launched (fused C3k2 blocks, the conv pair, paired head launches) against the per-op table of the same
     engine, heads and block outputs; 96^2 puts partial tiles on every level. Kernel families of the split mode may order
     their fp32 sums differently (no bit-identity contract here): fp32 rounding noise only."""
     from unina_yolo_dla_amd import export
     from unina_yolo_dla_amd.engine import Engine
-    e = Engine.from_state_dict(sd7, pkg.graph.Graph(in_h=size, in_w=size), precision=export.STRICT)
+    path = str(tmp_path / "s.une")
+    e = Engine.from_state_dict(sd7, pkg.graph.Graph(in_h=size, in_w=size), path=path, precision=export.STRICT)
     try:
         assert e.set_fusion(True) >= 8                            # 7 C3k2 blocks + the SPPF / lateral pair
+        assert e.L.unina_fusion_groups(e.h) == e.L.unina_debug_fusable_groups(path.encode())   # the hook is the loader's host side
         kernels = " ".join(o["kernel"] for o in e.op_infos())
         assert "c3k2_fused<s16" in kernels and "conv_pair<s16" in kernels and "conv_dual_head3x3_ws_s16" in kernels, kernels
         x = torch_cuda.from_numpy(pkg.rng.frame(1234, size, size)).cuda()

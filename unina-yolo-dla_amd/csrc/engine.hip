@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -115,8 +116,7 @@ struct unina_engine {
   hipGraph_t fgraph = nullptr;
   hipGraphExec_t fexec = nullptr;
   hipGraphNode_t stem_node = nullptr, post_node = nullptr, post_node2 = nullptr;
-  bool post_split = true;            // post-process as two launches (UNINA_POST_SPLIT=0: everything in one workgroup)
-  int post_mode = 2;                 // 2: the two-launch form (compact candidate list, sort-free NMS); 0 (UNINA_POST_SPLIT=0): everything in one launch
+  bool post_split = true;            // post-process mode 2: two launches, compact candidate list, sort-free NMS (UNINA_POST_SPLIT=0: mode 0, one launch)
   bool fold_heads = true;            // full-frame graph: the heads' output convs run inside the decode launch (UNINA_POST_FOLD=0: off)
   int fold_op[3] = {-1, -1, -1};     // per head: the output-conv op the decode launch absorbs (-1: the head is read from its planes)
   int stem_op = -1;
@@ -178,6 +178,39 @@ struct Region {
   int buf, c0, c1;
 };
 bool overlaps(const Region& a, const Region& b) { return a.buf == b.buf && a.c0 < b.c1 && b.c0 < a.c1; }
+Region whole(int buf) { return {buf, INT_MIN, INT_MAX}; }   // every channel of a buffer
+
+// What op `d` reads and writes, as the op table describes it (no fusion). Where a kernel's access is wider than its slices
+// the footprint is too: QUANT (and UPSAMPLE, which no kernel executes) covers whole buffers, the SPPF pool reads its
+// whole buffer (x and the maps it chains through) and writes y1..y3 behind x, a residual is a read of its whole buffer.
+void footprint(const OpDesc& d, std::vector<Region>* reads, std::vector<Region>* writes) {
+  const bool whole_bufs = d.kind == kOpQuant || d.kind == kOpUpsample;
+  for (uint32_t s = 0; s < d.nseg; ++s) {
+    const SegDesc& sd = d.seg[s];
+    const int cin = d.kind == kOpStem ? 3 : (int)d.cin;
+    const bool ranged = d.kind == kOpConv || d.kind == kOpStem;
+    reads->push_back(ranged ? Region{(int)d.src_buf, (int)sd.src_coff, (int)sd.src_coff + cin} : whole((int)d.src_buf));
+    writes->push_back(whole_bufs ? whole((int)sd.dst_buf) : Region{(int)sd.dst_buf, (int)sd.dst_coff, (int)(sd.dst_coff + sd.n_count)});
+  }
+  if (d.kind == kOpSppfPool) {
+    const int c0 = (int)d.seg[0].src_coff, C = (int)d.cin;
+    writes->push_back({(int)d.src_buf, c0 + C, c0 + 4 * C});
+  }
+  if (d.res_buf >= 0) reads->push_back(whole(d.res_buf));
+}
+
+// Does any op outside ops [lo, hi] read or write region `r`? (The fusion matchers' test that a tensor is private to a group.)
+bool touched_outside(const unina_engine* e, const Region& r, size_t lo, size_t hi) {
+  std::vector<Region> rw;   // reads and writes alike
+  for (size_t k = 0; k < e->ops.size(); ++k) {
+    if (k >= lo && k <= hi) continue;
+    rw.clear();
+    footprint(e->ops[k].d, &rw, &rw);
+    for (const Region& x : rw)
+      if (overlaps(r, x)) return true;
+  }
+  return false;
+}
 
 void op_regions(const unina_engine* e, size_t i, std::vector<Region>* reads, std::vector<Region>* writes) {
   const OpDesc& d = e->ops[i].d;
@@ -227,31 +260,16 @@ void op_regions(const unina_engine* e, size_t i, std::vector<Region>* reads, std
     }
     return;
   }
-  if (d.kind == kOpSppfPool) {
-    const int c0 = (int)d.seg[0].src_coff, C = (int)d.cin;
-    reads->push_back({(int)d.src_buf, c0, c0 + C});
-    writes->push_back({(int)d.src_buf, c0 + C, c0 + 4 * C});
-    return;
-  }
-  for (uint32_t s = 0; s < d.nseg; ++s) {
-    const SegDesc& sd = d.seg[s];
-    const int cin = d.kind == kOpStem ? 3 : (int)d.cin;
-    reads->push_back({(int)d.src_buf, (int)sd.src_coff, (int)sd.src_coff + cin});
-    writes->push_back({(int)sd.dst_buf, (int)sd.dst_coff, (int)(sd.dst_coff + sd.n_count)});
-    if (d.res_buf >= 0) reads->push_back({d.res_buf, d.res_coff, d.res_coff + (int)sd.n_count});
-  }
+  footprint(d, reads, writes);
 }
 
-// (Re)computes kernel parameters from the current buffer addresses. Element types are properties of the BUFFERS
-// (fp16 / fp32 / int8 NHWC): a conv runs in the type of its source buffer and converts to the type of each
-// destination buffer in its epilogue, so fp16, fp32 and mixed int8/fp16 engines share one planner.
 // Which heads' output convs (model.py:292,299: Conv2d(C, nc | 4, 1) with bias, the `.2` layers) can run inside the decode
 // launch of the post-process (postprocess.hip, fold): a plain fp16 1x1 conv op of two slices that write the head's cls
 // and reg planes, at most 16 output channels each. A head whose output conv already lives in a fused launch (the P2
 // head kernel) is read from its planes instead.
 void find_fold_ops(unina_engine* e) {
   for (int h = 0; h < 3; ++h) e->fold_op[h] = -1;
-  if (!e->fold_heads || e->post_mode != 2) return;
+  if (!e->fold_heads || !e->post_split) return;
   for (size_t i = 0; i < e->ops.size(); ++i) {
     const PlannedOp& op = e->ops[i];
     if (op.d.kind != kOpConv || (e->fuse && op.fuse_role)) continue;
@@ -268,437 +286,420 @@ void find_fold_ops(unina_engine* e) {
   }
 }
 
-int plan(unina_engine* e) {
+// Kernel parameters and info of op `i` as a launch of its own.
+int plan_op(unina_engine* e, size_t i) {
   const char* blob = static_cast<const char*>(e->d_blob);
-  for (size_t i = 0; i < e->ops.size(); ++i) {
-    PlannedOp& op = e->ops[i];
-    const OpDesc& d = op.d;
-    const Buffer& src = e->bufs[d.src_buf];
-    unina_op_info& info = op.info;
-    memset(&info, 0, sizeof info);
-    snprintf(info.name, sizeof info.name, "%s", d.name);
-    info.kind = (int)d.kind;
-    if (d.kind == kOpConv) {
-      ConvParams& p = op.cp;
-      memset(&p, 0, sizeof p);
-      const int dt = act_dtype_of(src.d.dtype);
-      if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: source is not an activation buffer", i);
-      const size_t esz = dtype_size(dt);
-      p.dtype = dt;
-      p.src = src.ptr;
-      p.src_lo = lo_plane(src.d);
-      p.src_ld = (int)src.d.c;
-      p.H = (int)d.in_h; p.W = (int)d.in_w; p.Cin = (int)d.cin;
-      p.Ho = (int)d.out_h; p.Wo = (int)d.out_w; p.M = p.Ho * p.Wo;
-      p.ksize = (int)d.ksize; p.stride = (int)d.stride; p.pad = (int)d.ksize / 2;
-      p.relu = (int)d.relu;
-      if (d.res_buf >= 0) {
-        const Buffer& rb = e->bufs[d.res_buf];
-        const int rdt = act_dtype_of(rb.d.dtype);
-        if (rdt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: residual is not an activation buffer", i);
-        p.res = static_cast<const char*>(rb.ptr) + (size_t)d.res_coff * dtype_size(rdt);
-        p.res_ld = (int)rb.d.c;
-        p.res_dtype = rdt;
-        p.res_lo = lo_plane(rb.d);
-        p.res_scale = rb.d.scale;
-        if ((rdt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv with a residual of another type", i);
-      }
-      p.nseg = (int)d.nseg;
-      p.zeros = e->d_zeros;
-      p.force_cfg = i < e->force_cfg.size() ? e->force_cfg[i] : -1;
-      int ntot = 0;
-      double out_bytes = 0;
-      for (int s = 0; s < p.nseg; ++s) {
-        const SegDesc& sd = d.seg[s];
-        const Buffer& db = e->bufs[sd.dst_buf];
-        ConvSeg& cs = p.seg[s];
-        cs.w = blob + sd.w_off;
-        cs.w_lane = op.w_lane_off[s] ? blob + op.w_lane_off[s] : nullptr;
-        cs.bias = reinterpret_cast<const float*>(blob + sd.b_off);
-        cs.mult = sd.m_off ? reinterpret_cast<const float*>(blob + sd.m_off) : nullptr;
-        if (dt == kI8 && !cs.mult) return fail(e, UNINA_ERR_FORMAT, "op %zu: int8 conv without multipliers", i);
-        cs.src_coff = (int)sd.src_coff;
-        cs.n_count = (int)sd.n_count;
-        cs.up2 = (sd.flags & kSegUp2) ? 1 : 0;
-        if (sd.flags & kSegPlanarF32) {
-          if (db.d.dtype != kBufF32Planar) return fail(e, UNINA_ERR_FORMAT, "op %zu: planar slice into non-planar buffer", i);
-          cs.dst_planar = static_cast<float*>(db.ptr);
-          cs.dst = nullptr;
-          cs.dst_ld = 0;
-          cs.out_dtype = kF32;
-          out_bytes += 4.0 * sd.n_count * p.M;
-        } else {
-          const int odt = act_dtype_of(db.d.dtype);
-          const uint32_t al = odt == kI8 ? 16 : 8;   // a 16-byte store chunk must not straddle the slice
-          if (odt < 0 || sd.n_count % al || sd.dst_coff % al || db.d.c % al)
-            return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: NHWC slice needs channel counts/offsets that are multiples of %u", i, al);
-          cs.dst = static_cast<char*>(db.ptr) + (size_t)sd.dst_coff * dtype_size(odt);
-          cs.dst_planar = nullptr;
-          cs.dst_ld = (int)db.d.c;
-          cs.out_dtype = odt;
-          cs.dst_lo = lo_plane(db.d);
-          if ((odt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv into a buffer of another type", i);
-          cs.out_inv_scale = odt == kI8 ? 1.0f / db.d.scale : 1.0f;
-          out_bytes += dtype_bytes(odt) * sd.n_count * p.M * (cs.up2 ? 4 : 1);
-        }
-        ntot += (int)sd.n_count;
-      }
-      const int kb = dt == kF32 ? 16 : (dt == kI8 ? 64 : 32);
-      if (p.Cin % kb || (p.src_ld * esz) % 16) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu (%s): Cin %% %d != 0", i, d.name, kb);
-      if (p.force_cfg >= 0 && !conv_config_valid(p, p.force_cfg)) p.force_cfg = -1;
-      op.cl = conv_plan(p);
-      const int K = p.ksize * p.ksize * p.Cin;
-      info.m = p.M; info.n = ntot; info.k = K;
-      info.flops = 2.0 * p.M * (double)ntot * K;
-      // algorithmic bytes: each distinct input element once, weights once, outputs once, residual once
-      const bool shared_src = p.nseg == 1 || d.seg[0].src_coff == d.seg[1].src_coff;
-      info.bytes = dtype_bytes(dt) * p.H * p.W * p.Cin * (shared_src ? 1 : p.nseg) + dtype_bytes(dt) * ntot * K + 4.0 * ntot + out_bytes +
-                   (p.res ? dtype_bytes(p.res_dtype) * p.M * ntot : 0.0);
-      snprintf(info.kernel, sizeof info.kernel, "%s", op.cl.kernel_name);
-      info.grid = (int)(op.cl.grid.x * op.cl.grid.y);
-      info.block = (int)op.cl.block.x;
-    } else if (d.kind == kOpStem) {
-      const SegDesc& sd = d.seg[0];
+  PlannedOp& op = e->ops[i];
+  const OpDesc& d = op.d;
+  const Buffer& src = e->bufs[d.src_buf];
+  unina_op_info& info = op.info;
+  memset(&info, 0, sizeof info);
+  snprintf(info.name, sizeof info.name, "%s", d.name);
+  info.kind = (int)d.kind;
+  if (d.kind == kOpConv) {
+    ConvParams& p = op.cp;
+    memset(&p, 0, sizeof p);
+    const int dt = act_dtype_of(src.d.dtype);
+    if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: source is not an activation buffer", i);
+    const size_t esz = dtype_size(dt);
+    p.dtype = dt;
+    p.src = src.ptr;
+    p.src_lo = lo_plane(src.d);
+    p.src_ld = (int)src.d.c;
+    p.H = (int)d.in_h; p.W = (int)d.in_w; p.Cin = (int)d.cin;
+    p.Ho = (int)d.out_h; p.Wo = (int)d.out_w; p.M = p.Ho * p.Wo;
+    p.ksize = (int)d.ksize; p.stride = (int)d.stride; p.pad = (int)d.ksize / 2;
+    p.relu = (int)d.relu;
+    if (d.res_buf >= 0) {
+      const Buffer& rb = e->bufs[d.res_buf];
+      const int rdt = act_dtype_of(rb.d.dtype);
+      if (rdt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: residual is not an activation buffer", i);
+      p.res = static_cast<const char*>(rb.ptr) + (size_t)d.res_coff * dtype_size(rdt);
+      p.res_ld = (int)rb.d.c;
+      p.res_dtype = rdt;
+      p.res_lo = lo_plane(rb.d);
+      p.res_scale = rb.d.scale;
+      if ((rdt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv with a residual of another type", i);
+    }
+    p.nseg = (int)d.nseg;
+    p.zeros = e->d_zeros;
+    p.force_cfg = i < e->force_cfg.size() ? e->force_cfg[i] : -1;
+    int ntot = 0;
+    double out_bytes = 0;
+    for (int s = 0; s < p.nseg; ++s) {
+      const SegDesc& sd = d.seg[s];
       const Buffer& db = e->bufs[sd.dst_buf];
-      StemParams& p = op.sp;
-      const int odt = act_dtype_of(db.d.dtype);
-      if (odt != kF16 && odt != kF32 && odt != kS16) return fail(e, UNINA_ERR_UNSUPPORTED, "stem output must be fp16, fp32 or split fp16");
-      p.dtype = odt;
-      p.dst_lo = lo_plane(db.d);
-      p.src = static_cast<const float*>(src.ptr);
-      p.w = reinterpret_cast<const float*>(blob + sd.w_off);
-      p.wt = reinterpret_cast<const float*>(blob + op.wt_off);
-      p.bias = reinterpret_cast<const float*>(blob + sd.b_off);
-      p.dst = static_cast<char*>(db.ptr) + (size_t)sd.dst_coff * dtype_size(odt);
-      p.H = (int)d.in_h; p.W = (int)d.in_w; p.Ho = (int)d.out_h; p.Wo = (int)d.out_w;
-      p.Co = (int)sd.n_count; p.dst_ld = (int)db.d.c;
-      info.m = p.Ho * p.Wo; info.n = p.Co; info.k = 27;
-      info.flops = 2.0 * info.m * info.n * 27;
-      info.bytes = 4.0 * 3 * p.H * p.W + dtype_bytes(odt) * info.m * p.Co;
-      {
-        LaunchDesc sl;
-        const bool tiled = stem_desc(p, &sl) == hipSuccess && sl.block.x == 128;
-        snprintf(info.kernel, sizeof info.kernel, "%s<%s,%d>", tiled ? "stem_tile_kernel" : "stem_conv_kernel", odt == kF32 ? "f32" : (odt == kS16 ? "s16" : "f16"), p.Co);
-        info.grid = tiled ? (int)sl.grid.x : (2 * info.m + 255) / 256;
-        info.block = tiled ? 128 : 256;
+      ConvSeg& cs = p.seg[s];
+      cs.w = blob + sd.w_off;
+      cs.w_lane = op.w_lane_off[s] ? blob + op.w_lane_off[s] : nullptr;
+      cs.bias = reinterpret_cast<const float*>(blob + sd.b_off);
+      cs.mult = sd.m_off ? reinterpret_cast<const float*>(blob + sd.m_off) : nullptr;
+      if (dt == kI8 && !cs.mult) return fail(e, UNINA_ERR_FORMAT, "op %zu: int8 conv without multipliers", i);
+      cs.src_coff = (int)sd.src_coff;
+      cs.n_count = (int)sd.n_count;
+      cs.up2 = (sd.flags & kSegUp2) ? 1 : 0;
+      if (sd.flags & kSegPlanarF32) {
+        if (db.d.dtype != kBufF32Planar) return fail(e, UNINA_ERR_FORMAT, "op %zu: planar slice into non-planar buffer", i);
+        cs.dst_planar = static_cast<float*>(db.ptr);
+        cs.dst = nullptr;
+        cs.dst_ld = 0;
+        cs.out_dtype = kF32;
+        out_bytes += 4.0 * sd.n_count * p.M;
+      } else {
+        const int odt = act_dtype_of(db.d.dtype);
+        const uint32_t al = odt == kI8 ? 16 : 8;   // a 16-byte store chunk must not straddle the slice
+        if (odt < 0 || sd.n_count % al || sd.dst_coff % al || db.d.c % al)
+          return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: NHWC slice needs channel counts/offsets that are multiples of %u", i, al);
+        cs.dst = static_cast<char*>(db.ptr) + (size_t)sd.dst_coff * dtype_size(odt);
+        cs.dst_planar = nullptr;
+        cs.dst_ld = (int)db.d.c;
+        cs.out_dtype = odt;
+        cs.dst_lo = lo_plane(db.d);
+        if ((odt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv into a buffer of another type", i);
+        cs.out_inv_scale = odt == kI8 ? 1.0f / db.d.scale : 1.0f;
+        out_bytes += dtype_bytes(odt) * sd.n_count * p.M * (cs.up2 ? 4 : 1);
       }
-    } else if (d.kind == kOpSppfPool) {
-      PoolParams& p = op.pp;
-      const int dt = act_dtype_of(src.d.dtype);
-      if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: pool on a non-activation buffer", i);
-      p.dtype = dt;
-      p.buf = src.ptr;
-      p.lo = lo_plane(src.d);
-      p.H = (int)d.in_h; p.W = (int)d.in_w; p.C = (int)d.cin; p.ld = (int)src.d.c; p.coff = (int)d.seg[0].src_coff;
-      info.bytes = dtype_bytes(dt) * p.H * p.W * p.C * 4;
-      snprintf(info.kernel, sizeof info.kernel, dt == kS16 ? "sppf_pool_split_kernel<%s32>" : "sppf_pool_kernel<%s,32>", dt == kF32 ? "f32" : (dt == kI8 ? "i8" : (dt == kS16 ? "" : "f16")));
-      info.grid = p.H * (p.C / 32);
-      info.block = 256;
-    } else if (d.kind == kOpQuant) {
-      const Buffer& db = e->bufs[d.seg[0].dst_buf];
-      if (src.d.dtype != kBufF16Nhwc || db.d.dtype != kBufI8Nhwc || src.d.c != db.d.c || src.d.h != db.d.h || src.d.w != db.d.w)
-        return fail(e, UNINA_ERR_FORMAT, "op %zu: QUANT needs an fp16 source and an int8 twin of the same shape", i);
-      QuantParams& p = op.qp;
-      p.src = static_cast<const half_t*>(src.ptr);
-      p.dst = static_cast<signed char*>(db.ptr);
-      p.n = (size_t)src.d.h * src.d.w * src.d.c;
-      p.inv_scale = 1.0f / db.d.scale;
-      info.bytes = 3.0 * p.n;
-      snprintf(info.kernel, sizeof info.kernel, "quant_f16_i8_kernel");
-      info.grid = (int)((p.n / 16 + 255) / 256);
-      info.block = 256;
-    } else {
-      return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: kind %u not executable", i, d.kind);
+      ntot += (int)sd.n_count;
     }
+    const int kb = dt == kF32 ? 16 : (dt == kI8 ? 64 : 32);
+    if (p.Cin % kb || (p.src_ld * esz) % 16) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu (%s): Cin %% %d != 0", i, d.name, kb);
+    if (p.force_cfg >= 0 && !conv_config_valid(p, p.force_cfg)) p.force_cfg = -1;
+    op.cl = conv_plan(p);
+    const int K = p.ksize * p.ksize * p.Cin;
+    info.m = p.M; info.n = ntot; info.k = K;
+    info.flops = 2.0 * p.M * (double)ntot * K;
+    // algorithmic bytes: each distinct input element once, weights once, outputs once, residual once
+    const bool shared_src = p.nseg == 1 || d.seg[0].src_coff == d.seg[1].src_coff;
+    info.bytes = dtype_bytes(dt) * p.H * p.W * p.Cin * (shared_src ? 1 : p.nseg) + dtype_bytes(dt) * ntot * K + 4.0 * ntot + out_bytes +
+                 (p.res ? dtype_bytes(p.res_dtype) * p.M * ntot : 0.0);
+    snprintf(info.kernel, sizeof info.kernel, "%s", op.cl.kernel_name);
+    info.grid = (int)(op.cl.grid.x * op.cl.grid.y);
+    info.block = (int)op.cl.block.x;
+  } else if (d.kind == kOpStem) {
+    const SegDesc& sd = d.seg[0];
+    const Buffer& db = e->bufs[sd.dst_buf];
+    StemParams& p = op.sp;
+    const int odt = act_dtype_of(db.d.dtype);
+    if (odt != kF16 && odt != kF32 && odt != kS16) return fail(e, UNINA_ERR_UNSUPPORTED, "stem output must be fp16, fp32 or split fp16");
+    p.dtype = odt;
+    p.dst_lo = lo_plane(db.d);
+    p.src = static_cast<const float*>(src.ptr);
+    p.w = reinterpret_cast<const float*>(blob + sd.w_off);
+    p.wt = reinterpret_cast<const float*>(blob + op.wt_off);
+    p.bias = reinterpret_cast<const float*>(blob + sd.b_off);
+    p.dst = static_cast<char*>(db.ptr) + (size_t)sd.dst_coff * dtype_size(odt);
+    p.H = (int)d.in_h; p.W = (int)d.in_w; p.Ho = (int)d.out_h; p.Wo = (int)d.out_w;
+    p.Co = (int)sd.n_count; p.dst_ld = (int)db.d.c;
+    info.m = p.Ho * p.Wo; info.n = p.Co; info.k = 27;
+    info.flops = 2.0 * info.m * info.n * 27;
+    info.bytes = 4.0 * 3 * p.H * p.W + dtype_bytes(odt) * info.m * p.Co;
+    {
+      LaunchDesc sl;
+      const bool tiled = stem_desc(p, &sl) == hipSuccess && sl.block.x == 128;
+      snprintf(info.kernel, sizeof info.kernel, "%s<%s,%d>", tiled ? "stem_tile_kernel" : "stem_conv_kernel", odt == kF32 ? "f32" : (odt == kS16 ? "s16" : "f16"), p.Co);
+      info.grid = tiled ? (int)sl.grid.x : (2 * info.m + 255) / 256;
+      info.block = tiled ? 128 : 256;
+    }
+  } else if (d.kind == kOpSppfPool) {
+    PoolParams& p = op.pp;
+    const int dt = act_dtype_of(src.d.dtype);
+    if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: pool on a non-activation buffer", i);
+    p.dtype = dt;
+    p.buf = src.ptr;
+    p.lo = lo_plane(src.d);
+    p.H = (int)d.in_h; p.W = (int)d.in_w; p.C = (int)d.cin; p.ld = (int)src.d.c; p.coff = (int)d.seg[0].src_coff;
+    info.bytes = dtype_bytes(dt) * p.H * p.W * p.C * 4;
+    snprintf(info.kernel, sizeof info.kernel, dt == kS16 ? "sppf_pool_split_kernel<%s32>" : "sppf_pool_kernel<%s,32>", dt == kF32 ? "f32" : (dt == kI8 ? "i8" : (dt == kS16 ? "" : "f16")));
+    info.grid = p.H * (p.C / 32);
+    info.block = 256;
+  } else if (d.kind == kOpQuant) {
+    const Buffer& db = e->bufs[d.seg[0].dst_buf];
+    if (src.d.dtype != kBufF16Nhwc || db.d.dtype != kBufI8Nhwc || src.d.c != db.d.c || src.d.h != db.d.h || src.d.w != db.d.w)
+      return fail(e, UNINA_ERR_FORMAT, "op %zu: QUANT needs an fp16 source and an int8 twin of the same shape", i);
+    QuantParams& p = op.qp;
+    p.src = static_cast<const half_t*>(src.ptr);
+    p.dst = static_cast<signed char*>(db.ptr);
+    p.n = (size_t)src.d.h * src.d.w * src.d.c;
+    p.inv_scale = 1.0f / db.d.scale;
+    info.bytes = 3.0 * p.n;
+    snprintf(info.kernel, sizeof info.kernel, "quant_f16_i8_kernel");
+    info.grid = (int)((p.n / 16 + 255) / 256);
+    info.block = 256;
+  } else {
+    return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: kind %u not executable", i, d.kind);
   }
-  // fused groups: parameters of the one-launch form; op infos describe what actually runs
-  for (size_t i = 0; i < e->ops.size(); ++i) {
-    PlannedOp& op = e->ops[i];
-    if (op.fuse_role != 1) continue;
-    if (op.fuse_kind == 4) {
-      const OpDesc& a = e->ops[i + op.fuse_pre].d;
-      PlannedOp& zb = e->ops[op.group_last];
-      const OpDesc& z = zb.d;
-      const Buffer& src = e->bufs[a.src_buf];
-      const Buffer& mid = e->bufs[a.seg[0].dst_buf];
-      const Buffer& out = e->bufs[z.seg[0].dst_buf];
-      PairParams& f = op.pr;
-      memset(&f, 0, sizeof f);
-      f.dtype = act_dtype_of(src.d.dtype);
-      const size_t esz = dtype_size(f.dtype);
-      f.src = static_cast<const char*>(src.ptr) + a.seg[0].src_coff * esz;
-      f.src_ld = (int)src.d.c;
-      f.c0 = (int)a.cin; f.c1 = (int)a.seg[0].n_count; f.c2 = (int)z.seg[0].n_count;
-      f.H = (int)a.in_h; f.W = (int)a.in_w;
-      f.dst = static_cast<char*>(mid.ptr) + a.seg[0].dst_coff * esz;
-      f.dst_ld = (int)mid.d.c;
-      f.dst2 = static_cast<char*>(out.ptr) + z.seg[0].dst_coff * esz;
-      f.dst2_ld = (int)out.d.c;
-      f.up2 = (z.seg[0].flags & kSegUp2) ? 1 : 0;
-      f.src_lo = lo_plane(src.d); f.dst_lo = lo_plane(mid.d); f.dst2_lo = lo_plane(out.d);
-      f.pool = op.fuse_pre;
-      f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
-      f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
-      f.zeros = e->d_zeros;
-      if (!pair_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused conv pair does not fit", i);
-      if (!e->fuse) continue;
-      if (op.fuse_pre) {   // the pool op is the group's head: the infos of cv2 move onto it
-        unina_op_info& ai = e->ops[i + 1].info;
-        op.info.flops = ai.flops;
-        op.info.bytes = ai.bytes - dtype_bytes(f.dtype) * f.H * f.W * 3 * (f.c0 / 4);   // the pooled maps are formed in LDS
-        op.info.m = ai.m; op.info.n = ai.n;
-        ai.flops = 0; ai.bytes = 0; ai.grid = 0;
-        snprintf(ai.kernel, sizeof ai.kernel, "(fused into op %zu)", i);
-      }
-      op.info.flops += zb.info.flops;
-      op.info.bytes += zb.info.bytes - dtype_bytes(f.dtype) * f.H * f.W * f.c1;     // the second conv reads the first's output from LDS
-      op.info.grid = f.tiles_x * f.tiles_y;
-      op.info.block = pair_block_threads(f);
-      op.info.k = 0;
-      snprintf(op.info.kernel, sizeof op.info.kernel, "%s", pair_kernel_name(f));
-      snprintf(op.info.name, sizeof op.info.name, "%.40s+%.40s", a.name, z.name);
-      zb.info.flops = 0;
-      zb.info.bytes = 0;
-      zb.info.grid = 0;
-      snprintf(zb.info.kernel, sizeof zb.info.kernel, "(fused into op %zu)", i);
-      continue;
-    }
-    if (op.fuse_kind == 2) {
-      const OpDesc& a = op.d;
-      const OpDesc& z = e->ops[op.group_last].d;
-      const Buffer& src = e->bufs[a.src_buf];
-      HeadParams& f = op.hp;
-      memset(&f, 0, sizeof f);
-      f.src = static_cast<const half_t*>(src.ptr) + a.seg[0].src_coff;
-      f.src_ld = (int)src.d.c;
-      f.C = (int)a.cin;
-      f.H = (int)a.in_h;
-      f.W = (int)a.in_w;
-      f.out_cls = static_cast<float*>(e->bufs[z.seg[0].dst_buf].ptr);
-      f.out_reg = static_cast<float*>(e->bufs[z.seg[1].dst_buf].ptr);
-      f.n_cls = (int)z.seg[0].n_count;
-      f.n_reg = (int)z.seg[1].n_count;
-      f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
-      f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
-      f.zeros = e->d_zeros;
-      if (!head_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused head does not fit", i);
-      if (!e->fuse) continue;
-      unina_op_info& info = op.info;
-      double flops = 0, wbytes = 0;
-      for (int k = (int)i; k <= op.group_last; ++k) {
-        flops += e->ops[k].info.flops;
-        wbytes += 2.0 * e->ops[k].info.n * e->ops[k].info.k + 4.0 * e->ops[k].info.n;
-        if (k > (int)i) {
-          unina_op_info& ai = e->ops[k].info;
-          ai.flops = 0;
-          ai.bytes = 0;
-          ai.grid = 0;
-          snprintf(ai.kernel, sizeof ai.kernel, "(fused into op %zu)", i);
-        }
-      }
-      info.flops = flops;
-      info.bytes = 2.0 * f.H * f.W * f.C + wbytes + 4.0 * f.H * f.W * (f.n_cls + f.n_reg);
-      info.n = f.n_cls + f.n_reg;
-      info.k = 0;
-      info.grid = f.tiles_x * f.tiles_y;
-      info.block = head_block_threads(f.C);
-      snprintf(info.kernel, sizeof info.kernel, "%s", head_kernel_name(f.C));
-      snprintf(info.name, sizeof info.name, "%.*s[head]", (int)(strchr(a.name, '.') ? strchr(a.name, '.') - a.name : 60), a.name);
-      continue;
-    }
-    const OpDesc& a = e->ops[i + op.fuse_pre].d;   // the block's cv1|cv2
-    const OpDesc& z = e->ops[op.group_last].d;
-    const OpDesc& in = op.d;                       // the op whose input the kernel reads (the pre-conv, or cv1|cv2 itself)
-    const Buffer& src = e->bufs[in.src_buf];
-    const Buffer& dst = e->bufs[z.seg[0].dst_buf];
-    C3k2Params& f = op.fp;
-    memset(&f, 0, sizeof f);
-    f.dtype = act_dtype_of(src.d.dtype);
-    const size_t fesz = dtype_size(f.dtype);
-    const double fb = dtype_bytes(f.dtype);
-    f.src = static_cast<const char*>(src.ptr) + in.seg[0].src_coff * fesz;
-    f.src_ld = (int)src.d.c;
-    if (op.fuse_pre) {
-      f.cpre = (int)in.cin;
-      f.preH = (int)in.in_h;
-      f.preW = (int)in.in_w;
-      f.cx = (int)in.seg[0].n_count;
-      const Buffer& xb = e->bufs[a.src_buf];   // the rest of the block's input (a concat's other part) still comes from HBM
-      f.src2 = static_cast<const char*>(xb.ptr) + (a.seg[0].src_coff + f.cx) * fesz;
-      f.src2_ld = (int)xb.d.c;
-      f.src2_lo = lo_plane(xb.d);
-    }
-    f.src_lo = lo_plane(src.d);
-    f.dst_lo = lo_plane(dst.d);
-    f.Cin = (int)a.cin;
-    f.H = (int)a.in_h;
-    f.W = (int)a.in_w;
-    f.dst = static_cast<char*>(dst.ptr) + z.seg[0].dst_coff * fesz;
-    f.dst_ld = (int)dst.d.c;
-    for (int b = 0; b < op.nb; ++b) {   // int8: scale of each bottleneck's shortcut tensor (the 3x3's residual buffer)
-      const OpDesc& c2 = e->ops[i + op.fuse_pre + 2 + 2 * b].d;
-      f.res_scale[b] = c2.res_buf >= 0 ? e->bufs[c2.res_buf].d.scale : 1.0f;
-    }
-    f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
-    f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
-    f.zeros = e->d_zeros;
-    f.hid = op.hid;
-    f.nb = op.nb;
-    if (op.tail_op >= 0) {
-      const SegDesc& ts = e->ops[op.tail_op].d.seg[0];
-      const Buffer& tb = e->bufs[ts.dst_buf];
-      f.tail = op.tail_kind;
-      f.dst2 = static_cast<char*>(tb.ptr) + ts.dst_coff * (op.tail_kind == 3 ? 2 : fesz);
-      f.dst2_ld = (int)tb.d.c;
-      f.dst2_lo = lo_plane(tb.d);
-    }
-    if (op.quant_op >= 0) {
-      const Buffer& qb = e->bufs[e->ops[op.quant_op].d.seg[0].dst_buf];
-      f.dst_q = static_cast<signed char*>(qb.ptr);
-      f.dst_q_ld = (int)qb.d.c;
-      f.q_inv = 1.0f / qb.d.scale;   // as the QUANT op's own parameter
-    }
-    if (!c3k2_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused C3k2 block does not fit", i);
-    if (!e->fuse) continue;
-    if (op.quant_op >= 0) {
-      unina_op_info& qi = e->ops[op.quant_op].info;
-      qi.flops = 0;
-      qi.bytes = 0;
-      qi.grid = 0;
-      snprintf(qi.kernel, sizeof qi.kernel, "(fused into op %zu)", i);
-    }
-    unina_op_info& info = op.info;
-    double flops = 0, wbytes = 0;
-    const int last_op = op.tail_op >= 0 ? op.tail_op : op.group_last;
-    for (int k = (int)i; k <= last_op; ++k) {
-      flops += e->ops[k].info.flops;
-      wbytes += fb * e->ops[k].info.n * e->ops[k].info.k + 4.0 * e->ops[k].info.n;
-      if (k > (int)i) {
-        unina_op_info& ai = e->ops[k].info;
-        ai.flops = 0;
-        ai.bytes = 0;
-        ai.grid = 0;
-        snprintf(ai.kernel, sizeof ai.kernel, "(fused into op %zu)", i);
-      }
-    }
-    info.flops = flops;
-    info.bytes = (f.cpre ? fb * (f.preH * f.preW * f.cpre + f.H * f.W * (f.Cin - f.cx)) : fb * f.H * f.W * f.Cin) + wbytes + fb * f.H * f.W * 2 * f.hid +   // input once, weights once, output once
-                 (f.tail ? fb * (f.tail == 1 ? 4 : 1) * f.H * f.W * f.hid : 0.0);            // (+ the tail conv's output)
-    info.n = 2 * f.hid;
-    info.k = 0;
-    info.grid = f.tiles_x * f.tiles_y;
-    info.block = c3k2_block_threads(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx);
-    snprintf(info.kernel, sizeof info.kernel, "%s", c3k2_kernel_name(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx));
-    snprintf(info.name, sizeof info.name, "%.*s[c3k2 x%d]", (int)(strchr(a.name, '+') ? strchr(a.name, '+') - a.name - 4 : 60), a.name, f.nb);
+  return UNINA_OK;
+}
+
+// Op b's work now runs inside op `at`'s launch, whose info is `a` (`how`: "fused into" / "dual launch with"): a takes over
+// b's flops, bytes and grid, b names that launch.
+void absorb_info(unina_op_info* a, unina_op_info* b, const char* how, size_t at) {
+  a->flops += b->flops;
+  a->bytes += b->bytes;
+  a->grid += b->grid;
+  b->flops = 0;
+  b->bytes = 0;
+  b->grid = 0;
+  snprintf(b->kernel, sizeof b->kernel, "(%s op %zu)", how, at);
+}
+
+// Fused conv pair led by op `i` (conv_pair.hip), with the SPPF pool in front when fuse_pre.
+int plan_pair(unina_engine* e, size_t i) {
+  const char* blob = static_cast<const char*>(e->d_blob);
+  PlannedOp& op = e->ops[i];
+  const OpDesc& a = e->ops[i + op.fuse_pre].d;
+  PlannedOp& zb = e->ops[op.group_last];
+  const OpDesc& z = zb.d;
+  const Buffer& src = e->bufs[a.src_buf];
+  const Buffer& mid = e->bufs[a.seg[0].dst_buf];
+  const Buffer& out = e->bufs[z.seg[0].dst_buf];
+  PairParams& f = op.pr;
+  memset(&f, 0, sizeof f);
+  f.dtype = act_dtype_of(src.d.dtype);
+  const size_t esz = dtype_size(f.dtype);
+  f.src = static_cast<const char*>(src.ptr) + a.seg[0].src_coff * esz;
+  f.src_ld = (int)src.d.c;
+  f.c0 = (int)a.cin; f.c1 = (int)a.seg[0].n_count; f.c2 = (int)z.seg[0].n_count;
+  f.H = (int)a.in_h; f.W = (int)a.in_w;
+  f.dst = static_cast<char*>(mid.ptr) + a.seg[0].dst_coff * esz;
+  f.dst_ld = (int)mid.d.c;
+  f.dst2 = static_cast<char*>(out.ptr) + z.seg[0].dst_coff * esz;
+  f.dst2_ld = (int)out.d.c;
+  f.up2 = (z.seg[0].flags & kSegUp2) ? 1 : 0;
+  f.src_lo = lo_plane(src.d); f.dst_lo = lo_plane(mid.d); f.dst2_lo = lo_plane(out.d);
+  f.pool = op.fuse_pre;
+  f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
+  f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
+  f.zeros = e->d_zeros;
+  if (!pair_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused conv pair does not fit", i);
+  if (!e->fuse) return UNINA_OK;
+  if (op.fuse_pre) {   // the pool op is the group's head: the infos of cv2 move onto it (the pool's own traffic is not counted)
+    unina_op_info& ai = e->ops[i + 1].info;
+    op.info.m = ai.m; op.info.n = ai.n;
+    op.info.flops = op.info.bytes = 0;
+    absorb_info(&op.info, &ai, "fused into", i);
+    op.info.bytes -= dtype_bytes(f.dtype) * f.H * f.W * 3 * (f.c0 / 4);   // the pooled maps are formed in LDS
   }
-  // dual launches: pair independent convs of one kernel family (the P3 / P4 head layers) into one grid each. The later
-  // op moves to the earlier one's position, so nothing between them may feed it or touch what it writes.
+  absorb_info(&op.info, &zb.info, "fused into", i);
+  op.info.bytes -= dtype_bytes(f.dtype) * f.H * f.W * f.c1;     // the second conv reads the first's output from LDS
+  op.info.grid = f.tiles_x * f.tiles_y;
+  op.info.block = pair_block_threads(f);
+  op.info.k = 0;
+  snprintf(op.info.kernel, sizeof op.info.kernel, "%s", pair_kernel_name(f));
+  snprintf(op.info.name, sizeof op.info.name, "%.40s+%.40s", a.name, z.name);
+  return UNINA_OK;
+}
+
+// Fused DetectionHead led by op `i` (head_fused.hip).
+int plan_head(unina_engine* e, size_t i) {
+  const char* blob = static_cast<const char*>(e->d_blob);
+  PlannedOp& op = e->ops[i];
+  const OpDesc& a = op.d;
+  const OpDesc& z = e->ops[op.group_last].d;
+  const Buffer& src = e->bufs[a.src_buf];
+  HeadParams& f = op.hp;
+  memset(&f, 0, sizeof f);
+  f.src = static_cast<const half_t*>(src.ptr) + a.seg[0].src_coff;
+  f.src_ld = (int)src.d.c;
+  f.C = (int)a.cin;
+  f.H = (int)a.in_h;
+  f.W = (int)a.in_w;
+  f.out_cls = static_cast<float*>(e->bufs[z.seg[0].dst_buf].ptr);
+  f.out_reg = static_cast<float*>(e->bufs[z.seg[1].dst_buf].ptr);
+  f.n_cls = (int)z.seg[0].n_count;
+  f.n_reg = (int)z.seg[1].n_count;
+  f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
+  f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
+  f.zeros = e->d_zeros;
+  if (!head_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused head does not fit", i);
+  if (!e->fuse) return UNINA_OK;
+  unina_op_info& info = op.info;
+  double wbytes = 0;
+  for (int k = (int)i; k <= op.group_last; ++k) {
+    wbytes += 2.0 * e->ops[k].info.n * e->ops[k].info.k + 4.0 * e->ops[k].info.n;
+    if (k > (int)i) absorb_info(&info, &e->ops[k].info, "fused into", i);
+  }
+  info.bytes = 2.0 * f.H * f.W * f.C + wbytes + 4.0 * f.H * f.W * (f.n_cls + f.n_reg);
+  info.n = f.n_cls + f.n_reg;
+  info.k = 0;
+  info.grid = f.tiles_x * f.tiles_y;
+  info.block = head_block_threads(f.C);
+  snprintf(info.kernel, sizeof info.kernel, "%s", head_kernel_name(f.C));
+  snprintf(info.name, sizeof info.name, "%.*s[head]", (int)(strchr(a.name, '.') ? strchr(a.name, '.') - a.name : 60), a.name);
+  return UNINA_OK;
+}
+
+// Fused C3k2 block led by op `i` (c3k2_fused.hip), with its pre-conv, tail conv and QUANT store where the matcher found them.
+int plan_c3k2(unina_engine* e, size_t i) {
+  const char* blob = static_cast<const char*>(e->d_blob);
+  PlannedOp& op = e->ops[i];
+  const OpDesc& a = e->ops[i + op.fuse_pre].d;   // the block's cv1|cv2
+  const OpDesc& z = e->ops[op.group_last].d;
+  const OpDesc& in = op.d;                       // the op whose input the kernel reads (the pre-conv, or cv1|cv2 itself)
+  const Buffer& src = e->bufs[in.src_buf];
+  const Buffer& dst = e->bufs[z.seg[0].dst_buf];
+  C3k2Params& f = op.fp;
+  memset(&f, 0, sizeof f);
+  f.dtype = act_dtype_of(src.d.dtype);
+  const size_t fesz = dtype_size(f.dtype);
+  const double fb = dtype_bytes(f.dtype);
+  f.src = static_cast<const char*>(src.ptr) + in.seg[0].src_coff * fesz;
+  f.src_ld = (int)src.d.c;
+  if (op.fuse_pre) {
+    f.cpre = (int)in.cin;
+    f.preH = (int)in.in_h;
+    f.preW = (int)in.in_w;
+    f.cx = (int)in.seg[0].n_count;
+    const Buffer& xb = e->bufs[a.src_buf];   // the rest of the block's input (a concat's other part) still comes from HBM
+    f.src2 = static_cast<const char*>(xb.ptr) + (a.seg[0].src_coff + f.cx) * fesz;
+    f.src2_ld = (int)xb.d.c;
+    f.src2_lo = lo_plane(xb.d);
+  }
+  f.src_lo = lo_plane(src.d);
+  f.dst_lo = lo_plane(dst.d);
+  f.Cin = (int)a.cin;
+  f.H = (int)a.in_h;
+  f.W = (int)a.in_w;
+  f.dst = static_cast<char*>(dst.ptr) + z.seg[0].dst_coff * fesz;
+  f.dst_ld = (int)dst.d.c;
+  for (int b = 0; b < op.nb; ++b) {   // int8: scale of each bottleneck's shortcut tensor (the 3x3's residual buffer)
+    const OpDesc& c2 = e->ops[i + op.fuse_pre + 2 + 2 * b].d;
+    f.res_scale[b] = c2.res_buf >= 0 ? e->bufs[c2.res_buf].d.scale : 1.0f;
+  }
+  f.wstream = reinterpret_cast<const unsigned char*>(blob + op.stream_off);
+  f.bias = reinterpret_cast<const float*>(blob + op.fbias_off);
+  f.zeros = e->d_zeros;
+  f.hid = op.hid;
+  f.nb = op.nb;
+  if (op.tail_op >= 0) {
+    const SegDesc& ts = e->ops[op.tail_op].d.seg[0];
+    const Buffer& tb = e->bufs[ts.dst_buf];
+    f.tail = op.tail_kind;
+    f.dst2 = static_cast<char*>(tb.ptr) + ts.dst_coff * (op.tail_kind == 3 ? 2 : fesz);
+    f.dst2_ld = (int)tb.d.c;
+    f.dst2_lo = lo_plane(tb.d);
+  }
+  if (op.quant_op >= 0) {
+    const Buffer& qb = e->bufs[e->ops[op.quant_op].d.seg[0].dst_buf];
+    f.dst_q = static_cast<signed char*>(qb.ptr);
+    f.dst_q_ld = (int)qb.d.c;
+    f.q_inv = 1.0f / qb.d.scale;   // as the QUANT op's own parameter
+  }
+  if (!c3k2_layout(&f)) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: fused C3k2 block does not fit", i);
+  if (!e->fuse) return UNINA_OK;
+  unina_op_info& info = op.info;
+  double wbytes = 0;
+  const int last_op = op.tail_op >= 0 ? op.tail_op : op.group_last;
+  for (int k = (int)i; k <= last_op; ++k) {
+    wbytes += fb * e->ops[k].info.n * e->ops[k].info.k + 4.0 * e->ops[k].info.n;
+    if (k > (int)i) absorb_info(&info, &e->ops[k].info, "fused into", i);
+  }
+  if (op.quant_op >= 0) absorb_info(&info, &e->ops[op.quant_op].info, "fused into", i);
+  info.bytes = (f.cpre ? fb * (f.preH * f.preW * f.cpre + f.H * f.W * (f.Cin - f.cx)) : fb * f.H * f.W * f.Cin) + wbytes + fb * f.H * f.W * 2 * f.hid +   // input once, weights once, output once
+               (f.tail ? fb * (f.tail == 1 ? 4 : 1) * f.H * f.W * f.hid : 0.0);            // (+ the tail conv's output)
+  info.n = 2 * f.hid;
+  info.k = 0;
+  info.grid = f.tiles_x * f.tiles_y;
+  info.block = c3k2_block_threads(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx);
+  snprintf(info.kernel, sizeof info.kernel, "%s", c3k2_kernel_name(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx));
+  snprintf(info.name, sizeof info.name, "%.*s[c3k2 x%d]", (int)(strchr(a.name, '+') ? strchr(a.name, '+') - a.name - 4 : 60), a.name, f.nb);
+  return UNINA_OK;
+}
+
+// May an op that reads `r` and writes `w` move across ops [lo, hi] (to either side of them)? None of them may write what it
+// reads, or read or write what it writes. Their regions are taken as they stand, so pairs already made count.
+bool may_cross(const unina_engine* e, size_t lo, size_t hi, const std::vector<Region>& r, const std::vector<Region>& w) {
+  std::vector<Region> rk, wk;
+  for (size_t k = lo; k <= hi; ++k) {
+    op_regions(e, k, &rk, &wk);
+    for (const Region& x : wk) {
+      for (const Region& y : r)
+        if (overlaps(x, y)) return false;
+      for (const Region& y : w)
+        if (overlaps(x, y)) return false;
+    }
+    for (const Region& x : rk)
+      for (const Region& y : w)
+        if (overlaps(x, y)) return false;
+  }
+  return true;
+}
+
+// Dual launches: pair independent convs of one kernel family (the P3 / P4 head layers) into one grid each. The later
+// op moves to the earlier one's position, so nothing between them may feed it or touch what it writes.
+void plan_duals(unina_engine* e) {
   for (auto& op : e->ops) {
     op.dual_with = op.dual_kind = -1;
     op.dual_absorbed = false;
   }
-  if (e->fuse && !getenv("UNINA_NO_DUAL")) {
-    const size_t n = e->ops.size();
-    std::vector<Region> ri, wi, rj, wj;
-    // a fused C3k2 block and the fused head that does not depend on it (pan_c3k2_2 and head_p2): block_dual.hip
-    for (size_t i = 0; i < n; ++i) {
-      PlannedOp& a = e->ops[i];
-      if (a.fuse_role != 1 || a.fuse_kind != 1 || a.dual_with >= 0) continue;
-      for (size_t j = i + 1; j < n; ++j) {
-        PlannedOp& b = e->ops[j];
-        if (b.fuse_role != 1 || b.fuse_kind != 2 || b.dual_absorbed || !block_dual_match(a.fp, b.hp)) continue;
-        op_regions(e, j, &rj, &wj);
-        bool legal = true;
-        for (size_t k = i; k < j && legal; ++k) {
-          op_regions(e, k, &ri, &wi);
-          for (const Region& w : wi) {
-            for (const Region& r : rj) legal = legal && !overlaps(w, r);
-            for (const Region& w2 : wj) legal = legal && !overlaps(w, w2);
-          }
-          for (const Region& r : ri)
-            for (const Region& w2 : wj) legal = legal && !overlaps(r, w2);
-        }
-        if (!legal) continue;
-        a.dual_with = (int)j;
-        b.dual_absorbed = true;
-        a.info.flops += b.info.flops;
-        a.info.bytes += b.info.bytes;
-        a.info.grid += b.info.grid;
-        snprintf(a.info.kernel, sizeof a.info.kernel, "%s", block_dual_name(a.fp.dtype, a.fp.cpre));
-        b.info.flops = 0;
-        b.info.bytes = 0;
-        b.info.grid = 0;
-        snprintf(b.info.kernel, sizeof b.info.kernel, "(dual launch with op %zu)", i);
-        break;
-      }
+  if (!e->fuse || getenv("UNINA_NO_DUAL")) return;
+  const size_t n = e->ops.size();
+  std::vector<Region> ra, wa, rb, wb;
+  // a fused C3k2 block and the fused head that does not depend on it (pan_c3k2_2 and head_p2): block_dual.hip
+  for (size_t i = 0; i < n; ++i) {
+    PlannedOp& a = e->ops[i];
+    if (a.fuse_role != 1 || a.fuse_kind != 1 || a.dual_with >= 0) continue;
+    for (size_t j = i + 1; j < n; ++j) {
+      PlannedOp& b = e->ops[j];
+      if (b.fuse_role != 1 || b.fuse_kind != 2 || b.dual_absorbed || !block_dual_match(a.fp, b.hp)) continue;
+      op_regions(e, j, &rb, &wb);
+      if (!may_cross(e, i, j - 1, rb, wb)) continue;
+      a.dual_with = (int)j;
+      b.dual_absorbed = true;
+      absorb_info(&a.info, &b.info, "dual launch with", i);
+      snprintf(a.info.kernel, sizeof a.info.kernel, "%s", block_dual_name(a.fp.dtype, a.fp.cpre));
+      break;
     }
-    for (size_t i = 0; i < n; ++i) {
-      PlannedOp& a = e->ops[i];
-      if (a.d.kind != kOpConv || a.fuse_role || a.dual_absorbed || a.dual_with >= 0 || a.cp.force_cfg >= 0) continue;
-      for (size_t j = i + 1; j < n; ++j) {
-        PlannedOp& b = e->ops[j];
-        if (b.d.kind != kOpConv || b.fuse_role || b.dual_absorbed || b.dual_with >= 0 || b.cp.force_cfg >= 0) continue;
-        const int kind = conv_dual_match(a.cp, b.cp);
-        if (kind < 0) continue;
-        op_regions(e, j, &rj, &wj);
-        bool legal = true;
-        for (size_t k = i; k < j && legal; ++k) {
-          op_regions(e, k, &ri, &wi);
-          for (const Region& w : wi) {
-            for (const Region& r : rj) legal = legal && !overlaps(w, r);
-            for (const Region& w2 : wj) legal = legal && !overlaps(w, w2);
-          }
-          for (const Region& r : ri)
-            for (const Region& w2 : wj) legal = legal && !overlaps(r, w2);
-        }
-        if (!legal) {
-          // the other direction: the EARLIER op sinks to the later one's position (an INT8 engine's P3 output conv
-          // waits for the P4 head's): nothing in between may read what it writes or write what it reads / writes
-          const int kind2 = conv_dual_match(b.cp, a.cp);
-          if (kind2 < 0) continue;
-          std::vector<Region> ra, wa;
-          op_regions(e, i, &ra, &wa);
-          bool sink = true;
-          for (size_t k = i + 1; k <= j && sink; ++k) {
-            op_regions(e, k, &ri, &wi);
-            for (const Region& w : wi) {
-              for (const Region& r : ra) sink = sink && !overlaps(w, r);
-              for (const Region& w2 : wa) sink = sink && !overlaps(w, w2);
-            }
-            for (const Region& r : ri)
-              for (const Region& w2 : wa) sink = sink && !overlaps(r, w2);
-          }
-          if (!sink) continue;
-          b.dual_with = (int)i;
-          b.dual_kind = kind2;
-          a.dual_absorbed = true;
-          b.info.flops += a.info.flops;
-          b.info.bytes += a.info.bytes;
-          b.info.grid += a.info.grid;
-          snprintf(b.info.kernel, sizeof b.info.kernel, "%s", conv_dual_name(kind2));
-          a.info.flops = 0;
-          a.info.bytes = 0;
-          a.info.grid = 0;
-          snprintf(a.info.kernel, sizeof a.info.kernel, "(dual launch with op %zu)", j);
-          break;
-        }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    PlannedOp& a = e->ops[i];
+    if (a.d.kind != kOpConv || a.fuse_role || a.dual_absorbed || a.dual_with >= 0 || a.cp.force_cfg >= 0) continue;
+    for (size_t j = i + 1; j < n; ++j) {
+      PlannedOp& b = e->ops[j];
+      if (b.d.kind != kOpConv || b.fuse_role || b.dual_absorbed || b.dual_with >= 0 || b.cp.force_cfg >= 0) continue;
+      const int kind = conv_dual_match(a.cp, b.cp);
+      if (kind < 0) continue;
+      op_regions(e, j, &rb, &wb);
+      if (may_cross(e, i, j - 1, rb, wb)) {
         a.dual_with = (int)j;
         a.dual_kind = kind;
         b.dual_absorbed = true;
-        int grid = 0;
-        (void)grid;
-        a.info.flops += b.info.flops;
-        a.info.bytes += b.info.bytes;
-        a.info.grid += b.info.grid;
+        absorb_info(&a.info, &b.info, "dual launch with", i);
         snprintf(a.info.kernel, sizeof a.info.kernel, "%s", conv_dual_name(kind));
-        b.info.flops = 0;
-        b.info.bytes = 0;
-        b.info.grid = 0;
-        snprintf(b.info.kernel, sizeof b.info.kernel, "(dual launch with op %zu)", i);
         break;
       }
+      // the other direction: the EARLIER op sinks to the later one's position (an INT8 engine's P3 output conv
+      // waits for the P4 head's): nothing in between may read what it writes or write what it reads / writes
+      const int kind2 = conv_dual_match(b.cp, a.cp);
+      if (kind2 < 0) continue;
+      op_regions(e, i, &ra, &wa);
+      if (!may_cross(e, i + 1, j, ra, wa)) continue;
+      b.dual_with = (int)i;
+      b.dual_kind = kind2;
+      a.dual_absorbed = true;
+      absorb_info(&b.info, &a.info, "dual launch with", j);
+      snprintf(b.info.kernel, sizeof b.info.kernel, "%s", conv_dual_name(kind2));
+      break;
     }
   }
+}
+
+// (Re)computes kernel parameters from the current buffer addresses. Element types are properties of the BUFFERS
+// (fp16 / fp32 / int8 NHWC): a conv runs in the type of its source buffer and converts to the type of each
+// destination buffer in its epilogue, so fp16, fp32 and mixed int8/fp16 engines share one planner. Fused groups get the
+// parameters of their one-launch form, and op infos describe what actually runs.
+int plan(unina_engine* e) {
+  for (size_t i = 0; i < e->ops.size(); ++i) {
+    const int rc = plan_op(e, i);
+    if (rc != UNINA_OK) return rc;
+  }
+  for (size_t i = 0; i < e->ops.size(); ++i) {
+    const PlannedOp& op = e->ops[i];
+    if (op.fuse_role != 1) continue;
+    const int rc = op.fuse_kind == 4 ? plan_pair(e, i) : (op.fuse_kind == 2 ? plan_head(e, i) : plan_c3k2(e, i));
+    if (rc != UNINA_OK) return rc;
+  }
+  plan_duals(e);
   find_fold_ops(e);
   e->plan_dirty = false;
   drop_graph(e);
@@ -766,6 +767,39 @@ bool is_plain_conv(const OpDesc& d, uint32_t k, uint32_t nseg, bool int8 = false
   return true;
 }
 
+// Conv op `o` as one step of a packed block stream: `padded` counts the stored rows (n_pad) instead of the live ones,
+// `i8` adds the int8 multipliers and output scales.
+C3k2Conv pack_conv(const unina_engine* e, const std::vector<char>& blob, const OpDesc& o, bool padded, bool i8) {
+  C3k2Conv cv;
+  memset(&cv, 0, sizeof cv);
+  for (uint32_t s = 0; s < o.nseg; ++s) {
+    const SegDesc& sg = o.seg[s];
+    cv.w[s] = reinterpret_cast<const unsigned char*>(blob.data() + sg.w_off);
+    cv.bias[s] = reinterpret_cast<const float*>(blob.data() + sg.b_off);
+    cv.n[s] = (int)(padded ? sg.n_pad : sg.n_count);
+    if (i8) {
+      cv.mult[s] = reinterpret_cast<const float*>(blob.data() + sg.m_off);
+      cv.out_inv[s] = 1.0f / e->bufs[sg.dst_buf].d.scale;   // as plan() computes ConvSeg::out_inv_scale
+    }
+  }
+  cv.K = (int)(o.ksize * o.ksize * o.cin);
+  return cv;
+}
+
+// Appends `bytes` bytes at the blob's next 256-byte boundary; returns their offset.
+uint64_t append_aligned(std::vector<char>* blob, const void* p, size_t bytes) {
+  blob->resize((blob->size() + 255) & ~(size_t)255);
+  const uint64_t off = blob->size();
+  blob->insert(blob->end(), static_cast<const char*>(p), static_cast<const char*>(p) + bytes);
+  return off;
+}
+
+// A fused group's packed weight stream and biases, appended to the blob for the group's first op.
+void append_stream(std::vector<char>* blob, const std::vector<unsigned char>& stream, const std::vector<float>& bias, PlannedOp* head) {
+  head->stream_off = append_aligned(blob, stream.data(), stream.size());
+  head->fbias_off = append_aligned(blob, bias.data(), bias.size() * sizeof(float));
+}
+
 void find_c3k2_groups(unina_engine* e, std::vector<char>* blob) {
   const size_t n = e->ops.size();
   for (size_t i = 0; i + 3 < n; ++i) {
@@ -806,42 +840,28 @@ void find_c3k2_groups(unina_engine* e, std::vector<char>* blob) {
     if (e->bufs[z.seg[0].dst_buf].d.dtype != bdt || z.seg[0].dst_coff % al || e->bufs[z.seg[0].dst_buf].d.c % al) continue;
     if (a.in_h != z.out_h || a.in_w != z.out_w) continue;
     if (!c3k2_supported((int)h, nb, (int)a.cin, 0, dt)) continue;
-    // an FPN block is followed by its lateral conv (model.py:256,259: ConvBlock 1x1, 2h -> h) whose store does the
-    // nearest x2 upsample: it becomes the block kernel's last step when that class exists
-    size_t jt = j;   // last op of the group incl. the tail
-    if (j + 1 < n && !i8) {
+    // A 1x1 ConvBlock 2h -> h on cv3's output that becomes the block kernel's last step (tail kind 1-3), with the slice
+    // flags, int8 multipliers and destination type that tail kind takes.
+    auto is_tail = [&](const OpDesc& t, uint32_t flags, bool mult, uint32_t dst_dtype, int kind) {
+      const SegDesc& ts = t.seg[0];
+      const BufferDesc& tb = e->bufs[ts.dst_buf].d;
+      const uint32_t tal = dst_dtype == kBufI8Nhwc ? 16 : 8;
+      return t.kind == kOpConv && t.ksize == 1 && t.stride == 1 && t.relu && t.nseg == 1 && t.res_buf < 0 && ts.flags == flags &&
+             (ts.m_off != 0) == mult && ts.n_pad == ts.n_count && t.cin == 2 * h && ts.n_count == h && t.src_buf == z.seg[0].dst_buf &&
+             ts.src_coff == z.seg[0].dst_coff && tb.dtype == dst_dtype && ts.dst_coff % tal == 0 && tb.c % tal == 0 &&
+             ts.dst_buf != z.seg[0].dst_buf && t.in_h == z.out_h && t.in_w == z.out_w && c3k2_supported((int)h, nb, (int)a.cin, kind, dt);
+    };
+    int tail_kind = 0;
+    if (j + 1 < n) {
       const OpDesc& t = e->ops[j + 1].d;
-      if (t.kind == kOpConv && t.ksize == 1 && t.stride == 1 && t.relu && t.nseg == 1 && t.res_buf < 0 && t.seg[0].flags == kSegUp2 &&
-          !t.seg[0].m_off && t.seg[0].n_pad == t.seg[0].n_count && t.cin == 2 * h && t.seg[0].n_count == h &&
-          t.src_buf == z.seg[0].dst_buf && t.seg[0].src_coff == z.seg[0].dst_coff &&
-          e->bufs[t.seg[0].dst_buf].d.dtype == bdt && t.seg[0].dst_coff % 8 == 0 && e->bufs[t.seg[0].dst_buf].d.c % 8 == 0 &&
-          t.seg[0].dst_buf != z.seg[0].dst_buf && c3k2_supported((int)h, nb, (int)a.cin, 1, dt))
-        jt = j + 1;
+      // 1: an FPN block's lateral conv (model.py:256,259: ConvBlock 1x1, 2h -> h) whose store does the nearest x2 upsample
+      if (!i8 && is_tail(t, kSegUp2, false, bdt, 1)) tail_kind = 1;
+      // 2: a plain 1x1 ConvBlock on the block's output (stage3_c3k2 -> sppf.cv1, model.py:215-216), fp16 or int8
+      else if (is_tail(t, 0, i8, bdt, 2)) tail_kind = 2;
+      // 3 (INT8 engines): an int8 FPN block whose lateral (int8 conv) writes the fp16 concat buffer of a narrow fp16 block
+      else if (i8 && is_tail(t, kSegUp2, true, kBufF16Nhwc, 3)) tail_kind = 3;
     }
-    // ... or by a plain 1x1 ConvBlock 2h -> h on its output (stage3_c3k2 -> sppf.cv1, model.py:215-216), fp16 or int8
-    int tail_kind = jt > j ? 1 : 0;
-    if (jt == j && j + 1 < n) {
-      const OpDesc& t = e->ops[j + 1].d;
-      if (is_plain_conv(t, 1, 1, i8) && t.res_buf < 0 && t.cin == 2 * h && t.seg[0].n_count == h && t.src_buf == z.seg[0].dst_buf &&
-          t.seg[0].src_coff == z.seg[0].dst_coff && e->bufs[t.seg[0].dst_buf].d.dtype == bdt && t.seg[0].dst_coff % al == 0 &&
-          e->bufs[t.seg[0].dst_buf].d.c % al == 0 && t.seg[0].dst_buf != z.seg[0].dst_buf && t.in_h == z.out_h && t.in_w == z.out_w &&
-          c3k2_supported((int)h, nb, (int)a.cin, 2, dt)) {
-        jt = j + 1;
-        tail_kind = 2;
-      }
-    }
-    // INT8 engines: an int8 FPN block whose lateral (int8 conv) writes the fp16 concat buffer of a narrow fp16 block
-    if (jt == j && i8 && j + 1 < n) {
-      const OpDesc& t = e->ops[j + 1].d;
-      if (t.kind == kOpConv && t.ksize == 1 && t.stride == 1 && t.relu && t.nseg == 1 && t.res_buf < 0 && t.seg[0].flags == kSegUp2 &&
-          t.seg[0].m_off && t.seg[0].n_pad == t.seg[0].n_count && t.cin == 2 * h && t.seg[0].n_count == h &&
-          t.src_buf == z.seg[0].dst_buf && t.seg[0].src_coff == z.seg[0].dst_coff &&
-          e->bufs[t.seg[0].dst_buf].d.dtype == kBufF16Nhwc && t.seg[0].dst_coff % 8 == 0 && e->bufs[t.seg[0].dst_buf].d.c % 8 == 0 &&
-          c3k2_supported((int)h, nb, (int)a.cin, 3, dt)) {
-        jt = j + 1;
-        tail_kind = 3;
-      }
-    }
+    const size_t jt = tail_kind ? j + 1 : j;   // last op of the group incl. the tail
     // INT8 engines: an fp16 block whose output gets an int8 twin from the QUANT op that follows (mixed readers)
     int quant_op = -1;
     if (!i8 && dt == kF16 && jt + 1 < n) {
@@ -858,80 +878,40 @@ void find_c3k2_groups(unina_engine* e, std::vector<char>* blob) {
       const OpDesc& pz = e->ops[i - 1].d;
       const uint32_t cx = pz.seg[0].n_count;   // the pre-conv writes the FIRST cx channels of the block's input (all of it, or
                                                // the down-sampling half of a PAN concat)
-      bool ok = pz.kind == kOpConv && pz.ksize == 3 && pz.stride == 2 && pz.relu && pz.nseg == 1 && pz.res_buf < 0 && !pz.seg[0].flags &&
-                (pz.seg[0].m_off != 0) == i8 && pz.seg[0].n_pad == pz.seg[0].n_count && pz.seg[0].dst_buf == a.src_buf &&
-                pz.seg[0].dst_coff == a.seg[0].src_coff && cx <= a.cin && cx % al == 0 &&
-                e->bufs[pz.src_buf].d.dtype == bdt && pz.seg[0].src_coff % al == 0 && e->bufs[pz.src_buf].d.c % al == 0 &&
-                pz.out_h == a.in_h && pz.out_w == a.in_w && pz.src_buf != a.src_buf &&
-                c3k2_supported((int)h, nb, (int)a.cin, tail_kind, dt, (int)pz.cin, (int)cx);
-      // its output must be private to the group: nothing else reads or writes those channels
-      const Region out{(int)a.src_buf, (int)pz.seg[0].dst_coff, (int)(pz.seg[0].dst_coff + cx)};
-      for (size_t k = 0; k < n && ok; ++k) {
-        if (k >= i - 1 && k <= j) continue;
-        const OpDesc& o = e->ops[k].d;
-        if (o.kind == kOpConv || o.kind == kOpQuant || o.kind == kOpSppfPool || o.kind == kOpUpsample)
-          for (uint32_t sgi = 0; sgi < o.nseg; ++sgi) {
-            const int rc0 = (int)o.seg[sgi].src_coff, rc1 = rc0 + (int)(o.kind == kOpConv ? o.cin : o.seg[sgi].n_count);
-            if (overlaps(out, Region{(int)o.src_buf, rc0, o.kind == kOpSppfPool ? (int)e->bufs[o.src_buf].d.c : rc1})) ok = false;
-            if (overlaps(out, Region{(int)o.seg[sgi].dst_buf, (int)o.seg[sgi].dst_coff, (int)(o.seg[sgi].dst_coff + o.seg[sgi].n_count)})) ok = false;
-          }
-        if (o.res_buf == (int)a.src_buf) ok = false;
-      }
-      if (e->bufs[a.src_buf].d.flags & (kBufInput | kBufOutput)) ok = false;
+      const bool ok = pz.kind == kOpConv && pz.ksize == 3 && pz.stride == 2 && pz.relu && pz.nseg == 1 && pz.res_buf < 0 && !pz.seg[0].flags &&
+                      (pz.seg[0].m_off != 0) == i8 && pz.seg[0].n_pad == pz.seg[0].n_count && pz.seg[0].dst_buf == a.src_buf &&
+                      pz.seg[0].dst_coff == a.seg[0].src_coff && cx <= a.cin && cx % al == 0 &&
+                      e->bufs[pz.src_buf].d.dtype == bdt && pz.seg[0].src_coff % al == 0 && e->bufs[pz.src_buf].d.c % al == 0 &&
+                      pz.out_h == a.in_h && pz.out_w == a.in_w && pz.src_buf != a.src_buf &&
+                      c3k2_supported((int)h, nb, (int)a.cin, tail_kind, dt, (int)pz.cin, (int)cx) &&
+                      !(e->bufs[a.src_buf].d.flags & (kBufInput | kBufOutput)) &&
+                      // its output must be private to the group: nothing else reads or writes those channels
+                      !touched_outside(e, Region{(int)a.src_buf, (int)pz.seg[0].dst_coff, (int)(pz.seg[0].dst_coff + cx)}, i - 1, j);
       if (ok) i0 = i - 1;
     }
     const OpDesc& first = e->ops[i0].d;
     // the group's intermediates must be private to it, and must not be its own input or output
     bool priv = true;
-    for (uint32_t b : inter) {
-      if (e->bufs[b].d.dtype != bdt) priv = false;   // (an INT8 engine's fp16 conv may still write an int8 buffer)
-      if (b == first.src_buf || b == z.seg[0].dst_buf || (e->bufs[b].d.flags & (kBufInput | kBufOutput))) priv = false;
-      for (size_t k = 0; k < n && priv; ++k) {
-        if (k >= i0 && k <= j) continue;
-        const OpDesc& o = e->ops[k].d;
-        if (o.src_buf == b || o.res_buf == (int)b) priv = false;
-        for (uint32_t s = 0; s < o.nseg; ++s)
-          if (o.seg[s].dst_buf == b) priv = false;
-      }
-    }
+    for (uint32_t b : inter)
+      priv = priv && e->bufs[b].d.dtype == bdt &&   // (an INT8 engine's fp16 conv may still write an int8 buffer)
+             b != first.src_buf && b != z.seg[0].dst_buf && !(e->bufs[b].d.flags & (kBufInput | kBufOutput)) &&
+             !touched_outside(e, whole((int)b), i0, j);
     if (!priv) continue;
     // pack
     std::vector<C3k2Conv> convs;
-    for (size_t k = i0; k <= jt; ++k) {
-      const OpDesc& o = e->ops[k].d;
-      C3k2Conv cv;
-      memset(&cv, 0, sizeof cv);
-      for (uint32_t s = 0; s < o.nseg; ++s) {
-        cv.w[s] = reinterpret_cast<const unsigned char*>(blob->data() + o.seg[s].w_off);
-        cv.bias[s] = reinterpret_cast<const float*>(blob->data() + o.seg[s].b_off);
-        cv.n[s] = (int)o.seg[s].n_count;
-        if (i8) {
-          cv.mult[s] = reinterpret_cast<const float*>(blob->data() + o.seg[s].m_off);
-          cv.out_inv[s] = 1.0f / e->bufs[o.seg[s].dst_buf].d.scale;   // as plan() computes ConvSeg::out_inv_scale
-        }
-      }
-      cv.K = (int)(o.ksize * o.ksize * o.cin);
-      convs.push_back(cv);
-    }
+    for (size_t k = i0; k <= jt; ++k) convs.push_back(pack_conv(e, *blob, e->ops[k].d, false, i8));
     std::vector<unsigned char> stream;
     std::vector<float> bias;
     if (!c3k2_pack((int)h, nb, (int)a.cin, tail_kind, convs.data(), &stream, &bias, dt, i0 < i ? (int)first.cin : 0,
                    i0 < i ? (int)first.seg[0].n_count : 0)) continue;
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t so = blob->size();
-    blob->insert(blob->end(), stream.begin(), stream.end());
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t bo = blob->size();
-    blob->insert(blob->end(), reinterpret_cast<const char*>(bias.data()), reinterpret_cast<const char*>(bias.data() + bias.size()));
     PlannedOp& head = e->ops[i0];
+    append_stream(blob, stream, bias, &head);
     head.fuse_role = 1;
     head.fuse_kind = 1;
     head.fuse_pre = i0 < i ? 1 : 0;
     head.group_last = (int)j;
     head.hid = (int)h;
     head.nb = nb;
-    head.stream_off = so;
-    head.fbias_off = bo;
     head.tail_op = jt > j ? (int)jt : -1;
     head.tail_kind = tail_kind;
     head.quant_op = quant_op;
@@ -956,20 +936,9 @@ void find_pair_groups(unina_engine* e, std::vector<char>* blob) {
     int pool = 0;
     if (i > 0 && !e->ops[i - 1].fuse_role && e->ops[i - 1].d.kind == kOpSppfPool) {
       const OpDesc& pl = e->ops[i - 1].d;
-      bool ok = pl.src_buf == a.src_buf && pl.seg[0].src_coff == a.seg[0].src_coff && a.cin == 4 * pl.cin;
       const Region pooled{(int)pl.src_buf, (int)(pl.seg[0].src_coff + pl.cin), (int)(pl.seg[0].src_coff + 4 * pl.cin)};
-      for (size_t k = 0; k < n && ok; ++k) {
-        if (k == i - 1 || k == i) continue;
-        const OpDesc& o = e->ops[k].d;
-        if (o.kind == kOpStem) continue;
-        for (uint32_t sgi = 0; sgi < o.nseg; ++sgi) {
-          const int rc0 = (int)o.seg[sgi].src_coff, rc1 = rc0 + (int)(o.kind == kOpConv ? o.cin : o.seg[sgi].n_count);
-          if (overlaps(pooled, Region{(int)o.src_buf, rc0, rc1})) ok = false;
-          if (overlaps(pooled, Region{(int)o.seg[sgi].dst_buf, (int)o.seg[sgi].dst_coff, (int)(o.seg[sgi].dst_coff + o.seg[sgi].n_count)})) ok = false;
-        }
-        if (o.res_buf == (int)pl.src_buf) ok = false;
-      }
-      if (ok) pool = 1;
+      if (pl.src_buf == a.src_buf && pl.seg[0].src_coff == a.seg[0].src_coff && a.cin == 4 * pl.cin && !touched_outside(e, pooled, i - 1, i))
+        pool = 1;
     }
     const uint32_t bdt = e->bufs[a.src_buf].d.dtype;
     if (bdt != kBufF16Nhwc && bdt != kBufI8Nhwc && bdt != kBufS16Nhwc) continue;
@@ -986,36 +955,16 @@ void find_pair_groups(unina_engine* e, std::vector<char>* blob) {
     const int dt = i8 ? kI8 : (bdt == kBufS16Nhwc ? kS16 : kF16), up2 = (z.seg[0].flags & kSegUp2) ? 1 : 0;
     if (pool && !pair_supported(dt, (int)a.cin, (int)a.seg[0].n_count, (int)z.seg[0].n_count, up2, 1)) pool = 0;
     if (!pair_supported(dt, (int)a.cin, (int)a.seg[0].n_count, (int)z.seg[0].n_count, up2, pool)) continue;
-    C3k2Conv cv[2];
-    memset(cv, 0, sizeof cv);
-    const OpDesc* od[2] = {&a, &z};
-    for (int k = 0; k < 2; ++k) {
-      const SegDesc& sg = od[k]->seg[0];
-      cv[k].w[0] = reinterpret_cast<const unsigned char*>(blob->data() + sg.w_off);
-      cv[k].bias[0] = reinterpret_cast<const float*>(blob->data() + sg.b_off);
-      cv[k].n[0] = (int)sg.n_count;
-      cv[k].K = (int)od[k]->cin;
-      if (i8) {
-        cv[k].mult[0] = reinterpret_cast<const float*>(blob->data() + sg.m_off);
-        cv[k].out_inv[0] = 1.0f / e->bufs[sg.dst_buf].d.scale;
-      }
-    }
+    const C3k2Conv cv[2] = {pack_conv(e, *blob, a, false, i8), pack_conv(e, *blob, z, false, i8)};
     std::vector<unsigned char> stream;
     std::vector<float> bias;
     block_pack(cv, 2, &stream, &bias, dt);
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t so = blob->size();
-    blob->insert(blob->end(), stream.begin(), stream.end());
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t bo = blob->size();
-    blob->insert(blob->end(), reinterpret_cast<const char*>(bias.data()), reinterpret_cast<const char*>(bias.data() + bias.size()));
     PlannedOp& head = e->ops[i - pool];
+    append_stream(blob, stream, bias, &head);
     head.fuse_role = 1;
     head.fuse_kind = 4;
     head.fuse_pre = pool;            // 1: this op is the SPPF pool, the conv pair are the next two ops
     head.group_last = (int)(i + 1);
-    head.stream_off = so;
-    head.fbias_off = bo;
     if (pool) e->ops[i].fuse_role = 2;
     e->ops[i + 1].fuse_role = 2;
     ++e->n_groups;
@@ -1049,47 +998,20 @@ void find_head_groups(unina_engine* e, std::vector<char>* blob) {
            c.seg[s].dst_coff == 0 && e->bufs[c.seg[s].dst_buf].d.dtype == kBufF32Planar;
     if (!ok || e->bufs[a.src_buf].d.dtype != kBufF16Nhwc || !head_supported((int)C)) continue;
     if (a.in_h != c.out_h || a.in_w != c.out_w) continue;
-    for (uint32_t hb : {h0, h1}) {
-      if (e->bufs[hb].d.dtype != kBufF16Nhwc) ok = false;
-      if (hb == a.src_buf || (e->bufs[hb].d.flags & (kBufInput | kBufOutput))) ok = false;
-      for (size_t k = 0; k < n && ok; ++k) {
-        if (k >= i && k <= i + 2) continue;
-        const OpDesc& o = e->ops[k].d;
-        if (o.src_buf == hb || o.res_buf == (int)hb) ok = false;
-        for (uint32_t s = 0; s < o.nseg; ++s)
-          if (o.seg[s].dst_buf == hb) ok = false;
-      }
-    }
+    for (uint32_t hb : {h0, h1})
+      ok = ok && e->bufs[hb].d.dtype == kBufF16Nhwc && hb != a.src_buf && !(e->bufs[hb].d.flags & (kBufInput | kBufOutput)) &&
+           !touched_outside(e, whole((int)hb), i, i + 2);
     if (!ok) continue;
-    std::vector<C3k2Conv> convs;
-    for (size_t k = i; k <= i + 2; ++k) {
-      const OpDesc& o = e->ops[k].d;
-      C3k2Conv cv;
-      memset(&cv, 0, sizeof cv);
-      for (uint32_t s = 0; s < 2; ++s) {
-        cv.w[s] = reinterpret_cast<const unsigned char*>(blob->data() + o.seg[s].w_off);
-        cv.bias[s] = reinterpret_cast<const float*>(blob->data() + o.seg[s].b_off);
-        cv.n[s] = (int)o.seg[s].n_pad;
-      }
-      cv.K = (int)(o.ksize * o.ksize * o.cin);
-      convs.push_back(cv);
-    }
+    const C3k2Conv convs[3] = {pack_conv(e, *blob, a, true, false), pack_conv(e, *blob, b, true, false), pack_conv(e, *blob, c, true, false)};
     std::vector<unsigned char> stream;
     std::vector<float> bias;
-    block_pack(convs.data(), 3, &stream, &bias);
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t so = blob->size();
-    blob->insert(blob->end(), stream.begin(), stream.end());
-    blob->resize((blob->size() + 255) & ~(size_t)255);
-    const uint64_t bo = blob->size();
-    blob->insert(blob->end(), reinterpret_cast<const char*>(bias.data()), reinterpret_cast<const char*>(bias.data() + bias.size()));
+    block_pack(convs, 3, &stream, &bias);
     PlannedOp& head = e->ops[i];
+    append_stream(blob, stream, bias, &head);
     head.fuse_role = 1;
     head.fuse_kind = 2;
     head.group_last = (int)i + 2;
     head.hid = (int)C;
-    head.stream_off = so;
-    head.fbias_off = bo;
     e->ops[i + 1].fuse_role = e->ops[i + 2].fuse_role = 2;
     ++e->n_groups;
     i += 2;
@@ -1273,7 +1195,7 @@ int fill_post_params(unina_engine* e, PostParams* pp, float conf, float iou, flo
   pp->cand = e->d_cand;
   pp->block_count = e->d_block_count;
   pp->ticket = e->d_ticket;
-  pp->mode = e->post_split ? e->post_mode : 0;
+  pp->mode = e->post_split ? 2 : 0;
   if (pp->mode) post_bind_workspace(pp, e->d_post_ws);
   if (pp->mode == 2) {
     for (int h = 0; h < 3 && fold; ++h) {
@@ -1304,31 +1226,24 @@ int fill_post_params(unina_engine* e, PostParams* pp, float conf, float iou, flo
   return UNINA_OK;
 }
 
-}  // namespace
+// Bytes of a conv slice's weight blocks in the blob (fp32 and split-fp16 engines: 4 per weight, int8: 1, fp16: 2).
+uint64_t weight_bytes(const unina_engine* e, const OpDesc& d, const SegDesc& sd) {
+  const uint32_t sdt = e->bufs[d.src_buf].d.dtype;
+  return (uint64_t)sd.n_pad * d.ksize * d.ksize * d.cin * ((sdt == kBufF32Nhwc || sdt == kBufS16Nhwc) ? 4 : (sdt == kBufI8Nhwc ? 1 : 2));
+}
 
-extern "C" {
-
-#ifndef UNINA_SOURCE_HASH
-#define UNINA_SOURCE_HASH "unhashed"
-#endif
-// "... src:<hash of the sources this binary was built from>" (build.py source_hash(); tests compare it with the tree's)
-const char* unina_version(void) { return "unina_mi355 0.3.0 gfx950 src:" UNINA_SOURCE_HASH; }
-
-const char* unina_last_error(const unina_engine_t* e) { return e ? e->err.c_str() : g_load_error.c_str(); }
-
-int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
-  if (!path || !out) return fail(nullptr, UNINA_ERR_ARG, "unina_load_engine: null argument");
-  *out = nullptr;
+// Host side of loading an engine file: reads and validates it, appends the lane-order weight twins, the stem transpose and
+// the fused groups' streams to `blob` and sets e->fuse. No device is touched (unina_debug_fusable_groups runs exactly this).
+// On error: the code, with the message in g_load_error.
+int load_host(const char* path, unina_engine* e, std::vector<char>* blob_out) {
   FILE* f = fopen(path, "rb");
   if (!f) return fail(nullptr, UNINA_ERR_IO, "cannot open %s", path);
-  unina_engine* e = new unina_engine();
-  e->device = device_id;
   auto bail = [&](int code, const char* msg) {
     g_load_error = msg;
     if (f) fclose(f);
-    unina_unload_engine(e);
     return code;
   };
+  std::vector<char>& blob = *blob_out;
   if (fread(&e->h, sizeof e->h, 1, f) != 1) return bail(UNINA_ERR_FORMAT, "truncated header");
   if (memcmp(e->h.magic, kMagic, 8)) return bail(UNINA_ERR_FORMAT, "bad magic (not a UNINAENG file)");
   if (e->h.version != kVersion) return bail(UNINA_ERR_FORMAT, "unsupported engine file version");
@@ -1342,11 +1257,10 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
   e->ops.resize(e->h.n_ops);
   for (auto& o : e->ops)
     if (fread(&o.d, sizeof o.d, 1, f) != 1) return bail(UNINA_ERR_FORMAT, "truncated op table");
-  std::vector<char> blob(e->h.blob_bytes);
+  blob.resize(e->h.blob_bytes);
   if (e->h.blob_bytes && fread(blob.data(), 1, blob.size(), f) != blob.size()) return bail(UNINA_ERR_FORMAT, "truncated weight blob");
   fclose(f);
   f = nullptr;
-  const size_t file_blob_bytes = blob.size();
 
   // table validation (indices, offsets) before anything touches the GPU
   for (auto& o : e->ops) {
@@ -1357,8 +1271,7 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
       const SegDesc& sd = o.d.seg[s];
       if (sd.dst_buf >= e->h.n_buffers) return bail(UNINA_ERR_FORMAT, "op table: bad destination buffer");
       if (o.d.kind == kOpConv) {
-        const uint32_t sdt = e->bufs[o.d.src_buf].d.dtype;
-        const uint64_t wbytes = (uint64_t)sd.n_pad * o.d.ksize * o.d.ksize * o.d.cin * ((sdt == kBufF32Nhwc || sdt == kBufS16Nhwc) ? 4 : (sdt == kBufI8Nhwc ? 1 : 2));
+        const uint64_t wbytes = weight_bytes(e, o.d, sd);
         if (sd.m_off && (sd.m_off + (uint64_t)sd.n_pad * 4 > e->h.blob_bytes || sd.m_off % 16)) return bail(UNINA_ERR_FORMAT, "op table: multiplier offset outside blob");
         if (sd.w_off + wbytes > e->h.blob_bytes || sd.b_off + (uint64_t)sd.n_pad * 4 > e->h.blob_bytes || sd.w_off % 16 || sd.b_off % 16)
           return bail(UNINA_ERR_FORMAT, "op table: weight offset outside blob");
@@ -1393,10 +1306,9 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
   // what the LDS-DMA kernels copy into LDS
   for (auto& op : e->ops) {
     if (op.d.kind != kOpConv) continue;
-    const uint32_t sdt = e->bufs[op.d.src_buf].d.dtype;
     for (uint32_t s = 0; s < op.d.nseg; ++s) {
       const SegDesc& sd = op.d.seg[s];
-      const uint64_t wbytes = (uint64_t)sd.n_pad * op.d.ksize * op.d.ksize * op.d.cin * ((sdt == kBufF32Nhwc || sdt == kBufS16Nhwc) ? 4 : (sdt == kBufI8Nhwc ? 1 : 2));
+      const uint64_t wbytes = weight_bytes(e, op.d, sd);
       if (wbytes == 0 || wbytes % 1024) continue;
       blob.resize((blob.size() + 255) & ~(size_t)255);
       op.w_lane_off[s] = blob.size();
@@ -1417,9 +1329,7 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
     const float* w = reinterpret_cast<const float*>(blob.data() + sd.w_off);
     for (uint32_t c = 0; c < co; ++c)
       for (int k = 0; k < 27; ++k) wt[(size_t)k * co + c] = w[(size_t)c * 27 + k];
-    blob.resize((blob.size() + 255) & ~(size_t)255);
-    op.wt_off = blob.size();
-    blob.insert(blob.end(), reinterpret_cast<const char*>(wt.data()), reinterpret_cast<const char*>(wt.data() + wt.size()));
+    op.wt_off = append_aligned(&blob, wt.data(), wt.size() * sizeof(float));
   }
   // fusable groups: their packed weight streams are appended to the blob before upload. The matchers accept all-fp16
   // groups (in an INT8 engine: the carved-out P2 head, train.py:779) and, for C3k2 blocks, all-int8 groups
@@ -1430,16 +1340,16 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
     const char* fz = getenv("UNINA_FUSE");
     e->fuse = e->n_groups > 0 && !(fz && fz[0] == '0');
   }
-  (void)file_blob_bytes;
+  return UNINA_OK;
+}
 
-  // ---- device side ----
+// Device side of loading: uploads the blob, allocates the activation arena and the post-process workspace, initialises
+// the kernel families. On error: the code, with the message in g_load_error.
+int load_device(unina_engine* e, const std::vector<char>& blob) {
   hipError_t err;
-#define LOADCHK(call)                                                            \
-  if ((err = (call)) != hipSuccess) {                                            \
-    std::string m = std::string(#call) + ": " + hipGetErrorString(err);          \
-    return bail(UNINA_ERR_HIP, m.c_str());                                       \
-  }
-  LOADCHK(hipSetDevice(device_id));
+#define LOADCHK(call) \
+  if ((err = (call)) != hipSuccess) return fail(nullptr, UNINA_ERR_HIP, "%s: %s", #call, hipGetErrorString(err));
+  LOADCHK(hipSetDevice(e->device));
   LOADCHK(hipMalloc(&e->d_blob, blob.size() ? blob.size() : 16));
   LOADCHK(hipMemcpy(e->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
   size_t arena = 0;
@@ -1469,7 +1379,7 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
     gh[i] = (int)e->bufs[e->out_buf[2 * i]].d.h;
   }
   e->post_blocks = post_num_blocks(gw, gh);
-  if (e->post_blocks > kPostBlock) return bail(UNINA_ERR_UNSUPPORTED, "input too large for the post-process workspace");
+  if (e->post_blocks > kPostBlock) return fail(nullptr, UNINA_ERR_UNSUPPORTED, "input too large for the post-process workspace");
   {  // candidate segments: post_blocks x 1024 records (modes 0 / 1) or up to 1024 workgroups x 256 (mode 2)
     const size_t recs = (size_t)e->post_blocks * kPostBlock > (size_t)1024 * kPost2Block ? (size_t)e->post_blocks * kPostBlock : (size_t)1024 * kPost2Block;
     LOADCHK(hipMalloc(&e->d_cand, sizeof(GpuDetection) * recs));
@@ -1490,6 +1400,32 @@ int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
   LOADCHK(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
   LOADCHK(hipDeviceSynchronize());
 #undef LOADCHK
+  return UNINA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+#ifndef UNINA_SOURCE_HASH
+#define UNINA_SOURCE_HASH "unhashed"
+#endif
+// "... src:<hash of the sources this binary was built from>" (build.py source_hash(); tests compare it with the tree's)
+const char* unina_version(void) { return "unina_mi355 0.3.0 gfx950 src:" UNINA_SOURCE_HASH; }
+
+const char* unina_last_error(const unina_engine_t* e) { return e ? e->err.c_str() : g_load_error.c_str(); }
+
+int unina_load_engine(const char* path, int device_id, unina_engine_t** out) {
+  if (!path || !out) return fail(nullptr, UNINA_ERR_ARG, "unina_load_engine: null argument");
+  *out = nullptr;
+  unina_engine* e = new unina_engine();
+  e->device = device_id;
+  std::vector<char> blob;
+  int rc = load_host(path, e, &blob);
+  if (rc == UNINA_OK) rc = load_device(e, blob);
+  if (rc != UNINA_OK) {
+    unina_unload_engine(e);
+    return rc;
+  }
   const char* ng = getenv("UNINA_NO_GRAPH");
   e->use_graph = !(ng && ng[0] == '1');
   if (const char* fg = getenv("UNINA_FULL_GRAPH")) e->full_graph = fg[0] != '0';
@@ -1856,36 +1792,13 @@ int unina_get_op_info(const unina_engine_t* ce, int index, unina_op_info* info) 
   return UNINA_OK;
 }
 
-// Load-time analysis only (no device is touched): how many C3k2 blocks of the engine file would run fused.
+// Load-time analysis alone (no device is touched): the loader's host side, checks and matchers, on the engine file.
 int unina_debug_fusable_groups(const char* path) {
   if (!path) return -UNINA_ERR_ARG;
-  FILE* f = fopen(path, "rb");
-  if (!f) return -UNINA_ERR_IO;
   unina_engine e;
-  bool ok = fread(&e.h, sizeof e.h, 1, f) == 1 && !memcmp(e.h.magic, kMagic, 8) && e.h.version == kVersion &&
-            e.h.n_buffers && e.h.n_buffers <= 4096 && e.h.n_ops && e.h.n_ops <= 4096;
   std::vector<char> blob;
-  if (ok) {
-    e.bufs.resize(e.h.n_buffers);
-    e.ops.resize(e.h.n_ops);
-    for (auto& b : e.bufs) ok = ok && fread(&b.d, sizeof b.d, 1, f) == 1;
-    for (auto& o : e.ops) ok = ok && fread(&o.d, sizeof o.d, 1, f) == 1;
-    blob.resize(e.h.blob_bytes);
-    ok = ok && (!e.h.blob_bytes || fread(blob.data(), 1, blob.size(), f) == blob.size());
-  }
-  fclose(f);
-  if (!ok) return -UNINA_ERR_FORMAT;
-  for (auto& o : e.ops) {
-    if (o.d.src_buf >= e.h.n_buffers || o.d.nseg < 1 || o.d.nseg > 2 || o.d.res_buf >= (int)e.h.n_buffers) return -UNINA_ERR_FORMAT;
-    for (uint32_t s = 0; s < o.d.nseg; ++s)
-      if (o.d.seg[s].dst_buf >= e.h.n_buffers || o.d.seg[s].w_off > blob.size() || o.d.seg[s].b_off > blob.size()) return -UNINA_ERR_FORMAT;
-  }
-  if (e.h.precision == kFp16 || e.h.precision == kInt8) {
-    find_c3k2_groups(&e, &blob);
-    find_head_groups(&e, &blob);
-    find_pair_groups(&e, &blob);
-  }
-  return e.n_groups;
+  const int rc = load_host(path, &e, &blob);
+  return rc != UNINA_OK ? -rc : e.n_groups;
 }
 
 int unina_set_fusion(unina_engine_t* e, int enable) {
