@@ -49,20 +49,27 @@ BLOCK_DUAL_WS(block_dual_c3k2_128x384_head64ws, 128, 4, 4, 1, 384, 8, 16, 0)
 BLOCK_DUAL_WS(block_dual_c3k2i8_128x384_head64ws, 128, 4, 4, 1, 384, 8, 8, 0, EltI8)
 #undef BLOCK_DUAL_WS
 
-hipError_t block_dual_init() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(block_dual_c3k2_128x384_head64),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return e;
-  for (const void* f : {reinterpret_cast<const void*>(block_dual_s2c3k2_128x384_head64),
-                        reinterpret_cast<const void*>(block_dual_s2c3k2_128x384_head64ws), reinterpret_cast<const void*>(block_dual_s2c3k2i8_128x384_head64ws),
-                        reinterpret_cast<const void*>(block_dual_c3k2_128x384_head64ws), reinterpret_cast<const void*>(block_dual_c3k2i8_128x384_head64ws),
-                        reinterpret_cast<const void*>(block_dual_s2c3k2i8_128x384_head64)}) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(block_dual_c3k2i8_128x384_head64),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
+namespace {
+struct BlockDual {
+  int dtype;   // of the block (the head is fp16)
+  bool s2;     // the block runs its 3x3/s2 pre-conv (cpre = 128) first
+  bool ws;     // the head is the row-streaming class (head_ws_body), otherwise the 8x16 tile class
+  const char* name;
+  void (*fn)(const C3k2Params, const HeadParams, int);
+};
+const BlockDual kBlockDuals[] = {
+    {kF16, false, false, "block_dual_c3k2_128x384_head64<c3k2 128,4x4,1,384 | head 64,8x16>", block_dual_c3k2_128x384_head64},
+    {kI8, false, false, "block_dual_c3k2i8_128x384_head64<c3k2 i8,128,4x4,1,384 | head 64,8x16>", block_dual_c3k2i8_128x384_head64},
+    {kF16, true, false, "block_dual_s2c3k2_128x384_head64<s2conv 128 + c3k2 128,4x4,1,384 | head 64,8x16>", block_dual_s2c3k2_128x384_head64},
+    {kI8, true, false, "block_dual_s2c3k2i8_128x384_head64<s2conv 128 + c3k2 i8,128,4x4,1,384 | head 64,8x16>", block_dual_s2c3k2i8_128x384_head64},
+    {kF16, false, true, "block_dual_c3k2_128x384_head64ws<c3k2 128,4x4,1,384 | head_ws 64,13x14>", block_dual_c3k2_128x384_head64ws},
+    {kI8, false, true, "block_dual_c3k2i8_128x384_head64ws<c3k2 i8,128,4x4,1,384 | head_ws 64,13x14>", block_dual_c3k2i8_128x384_head64ws},
+    {kF16, true, true, "block_dual_s2c3k2_128x384_head64ws<s2conv 128 + c3k2 128,4x4,1,384 | head_ws 64,13x14>", block_dual_s2c3k2_128x384_head64ws},
+    {kI8, true, true, "block_dual_s2c3k2i8_128x384_head64ws<s2conv 128 + c3k2 i8,128,4x4,1,384 | head_ws 64,13x14>", block_dual_s2c3k2i8_128x384_head64ws},
+};
+}  // namespace
+
+hipError_t block_dual_init() { return set_lds_limits(kBlockDuals); }
 
 bool block_dual_match(const C3k2Params& pc, const HeadParams& ph) {
   if (head_tile_is(ph, kHeadWsTH, 14))   // the row-streaming head: next to either block form, fp16 or int8
@@ -73,36 +80,17 @@ bool block_dual_match(const C3k2Params& pc, const HeadParams& ph) {
          c3k2_tile_is(pc, 4, 4) && head_tile_is(ph, 8, 16);
 }
 
-const char* block_dual_name(int dtype, int cpre) {
-  if (head_is_ws(64)) {
-    if (cpre) return dtype == kI8 ? "block_dual_s2c3k2i8_128x384_head64ws<s2conv 128 + c3k2 i8,128,4x4,1,384 | head_ws 64,13x14>"
-                                  : "block_dual_s2c3k2_128x384_head64ws<s2conv 128 + c3k2 128,4x4,1,384 | head_ws 64,13x14>";
-    return dtype == kI8 ? "block_dual_c3k2i8_128x384_head64ws<c3k2 i8,128,4x4,1,384 | head_ws 64,13x14>"
-                        : "block_dual_c3k2_128x384_head64ws<c3k2 128,4x4,1,384 | head_ws 64,13x14>";
+hipError_t block_dual_desc(const C3k2Params& pc, const HeadParams& ph, LaunchDesc* d, int* split) {
+  const int dtype = pc.dtype == kI8 ? kI8 : kF16;
+  const bool ws = head_tile_is(ph, kHeadWsTH, 14);
+  for (const BlockDual& k : kBlockDuals) {
+    if (k.dtype != dtype || k.s2 != (pc.cpre != 0) || k.ws != ws) continue;
+    *split = pc.tiles_x * pc.tiles_y;
+    const int smem = pc.smem_bytes > ph.smem_bytes ? pc.smem_bytes : ph.smem_bytes;
+    *d = {reinterpret_cast<const void*>(k.fn), dim3(*split + ph.tiles_x * ph.tiles_y), dim3(512), (unsigned)smem, k.name};
+    return hipSuccess;
   }
-  if (cpre) return dtype == kI8 ? "block_dual_s2c3k2i8_128x384_head64<s2conv 128 + c3k2 i8,128,4x4,1,384 | head 64,8x16>"
-                                : "block_dual_s2c3k2_128x384_head64<s2conv 128 + c3k2 128,4x4,1,384 | head 64,8x16>";
-  return dtype == kI8 ? "block_dual_c3k2i8_128x384_head64<c3k2 i8,128,4x4,1,384 | head 64,8x16>"
-                      : "block_dual_c3k2_128x384_head64<c3k2 128,4x4,1,384 | head 64,8x16>";
-}
-
-hipError_t block_dual_launch(const C3k2Params& pc, const HeadParams& ph, hipStream_t stream, int* grid_out) {
-  const int nc = pc.tiles_x * pc.tiles_y, nh = ph.tiles_x * ph.tiles_y;
-  const int smem = pc.smem_bytes > ph.smem_bytes ? pc.smem_bytes : ph.smem_bytes;
-  if (grid_out) *grid_out = nc + nh;
-  if (head_tile_is(ph, kHeadWsTH, 14)) {
-    auto fn = pc.cpre ? (pc.dtype == kI8 ? block_dual_s2c3k2i8_128x384_head64ws : block_dual_s2c3k2_128x384_head64ws)
-                      : (pc.dtype == kI8 ? block_dual_c3k2i8_128x384_head64ws : block_dual_c3k2_128x384_head64ws);
-    hipLaunchKernelGGL(fn, dim3(nc + nh, 1, 1), dim3(512, 1, 1), smem, stream, pc, ph, nc);
-  } else if (pc.cpre && pc.dtype == kI8)
-    hipLaunchKernelGGL(block_dual_s2c3k2i8_128x384_head64, dim3(nc + nh, 1, 1), dim3(512, 1, 1), smem, stream, pc, ph, nc);
-  else if (pc.cpre)
-    hipLaunchKernelGGL(block_dual_s2c3k2_128x384_head64, dim3(nc + nh, 1, 1), dim3(512, 1, 1), smem, stream, pc, ph, nc);
-  else if (pc.dtype == kI8)
-    hipLaunchKernelGGL(block_dual_c3k2i8_128x384_head64, dim3(nc + nh, 1, 1), dim3(512, 1, 1), smem, stream, pc, ph, nc);
-  else
-    hipLaunchKernelGGL(block_dual_c3k2_128x384_head64, dim3(nc + nh, 1, 1), dim3(512, 1, 1), smem, stream, pc, ph, nc);
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 }  // namespace unina

@@ -58,6 +58,7 @@ struct Class {
   void (*fn)(const C3k2Params);
   int cpre;   // 0, or the pre-conv's input channels
   int cx;     // channels the pre-conv produces (0 without one)
+  bool stamped = false;   // debug twin with per-step stamps (C3k2Params::stamps)
 };
 #define C3K2(H_, TH, TW, NB, CIN, NW, D) \
   {kF16, H_, NB, CIN, 0, TH, TW, NW, "c3k2_fused<" #H_ "," #TH "x" #TW "," #NB "," #CIN "," #NW "w>", c3k2_fused_kernel<H_, TH, TW, NB, CIN, NW, D, 0>, 0, 0}
@@ -124,6 +125,9 @@ const Class kClasses[] = {
     C3K2X(128, 4, 4, 2, 256, 8, 8, 0, ""),          // backbone.stage3_c3k2
     C3K2X(128, 4, 4, 2, 256, 8, 8, 2, ",+1x1"),     // backbone.stage3_c3k2 + backbone.sppf.cv1
     C3K2X(128, 4, 4, 1, 384, 8, 8, 0, ""),          // neck.pan_c3k2_2
+    // debug twins of the 40^2 blocks (unina_debug_block_stamps)
+    {kF16, 128, 2, 256, 2, 4, 4, 8, "c3k2_fused<128,4x4,2,256,8w,+1x1,stamped>", c3k2_fused_stage3_stamped, 0, 0, true},
+    {kF16, 128, 1, 384, 0, 4, 4, 8, "c3k2_fused<128,4x4,1,384,8w,s2conv 128,stamped>", c3k2_fused_pan2_stamped, 128, 128, true},
 };
 #undef C3K2
 #undef C3K2T
@@ -135,36 +139,17 @@ const Class kClasses[] = {
 #undef C3K2IP
 #undef C3K2X
 #undef C3K2XS
-const Class* find_class(int hid, int nb, int cin, int tail, int dtype, int cpre = 0, int cx = 0) {
+const Class* find_class(int hid, int nb, int cin, int tail, int dtype, int cpre = 0, int cx = 0, bool stamped = false) {
   for (const Class& c : kClasses)
-    if (c.dtype == dtype && c.hid == hid && c.nb == nb && c.cin == cin && c.tail == tail && c.cpre == cpre && (!cpre || c.cx == cx)) return &c;
+    if (c.dtype == dtype && c.hid == hid && c.nb == nb && c.cin == cin && c.tail == tail && c.cpre == cpre && (!cpre || c.cx == cx) &&
+        c.stamped == stamped) return &c;
   return nullptr;
 }
-constexpr int kMaxLds = 160 * 1024;
 int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-hipError_t c3k2_launch_stamped(const C3k2Params& p, hipStream_t stream) {
-  void (*fn)(const C3k2Params) = nullptr;
-  if (p.dtype == kF16 && p.hid == 128 && p.nb == 2 && p.Cin == 256 && p.tail == 2 && !p.cpre) fn = c3k2_fused_stage3_stamped;
-  if (p.dtype == kF16 && p.hid == 128 && p.nb == 1 && p.Cin == 384 && p.tail == 0 && p.cpre == 128 && p.cx == 128) fn = c3k2_fused_pan2_stamped;
-  if (!fn) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fn, dim3(p.tiles_x * p.tiles_y, 1, 1), dim3(512, 1, 1), p.smem_bytes, stream, p);
-  return hipGetLastError();
-}
-
-hipError_t c3k2_init() {
-  for (const void* f : {reinterpret_cast<const void*>(c3k2_fused_stage3_stamped), reinterpret_cast<const void*>(c3k2_fused_pan2_stamped)}) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-    if (e != hipSuccess) return e;
-  }
-  for (const Class& c : kClasses) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+hipError_t c3k2_init() { return set_lds_limits(kClasses); }
 
 bool c3k2_supported(int hid, int nb, int cin, int tail, int dtype, int cpre, int cx) {
   C3k2Params p;
@@ -281,26 +266,16 @@ bool c3k2_pack(int hid, int nb, int cin, int tail, const C3k2Conv* convs, std::v
   return true;
 }
 
-hipError_t c3k2_launch(const C3k2Params& p, hipStream_t stream) {
-  const Class* c = find_class(p.hid, p.nb, p.Cin, p.tail, p.dtype, p.cpre, p.cx);
+hipError_t c3k2_desc(const C3k2Params& p, LaunchDesc* d) {
+  const Class* c = find_class(p.hid, p.nb, p.Cin, p.tail, p.dtype, p.cpre, p.cx, p.stamps != nullptr);
   if (!c) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(c->fn, dim3(p.tiles_x * p.tiles_y, 1, 1), dim3(c->nw * 64, 1, 1), p.smem_bytes, stream, p);
-  return hipGetLastError();
+  *d = {reinterpret_cast<const void*>(c->fn), dim3(p.tiles_x * p.tiles_y), dim3(c->nw * 64), (unsigned)p.smem_bytes, c->name};
+  return hipSuccess;
 }
 
 bool c3k2_tile_is(const C3k2Params& p, int th, int tw) {
   const Class* c = find_class(p.hid, p.nb, p.Cin, p.tail, p.dtype, p.cpre, p.cx);
   return c && c->th == th && c->tw == tw;
-}
-
-const char* c3k2_kernel_name(int hid, int nb, int cin, int tail, int dtype, int cpre, int cx) {
-  const Class* c = find_class(hid, nb, cin, tail, dtype, cpre, cx);
-  return c ? c->name : "c3k2_fused<?>";
-}
-
-int c3k2_block_threads(int hid, int nb, int cin, int tail, int dtype, int cpre, int cx) {
-  const Class* c = find_class(hid, nb, cin, tail, dtype, cpre, cx);
-  return c ? c->nw * 64 : 0;
 }
 
 }  // namespace unina

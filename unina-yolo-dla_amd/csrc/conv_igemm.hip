@@ -1392,34 +1392,54 @@ inline size_t smem_for(const ConvParams& p, const CfgInfo& c) {
   const size_t patch = (size_t)(c.th + 2) * (c.tw + 2) * p.Cin * esize(p);
   return max_sz(c.smem + ((patch + 1023) & ~(size_t)1023), stage_bytes(c.bm, c.bn));
 }
-constexpr size_t kMaxLds = 160 * 1024;
-
 int n_tiles(const ConvParams& p, int bn) {
   int t = 0;
   for (int s = 0; s < p.nseg; ++s) t += (((p.seg[s].n_count + 15) & ~15) + bn - 1) / bn;
   return t;
 }
 
+// (M tiles, N tiles) of `p` under configuration `cfg`; the launch is 1-D (see tile_of_block)
+dim3 conv_grid(const ConvParams& p, int cfg) {
+  const CfgInfo& c = kCfg[p.dtype][cfg];
+  if (c.th) return dim3(((p.Ho + c.th - 1) / c.th) * ((p.Wo + c.tw - 1) / c.tw), n_tiles(p, c.bn), 1);
+  return dim3((p.M + c.bm - 1) / c.bm, n_tiles(p, c.bn), 1);
+}
+
+// ---- dual launches (conv_dual_head3x3 / conv_dual_head1x1) ----
+struct DualKind {
+  int cfg_a, cfg_b, threads;
+  const char* name;
+  void (*fn)(const ConvParams, const ConvParams, int);
+  bool b_first;   // the weights-stationary pairs put conv B's workgroups first
+  int twin;       // the kind of the stamped debug twin (-1: none)
+};
+enum { kDualRegq = 0, kDual1x1, kDualRegqI8, kDualWs, kDualWsI8, kDualRegqS16, kDualWsS16, kDualWsSmall, kDualWsStamped, kDualWsS16Stamped,
+       kDualKinds };
+#define WS_PAIR "conv_dual_head3x3_ws<ws 16x16,64,128/2 | ws 8x16,64,256/4>"
+#define WS_S16_PAIR "conv_dual_head3x3_ws_s16<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>"
+const DualKind kDual[kDualKinds] = {
+    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3<regq 8x16,64,128 | regq 8x8,64,256>", conv_dual_head3x3, false, -1},
+    {kCfg128x16k64, kCfg128x16k64, 256, "conv_dual_head1x1<glds 128,16,64 x2>", conv_dual_head1x1, false, -1},
+    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_i8<regq i8,8x16,64,128 | regq i8,8x8,64,256>", conv_dual_head3x3_i8, false, -1},
+    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, WS_PAIR, conv_dual_head3x3_ws, true, kDualWsStamped},
+    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws_i8<ws i8,16x16,64,128/2 | ws i8,8x16,64,256/4>", conv_dual_head3x3_ws_i8, true, -1},
+    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_s16<regq s16,8x16,64,128 | regq s16,8x8,64,256>", conv_dual_head3x3_s16, false, -1},
+    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, WS_S16_PAIR, conv_dual_head3x3_ws_s16, true, kDualWsS16Stamped},
+    {kCfgWs8x16n64c128, kCfgWs4x16n64c256, 256, "conv_dual_head3x3_ws_small<ws 8x16,64,128/2 | ws 4x16,64,256/4, 2 per CU>", conv_dual_head3x3_ws_small, true, -1},
+    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, WS_PAIR, conv_dual_head3x3_ws_stamped, true, -1},
+    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, WS_S16_PAIR, conv_dual_head3x3_ws_s16_stamped, true, -1},
+};
+#undef WS_PAIR
+#undef WS_S16_PAIR
+
 }  // namespace
 
 hipError_t conv_init() {
-  for (const void* f : {reinterpret_cast<const void*>(conv_dual_head3x3), reinterpret_cast<const void*>(conv_dual_head1x1),
-                        reinterpret_cast<const void*>(conv_dual_head3x3_i8), reinterpret_cast<const void*>(conv_dual_head3x3_s16),
-                        reinterpret_cast<const void*>(conv_dual_head3x3_ws_s16), reinterpret_cast<const void*>(conv_dual_head3x3_ws_s16_stamped),
-                        reinterpret_cast<const void*>(conv_dual_head3x3_ws), reinterpret_cast<const void*>(conv_dual_head3x3_ws_stamped),
-                        reinterpret_cast<const void*>(conv_dual_head3x3_ws_i8),
-                        }) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+  for (const auto& row : kCfg) {
+    const hipError_t e = set_lds_limits(row);
     if (e != hipSuccess) return e;
   }
-  for (int d = 0; d < kNumDTypes; ++d)
-    for (int c = 0; c < kCfgCount; ++c) {
-      if (!kCfg[d][c].fn) continue;
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kCfg[d][c].fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(kCfg[d][c].th ? kMaxLds : kCfg[d][c].smem));
-      if (e != hipSuccess) return e;
-    }
-  return hipSuccess;
+  return set_lds_limits(kDual);
 }
 
 bool conv_config_valid(const ConvParams& p, int cfg) {
@@ -1453,25 +1473,14 @@ bool conv_config_valid(const ConvParams& p, int cfg) {
   return c.bn <= min_npad || (c.bn == 16);
 }
 
-ConvLaunch conv_plan_with(const ConvParams& p, int cfg) {
-  const CfgInfo& c = kCfg[p.dtype][cfg];
-  ConvLaunch l;
-  l.cfg = (ConvConfig)cfg;
-  if (c.th) l.grid = dim3(((p.Ho + c.th - 1) / c.th) * ((p.Wo + c.tw - 1) / c.tw), n_tiles(p, c.bn), 1);
-  else l.grid = dim3((p.M + c.bm - 1) / c.bm, n_tiles(p, c.bn), 1);
-  l.block = dim3(c.nthreads, 1, 1);
-  l.kernel_name = c.name;
-  return l;
-}
-
 // Heuristic: the widest tile that still yields >= ~1.5 workgroups per CU (256 CUs), K-step 64 when Cin allows.
-ConvLaunch conv_plan(const ConvParams& p) {
+int conv_plan(const ConvParams& p) {
   const int override_cfg = p.force_cfg;
-  if (override_cfg >= 0 && conv_config_valid(p, override_cfg)) return conv_plan_with(p, override_cfg);
+  if (override_cfg >= 0 && conv_config_valid(p, override_cfg)) return override_cfg;
   if (p.dtype == kS16 && p.ksize == 3) {   // STRICT engines: 3x3 convs on the patch-resident kernels even without autotuning
     for (int c : {(int)kCfgWsS8x16n64c64, (int)kCfgWsS8x16n64c128, (int)kCfgWsS8x16n64c256, (int)kCfgRegqS2_8x16n64c32, (int)kCfgRegqS2_8x8n64c64,
                   (int)kCfgRegqS2_4x8n64c128, (int)kCfgRegq8x16n64c64, (int)kCfgRegq8x16n64c128, (int)kCfgRegq8x8n64c256})
-      if (conv_config_valid(p, c)) return conv_plan_with(p, c);
+      if (conv_config_valid(p, c)) return c;
   }
   const bool k64 = (p.Cin % (2 * block_k(p.dtype))) == 0;
   int min_npad = 1 << 30;
@@ -1491,23 +1500,23 @@ ConvLaunch conv_plan(const ConvParams& p) {
     else cfg = kCfg32x64k64;
   }
   if (!conv_config_valid(p, cfg)) cfg = k64 ? kCfg64x64k64 : kCfg64x64k32;
-  return conv_plan_with(p, cfg);
+  return cfg;
 }
 
 namespace {
 // launch-time fields of a ConvParams for configuration `cfg` (tile counts, division magics, slice -> tile ranges)
-dim3 conv_prepare(ConvParams& p, int cfg) {
+int conv_prepare(ConvParams& p, int cfg) {
   const CfgInfo& c = kCfg[p.dtype][cfg];
-  const ConvLaunch l = conv_plan_with(p, cfg);
-  p.grid_m = (int)l.grid.x;
-  p.gm_magic = div_magic(l.grid.x);
-  p.grid_n = (int)l.grid.y;
-  p.gn_magic = div_magic(l.grid.y);
+  const dim3 g = conv_grid(p, cfg);
+  p.grid_m = (int)g.x;
+  p.gm_magic = div_magic(g.x);
+  p.grid_n = (int)g.y;
+  p.gn_magic = div_magic(g.y);
   {  // which operand should each XCD's L2 see only its share of? The other one is fetched by all 8 XCDs.
     const double in_bytes = (double)esize(p) * p.H * p.W * p.Cin * ((p.nseg > 1 && p.seg[0].src_coff != p.seg[1].src_coff) ? p.nseg : 1);
     double w_bytes = 0;
     for (int s = 0; s < p.nseg; ++s) w_bytes += (double)esize(p) * ((p.seg[s].n_count + 15) & ~15) * p.ksize * p.ksize * p.Cin;
-    p.xcd_m_major = (l.grid.x >= 8 && in_bytes + 8.0 * w_bytes < 8.0 * in_bytes + w_bytes) ? 1 : 0;
+    p.xcd_m_major = (g.x >= 8 && in_bytes + 8.0 * w_bytes < 8.0 * in_bytes + w_bytes) ? 1 : 0;
   }
   p.wo_magic = div_magic((unsigned)p.Wo);
   p.spt_magic = div_magic((unsigned)(p.Cin / kstep_of(p, c)));
@@ -1517,37 +1526,17 @@ dim3 conv_prepare(ConvParams& p, int cfg) {
     p.seg[s].tile0 = t;
     t += (((p.seg[s].n_count + 15) & ~15) + c.bn - 1) / c.bn;
   }
-  return l.grid;
+  return (int)(g.x * g.y);
 }
 }  // namespace
 
-hipError_t conv_launch(const ConvParams& pin, const ConvLaunch& l, hipStream_t stream) {
-  ConvParams p = pin;
-  const CfgInfo& c = kCfg[p.dtype][l.cfg];
-  const dim3 g = conv_prepare(p, l.cfg);
-  hipLaunchKernelGGL(c.fn, dim3(g.x * g.y, 1, 1), l.block, smem_for(p, c), stream, p);  // 1-D: see tile_of_block
-  return hipGetLastError();
+hipError_t conv_desc(ConvParams& p, int cfg, LaunchDesc* d) {
+  if (cfg < 0 || cfg >= kCfgCount || !kCfg[p.dtype][cfg].fn) return hipErrorInvalidValue;
+  const CfgInfo& c = kCfg[p.dtype][cfg];
+  const int n = conv_prepare(p, cfg);
+  *d = {reinterpret_cast<const void*>(c.fn), dim3(n), dim3(c.nthreads), (unsigned)smem_for(p, c), c.name};
+  return hipSuccess;
 }
-
-// ---- dual launches (conv_dual_head3x3 / conv_dual_head1x1) ----
-namespace {
-struct DualKind {
-  int cfg_a, cfg_b, threads;
-  const char* name;
-  void (*fn)(const ConvParams, const ConvParams, int);
-};
-enum { kDualRegq = 0, kDual1x1, kDualRegqI8, kDualWs, kDualWsI8, kDualRegqS16, kDualWsS16, kDualWsSmall, kDualKinds };
-const DualKind kDual[kDualKinds] = {
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3<regq 8x16,64,128 | regq 8x8,64,256>", conv_dual_head3x3},
-    {kCfg128x16k64, kCfg128x16k64, 256, "conv_dual_head1x1<glds 128,16,64 x2>", conv_dual_head1x1},
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_i8<regq i8,8x16,64,128 | regq i8,8x8,64,256>", conv_dual_head3x3_i8},
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws<ws 16x16,64,128/2 | ws 8x16,64,256/4>", conv_dual_head3x3_ws},
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws_i8<ws i8,16x16,64,128/2 | ws i8,8x16,64,256/4>", conv_dual_head3x3_ws_i8},
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_s16<regq s16,8x16,64,128 | regq s16,8x8,64,256>", conv_dual_head3x3_s16},
-    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, "conv_dual_head3x3_ws_s16<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>", conv_dual_head3x3_ws_s16},
-    {kCfgWs8x16n64c128, kCfgWs4x16n64c256, 256, "conv_dual_head3x3_ws_small<ws 8x16,64,128/2 | ws 4x16,64,256/4, 2 per CU>", conv_dual_head3x3_ws_small},
-};
-}  // namespace
 
 int conv_dual_match(const ConvParams& a, const ConvParams& b) {
   if (a.stamps || b.stamps) return -1;   // (stamped launches go through conv_dual_launch with an explicit kind)
@@ -1569,7 +1558,8 @@ int conv_dual_match(const ConvParams& a, const ConvParams& b) {
   // flight, serial latency equal within noise; workgroup lives 9-11 us against 12-15). UNINA_DUAL_WS=0 falls back.
   if (ws && fits(kDualWs)) {
     // more workgroups than CUs with the full-height tiles: the half-height form, two workgroups per CU
-    if (fits(kDualWsSmall) && conv_dual_grid(kDualWs, a, b) > 256) return kDualWsSmall;
+    const dim3 ga = conv_grid(a, kDual[kDualWs].cfg_a), gb = conv_grid(b, kDual[kDualWs].cfg_b);
+    if (fits(kDualWsSmall) && ga.x * ga.y + gb.x * gb.y > 256) return kDualWsSmall;
     return kDualWs;
   }
   if (fits(kDualRegq)) return kDualRegq;
@@ -1582,30 +1572,15 @@ int conv_dual_match(const ConvParams& a, const ConvParams& b) {
   return -1;
 }
 
-const char* conv_dual_name(int kind) { return kind >= 0 && kind < kDualKinds ? kDual[kind].name : "?"; }
-
-int conv_dual_grid(int kind, const ConvParams& pa_in, const ConvParams& pb_in) {
-  if (kind < 0 || kind >= kDualKinds) return -1;
-  ConvParams pa = pa_in, pb = pb_in;
-  const dim3 ga = conv_prepare(pa, kDual[kind].cfg_a), gb = conv_prepare(pb, kDual[kind].cfg_b);
-  return (int)(ga.x * ga.y + gb.x * gb.y);
-}
-
-hipError_t conv_dual_launch(int kind, const ConvParams& pa_in, const ConvParams& pb_in, hipStream_t stream, int* grid_out) {
+hipError_t conv_dual_desc(int kind, ConvParams& a, ConvParams& b, LaunchDesc* d, int* split) {
+  if (kind >= 0 && kind < kDualKinds && (a.stamps || b.stamps)) kind = kDual[kind].twin;   // debug: the stamped twin
   if (kind < 0 || kind >= kDualKinds) return hipErrorInvalidValue;
   const DualKind& k = kDual[kind];
-  ConvParams pa = pa_in, pb = pb_in;
-  const dim3 ga = conv_prepare(pa, k.cfg_a), gb = conv_prepare(pb, k.cfg_b);
-  const int na = (int)(ga.x * ga.y), nb = (int)(gb.x * gb.y);
-  const size_t sa = smem_for(pa, kCfg[pa.dtype][k.cfg_a]), sb = smem_for(pb, kCfg[pb.dtype][k.cfg_b]);
-  if (grid_out) *grid_out = na + nb;
-  auto fn = k.fn;
-  if (pa.stamps || pb.stamps) {   // debug: the stamped twin (only the default fp16 pair has one)
-    if (kind != kDualWs && kind != kDualWsS16) return hipErrorInvalidValue;
-    fn = kind == kDualWs ? conv_dual_head3x3_ws_stamped : conv_dual_head3x3_ws_s16_stamped;
-  }
-  hipLaunchKernelGGL(fn, dim3(na + nb, 1, 1), dim3(k.threads, 1, 1), max_sz(sa, sb), stream, pa, pb, (kind == kDualWs || kind == kDualWsI8 || kind == kDualWsS16 || kind == kDualWsSmall) ? nb : na);   // (the weights-stationary pairs put conv B first)
-  return hipGetLastError();
+  const int na = conv_prepare(a, k.cfg_a), nb = conv_prepare(b, k.cfg_b);
+  *split = k.b_first ? nb : na;
+  const size_t smem = max_sz(smem_for(a, kCfg[a.dtype][k.cfg_a]), smem_for(b, kCfg[b.dtype][k.cfg_b]));
+  *d = {reinterpret_cast<const void*>(k.fn), dim3(na + nb), dim3(k.threads), (unsigned)smem, k.name};
+  return hipSuccess;
 }
 
 const char* conv_config_name(int cfg, int dtype) {

@@ -223,13 +223,7 @@ int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-hipError_t pair_init() {
-  for (const PClass& c : kPairClasses) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+hipError_t pair_init() { return set_lds_limits(kPairClasses); }
 
 bool pair_supported(int dtype, int c0, int c1, int c2, int up2, int pool) { return find_pclass(dtype, c0, c1, c2, up2, pool) != nullptr; }
 
@@ -260,23 +254,14 @@ bool pair_layout(PairParams* p) {
     off += p->lds_lo;
   }
   p->smem_bytes = off;
-  return off <= 160 * 1024;
+  return off <= kMaxLds;
 }
 
-hipError_t pair_launch(const PairParams& p, hipStream_t stream) {
+hipError_t pair_desc(const PairParams& p, LaunchDesc* d) {
   const PClass* c = find_pclass(p.dtype, p.c0, p.c1, p.c2, p.up2, p.pool);
   if (!c) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(c->fn, dim3(p.tiles_x * p.tiles_y, 1, 1), dim3(c->nw * 64, 1, 1), p.smem_bytes, stream, p);
-  return hipGetLastError();
-}
-
-const char* pair_kernel_name(const PairParams& p) {
-  const PClass* c = find_pclass(p.dtype, p.c0, p.c1, p.c2, p.up2, p.pool);
-  return c ? c->name : "conv_pair<?>";
-}
-int pair_block_threads(const PairParams& p) {
-  const PClass* c = find_pclass(p.dtype, p.c0, p.c1, p.c2, p.up2, p.pool);
-  return c ? c->nw * 64 : 0;
+  *d = {reinterpret_cast<const void*>(c->fn), dim3(p.tiles_x * p.tiles_y), dim3(c->nw * 64), (unsigned)p.smem_bytes, c->name};
+  return hipSuccess;
 }
 
 }  // namespace unina

@@ -23,6 +23,14 @@
 
 using namespace unina;
 
+hipError_t unina::kernels_init() {
+  for (hipError_t (*init)() : {conv_init, c3k2_init, head_init, pair_init, block_dual_init, stem_pool_init, post_init}) {
+    const hipError_t e = init();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 namespace {
 
 thread_local std::string g_load_error = "";
@@ -37,7 +45,7 @@ struct Buffer {
 struct PlannedOp {
   OpDesc d;
   ConvParams cp;
-  ConvLaunch cl;
+  int cfg = -1;             // conv: tile configuration (conv_plan)
   StemParams sp;
   PoolParams pp;
   QuantParams qp;
@@ -364,7 +372,7 @@ int plan_op(unina_engine* e, size_t i) {
     const int kb = dt == kF32 ? 16 : (dt == kI8 ? 64 : 32);
     if (p.Cin % kb || (p.src_ld * esz) % 16) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu (%s): Cin %% %d != 0", i, d.name, kb);
     if (p.force_cfg >= 0 && !conv_config_valid(p, p.force_cfg)) p.force_cfg = -1;
-    op.cl = conv_plan(p);
+    op.cfg = conv_plan(p);
     const int K = p.ksize * p.ksize * p.Cin;
     info.m = p.M; info.n = ntot; info.k = K;
     info.flops = 2.0 * p.M * (double)ntot * K;
@@ -372,9 +380,6 @@ int plan_op(unina_engine* e, size_t i) {
     const bool shared_src = p.nseg == 1 || d.seg[0].src_coff == d.seg[1].src_coff;
     info.bytes = dtype_bytes(dt) * p.H * p.W * p.Cin * (shared_src ? 1 : p.nseg) + dtype_bytes(dt) * ntot * K + 4.0 * ntot + out_bytes +
                  (p.res ? dtype_bytes(p.res_dtype) * p.M * ntot : 0.0);
-    snprintf(info.kernel, sizeof info.kernel, "%s", op.cl.kernel_name);
-    info.grid = (int)(op.cl.grid.x * op.cl.grid.y);
-    info.block = (int)op.cl.block.x;
   } else if (d.kind == kOpStem) {
     const SegDesc& sd = d.seg[0];
     const Buffer& db = e->bufs[sd.dst_buf];
@@ -393,13 +398,6 @@ int plan_op(unina_engine* e, size_t i) {
     info.m = p.Ho * p.Wo; info.n = p.Co; info.k = 27;
     info.flops = 2.0 * info.m * info.n * 27;
     info.bytes = 4.0 * 3 * p.H * p.W + dtype_bytes(odt) * info.m * p.Co;
-    {
-      LaunchDesc sl;
-      const bool tiled = stem_desc(p, &sl) == hipSuccess && sl.block.x == 128;
-      snprintf(info.kernel, sizeof info.kernel, "%s<%s,%d>", tiled ? "stem_tile_kernel" : "stem_conv_kernel", odt == kF32 ? "f32" : (odt == kS16 ? "s16" : "f16"), p.Co);
-      info.grid = tiled ? (int)sl.grid.x : (2 * info.m + 255) / 256;
-      info.block = tiled ? 128 : 256;
-    }
   } else if (d.kind == kOpSppfPool) {
     PoolParams& p = op.pp;
     const int dt = act_dtype_of(src.d.dtype);
@@ -409,9 +407,6 @@ int plan_op(unina_engine* e, size_t i) {
     p.lo = lo_plane(src.d);
     p.H = (int)d.in_h; p.W = (int)d.in_w; p.C = (int)d.cin; p.ld = (int)src.d.c; p.coff = (int)d.seg[0].src_coff;
     info.bytes = dtype_bytes(dt) * p.H * p.W * p.C * 4;
-    snprintf(info.kernel, sizeof info.kernel, dt == kS16 ? "sppf_pool_split_kernel<%s32>" : "sppf_pool_kernel<%s,32>", dt == kF32 ? "f32" : (dt == kI8 ? "i8" : (dt == kS16 ? "" : "f16")));
-    info.grid = p.H * (p.C / 32);
-    info.block = 256;
   } else if (d.kind == kOpQuant) {
     const Buffer& db = e->bufs[d.seg[0].dst_buf];
     if (src.d.dtype != kBufF16Nhwc || db.d.dtype != kBufI8Nhwc || src.d.c != db.d.c || src.d.h != db.d.h || src.d.w != db.d.w)
@@ -422,9 +417,6 @@ int plan_op(unina_engine* e, size_t i) {
     p.n = (size_t)src.d.h * src.d.w * src.d.c;
     p.inv_scale = 1.0f / db.d.scale;
     info.bytes = 3.0 * p.n;
-    snprintf(info.kernel, sizeof info.kernel, "quant_f16_i8_kernel");
-    info.grid = (int)((p.n / 16 + 255) / 256);
-    info.block = 256;
   } else {
     return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: kind %u not executable", i, d.kind);
   }
@@ -432,11 +424,10 @@ int plan_op(unina_engine* e, size_t i) {
 }
 
 // Op b's work now runs inside op `at`'s launch, whose info is `a` (`how`: "fused into" / "dual launch with"): a takes over
-// b's flops, bytes and grid, b names that launch.
+// b's flops and bytes, b names that launch. (a's kernel and geometry are its launch's: launch_info.)
 void absorb_info(unina_op_info* a, unina_op_info* b, const char* how, size_t at) {
   a->flops += b->flops;
   a->bytes += b->bytes;
-  a->grid += b->grid;
   b->flops = 0;
   b->bytes = 0;
   b->grid = 0;
@@ -482,10 +473,7 @@ int plan_pair(unina_engine* e, size_t i) {
   }
   absorb_info(&op.info, &zb.info, "fused into", i);
   op.info.bytes -= dtype_bytes(f.dtype) * f.H * f.W * f.c1;     // the second conv reads the first's output from LDS
-  op.info.grid = f.tiles_x * f.tiles_y;
-  op.info.block = pair_block_threads(f);
   op.info.k = 0;
-  snprintf(op.info.kernel, sizeof op.info.kernel, "%s", pair_kernel_name(f));
   snprintf(op.info.name, sizeof op.info.name, "%.40s+%.40s", a.name, z.name);
   return UNINA_OK;
 }
@@ -522,9 +510,6 @@ int plan_head(unina_engine* e, size_t i) {
   info.bytes = 2.0 * f.H * f.W * f.C + wbytes + 4.0 * f.H * f.W * (f.n_cls + f.n_reg);
   info.n = f.n_cls + f.n_reg;
   info.k = 0;
-  info.grid = f.tiles_x * f.tiles_y;
-  info.block = head_block_threads(f.C);
-  snprintf(info.kernel, sizeof info.kernel, "%s", head_kernel_name(f.C));
   snprintf(info.name, sizeof info.name, "%.*s[head]", (int)(strchr(a.name, '.') ? strchr(a.name, '.') - a.name : 60), a.name);
   return UNINA_OK;
 }
@@ -599,9 +584,6 @@ int plan_c3k2(unina_engine* e, size_t i) {
                (f.tail ? fb * (f.tail == 1 ? 4 : 1) * f.H * f.W * f.hid : 0.0);            // (+ the tail conv's output)
   info.n = 2 * f.hid;
   info.k = 0;
-  info.grid = f.tiles_x * f.tiles_y;
-  info.block = c3k2_block_threads(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx);
-  snprintf(info.kernel, sizeof info.kernel, "%s", c3k2_kernel_name(f.hid, f.nb, f.Cin, f.tail, f.dtype, f.cpre, f.cx));
   snprintf(info.name, sizeof info.name, "%.*s[c3k2 x%d]", (int)(strchr(a.name, '+') ? strchr(a.name, '+') - a.name - 4 : 60), a.name, f.nb);
   return UNINA_OK;
 }
@@ -647,7 +629,6 @@ void plan_duals(unina_engine* e) {
       a.dual_with = (int)j;
       b.dual_absorbed = true;
       absorb_info(&a.info, &b.info, "dual launch with", i);
-      snprintf(a.info.kernel, sizeof a.info.kernel, "%s", block_dual_name(a.fp.dtype, a.fp.cpre));
       break;
     }
   }
@@ -665,7 +646,6 @@ void plan_duals(unina_engine* e) {
         a.dual_kind = kind;
         b.dual_absorbed = true;
         absorb_info(&a.info, &b.info, "dual launch with", i);
-        snprintf(a.info.kernel, sizeof a.info.kernel, "%s", conv_dual_name(kind));
         break;
       }
       // the other direction: the EARLIER op sinks to the later one's position (an INT8 engine's P3 output conv
@@ -678,10 +658,117 @@ void plan_duals(unina_engine* e) {
       b.dual_kind = kind2;
       a.dual_absorbed = true;
       absorb_info(&b.info, &a.info, "dual launch with", j);
-      snprintf(b.info.kernel, sizeof b.info.kernel, "%s", conv_dual_name(kind2));
       break;
     }
   }
+}
+
+enum LaunchForm { kNoLaunch, kLaunchConv, kLaunchConvDual, kLaunchStem, kLaunchPool, kLaunchQuant, kLaunchC3k2, kLaunchHead, kLaunchPair,
+                  kLaunchBlockDual, kLaunchBad };
+// The launch op i would make on its own.
+LaunchForm own_form(const PlannedOp& op) {
+  switch (op.d.kind) {
+    case kOpConv: return kLaunchConv;
+    case kOpStem: return kLaunchStem;
+    case kOpSppfPool: return kLaunchPool;
+    case kOpQuant: return kLaunchQuant;
+    default: return kLaunchBad;
+  }
+}
+
+// The launch of the fused group op i leads (fuse_role 1).
+LaunchForm group_form(const PlannedOp& op) { return op.fuse_kind == 4 ? kLaunchPair : (op.fuse_kind == 2 ? kLaunchHead : kLaunchC3k2); }
+
+// Which launch op i makes: its own, its fused group's, a dual launch it leads, or none (it runs inside another op's).
+LaunchForm launch_form(const unina_engine* e, size_t i) {
+  const PlannedOp& op = e->ops[i];
+  if (op.dual_absorbed || (e->fuse && op.fuse_role == 2)) return kNoLaunch;
+  if (e->fuse && op.fuse_role == 1) return op.dual_with >= 0 ? kLaunchBlockDual : group_form(op);
+  return op.dual_with >= 0 ? kLaunchConvDual : own_form(op);
+}
+
+// One launch: its descriptor and the argument values it passes (copies of the planned parameters, finalised by the family's
+// desc function). args points into the object itself, hence no copies.
+struct OpLaunch {
+  LaunchDesc d{};           // d.func == nullptr: nothing to launch
+  int cfg = -1;             // kLaunchConv: the tile configuration
+  ConvParams cp[2];         // conv (A, and B of a dual launch)
+  C3k2Params fp;
+  HeadParams hp;
+  PairParams pr;
+  StemParams sp;
+  PoolParams pp;
+  QuantParams qp;
+  int split = 0;            // dual launches: the kernel's third argument
+  void* args[3] = {};
+  OpLaunch() = default;
+  OpLaunch(const OpLaunch&) = delete;
+};
+constexpr auto kNoEdit = [](OpLaunch&) {};
+
+// Fills `l` with op i's launch as `f` (launch_form, or a single conv / block for the autotuner and the debug entry points):
+// copies the parameters, lets `edit` change them (a forced configuration, debug stamps), then builds the descriptor.
+template <typename Edit = decltype(kNoEdit)>
+hipError_t op_launch(const unina_engine* e, size_t i, LaunchForm f, OpLaunch* l, Edit edit = kNoEdit) {
+  const PlannedOp& op = e->ops[i];
+  switch (f) {
+    case kNoLaunch: return hipSuccess;
+    case kLaunchConv: l->cp[0] = op.cp; l->cfg = op.cfg; break;
+    case kLaunchConvDual: l->cp[0] = op.cp; l->cp[1] = e->ops[op.dual_with].cp; break;
+    case kLaunchStem: l->sp = op.sp; break;
+    case kLaunchPool: l->pp = op.pp; break;
+    case kLaunchQuant: l->qp = op.qp; break;
+    case kLaunchC3k2: l->fp = op.fp; break;
+    case kLaunchHead: l->hp = op.hp; break;
+    case kLaunchPair: l->pr = op.pr; break;
+    case kLaunchBlockDual: l->fp = op.fp; l->hp = e->ops[op.dual_with].hp; break;
+    default: return hipErrorInvalidValue;
+  }
+  edit(*l);
+  void** a = l->args;
+  switch (f) {
+    case kLaunchConv: a[0] = &l->cp[0]; return conv_desc(l->cp[0], l->cfg, &l->d);
+    case kLaunchConvDual:
+      a[0] = &l->cp[0]; a[1] = &l->cp[1]; a[2] = &l->split;
+      return conv_dual_desc(op.dual_kind, l->cp[0], l->cp[1], &l->d, &l->split);
+    case kLaunchStem: a[0] = &l->sp; return stem_desc(l->sp, &l->d);
+    case kLaunchPool: a[0] = &l->pp; return sppf_pool_desc(l->pp, &l->d);
+    case kLaunchQuant: a[0] = &l->qp; return quant_desc(l->qp, &l->d);
+    case kLaunchC3k2: a[0] = &l->fp; return c3k2_desc(l->fp, &l->d);
+    case kLaunchHead: a[0] = &l->hp; return head_desc(l->hp, &l->d);
+    case kLaunchPair: a[0] = &l->pr; return pair_desc(l->pr, &l->d);
+    default: a[0] = &l->fp; a[1] = &l->hp; a[2] = &l->split; return block_dual_desc(l->fp, l->hp, &l->d, &l->split);
+  }
+}
+
+template <typename Edit = decltype(kNoEdit)>
+hipError_t launch_op_as(const unina_engine* e, size_t i, hipStream_t s, LaunchForm f, Edit edit = kNoEdit) {
+  OpLaunch l;
+  const hipError_t err = op_launch(e, i, f, &l, edit);
+  return err != hipSuccess || !l.d.func ? err : launch_desc(l.d, l.args, s);
+}
+hipError_t launch_op(const unina_engine* e, size_t i, hipStream_t s) { return launch_op_as(e, i, s, launch_form(e, i)); }
+
+// The op info's kernel, grid and block: those of op i's launch as `f`.
+void launch_info(unina_engine* e, size_t i, LaunchForm f) {
+  OpLaunch l;
+  if (op_launch(e, i, f, &l) != hipSuccess || !l.d.func) return;
+  unina_op_info& info = e->ops[i].info;
+  snprintf(info.kernel, sizeof info.kernel, "%s", l.d.name);
+  info.grid = (int)(l.d.grid.x * l.d.grid.y * l.d.grid.z);
+  info.block = (int)l.d.block.x;
+}
+
+// Does op j launch in a frame whose post-process is `pp`? Not if it runs inside another op's launch, nor if the decode launch
+// computes it (a head's output conv folded into the two-launch form; a dual launch only when both its convs are).
+bool launches_in_frame(const unina_engine* e, size_t j, const PostParams& pp) {
+  auto folded = [&](int k) {
+    for (int h = 0; h < 3; ++h)
+      if (pp.mode == 2 && e->fold_op[h] == k && pp.h1[h] != nullptr) return true;
+    return false;
+  };
+  const LaunchForm f = launch_form(e, j);
+  return f != kNoLaunch && !(folded((int)j) && (f != kLaunchConvDual || folded(e->ops[j].dual_with)));
 }
 
 // (Re)computes kernel parameters from the current buffer addresses. Element types are properties of the BUFFERS
@@ -692,35 +779,22 @@ int plan(unina_engine* e) {
   for (size_t i = 0; i < e->ops.size(); ++i) {
     const int rc = plan_op(e, i);
     if (rc != UNINA_OK) return rc;
+    launch_info(e, i, own_form(e->ops[i]));
   }
   for (size_t i = 0; i < e->ops.size(); ++i) {
     const PlannedOp& op = e->ops[i];
     if (op.fuse_role != 1) continue;
     const int rc = op.fuse_kind == 4 ? plan_pair(e, i) : (op.fuse_kind == 2 ? plan_head(e, i) : plan_c3k2(e, i));
     if (rc != UNINA_OK) return rc;
+    if (e->fuse) launch_info(e, i, group_form(op));
   }
   plan_duals(e);
   find_fold_ops(e);
+  for (size_t i = 0; i < e->ops.size(); ++i)   // what runs (an op a dual launch absorbs keeps its own block)
+    if (launch_form(e, i) != kNoLaunch) launch_info(e, i, launch_form(e, i));
   e->plan_dirty = false;
   drop_graph(e);
   return UNINA_OK;
-}
-
-hipError_t launch_op(unina_engine* e, size_t i, hipStream_t s) {
-  PlannedOp& op = e->ops[i];
-  if (op.dual_absorbed) return hipSuccess;
-  if (e->fuse && op.fuse_role == 1 && op.dual_with >= 0) return block_dual_launch(op.fp, e->ops[op.dual_with].hp, s);
-  if (e->fuse && op.fuse_role == 1 && op.fuse_kind == 4) return pair_launch(op.pr, s);
-  if (e->fuse && op.fuse_role == 1) return op.fuse_kind == 2 ? head_launch(op.hp, s) : c3k2_launch(op.fp, s);
-  if (op.dual_with >= 0) return conv_dual_launch(op.dual_kind, op.cp, e->ops[op.dual_with].cp, s);
-  if (e->fuse && op.fuse_role == 2) return hipSuccess;   // runs inside its group's launch
-  switch (op.d.kind) {
-    case kOpConv: return conv_launch(op.cp, op.cl, s);
-    case kOpStem: return stem_launch(op.sp, s);
-    case kOpSppfPool: return sppf_pool_launch(op.pp, s);
-    case kOpQuant: return quant_launch(op.qp, s);
-    default: return hipErrorInvalidValue;
-  }
 }
 
 // Ops that read the caller's "images" tensor (the stem) stay OUTSIDE the captured graph: a camera pipeline hands
@@ -1044,16 +1118,7 @@ int capture_full(unina_engine* e, const PostParams& pp) {
   hipError_t err = hipSuccess;
   int rc = UNINA_OK;
   for (size_t j = 0; j < e->ops.size() && err == hipSuccess; ++j) {
-    if (pp.mode == 2) {   // the heads' output convs that the decode launch computes itself are left out of the graph
-      auto used = [&](int k) {
-        for (int h = 0; h < 3; ++h)
-          if (e->fold_op[h] == k && pp.h1[h] != nullptr) return true;
-        return false;
-      };
-      const PlannedOp& oj = e->ops[j];
-      const bool dual_leader = oj.dual_with >= 0 && !(e->fuse && oj.fuse_role);
-      if (used((int)j) && (!dual_leader || used(oj.dual_with))) continue;
-    }
+    if (!launches_in_frame(e, j, pp)) continue;
     err = launch_op(e, j, st);
     if (err != hipSuccess) {
       rc = fail(e, UNINA_ERR_HIP, "op %zu (%s): %s", j, e->ops[j].d.name, hipGetErrorString(err));
@@ -1070,7 +1135,7 @@ int capture_full(unina_engine* e, const PostParams& pp) {
   for (int k = 0; k < npost && err == hipSuccess; ++k) {
     PostParams copy = pp;
     void* args[] = {&copy};
-    err = hipLaunchKernel(pd[k].func, pd[k].grid, pd[k].block, args, pd[k].shmem, st);
+    err = launch_desc(pd[k], args, st);
     if (err == hipSuccess) err = last_captured_node(st, k == 0 ? &e->post_node : &e->post_node2);
   }
   hipError_t end = hipStreamEndCapture(st, &e->fgraph);
@@ -1355,13 +1420,7 @@ int load_device(unina_engine* e, const std::vector<char>& blob) {
   size_t arena = 0;
   for (auto& b : e->bufs)
     if (!(b.d.flags & kBufInput)) arena += (b.bytes + 255) & ~(size_t)255;
-  LOADCHK(conv_init());
-  LOADCHK(c3k2_init());
-  LOADCHK(head_init());
-  LOADCHK(pair_init());
-  LOADCHK(block_dual_init());
-  LOADCHK(post_init());
-  LOADCHK(stem_init());
+  LOADCHK(kernels_init());
   LOADCHK(hipMalloc(&e->d_zeros, 256));
   LOADCHK(hipMemset(e->d_zeros, 0, 256));
   LOADCHK(hipMalloc(&e->d_arena, arena ? arena : 256));
@@ -1679,12 +1738,11 @@ int unina_debug_conv_stamps(unina_engine_t* e, int op_index, long long* out5, hi
     if (rc != UNINA_OK) return rc;
   }
   if (e->ops[op_index].d.kind != kOpConv) return fail(e, UNINA_ERR_ARG, "op %d is not a convolution", op_index);
-  ConvParams p = e->ops[op_index].cp;
-  p.stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
-  HIPCHK(e, hipMemsetAsync(p.stamps, 0, sizeof(long long) * 8, stream));
-  HIPCHK(e, conv_launch(p, e->ops[op_index].cl, stream));
+  long long* stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
+  HIPCHK(e, hipMemsetAsync(stamps, 0, sizeof(long long) * 8, stream));
+  HIPCHK(e, launch_op_as(e, op_index, stream, kLaunchConv, [&](OpLaunch& l) { l.cp[0].stamps = stamps; }));
   HIPCHK(e, hipStreamSynchronize(stream));
-  HIPCHK(e, hipMemcpy(out5, p.stamps, sizeof(long long) * 8, hipMemcpyDeviceToHost));  // 5 shader-clock stamps + 2 at 100 MHz + entry
+  HIPCHK(e, hipMemcpy(out5, stamps, sizeof(long long) * 8, hipMemcpyDeviceToHost));  // 5 shader-clock stamps + 2 at 100 MHz + entry
   return UNINA_OK;
 }
 
@@ -1700,13 +1758,14 @@ int unina_debug_dual_stamps(unina_engine_t* e, int op_index, long long* out16, h
   const PlannedOp& op = e->ops[op_index];
   if (op.d.kind != kOpConv || op.fuse_role || op.dual_with < 0 || op.dual_absorbed)
     return fail(e, UNINA_ERR_ARG, "op %d does not lead a dual conv launch", op_index);
-  ConvParams pa = op.cp, pb = e->ops[op.dual_with].cp;
-  pa.stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
-  pb.stamps = pa.stamps + 8;
-  HIPCHK(e, hipMemsetAsync(pa.stamps, 0, sizeof(long long) * 16, stream));
-  HIPCHK(e, conv_dual_launch(op.dual_kind, pa, pb, stream));
+  long long* stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
+  HIPCHK(e, hipMemsetAsync(stamps, 0, sizeof(long long) * 16, stream));
+  HIPCHK(e, launch_op_as(e, op_index, stream, kLaunchConvDual, [&](OpLaunch& l) {
+    l.cp[0].stamps = stamps;
+    l.cp[1].stamps = stamps + 8;
+  }));
   HIPCHK(e, hipStreamSynchronize(stream));
-  HIPCHK(e, hipMemcpy(out16, pa.stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(out16, stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
   return UNINA_OK;
 }
 
@@ -1723,12 +1782,11 @@ int unina_debug_block_stamps(unina_engine_t* e, int op_index, long long* out16, 
   const PlannedOp& op = e->ops[op_index];
   if (!e->fuse || op.fuse_role != 1 || op.fuse_kind != 1) return fail(e, UNINA_ERR_ARG, "op %d does not lead a fused C3k2 block", op_index);
   for (int i = 0; i < op_index; ++i) HIPCHK(e, launch_op(e, (size_t)i, stream));
-  C3k2Params p = op.fp;
-  p.stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
-  HIPCHK(e, hipMemsetAsync(p.stamps, 0, sizeof(long long) * 16, stream));
-  HIPCHK(e, c3k2_launch_stamped(p, stream));
+  long long* stamps = reinterpret_cast<long long*>(e->d_result->pad_stamps);
+  HIPCHK(e, hipMemsetAsync(stamps, 0, sizeof(long long) * 16, stream));
+  HIPCHK(e, launch_op_as(e, op_index, stream, kLaunchC3k2, [&](OpLaunch& l) { l.fp.stamps = stamps; }));
   HIPCHK(e, hipStreamSynchronize(stream));
-  HIPCHK(e, hipMemcpy(out16, p.stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(out16, stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
   return UNINA_OK;
 }
 
@@ -1748,30 +1806,34 @@ int unina_debug_dual_timeline(unina_engine_t* e, int op_index, long long* out, i
   }
   const PlannedOp& op = e->ops[op_index];
   if (op.d.kind != kOpConv || op.fuse_role || op.dual_with < 0 || op.dual_absorbed) return -UNINA_ERR_ARG;
-  ConvParams pa = op.cp, pb = e->ops[op.dual_with].cp;
   // every workgroup writes wg_times[2 * blockIdx.x ..]: the buffer is sized from the grid, known BEFORE anything is launched
-  const int grid = conv_dual_grid(op.dual_kind, pa, pb);
+  int grid = 0;
+  {
+    OpLaunch l;
+    if (op_launch(e, op_index, kLaunchConvDual, &l) != hipSuccess) return -UNINA_ERR_ARG;
+    grid = (int)l.d.grid.x;
+  }
   if (grid < 1 || 2 * grid + 2 > cap) return -UNINA_ERR_ARG;
   long long* d = nullptr;
   const size_t words = 18 + 2 * (size_t)grid;
   if (hipMalloc(&d, sizeof(long long) * words) != hipSuccess) return -UNINA_ERR_HIP;
   long long* marks = d + 16 + 2 * grid;
-  pa.stamps = d;
-  pb.stamps = d + 8;
-  pa.wg_times = pb.wg_times = d + 16;
-  int launched = 0;
   hipError_t he = hipMemsetAsync(d, 0, sizeof(long long) * words, stream);
   if (he == hipSuccess) {
     hipLaunchKernelGGL(unina::debug_stamp_kernel, dim3(1), dim3(64), 0, stream, marks);
     he = hipGetLastError();
   }
-  if (he == hipSuccess) he = conv_dual_launch(op.dual_kind, pa, pb, stream, &launched);
+  if (he == hipSuccess)
+    he = launch_op_as(e, op_index, stream, kLaunchConvDual, [&](OpLaunch& l) {
+      l.cp[0].stamps = d;
+      l.cp[1].stamps = d + 8;
+      l.cp[0].wg_times = l.cp[1].wg_times = d + 16;
+    });
   if (he == hipSuccess) {
     hipLaunchKernelGGL(unina::debug_stamp_kernel, dim3(1), dim3(64), 0, stream, marks + 1);
     he = hipGetLastError();
   }
   if (he == hipSuccess) he = hipStreamSynchronize(stream);
-  if (he == hipSuccess && launched != grid) he = hipErrorInvalidValue;     // (the planner's grid is the launch's)
   if (he == hipSuccess) he = hipMemcpy(out, d + 16, sizeof(long long) * 2 * grid, hipMemcpyDeviceToHost);
   if (he == hipSuccess) he = hipMemcpy(out + 2 * grid, marks, sizeof(long long) * 2, hipMemcpyDeviceToHost);
   (void)hipFree(d);
@@ -1854,9 +1916,9 @@ int unina_autotune(unina_engine_t* e, int iters, hipStream_t stream) {
     int best_cfg = -1;
     for (int cfg = 0; cfg < (int)kCfgCount; ++cfg) {
       if (!conv_config_valid(e->ops[i].cp, cfg)) continue;
-      const ConvLaunch l = conv_plan_with(e->ops[i].cp, cfg);
       float ms = 0.f;
-      rc = time_in_sequence(e, i, iters, stream, a, b, [&]() { return conv_launch(e->ops[i].cp, l, stream); }, &ms);
+      rc = time_in_sequence(e, i, iters, stream, a, b,
+                            [&]() { return launch_op_as(e, i, stream, kLaunchConv, [&](OpLaunch& l) { l.cfg = cfg; }); }, &ms);
       if (rc != UNINA_OK) return rc;
       if (ms < best) {
         best = ms;
@@ -1886,15 +1948,8 @@ int unina_profile_ops(unina_engine_t* e, int iters, float* ms_per_op, hipStream_
   HIPCHK(e, hipEventCreate(&b));
   PostParams pp;   // which head output convs the frame's decode launch computes itself (they are not launched in a frame)
   fill_post_params(e, &pp, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
-  auto folded = [&](int k) {
-    for (int h = 0; h < 3; ++h)
-      if (pp.mode == 2 && e->fold_op[h] == k && pp.h1[h] != nullptr) return true;
-    return false;
-  };
   for (size_t i = 0; i < e->ops.size(); ++i) {
-    const PlannedOp& op = e->ops[i];
-    const bool dual_leader = op.dual_with >= 0 && !(e->fuse && op.fuse_role);
-    if ((e->fuse && op.fuse_role == 2) || op.dual_absorbed || (folded((int)i) && (!dual_leader || folded(op.dual_with)))) {
+    if (!launches_in_frame(e, i, pp)) {
       ms_per_op[i] = 0.f;
       continue;
     }
@@ -1935,7 +1990,7 @@ int unina_profile_post(unina_engine_t* e, int iters, float conf, float iou, floa
         PostParams copy = pp;
         void* args[] = {&copy};
         HIPCHK(e, hipEventRecord(ev[k], stream));
-        HIPCHK(e, hipLaunchKernel(d[k].func, d[k].grid, d[k].block, args, d[k].shmem, stream));
+        HIPCHK(e, launch_desc(d[k], args, stream));
       }
       HIPCHK(e, hipEventRecord(ev[npost], stream));
       HIPCHK(e, hipEventSynchronize(ev[npost]));

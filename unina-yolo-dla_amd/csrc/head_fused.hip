@@ -53,18 +53,11 @@ const HClass* find_hclass(int c) {
   static const int alt = (getenv("UNINA_HEAD_ALT") && getenv("UNINA_HEAD_ALT")[0] == '0') ? 0 : 1;
   return kHeadClasses[alt].c == c ? &kHeadClasses[alt] : nullptr;
 }
-constexpr int kMaxLds = 160 * 1024;
 int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-hipError_t head_init() {
-  for (const HClass& c : kHeadClasses) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+hipError_t head_init() { return set_lds_limits(kHeadClasses); }
 
 bool head_supported(int c) { return find_hclass(c) != nullptr; }
 
@@ -96,29 +89,16 @@ bool head_layout(HeadParams* p) {
   return off <= kMaxLds;
 }
 
-hipError_t head_launch(const HeadParams& p, hipStream_t stream) {
+hipError_t head_desc(const HeadParams& p, LaunchDesc* d) {
   const HClass* c = find_hclass(p.C);
   if (!c) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(c->fn, dim3(p.tiles_x * p.tiles_y, 1, 1), dim3(c->nw * 64, 1, 1), p.smem_bytes, stream, p);
-  return hipGetLastError();
+  *d = {reinterpret_cast<const void*>(c->fn), dim3(p.tiles_x * p.tiles_y), dim3(c->nw * 64), (unsigned)p.smem_bytes, c->name};
+  return hipSuccess;
 }
 
 bool head_tile_is(const HeadParams& p, int th, int tw) {
   const HClass* k = find_hclass(p.C);
   return k && k->th == th && k->tw == tw;
-}
-
-bool head_is_ws(int c) {
-  const HClass* k = find_hclass(c);
-  return k && k->ws;
-}
-const char* head_kernel_name(int c) {
-  const HClass* k = find_hclass(c);
-  return k ? k->name : "head_fused<?>";
-}
-int head_block_threads(int c) {
-  const HClass* k = find_hclass(c);
-  return k ? k->nw * 64 : 0;
 }
 
 }  // namespace unina

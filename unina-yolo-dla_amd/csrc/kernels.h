@@ -18,6 +18,36 @@ constexpr int kNumDTypes = 4;
 struct s16_t { _Float16 v; };                        // one plane element of a kS16 tensor (pointer arithmetic in plane elements)
 
 // ------------------------------------------------------------------------------------------------
+// Launch descriptors. Every family has ONE function `*_desc` that picks the kernel, grid, block and dynamic LDS of a launch
+// from its parameters (finalising the launch-time fields of the caller's copy where the family has any); the engine launches
+// it with hipLaunchKernel, reports it in the op infos, and re-points captured graph nodes with it.
+// ------------------------------------------------------------------------------------------------
+struct LaunchDesc {
+  const void* func;
+  dim3 grid, block;
+  unsigned shmem;
+  const char* name;    // display name (op infos; engine.py keys the tune cache on op 1's)
+};
+inline hipError_t launch_desc(const LaunchDesc& d, void** args, hipStream_t stream) {
+  return hipLaunchKernel(d.func, d.grid, d.block, args, d.shmem, stream);
+}
+
+// Every kernel the engine launches is a row (`fn`, nullptr = an empty slot) of its family's table. The dynamic-LDS limit of
+// every row is the CU's 160 KB: a launch check only, each launch still asks for what it needs. Per device:
+// hipFuncSetAttribute applies to the current one.
+constexpr int kMaxLds = 160 * 1024;
+template <typename Row, size_t N>
+hipError_t set_lds_limits(const Row (&rows)[N]) {
+  for (const Row& r : rows) {
+    if (!r.fn) continue;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+hipError_t kernels_init();   // every family's table (engine.hip)
+
+// ------------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution  D[cout][pixel] = sum_k W[cout][k] * X[pixel][k]   (+bias, ReLU, +residual)
 //   X : NHWC fp16 activation buffer, read through (ld, channel offset) so concat slices are free
 //   W : fp16 [n_pad][K], K = (kh, kw, cin)  -- BatchNorm already folded in
@@ -81,22 +111,16 @@ enum ConvConfig : int {
   kCfgWs8x16n64c128, kCfgWs4x16n64c256,                        // fp16: the half-height tiles of the head pair on large frames (two workgroups per CU)
   kCfgCount
 };
-struct ConvLaunch {
-  ConvConfig cfg;
-  dim3 grid, block;
-  const char* kernel_name;
-};
-hipError_t conv_init();                                  // once per process: raise the dynamic-LDS limit of every instantiation
+hipError_t conv_init();
 bool conv_config_valid(const ConvParams& p, int cfg);
-ConvLaunch conv_plan(const ConvParams& p);               // heuristic (or p.force_cfg)
-ConvLaunch conv_plan_with(const ConvParams& p, int cfg);
+int conv_plan(const ConvParams& p);                      // heuristic (or p.force_cfg): a configuration
 const char* conv_config_name(int cfg, int dtype = kF16);
-hipError_t conv_launch(const ConvParams& p, const ConvLaunch& l, hipStream_t stream);
+// the launch of `p` with configuration `cfg`: fills p's launch-time fields (tile counts, magics, tile0, xcd_m_major)
+hipError_t conv_desc(ConvParams& p, int cfg, LaunchDesc* d);
 // Two independent convs of one kernel family as ONE grid (conv_igemm.hip, dual launches): kind >= 0 if the pair fits.
 int conv_dual_match(const ConvParams& a, const ConvParams& b);
-const char* conv_dual_name(int kind);
-hipError_t conv_dual_launch(int kind, const ConvParams& a, const ConvParams& b, hipStream_t stream, int* grid_out = nullptr);
-int conv_dual_grid(int kind, const ConvParams& a, const ConvParams& b);   // workgroups that launch will have (-1: bad kind)
+// the dual launch (its stamped twin if a or b has stamps); *split = the kernel's third argument (workgroups of the part first)
+hipError_t conv_dual_desc(int kind, ConvParams& a, ConvParams& b, LaunchDesc* d, int* split);
 
 // ------------------------------------------------------------------------------------------------
 // Fused C3k2 block (model.py:76-110): cv1|cv2 -> n x Bottleneck(1x1, 3x3 + shortcut) -> cv3 in ONE launch, all
@@ -150,10 +174,7 @@ bool c3k2_layout(C3k2Params* p);
 bool c3k2_supported(int hid, int nb, int cin, int tail = 0, int dtype = kF16, int cpre = 0, int cx = 0);
 bool c3k2_pack(int hid, int nb, int cin, int tail, const C3k2Conv* convs, std::vector<unsigned char>* stream, std::vector<float>* bias,
                int dtype = kF16, int cpre = 0, int cx = 0);   // with cpre: convs[0] is the pre-conv (cpre -> cx channels)
-hipError_t c3k2_launch(const C3k2Params& p, hipStream_t stream);
-hipError_t c3k2_launch_stamped(const C3k2Params& p, hipStream_t stream);   // debug twin with per-step stamps (p.stamps); InvalidValue if the class has none
-const char* c3k2_kernel_name(int hid, int nb, int cin, int tail = 0, int dtype = kF16, int cpre = 0, int cx = 0);
-int c3k2_block_threads(int hid, int nb, int cin, int tail = 0, int dtype = kF16, int cpre = 0, int cx = 0);
+hipError_t c3k2_desc(const C3k2Params& p, LaunchDesc* d);   // p.stamps: the debug twin with per-step stamps (InvalidValue if the class has none)
 
 // One 1-KiB weight fragment block (16 rows x 4 chunks of 16 bytes) from the engine file's LDS-image order -- slot(r, c) =
 // 4r + (c ^ G[r >> 2]), G = (0,2,3,1): what the LDS-DMA kernels (conv_glds, conv3x3_halo) copy into LDS and read
@@ -188,10 +209,7 @@ struct HeadParams {
 hipError_t head_init();
 bool head_supported(int c);
 bool head_layout(HeadParams* p);
-hipError_t head_launch(const HeadParams& p, hipStream_t stream);
-const char* head_kernel_name(int c);
-bool head_is_ws(int c);                // the row-streaming / weights-stationary class is selected (head_ws_body)
-int head_block_threads(int c);
+hipError_t head_desc(const HeadParams& p, LaunchDesc* d);
 
 // Two consecutive 1x1 ConvBlocks (SPPF cv2 -> FPN lateral, + x2 upsample store) in ONE launch (conv_pair.hip).
 struct PairParams {
@@ -220,15 +238,12 @@ struct PairParams {
 hipError_t pair_init();
 bool pair_supported(int dtype, int c0, int c1, int c2, int up2, int pool = 0);
 bool pair_layout(PairParams* p);
-hipError_t pair_launch(const PairParams& p, hipStream_t stream);
-const char* pair_kernel_name(const PairParams& p);
-int pair_block_threads(const PairParams& p);
+hipError_t pair_desc(const PairParams& p, LaunchDesc* d);
 
 // A fused C3k2 block and a fused head that do not depend on each other, side by side in one grid (block_dual.hip).
 hipError_t block_dual_init();
 bool block_dual_match(const C3k2Params& pc, const HeadParams& ph);
-const char* block_dual_name(int dtype = kF16, int cpre = 0);
-hipError_t block_dual_launch(const C3k2Params& pc, const HeadParams& ph, hipStream_t stream, int* grid_out = nullptr);
+hipError_t block_dual_desc(const C3k2Params& pc, const HeadParams& ph, LaunchDesc* d, int* split);   // *split: the block's workgroups
 bool c3k2_tile_is(const C3k2Params& p, int th, int tw);    // the tile the layout of `p` was computed for
 bool head_tile_is(const HeadParams& p, int th, int tw);
 // Rows of the row-streaming head's (head_ws_body) th x 14 pixel strips. 13: at 640^2 the P2 map's 160 rows x 12 strips give 156
@@ -255,16 +270,8 @@ struct StemParams {
   long long dst_lo;    // kS16: byte distance hi plane -> lo plane of dst
   int H, W, Ho, Wo, Co, dst_ld;
 };
-hipError_t stem_launch(const StemParams& p, hipStream_t stream, dim3* grid_out = nullptr, dim3* block_out = nullptr);
-// Launch descriptor of a kernel whose only argument is its parameter struct: what hipGraphExecKernelNodeSetParams needs
-// to re-point a captured node at new parameters (a different input frame, other thresholds / output buffers).
-struct LaunchDesc {
-  const void* func;
-  dim3 grid, block;
-  unsigned shmem;
-};
 hipError_t stem_desc(const StemParams& p, LaunchDesc* out);
-hipError_t stem_init();   // per device: dynamic-LDS limit of the tiled stem kernels
+hipError_t stem_pool_init();   // the stem, SPPF pool and quantise tables
 
 // ------------------------------------------------------------------------------------------------
 // SPPF pool pyramid: y1 = pool5(x), y2 = pool5(y1), y3 = pool5(y2) (== 5x5, 9x9, 13x13 clipped windows of x)
@@ -276,7 +283,7 @@ struct PoolParams {
   long long lo;        // kS16: byte distance hi plane -> lo plane
   int H, W, C, ld, coff;
 };
-hipError_t sppf_pool_launch(const PoolParams& p, hipStream_t stream, dim3* grid_out = nullptr, dim3* block_out = nullptr);
+hipError_t sppf_pool_desc(const PoolParams& p, LaunchDesc* d);
 
 // fp16 -> int8 re-quantisation of a whole NHWC buffer (int8 engines: tensors with both fp16 and int8 consumers)
 struct QuantParams {
@@ -285,16 +292,7 @@ struct QuantParams {
   size_t n;            // elements (multiple of 16)
   float inv_scale;
 };
-hipError_t quant_launch(const QuantParams& p, hipStream_t stream);
-
-// Standalone nearest x2 upsample into a channel slice (the graph folds this into the producer conv; kept for
-// op tables that cannot fold it and for tests).
-struct UpsampleParams {
-  const half_t* src;
-  half_t* dst;
-  int H, W, C, src_ld, dst_ld;
-};
-hipError_t upsample2x_launch(const UpsampleParams& p, hipStream_t stream);
+hipError_t quant_desc(const QuantParams& p, LaunchDesc* d);
 
 // ------------------------------------------------------------------------------------------------
 // Fused post-process (one launch): decode three heads -> candidates -> top-1024 -> stable sort -> greedy NMS
@@ -352,7 +350,7 @@ constexpr int kPostBlock = 1024;
 constexpr int kMaxNumClasses = 16383;                // class ids the two-launch form's 14-bit class field holds (unina_load_engine checks)
 constexpr int kPost2Block = 256;                     // threads per workgroup of the mode-2 kernels (= candidate segment size)
 int post_num_blocks(const int gw[3], const int gh[3]);
-hipError_t post_init();   // per device: raise the dynamic-LDS limit of the post-process kernels
+hipError_t post_init();   // the post-process table, the step-wise API's kernels included
 hipError_t postprocess_launch(const PostParams& p, hipStream_t stream);
 int postprocess_desc(const PostParams& p, LaunchDesc out[2]);   // number of launches (1 or 2), or -1 on error
 

@@ -1256,41 +1256,6 @@ bool post_plan_blocks(PostParams* p) {
   return false;
 }
 
-int postprocess_desc(const PostParams& p, LaunchDesc out[2]) {
-  if (p.mode == 2) {
-    if (p.bstart[3] < 1 || p.bstart[3] > 1024 || !p.ws_full) return -1;
-    out[0].func = reinterpret_cast<const void*>(&post_decode_kernel);
-    out[0].grid = dim3(p.bstart[3]);
-    out[0].block = dim3(kT2);
-    out[0].shmem = (unsigned)sizeof(SmemD);
-    out[1].func = reinterpret_cast<const void*>(&post_nms_kernel);
-    out[1].grid = dim3(kMaxTiles);   // n is only known on the device: tiles past the triangle just draw their ticket
-    out[1].block = dim3(kTN);
-    out[1].shmem = (unsigned)sizeof(SmemN);
-    return 2;
-  }
-  const int nb = post_num_blocks(p.gw, p.gh);
-  if (nb < 1 || nb > kPostBlock) return -1;
-  out[0].func = reinterpret_cast<const void*>(&postprocess_kernel);
-  out[0].grid = dim3(nb);
-  out[0].block = dim3(kPostBlock);
-  out[0].shmem = (unsigned)kPostSmemBytes;
-  return 1;
-}
-
-hipError_t postprocess_launch(const PostParams& p, hipStream_t stream) {
-  LaunchDesc d[2];
-  const int n = postprocess_desc(p, d);
-  if (n < 1) return hipErrorInvalidValue;
-  PostParams copy = p;
-  void* args[] = {&copy};
-  for (int k = 0; k < n; ++k) {
-    hipError_t e = hipLaunchKernel(d[k].func, d[k].grid, d[k].block, args, d[k].shmem, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
 // ================================================================================================ step-wise API
 // The reference's seven entry points (gpu_postprocess.h:42-80 / gpu_postprocess.cu:267-442), deterministic:
 //   decode_yolo_head appends the head's survivors in row-major order at the running counter (records past
@@ -1359,21 +1324,49 @@ __global__ __launch_bounds__(kPostBlock) void compact_valid_kernel(const GpuDete
   if (tid == 0) *num_selected = tot;
 }
 
+// The post-process table: the engine's forms and the step-wise API's kernels.
+enum { kPostOne = 0, kPostDecode, kPostNms };
+const struct { const char* name; const void* fn; } kPostKernelTable[] = {
+    {"postprocess_kernel", reinterpret_cast<const void*>(&postprocess_kernel)},
+    {"post_decode_kernel", reinterpret_cast<const void*>(&post_decode_kernel)},
+    {"post_nms_kernel", reinterpret_cast<const void*>(&post_nms_kernel)},
+    {"decode_head_append_kernel", reinterpret_cast<const void*>(&decode_head_append_kernel)},
+    {"nms_inplace_kernel", reinterpret_cast<const void*>(&nms_inplace_kernel)},
+    {"compact_valid_kernel", reinterpret_cast<const void*>(&compact_valid_kernel)},
+};
 
 }  // namespace
 
-// hipFuncSetAttribute applies to the CURRENT device: called by unina_load_engine after hipSetDevice (one handle per GPU)
-// and by init_postprocess_resources.
-hipError_t post_init() {
-  const void* fns[] = {reinterpret_cast<const void*>(postprocess_kernel), reinterpret_cast<const void*>(decode_head_append_kernel),
-                       reinterpret_cast<const void*>(nms_inplace_kernel), reinterpret_cast<const void*>(compact_valid_kernel)};
-  for (const void* f : fns) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPostSmemBytes);
+// called by unina_load_engine after hipSetDevice (one handle per GPU) and by init_postprocess_resources
+hipError_t post_init() { return set_lds_limits(kPostKernelTable); }
+
+int postprocess_desc(const PostParams& p, LaunchDesc out[2]) {
+  auto row = [&](int k, dim3 grid, dim3 block, size_t shmem) {
+    return LaunchDesc{kPostKernelTable[k].fn, grid, block, (unsigned)shmem, kPostKernelTable[k].name};
+  };
+  if (p.mode == 2) {
+    if (p.bstart[3] < 1 || p.bstart[3] > 1024 || !p.ws_full) return -1;
+    out[0] = row(kPostDecode, dim3(p.bstart[3]), dim3(kT2), sizeof(SmemD));
+    out[1] = row(kPostNms, dim3(kMaxTiles), dim3(kTN), sizeof(SmemN));   // n is only known on the device: tiles past the triangle just draw their ticket
+    return 2;
+  }
+  const int nb = post_num_blocks(p.gw, p.gh);
+  if (nb < 1 || nb > kPostBlock) return -1;
+  out[0] = row(kPostOne, dim3(nb), dim3(kPostBlock), kPostSmemBytes);
+  return 1;
+}
+
+hipError_t postprocess_launch(const PostParams& p, hipStream_t stream) {
+  LaunchDesc d[2];
+  const int n = postprocess_desc(p, d);
+  if (n < 1) return hipErrorInvalidValue;
+  PostParams copy = p;
+  void* args[] = {&copy};
+  for (int k = 0; k < n; ++k) {
+    hipError_t e = launch_desc(d[k], args, stream);
     if (e != hipSuccess) return e;
   }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(post_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemD));
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(post_nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemN));
+  return hipSuccess;
 }
 
 }  // namespace unina

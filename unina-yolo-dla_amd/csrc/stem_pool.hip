@@ -292,66 +292,37 @@ __global__ __launch_bounds__(kStemNT) void stem_tile_kernel(const StemParams p) 
   }
 }
 
-template <typename T, int CO>
-constexpr unsigned stem_tile_smem() { return StemTile<T, CO>::SMEM; }
-
-// per device: the fp32 / wide instantiations stage more than the default 64 KB of dynamic LDS
-hipError_t stem_init() {
-  struct { const void* fn; unsigned smem; } ks[] = {
-      {reinterpret_cast<const void*>(&stem_tile_kernel<half_t, 32>), stem_tile_smem<half_t, 32>()},
-      {reinterpret_cast<const void*>(&stem_tile_kernel<half_t, 64>), stem_tile_smem<half_t, 64>()},
-      {reinterpret_cast<const void*>(&stem_tile_kernel<float, 32>), stem_tile_smem<float, 32>()},
-      {reinterpret_cast<const void*>(&stem_tile_kernel<float, 64>), stem_tile_smem<float, 64>()},
-      {reinterpret_cast<const void*>(&stem_tile_kernel<s16_t, 32>), stem_tile_smem<s16_t, 32>()},
-      {reinterpret_cast<const void*>(&stem_tile_kernel<s16_t, 64>), stem_tile_smem<s16_t, 64>()}};
-  for (const auto& k : ks) {
-    hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.smem);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
+namespace {
+struct StemKernel {
+  int dtype, co;
+  bool tiled;          // stem_tile_kernel (staged through LDS), otherwise the one-thread-per-pixel stem_conv_kernel
+  const char* name;
+  void (*fn)(const StemParams);
+  unsigned smem;
+};
+#define STEM(T, DT, TN, CO)                                                                              \
+  {DT, CO, true, "stem_tile_kernel<" TN "," #CO ">", stem_tile_kernel<T, CO>, StemTile<T, CO>::SMEM},      \
+  {DT, CO, false, "stem_conv_kernel<" TN "," #CO ">", stem_conv_kernel<T, CO>, 0}
+const StemKernel kStemKernels[] = {STEM(half_t, kF16, "f16", 32), STEM(half_t, kF16, "f16", 64), STEM(float, kF32, "f32", 32),
+                                   STEM(float, kF32, "f32", 64), STEM(s16_t, kS16, "s16", 32), STEM(s16_t, kS16, "s16", 64)};
+#undef STEM
+}  // namespace
 
 hipError_t stem_desc(const StemParams& p, LaunchDesc* out) {
   if (!p.wt) return hipErrorInvalidValue;
-  out->block = dim3(256);
   static const bool legacy = getenv("UNINA_STEM_V1") && getenv("UNINA_STEM_V1")[0] == '1';   // the one-thread-per-pixel form
   // The form depends on the SHAPE only, never on the pointer of the frame at hand: the captured frame graph's stem node is
   // re-pointed per frame (hipGraphExecKernelNodeSetParams) and must keep its function, grid and block. The tiled kernel's aligned
   // 16-byte row loads need W % 4 == 0 and a 16-byte aligned tensor -- which unina_set_tensor_address / unina_infer guarantee
   // (they refuse any other address with UNINA_ERR_ARG).
-  if (!legacy && (p.W & 3) == 0 && p.dst_ld == p.Co) {
-    out->block = dim3(kStemNT);
-    out->grid = dim3(((p.Ho + kStemTH - 1) / kStemTH) * ((p.Wo + kStemTW - 1) / kStemTW));
-    if (p.Co == 32 && p.dtype == kF16) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<half_t, 32>); out->shmem = stem_tile_smem<half_t, 32>(); }
-    else if (p.Co == 64 && p.dtype == kF16) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<half_t, 64>); out->shmem = stem_tile_smem<half_t, 64>(); }
-    else if (p.Co == 32 && p.dtype == kF32) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<float, 32>); out->shmem = stem_tile_smem<float, 32>(); }
-    else if (p.Co == 64 && p.dtype == kF32) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<float, 64>); out->shmem = stem_tile_smem<float, 64>(); }
-    else if (p.Co == 32 && p.dtype == kS16) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<s16_t, 32>); out->shmem = stem_tile_smem<s16_t, 32>(); }
-    else if (p.Co == 64 && p.dtype == kS16) { out->func = reinterpret_cast<const void*>(&stem_tile_kernel<s16_t, 64>); out->shmem = stem_tile_smem<s16_t, 64>(); }
-    else return hipErrorInvalidValue;
+  const bool tiled = !legacy && (p.W & 3) == 0 && p.dst_ld == p.Co;
+  for (const StemKernel& k : kStemKernels) {
+    if (k.dtype != p.dtype || k.co != p.Co || k.tiled != tiled) continue;
+    if (tiled) *out = {reinterpret_cast<const void*>(k.fn), dim3(((p.Ho + kStemTH - 1) / kStemTH) * ((p.Wo + kStemTW - 1) / kStemTW)), dim3(kStemNT), k.smem, k.name};
+    else *out = {reinterpret_cast<const void*>(k.fn), dim3((p.Ho * p.Wo + 127) / 128), dim3(256), 0, k.name};   // 128 pixels x two channel halves per workgroup
     return hipSuccess;
   }
-  out->grid = dim3((p.Ho * p.Wo + 127) / 128);        // 128 pixels x two channel halves per 256-thread workgroup
-  out->shmem = 0;
-  if (p.Co == 32 && p.dtype == kF16) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<half_t, 32>);
-  else if (p.Co == 64 && p.dtype == kF16) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<half_t, 64>);
-  else if (p.Co == 32 && p.dtype == kF32) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<float, 32>);
-  else if (p.Co == 64 && p.dtype == kF32) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<float, 64>);
-  else if (p.Co == 32 && p.dtype == kS16) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<s16_t, 32>);
-  else if (p.Co == 64 && p.dtype == kS16) out->func = reinterpret_cast<const void*>(&stem_conv_kernel<s16_t, 64>);
-  else return hipErrorInvalidValue;
-  return hipSuccess;
-}
-
-hipError_t stem_launch(const StemParams& p, hipStream_t stream, dim3* grid_out, dim3* block_out) {
-  LaunchDesc d;
-  hipError_t e = stem_desc(p, &d);
-  if (e != hipSuccess) return e;
-  if (grid_out) *grid_out = d.grid;
-  if (block_out) *block_out = d.block;
-  StemParams copy = p;
-  void* args[] = {&copy};
-  return hipLaunchKernel(d.func, d.grid, d.block, args, d.shmem, stream);
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------- SPPF pool
@@ -538,20 +509,32 @@ __global__ __launch_bounds__(256) void sppf_pool_split_kernel(const PoolParams p
   }
 }
 
-hipError_t sppf_pool_launch(const PoolParams& p, hipStream_t stream, dim3* grid_out, dim3* block_out) {
-  constexpr int CH = 32;
-  if (p.C % CH) return hipErrorInvalidValue;
-  dim3 grid(p.H, p.C / CH), block(256);
+namespace {
+constexpr int kPoolCH = 32;   // channels per workgroup
+struct PoolKernel {
+  int dtype;
+  const char* name;
+  void (*fn)(const PoolParams);
+};
+const PoolKernel kPoolKernels[] = {
+    {kF16, "sppf_pool_kernel<f16,32>", sppf_pool_kernel<half_t, kPoolCH>},
+    {kF32, "sppf_pool_kernel<f32,32>", sppf_pool_kernel<float, kPoolCH>},
+    {kI8, "sppf_pool_kernel<i8,32>", sppf_pool_kernel<signed char, kPoolCH>},   // one scale per buffer: max commutes with it
+    {kS16, "sppf_pool_split_kernel<32>", sppf_pool_split_kernel<kPoolCH>},
+};
+}  // namespace
+
+hipError_t sppf_pool_desc(const PoolParams& p, LaunchDesc* d) {
+  if (p.C % kPoolCH) return hipErrorInvalidValue;
   const size_t esz = (p.dtype == kF32 || p.dtype == kS16) ? 4 : (p.dtype == kI8 ? 1 : 2);
-  const size_t smem = (size_t)3 * p.W * CH * esz;
+  const size_t smem = (size_t)3 * p.W * kPoolCH * esz;
   if (smem > 64 * 1024) return hipErrorInvalidValue;
-  if (grid_out) *grid_out = grid;
-  if (block_out) *block_out = block;
-  if (p.dtype == kS16) sppf_pool_split_kernel<CH><<<grid, block, smem, stream>>>(p);
-  else if (p.dtype == kF32) sppf_pool_kernel<float, CH><<<grid, block, smem, stream>>>(p);
-  else if (p.dtype == kI8) sppf_pool_kernel<signed char, CH><<<grid, block, smem, stream>>>(p);  // one scale per buffer: max commutes with it
-  else sppf_pool_kernel<half_t, CH><<<grid, block, smem, stream>>>(p);
-  return hipGetLastError();
+  for (const PoolKernel& k : kPoolKernels)
+    if (k.dtype == p.dtype) {
+      *d = {reinterpret_cast<const void*>(k.fn), dim3(p.H, p.C / kPoolCH), dim3(256), (unsigned)smem, k.name};
+      return hipSuccess;
+    }
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------- quantise
@@ -574,34 +557,22 @@ __global__ __launch_bounds__(256) void quant_f16_i8_kernel(const QuantParams p) 
   }
 }
 
-hipError_t quant_launch(const QuantParams& p, hipStream_t stream) {
+namespace {
+const struct { const char* name; void (*fn)(const QuantParams); } kQuantKernels[] = {{"quant_f16_i8_kernel", quant_f16_i8_kernel}};
+}  // namespace
+
+hipError_t quant_desc(const QuantParams& p, LaunchDesc* d) {
   if (p.n % 16) return hipErrorInvalidValue;
   size_t blocks = (p.n / 16 + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  quant_f16_i8_kernel<<<(int)blocks, 256, 0, stream>>>(p);
-  return hipGetLastError();
+  if (blocks > 2048) blocks = 2048;   // (grid-stride loop)
+  *d = {reinterpret_cast<const void*>(kQuantKernels[0].fn), dim3((unsigned)blocks), dim3(256), 0, kQuantKernels[0].name};
+  return hipSuccess;
 }
 
-// ---------------------------------------------------------------------------------------------- upsample
-__global__ __launch_bounds__(256) void upsample2x_kernel(const UpsampleParams p) {
-  const int vec = p.C / 8;
-  const size_t total = (size_t)4 * p.H * p.W * vec;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-    const int cv = t % vec;
-    const size_t pix = t / vec;
-    const int ox = pix % (2 * p.W), oy = pix / (2 * p.W);
-    const half8 v = *reinterpret_cast<const half8*>(p.src + ((size_t)(oy >> 1) * p.W + (ox >> 1)) * p.src_ld + cv * 8);
-    *reinterpret_cast<half8*>(p.dst + pix * p.dst_ld + cv * 8) = v;
-  }
-}
-
-hipError_t upsample2x_launch(const UpsampleParams& p, hipStream_t stream) {
-  if (p.C % 8) return hipErrorInvalidValue;
-  const size_t total = (size_t)4 * p.H * p.W * (p.C / 8);
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  upsample2x_kernel<<<blocks, 256, 0, stream>>>(p);
-  return hipGetLastError();
+hipError_t stem_pool_init() {
+  hipError_t e = set_lds_limits(kStemKernels);
+  if (e == hipSuccess) e = set_lds_limits(kPoolKernels);
+  return e == hipSuccess ? set_lds_limits(kQuantKernels) : e;
 }
 
 }  // namespace unina
