@@ -141,6 +141,48 @@ int unina_infer_async(unina_engine_t *e, const float *d_images_nchw, float conf_
 int unina_postprocess_async(unina_engine_t *e, float conf_threshold, float iou_threshold, float conformal_q,
                             GpuDetection *d_out, int *d_out_count, hipStream_t stream);
 
+/* ------------------------------------------------------------------ data mining (active_learning.py, mine_data.py)
+ * The reference's third consumer of the forward graph: the active-learning loop pushes an unlabeled image set through the
+ * detector and keeps, per image, a difficulty score and an embedding, then picks a diverse subset. These calls run BEHIND the
+ * raw-head forward (unina_enqueue's launch sequence); the frame path (unina_infer*) is untouched by them.
+ *
+ * scores8 (UNINA_MINE_SCORES floats), p = 1/(1+exp(-logit)) over the three cls planes:
+ *   [0..2] per level P2,P3,P4: max over classes and cells of -(p*log(p+1e-10) + (1-p)*log(1-p+1e-10))   active_learning.py:292-294
+ *   [3..5] per level: max over cells of 1 - |max_c p_c - 0.5| * 2                                        active_learning.py:298-301
+ *   [6] = max of [0..2]: the image's score in mode "entropy"; [7] = max of [3..5]: mode "loc_var"        active_learning.py:303
+ * embedding: mean over H, W of the backbone's P4 map before SPPF (features[2], the output of backbone.stage3_c3k2;
+ * adaptive_avg_pool2d, active_learning.py:57-60,90-91), fp32 accumulation in a fixed order: two runs give identical bits.
+ * Graph (B) engines (qat.py models: no .backbone) score but do not embed: UNINA_ERR_UNSUPPORTED. */
+#define UNINA_MINE_SCORES 8
+
+/* Length of the embedding (channels of the pooled map: 8 * base_channels of the model); < 0: -error code. */
+int unina_embedding_dim(const unina_engine_t *e);
+
+/* One iteration of the loops at active_learning.py:52-94 and :255-303 for one image: forward (all six head planes written,
+ * as unina_enqueue) + scores + pooled embedding, enqueued on `stream`; nothing is synchronised.
+ *   d_images_nchw : as unina_infer; NULL = keep the current binding
+ *   d_scores8     : device, UNINA_MINE_SCORES floats      d_embed : device, unina_embedding_dim floats, or NULL (scores only)
+ * Both may be rows of caller-owned [N,8] / [N,D] matrices, so the embeddings stay on the device for unina_kcenter. */
+int unina_mine_async(unina_engine_t *e, const float *d_images_nchw, float *d_scores8, float *d_embed, hipStream_t stream);
+
+/* The same with the results in HOST memory; synchronous (`.item()` / `.cpu().numpy()`, active_learning.py:93,294,301). */
+int unina_mine(unina_engine_t *e, const float *d_images_nchw, float *scores8, float *embed, hipStream_t stream);
+
+/* Scores only, from the six head tensors currently bound / owned (active_learning.py:276-303 on given outputs): what
+ * unina_postprocess_async is to unina_infer_async. */
+int unina_mine_heads_async(unina_engine_t *e, float *d_scores8, hipStream_t stream);
+
+/* K-center greedy (coreset_selection_kcenter, active_learning.py:139-161) on device data; no engine handle.
+ *   d_embeddings : device, fp32 [n, dim] row-major, 16-byte aligned      d_selected : device, k ints (selection order)
+ *   first_index  : the reference's random start (np.random.randint(n), :140)
+ *   d_min_dist   : device, n floats of workspace, or NULL: the call allocates it and then returns only after the selection
+ *                  has finished (it frees the workspace). With a workspace nothing is synchronised.
+ * Every step measures sqrt(sum (a-b)^2) to the row chosen last, keeps the running minimum, forces chosen rows to -1 and takes
+ * the arg-max with the lowest index winning ties (numpy's argmax); the next step reads the chosen index from device memory,
+ * so the k-1 steps run without a host round-trip. UNINA_ERR_ARG: null / misaligned pointer, k > n, first_index outside [0, n). */
+int unina_kcenter(const float *d_embeddings, int n, int dim, int k, int first_index, int *d_selected, float *d_min_dist,
+                  hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

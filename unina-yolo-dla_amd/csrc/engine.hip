@@ -20,6 +20,7 @@
 
 #include "engine_format.h"
 #include "kernels.h"
+#include "mining.h"
 
 using namespace unina;
 
@@ -130,6 +131,10 @@ struct unina_engine {
   int stem_op = -1;
   StemParams f_stem;
   PostParams f_post;
+  // data mining (mining.hip): the conv op whose output slice is the embedding's source (backbone.stage3_c3k2.cv3; -1: the
+  // engine has none, graph (B)), and the partial / staging workspace allocated by the first mining call
+  int embed_op = -1;
+  float* d_mine_ws = nullptr;
   std::string err;
 };
 
@@ -1359,6 +1364,8 @@ int load_host(const char* path, unina_engine* e, std::vector<char>* blob_out) {
     if (e->out_buf[i] < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks a head output buffer");
   }
   if (e->images_buf < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks the images input buffer");
+  for (size_t i = 0; i < e->ops.size(); ++i)   // graph (A)'s P4 before SPPF: what the mining path pools (unina_mine*)
+    if (e->ops[i].d.kind == kOpConv && e->ops[i].d.nseg == 1 && !strcmp(e->ops[i].d.name, "backbone.stage3_c3k2.cv3")) e->embed_op = (int)i;
   // the decode reads num_classes planes of every cls buffer; the two-launch NMS carries a class id in 14 bits
   if (e->h.num_classes == 0 || e->h.num_classes > (uint32_t)kMaxNumClasses)
     return bail(UNINA_ERR_UNSUPPORTED, "num_classes must be 1..16383");
@@ -1501,7 +1508,7 @@ void unina_unload_engine(unina_engine_t* e) {
   (void)hipSetDevice(e->device);
   drop_graph(e);
   if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
-  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result};
+  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (e->h_result) (void)hipHostFree(e->h_result);
@@ -1658,6 +1665,116 @@ int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou,
   if (n < 0 || n > MAX_DETECTIONS) return fail(e, UNINA_ERR_STATE, "post-process returned count %d", n);
   if (!copied) memcpy(out, e->h_result->det, sizeof(GpuDetection) * (size_t)n);   // (the UNINA_TIMING branch has copied them already)
   *out_count = n;
+  return UNINA_OK;
+}
+
+// ---- data mining (active_learning.py:31-99, 234-305): scores and embedding behind the raw-head forward ----
+static int embed_channels(const unina_engine* e) {
+  const SegDesc& sg = e->ops[e->embed_op].d.seg[0];
+  // a narrower model embedded at the file's width keeps its own channels first (export.py, statedict.widen_state_dict)
+  const uint32_t own = e->h.model_base_channels ? 8 * e->h.model_base_channels : sg.n_count;
+  return (int)(own < sg.n_count ? own : sg.n_count);
+}
+
+int unina_embedding_dim(const unina_engine_t* e) {
+  if (!e) return -UNINA_ERR_ARG;
+  if (e->embed_op < 0) return -UNINA_ERR_UNSUPPORTED;
+  return embed_channels(e);
+}
+
+// Fills the launch parameters from the current buffer addresses; embed: also the pooled slice (checked here, per call:
+// fusion can be switched at run time). The workspace is allocated on first use: [partials | 8 scores | embedding] (the last
+// two are unina_mine's staging).
+static int fill_mine_params(unina_engine* e, MineParams* mp, bool embed, float** stage) {
+  memset(mp, 0, sizeof *mp);
+  for (int i = 0; i < 3; ++i) {
+    const Buffer& c = e->bufs[e->out_buf[2 * i]];
+    if (!c.ptr) return fail(e, UNINA_ERR_STATE, "head tensor '%s' has no address", c.d.name);
+    mp->cls[i] = static_cast<const float*>(c.ptr);
+    mp->cells[i] = (int)(c.d.h * c.d.w);
+  }
+  mp->num_classes = (int)e->h.num_classes;
+  MineParams all = *mp;   // the workspace is sized for a call WITH the embedding, whatever this one asks for
+  if (e->embed_op >= 0) {
+    const PlannedOp& op = e->ops[e->embed_op];
+    const SegDesc& sg = op.d.seg[0];
+    const Buffer& b = e->bufs[sg.dst_buf];
+    all.hw = (int)(b.d.h * b.d.w);
+    all.ctot = (int)b.d.c;
+    all.coff = (int)sg.dst_coff;
+    all.c = embed_channels(e);
+    all.act = act_dtype_of(b.d.dtype);
+    all.scale = b.d.scale;
+    all.lo_off = lo_plane(b.d);
+    if (embed) {
+      if (all.act < 0 || all.c < kGapChunk || all.c % kGapChunk || all.coff % kGapChunk || all.ctot % kGapChunk || all.c > kGapMaxChannels)
+        return fail(e, UNINA_ERR_UNSUPPORTED, "embedding: slice [%d, %d) of '%s' does not fit the pool kernel's 8-channel chunks", all.coff, all.coff + all.c, b.d.name);
+      // the slice must be written to memory by whatever launches the op now: its own conv, or a fused C3k2 block whose OUTPUT
+      // it is (a block's output is always stored; only the tensors between its first conv and cv3 stay in LDS)
+      if (e->fuse && op.fuse_role == 2) {
+        bool stored = false;
+        for (const PlannedOp& g : e->ops) stored = stored || (g.fuse_role == 1 && g.fuse_kind == 1 && g.group_last == e->embed_op);
+        if (!stored) return fail(e, UNINA_ERR_UNSUPPORTED, "embedding: '%s' is internal to a fused launch and never written (unina_set_fusion(e, 0) writes it)", op.d.name);
+      }
+      all.src = b.ptr;
+    }
+  } else if (embed) {
+    return fail(e, UNINA_ERR_UNSUPPORTED, "embedding: this engine has no 'backbone.stage3_c3k2.cv3' (graph (B) models have no .backbone; the reference's extract_backbone_embeddings takes another route for them, which is not covered)");
+  }
+  mine_plan(&all);
+  const size_t part = (mine_workspace_floats(all) + 3) & ~(size_t)3;
+  if (!e->d_mine_ws) HIPCHK(e, hipMalloc(&e->d_mine_ws, sizeof(float) * (part + UNINA_MINE_SCORES + (size_t)(all.c > 0 ? all.c : 1))));
+  *mp = all;
+  mp->score_partial = e->d_mine_ws;
+  mp->gap_partial = e->d_mine_ws + (((size_t)2 * all.blk0[3] + 3) & ~(size_t)3);
+  if (stage) *stage = e->d_mine_ws + part;
+  return UNINA_OK;
+}
+
+int unina_mine_heads_async(unina_engine_t* e, float* d_scores8, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_scores8 || ((uintptr_t)d_scores8 & 3)) return fail(e, UNINA_ERR_ARG, "unina_mine_heads_async: null / misaligned score pointer");
+  HIPCHK(e, hipSetDevice(e->device));
+  MineParams mp;
+  int rc = fill_mine_params(e, &mp, false, nullptr);
+  if (rc != UNINA_OK) return rc;
+  mp.scores = d_scores8;
+  HIPCHK(e, mine_launch(mp, stream));
+  return UNINA_OK;
+}
+
+int unina_mine_async(unina_engine_t* e, const float* d_images, float* d_scores8, float* d_embed, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_scores8 || ((uintptr_t)d_scores8 & 3) || ((uintptr_t)d_embed & 3)) return fail(e, UNINA_ERR_ARG, "unina_mine_async: null / misaligned result pointer");
+  HIPCHK(e, hipSetDevice(e->device));
+  MineParams mp;
+  int rc = fill_mine_params(e, &mp, d_embed != nullptr, nullptr);   // before any launch: an unsupported engine enqueues nothing
+  if (rc != UNINA_OK) return rc;
+  if (d_images) {
+    rc = unina_set_tensor_address(e, "images", const_cast<float*>(d_images));
+    if (rc != UNINA_OK) return rc;
+  }
+  rc = unina_enqueue(e, stream);   // the raw-head forward: all six fp32 planes are written
+  if (rc != UNINA_OK) return rc;
+  mp.scores = d_scores8;
+  mp.embed = d_embed;
+  HIPCHK(e, mine_launch(mp, stream));
+  return UNINA_OK;
+}
+
+int unina_mine(unina_engine_t* e, const float* d_images, float* scores8, float* embed, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!scores8) return fail(e, UNINA_ERR_ARG, "unina_mine: null score pointer");
+  HIPCHK(e, hipSetDevice(e->device));
+  MineParams mp;
+  float* stage = nullptr;
+  int rc = fill_mine_params(e, &mp, embed != nullptr, &stage);
+  if (rc != UNINA_OK) return rc;
+  rc = unina_mine_async(e, d_images, stage, embed ? stage + UNINA_MINE_SCORES : nullptr, stream);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipStreamSynchronize(stream));
+  HIPCHK(e, hipMemcpy(scores8, stage, sizeof(float) * UNINA_MINE_SCORES, hipMemcpyDeviceToHost));
+  if (embed) HIPCHK(e, hipMemcpy(embed, stage + UNINA_MINE_SCORES, sizeof(float) * (size_t)mp.c, hipMemcpyDeviceToHost));
   return UNINA_OK;
 }
 

@@ -30,7 +30,9 @@ struct FileHeader {          // 128 bytes
   uint32_t strides[3];
   uint64_t blob_bytes;
   uint64_t macs;
-  uint8_t reserved[56];
+  uint32_t model_base_channels;   // != 0: the model is a narrower one embedded at this file's width (export.py: real channels
+                                  // first, zero channels behind them); its own base_channels. 0: the file's width is the model's
+  uint8_t reserved[52];
 };
 static_assert(sizeof(FileHeader) == 128, "FileHeader");
 

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "unina_last_error", "unina_op_count", "unina_get_op_info", "unina_profile_ops", "unina_profile_post", "unina_debug_read_buffer",
     "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_serial_latency",
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
+    "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -101,6 +102,12 @@ def load_library() -> C.CDLL:
     L.unina_debug_dual_timeline.argtypes = [vp, ci, C.POINTER(C.c_longlong), ci, vp]
     L.unina_debug_block_stamps.argtypes = [vp, ci, C.POINTER(C.c_longlong), vp]
     L.unina_serial_latency.argtypes = [vp, C.POINTER(vp), ci, ci, cf, cf, cf, C.POINTER(C.c_double), vp]
+    # data mining (csrc/mining.hip)
+    L.unina_embedding_dim.argtypes = [vp]
+    L.unina_mine_async.argtypes = [vp, vp, vp, vp, vp]
+    L.unina_mine.argtypes = [vp, vp, vp, vp, vp]
+    L.unina_mine_heads_async.argtypes = [vp, vp, vp]
+    L.unina_kcenter.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
     # multi-GPU: RCCL gather of detection slots behind the C ABI (csrc/comm.hip)
     L.unina_comm_unique_id.argtypes = [vp]
     L.unina_comm_init.argtypes = [C.POINTER(vp), vp, ci, ci, ci]
@@ -287,6 +294,51 @@ class Engine:
                                                    _stream_ptr(stream)))
         return self.unpack(self._det_buf)
 
+    # -- data mining (active_learning.py: difficulty scores + P4 embedding) ------------------------------------
+    @property
+    def embedding_dim(self) -> int:
+        """Length of the embedding (channels of the backbone's P4 map); raises for an engine without one (graph (B))."""
+        d = self.L.unina_embedding_dim(self.h)
+        if d < 0:
+            raise EngineError(f"[{ERRORS.get(-d, -d)}] this engine has no embedding (graph (B) models have no .backbone)")
+        return d
+
+    def _checked_images_ptr(self, images):
+        if images is None:
+            return None
+        if images is not getattr(self, "_images", None):
+            assert images.is_cuda and images.dtype == _torch().float32 and images.is_contiguous()
+            assert tuple(images.shape) == (1, 3, self.height, self.width), images.shape
+            self._images = images
+        return images.data_ptr()
+
+    def mine(self, images, embed: bool = True, stream=None):
+        """Forward + difficulty scores + pooled embedding of one frame, synchronous: (scores[8], embed[D] or None).
+        scores: [0..2] entropy score per level, [3..5] loc_var score per level, [6] / [7] the image's score in mode
+        "entropy" / "loc_var" (include/unina_mi355.h at UNINA_MINE_SCORES)."""
+        scores = np.empty(8, dtype=np.float32)
+        emb = np.empty(self.embedding_dim, dtype=np.float32) if embed else None
+        self._check(self.L.unina_mine(self.h, self._checked_images_ptr(images), scores.ctypes.data,
+                                      emb.ctypes.data if embed else None, _stream_ptr(stream)))
+        return scores, emb
+
+    def mine_async(self, images, scores_out, embed_out=None, stream=None) -> None:
+        """Asynchronous: results go to the CUDA fp32 tensors `scores_out` (8 values) and `embed_out` (D values or None),
+        e.g. rows of [N,8] / [N,D] matrices that stay on the device for kcenter()."""
+        assert scores_out.is_cuda and scores_out.dtype == _torch().float32 and scores_out.is_contiguous() and scores_out.numel() >= 8
+        if embed_out is not None:
+            assert embed_out.is_cuda and embed_out.dtype == _torch().float32 and embed_out.is_contiguous()
+            assert embed_out.numel() >= self.embedding_dim
+        self._check(self.L.unina_mine_async(self.h, self._checked_images_ptr(images), scores_out.data_ptr(),
+                                            None if embed_out is None else embed_out.data_ptr(), _stream_ptr(stream)))
+
+    def mine_heads(self, stream=None) -> np.ndarray:
+        """The 8 scores of whatever the six output tensors currently hold (synchronous)."""
+        torch = _torch()
+        out = torch.zeros(8, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._check(self.L.unina_mine_heads_async(self.h, out.data_ptr(), _stream_ptr(stream)))
+        return out.cpu().numpy()
+
     @staticmethod
     def unpack(buf) -> np.ndarray:
         """int32 result tensor (see infer_async) -> structured ndarray of the kept detections."""
@@ -410,6 +462,24 @@ class Engine:
         self._check(self.L.unina_debug_read_buffer(self.h, name.encode(), out.ctypes.data, out.size, C.byref(c),
                                                    C.byref(h), C.byref(w)))
         return out.reshape(c.value, h.value, w.value)
+
+
+def kcenter(embeddings, k: int, first_index: int, stream=None) -> np.ndarray:
+    """K-center greedy on the GPU (coreset_selection_kcenter's loop, active_learning.py:139-161): the `k` selected row
+    indices in selection order. `embeddings`: [N,D] fp32, a CUDA tensor (used in place) or an ndarray (uploaded)."""
+    L = load_library()
+    torch = _torch()
+    if not isinstance(embeddings, torch.Tensor):
+        embeddings = torch.from_numpy(np.ascontiguousarray(embeddings, dtype=np.float32)).cuda()
+    assert embeddings.is_cuda and embeddings.dtype == torch.float32 and embeddings.is_contiguous() and embeddings.dim() == 2
+    n, d = embeddings.shape
+    with torch.cuda.device(embeddings.device):
+        sel = torch.zeros(max(k, 1), dtype=torch.int32, device=embeddings.device)
+        ws = torch.empty(n, dtype=torch.float32, device=embeddings.device)
+        rc = L.unina_kcenter(embeddings.data_ptr(), n, d, k, first_index, sel.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_kcenter failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, k={k}, first_index={first_index})")
+        return sel.cpu().numpy()[:k].astype(np.int64)
 
 
 def calibrate_amax(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, device: int = 0,

@@ -39,7 +39,7 @@ OP_CONV, OP_STEM, OP_SPPF_POOL, OP_UPSAMPLE, OP_QUANT = 1, 2, 3, 4, 5
 SEG_UP2, SEG_PLANAR_F32 = 1, 2
 BN_EPS = 1e-5
 
-_HDR = struct.Struct("<8sII3II2II3IQQ56x")
+_HDR = struct.Struct("<8sII3II2II3IQQI52x")   # last word: base_channels of a narrower embedded model (0 = none)
 _BUF = struct.Struct("<3III40sf")
 _SEG = struct.Struct("<6IQQffQ8x")
 _OP_HEAD = struct.Struct("<4I2I2iI4If")
@@ -554,7 +554,7 @@ class EngineBuilder:
         g = self.g
         out = bytearray()
         out += _HDR.pack(MAGIC, VERSION, self.precision, 3, g.in_h, g.in_w, g.num_classes, len(self.buffers), len(self.ops),
-                         3, *STRIDES, len(self.blob), g.macs())
+                         3, *STRIDES, len(self.blob), g.macs(), self.narrow_base_channels)
         for name, h, w, c, dtype, flags, scale in self.buffers:
             out += _BUF.pack(h, w, c, dtype, flags, name.encode()[:39], scale)
         for op in self.ops:
@@ -769,8 +769,9 @@ def export_qat_checkpoint(ck: Dict[str, np.ndarray], path: str, in_h: int = 640,
 def read_engine_header(path: str) -> dict:
     with open(path, "rb") as f:
         raw = f.read(_HDR.size)
-    (magic, version, precision, in_c, in_h, in_w, nc, n_buf, n_ops, n_heads, s0, s1, s2, blob, macs) = _HDR.unpack(raw)
+    (magic, version, precision, in_c, in_h, in_w, nc, n_buf, n_ops, n_heads, s0, s1, s2, blob, macs, model_bc) = _HDR.unpack(raw)
     if magic != MAGIC:
         raise ValueError("not a UNINAENG file")
     return dict(version=version, precision=precision, in_c=in_c, in_h=in_h, in_w=in_w, num_classes=nc,
-                n_buffers=n_buf, n_ops=n_ops, n_heads=n_heads, strides=(s0, s1, s2), blob_bytes=blob, macs=macs)
+                n_buffers=n_buf, n_ops=n_ops, n_heads=n_heads, strides=(s0, s1, s2), blob_bytes=blob, macs=macs,
+                model_base_channels=model_bc)
