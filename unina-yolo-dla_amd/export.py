@@ -1,13 +1,16 @@
-"""Engine builder: state_dict of graph (A)  ->  .une engine file for libunina_mi355.so.
+"""Engine builder: state_dict of graph (A) or (B) (graph.py)  ->  .une engine file for libunina_mi355.so.
 
 Plays the role of the reference's ``export_trt.py::export_pipeline`` (export_trt.py:497-566:
 ONNX export -> TensorRT build -> serialized plan) for the MI355X engine. Instead of an opaque plan
-the output is an explicit table of FUSED ops over NHWC fp16 activation buffers:
+the output is an explicit table of FUSED ops over NHWC fp16 activation buffers. The table is DERIVED from graph.py's node
+list (EngineBuilder._lower walks Graph.blocks; layer names, widths, strides and concat orders are written only there);
+what this module adds are the fusion rules, each decided by a node's kind and users:
 
 * BatchNorm (eval) is folded into the conv:  W' = W*g/sqrt(var+eps),  b' = beta - mean*g/sqrt(var+eps)
   (model.py:41-50; eps = 1e-5); ReLU is an epilogue flag.
 * every ``torch.cat`` (model.py:110,132,257,260,264,267) becomes a shared buffer: producers write
-  channel slices, so concat costs nothing.
+  channel slices (offset = the channels of the concat's earlier members), the members' other users read them, so concat
+  costs nothing.
 * C3k2 ``cv1``/``cv2`` (same input, model.py:107-108) and the head's ``cls_branch.0``/``reg_branch.0``
   (same input, model.py:303) are merged into one implicit GEMM with two output slices; the head's
   ``.1`` and ``.2`` layers run as one two-group launch.
@@ -16,7 +19,7 @@ the output is an explicit table of FUSED ops over NHWC fp16 activation buffers:
   written to its 2x2 block of the FPN concat buffer).
 * the SPPF pool pyramid (model.py:129-131) is ONE op producing y1,y2,y3 into the 4-way concat buffer.
 
-67 reference convs -> 52 launches + 1 pool.
+Graph (A): 67 reference convs -> 50 conv ops + stem + pool = 52 ops; graph (B): 74 -> 56 + stem + pool = 58.
 """
 from __future__ import annotations
 
@@ -199,10 +202,7 @@ class EngineBuilder:
         self.buffers: List[list] = []   # [name, h, w, c, dtype, flags, scale]
         self.ops: List[Op] = []
         self.blob = bytearray()
-        if self.g.variant == "A":
-            self._lower()
-        else:
-            self._lower_b()
+        self._lower()
         if precision == INT8:
             self._quantize_pass()
         self._finalize()
@@ -225,208 +225,134 @@ class EngineBuilder:
         self.blob += arr.tobytes()
         return off
 
+    # ---- where a node's tensor lives: self.at[node index] = View -------------------------------------
+    def _share(self, name: str, members: List[int]) -> int:
+        """One buffer holding several nodes' tensors side by side, in the listed order: a concat (its producers write
+        channel slices, its members' other users read them) or the merged outputs of sibling convs."""
+        nodes = [self.g.nodes[i] for i in members]
+        b = self.buf(name, nodes[0].h, nodes[0].w, sum(n.c for n in nodes))
+        off = 0
+        for n in nodes:
+            assert n.idx not in self.at, n.name
+            self.at[n.idx] = View(b, off, n.c)
+            off += n.c
+        return b
+
+    def _cat(self, i: int):
+        n = self.g.nodes[i]
+        self.at[i] = View(self._share(n.name, n.srcs), 0, n.c)
+
+    def _own(self, i: int, name: str):
+        """A buffer of its own for node i, unless a concat already holds it."""
+        n = self.g.nodes[i]
+        if i not in self.at:
+            self.at[i] = self.view(name, n.h, n.w, n.c)
+
     # ---- op emitters ---------------------------------------------------------------------------
-    def conv(self, items, src_buf: int, cin: int, k: int, s: int = 1, relu: bool = True,
-             res: Optional[View] = None, bn: bool = True):
-        """items: list of (module, src_coff, dst View, flags). One launch, len(items) output slices."""
-        ih, iw = self._hw(src_buf)
-        p = k // 2
-        oh, ow = (ih + 2 * p - k) // s + 1, (iw + 2 * p - k) // s + 1
-        op = Op(OP_CONV, "+".join(m for m, *_ in items), src_buf, cin, k, s, int(relu), res, (ih, iw), (oh, ow))
-        for module, src_coff, dst, flags in items:
+    def _conv(self, idxs):
+        """Sibling conv nodes (inputs in one buffer, same geometry) -> one launch, one output slice each. A conv whose only
+        user is an `add` (Bottleneck shortcut) or an `up2` stores that node's tensor: the shortcut is the op's `res`,
+        added after the ReLU; the upsample is the SEG_UP2 store into the slice the `up2` owns in its concat."""
+        nodes = self.g.nodes
+        first = nodes[idxs[0]]
+        if first.srcs[0] < 0:
+            return self._stem(first)
+        cin, k, s, bn = first.cin, first.k, first.s, first.kind == "conv"
+        src_buf = self.at[first.srcs[0]].buf
+        op = Op(OP_CONV, "+".join(nodes[i].name for i in idxs), src_buf, cin, k, s, int(bn), None,
+                self._hw(src_buf), (first.h, first.w))
+        for n in (nodes[i] for i in idxs):
+            module, src, out, flags = n.name, self.at[n.srcs[0]], n, 0
+            assert (src.buf, n.kind, n.cin, n.k, n.s, n.h, n.w) == (src_buf, first.kind, cin, k, s, first.h, first.w), module
+            users = [nodes[u] for u in n.users]
+            if [u.kind for u in users] == ["add"]:
+                out = users[0]
+                op.res = self.at[next(x for x in out.srcs if x != n.idx)]
+            elif [u.kind for u in users] == ["up2"]:
+                out, flags = users[0], SEG_UP2
+            self._own(out.idx, out.name)
+            dst = self.at[out.idx]
+            if self.buffers[dst.buf][4] == BUF_F32_PLANAR:
+                flags |= SEG_PLANAR_F32
             if bn:
                 w, f, b = bn_terms(self.sd, module)
             else:
                 w = self.sd[f"{module}.weight"].astype(np.float64)
                 b = self.sd[f"{module}.bias"].astype(np.float64)
                 f = np.ones_like(b)
-            n = w.shape[0]
-            assert w.shape[1] == cin and w.shape[2] == k, (module, w.shape, cin, k)
-            dh, dw = self._hw(dst.buf)
-            want = (2 * oh, 2 * ow) if flags & SEG_UP2 else (oh, ow)
-            assert (dh, dw) == want, (module, (dh, dw), want)
-            assert dst.c == n, (module, dst.c, n)
-            seg = Seg(module, src_coff, n, dst, flags, n_pad=-(-n // 16) * 16)
-            seg.w_raw = np.transpose(w, (0, 2, 3, 1)).reshape(n, k * k * cin)      # [O][(kh,kw,C)]
+            assert w.shape == (n.c, cin, k, k), (module, w.shape, n.c, cin, k)
+            assert self._hw(dst.buf) == (out.h, out.w) and dst.c == n.c, (module, self._hw(dst.buf), dst.c)
+            seg = Seg(module, src.coff, n.c, dst, flags, n_pad=-(-n.c // 16) * 16)
+            seg.w_raw = np.transpose(w, (0, 2, 3, 1)).reshape(n.c, k * k * cin)      # [O][(kh,kw,C)]
             seg.fold, seg.bias, seg.bn = f, b, bn
             op.segs.append(seg)
         self.ops.append(op)
 
-    def c3k2(self, name: str, src: View, dst: View, n: int):
-        """C3k2 (model.py:76-110) -> 2 + 2n launches."""
-        h, w = self._hw(src.buf)
-        cout = dst.c
-        hid = cout // 2
-        cat = self.buf(f"{name}.cat", h, w, 2 * hid)
-        cur = self.view(f"{name}.cv1", h, w, hid)
-        self.conv([(f"{name}.cv1", src.coff, cur, 0), (f"{name}.cv2", src.coff, View(cat, hid, hid), 0)],
-                  src.buf, src.c, 1)
-        for i in range(n):
-            t = self.view(f"{name}.bottlenecks.{i}.cv1", h, w, hid)
-            self.conv([(f"{name}.bottlenecks.{i}.cv1", cur.coff, t, 0)], cur.buf, hid, 1)
-            out = View(cat, 0, hid) if i == n - 1 else self.view(f"{name}.bottlenecks.{i}", h, w, hid)
-            self.conv([(f"{name}.bottlenecks.{i}.cv2", t.coff, out, 0)], t.buf, hid, 3, res=cur)
-            cur = out
-        self.conv([(f"{name}.cv3", 0, dst, 0)], cat, 2 * hid, 1)
+    def _stem(self, n):
+        """The conv that reads the network input: its own op kind, folded fp32 weights [O][(c,kh,kw)]."""
+        images = self.at[-1].buf
+        self._own(n.idx, n.name)
+        w, b = fold_bn(self.sd, n.name)
+        op = Op(OP_STEM, n.name, images, n.cin, n.k, n.s, 1, None, self._hw(images), (n.h, n.w))
+        seg = Seg(n.name, 0, n.c, self.at[n.idx], 0, n_pad=n.c)
+        seg.w_raw, seg.fold, seg.bias = w.reshape(n.c, -1), np.ones(n.c), b
+        op.segs.append(seg)
+        self.ops.append(op)
 
-    def head(self, name: str, feat: View, out_cls: int, out_reg: int):
+    # ---- lowering rules, one per graph.Block kind -------------------------------------------------------
+    def conv(self, blk):
+        self._conv(blk.nodes)
+
+    def c3k2(self, blk):
+        """C3k2 (model.py:76-110) -> 2 + 2n launches: cv1+cv2, per Bottleneck cv1 and cv2(+shortcut), cv3."""
+        cv1, cv2, *bottlenecks, cat, cv3 = blk.nodes
+        self._own(cv3, blk.label or blk.name)
+        self._cat(cat)
+        self._conv([cv1, cv2])
+        for i in bottlenecks:
+            if self.g.nodes[i].kind == "conv":
+                self._conv([i])
+        self._conv([cv3])
+
+    def head(self, blk):
         """DetectionHead (model.py:274-303; qat.py:411-440) -> 3 launches (both branches per launch)."""
-        h, w = self._hw(feat.buf)
-        c = feat.c
-        h0 = self.buf(f"{name}.h0", h, w, 2 * c)
-        h1 = self.buf(f"{name}.h1", h, w, 2 * c)
-        cls, reg = (f"{name}.cls_branch", f"{name}.reg_branch") if self.g.variant == "A" else (f"{name}_cls", f"{name}_reg")
-        self.conv([(f"{cls}.0", feat.coff, View(h0, 0, c), 0),
-                   (f"{reg}.0", feat.coff, View(h0, c, c), 0)], feat.buf, c, 3)
-        self.conv([(f"{cls}.1", 0, View(h1, 0, c), 0),
-                   (f"{reg}.1", c, View(h1, c, c), 0)], h0, c, 3)
-        self.conv([(f"{cls}.2", 0, View(out_cls, 0, self.g.num_classes), SEG_PLANAR_F32),
-                   (f"{reg}.2", c, View(out_reg, 0, 4), SEG_PLANAR_F32)], h1, c, 1,
-                  relu=False, bn=False)
+        pairs = list(zip(blk.nodes[:3], blk.nodes[3:]))                  # (cls.i, reg.i)
+        for j, pair in enumerate(pairs[:-1]):                            # the .2 pair writes the outputs
+            self._share(f"{blk.name}.h{j}", pair)
+        for pair in pairs:
+            self._conv(pair)
 
-    def sppf(self, name: str, src: View, dst: View):
+    def sppf(self, blk):
         """SPPF_DLA (model.py:113-132; qat.py:328-345): cv1 -> ONE pool op (y1,y2,y3) -> cv2 over the 4-way concat."""
-        h, w = self._hw(src.buf)
-        hid = src.c // 2
-        sp = self.buf(f"{name}.cat", h, w, 4 * hid)
-        self.conv([(f"{name}.cv1", src.coff, View(sp, 0, hid), 0)], src.buf, src.c, 1)
-        pool = Op(OP_SPPF_POOL, f"{name}.pool1+pool2+pool3", sp, hid, 5, 1, 0, None, (h, w), (h, w))
-        pool.segs.append(Seg(f"{name}.pool", 0, 3 * hid, View(sp, hid, 3 * hid)))
+        cv1, *pools, cat, cv2 = blk.nodes
+        src = self.at[self.g.nodes[cv1].srcs[0]]
+        if src.c == self.buffers[src.buf][3]:
+            # buffer ORDER is part of the engine file (the activation arena is laid out in it), and the two graphs' SPPFs
+            # have always differed in it: one that reads a buffer of its own (graph B) gets its destination first, like a
+            # C3k2; one that reads a concat slice (graph A: the pre-SPPF P4 also feeds the PAN) gets it after its concat
+            self._own(cv2, blk.name)
+        self._cat(cat)
+        self._conv([cv1])
+        x, y, p = self.at[cv1], [self.at[i] for i in pools], self.g.nodes[pools[0]]
+        pool = Op(OP_SPPF_POOL, f"{blk.name}.pool1+pool2+pool3", x.buf, x.c, p.k, p.s, 0, None, (p.h, p.w), (p.h, p.w))
+        pool.segs.append(Seg(f"{blk.name}.pool", x.coff, sum(v.c for v in y), View(x.buf, y[0].coff, sum(v.c for v in y))))
         self.ops.append(pool)
-        self.conv([(f"{name}.cv2", 0, dst, 0)], sp, 4 * hid, 1)
+        self._own(cv2, blk.name)
+        self._conv([cv2])
 
-    def stem(self, name: str, images: int, dst: View):
-        H, W = self._hw(images)
-        w, b = fold_bn(self.sd, name)
-        c1 = dst.c
-        op = Op(OP_STEM, name, images, 3, 3, 2, 1, None, (H, W), (H // 2, W // 2))
-        seg = Seg(name, 0, c1, dst, 0, n_pad=c1)
-        seg.w_raw, seg.fold, seg.bias = w.reshape(c1, 27), np.ones(c1), b      # stem: folded fp32 [O][(c,kh,kw)]
-        op.segs.append(seg)
-        self.ops.append(op)
-
-    # ---- graph (B): UNINA_YOLO_DLA_QAT.forward (qat.py:443-491) -------------------------------------------
-    def _lower_b(self):
-        g = self.g
-        bc = g.base_channels
-        c1, c2, c3, c4, c5 = bc, 2 * bc, 4 * bc, 8 * bc, 16 * bc
-        H, W = g.in_h, g.in_w
-        images = self.buf("images", H, W, 3, BUF_F32_NCHW_IN, BUF_INPUT)
-        outs = {}
-        for name, s in zip(OUTPUT_NAMES, (4, 4, 8, 8, 16, 16)):
-            c = g.num_classes if name.endswith("cls") else 4
-            outs[name] = self.buf(name, H // s, W // s, c, BUF_F32_PLANAR, BUF_OUTPUT)
-        # concat buffers (orders: qat.py:464,467,470,473,476)
-        fpn1 = self.buf("cat_fpn1", H // 16, W // 16, c4 + c4)     # [p5_up | p4]
-        fpn2 = self.buf("cat_fpn2", H // 8, W // 8, c3 + c3)       # [p4_up | p3]
-        fpn3 = self.buf("cat_fpn3", H // 4, W // 4, c2 + c2)       # [p3_up | p2]
-        pan1 = self.buf("cat_pan1", H // 8, W // 8, c2 + c3)       # [p2_down | p3_fused]
-        pan2 = self.buf("cat_pan2", H // 16, W // 16, c3 + c4)     # [p3_down | p4_fused]
-        p2, p3, p4 = View(fpn3, c2, c2), View(fpn2, c3, c3), View(fpn1, c4, c4)
-        p3_fused, p4_fused = View(pan1, c2, c3), View(pan2, c3, c4)
-
-        stem = self.view("stem", H // 2, W // 2, c1)
-        self.stem("stem", images, stem)
-        s1 = self.view("stage1_conv", H // 4, W // 4, c2)
-        self.conv([("stage1_conv", 0, s1, 0)], stem.buf, c1, 3, 2)
-        self.c3k2("stage1_c3k2", s1, p2, 1)
-        s2 = self.view("stage2_conv", H // 8, W // 8, c3)
-        self.conv([("stage2_conv", p2.coff, s2, 0)], p2.buf, c2, 3, 2)
-        self.c3k2("stage2_c3k2", s2, p3, 2)
-        s3 = self.view("stage3_conv", H // 16, W // 16, c4)
-        self.conv([("stage3_conv", p3.coff, s3, 0)], p3.buf, c3, 3, 2)
-        self.c3k2("stage3_c3k2", s3, p4, 2)
-        s4 = self.view("stage4_conv", H // 32, W // 32, c5)
-        self.conv([("stage4_conv", p4.coff, s4, 0)], p4.buf, c4, 3, 2)
-        p5 = self.view("stage4_sppf", H // 32, W // 32, c5)
-        self.sppf("stage4_sppf", s4, p5)
-
-        self.conv([("lateral_p4", 0, View(fpn1, 0, c4), SEG_UP2)], p5.buf, c5, 1)
-        self.c3k2("fpn_c3k2_1", View(fpn1, 0, 2 * c4), p4_fused, 1)
-        self.conv([("lateral_p3", p4_fused.coff, View(fpn2, 0, c3), SEG_UP2)], p4_fused.buf, c4, 1)
-        self.c3k2("fpn_c3k2_2", View(fpn2, 0, 2 * c3), p3_fused, 1)
-        self.conv([("lateral_p2", p3_fused.coff, View(fpn3, 0, c2), SEG_UP2)], p3_fused.buf, c3, 1)
-        p2_fused = self.view("p2_fused", H // 4, W // 4, c2)
-        self.c3k2("fpn_c3k2_3", View(fpn3, 0, 2 * c2), p2_fused, 1)
-        self.conv([("down1", 0, View(pan1, 0, c2), 0)], p2_fused.buf, c2, 3, 2)
-        p3_out = self.view("p3_out", H // 8, W // 8, c3)
-        self.c3k2("pan_c3k2_1", View(pan1, 0, c2 + c3), p3_out, 1)
-        self.conv([("down2", 0, View(pan2, 0, c3), 0)], p3_out.buf, c3, 3, 2)
-        p4_out = self.view("p4_out", H // 16, W // 16, c4)
-        self.c3k2("pan_c3k2_2", View(pan2, 0, c3 + c4), p4_out, 1)
-
-        self.head("head_p2", p2_fused, outs["p2_cls"], outs["p2_reg"])
-        self.head("head_p3", p3_out, outs["p3_cls"], outs["p3_reg"])
-        self.head("head_p4", p4_out, outs["p4_cls"], outs["p4_reg"])
-
-    # ---- the network ---------------------------------------------------------------------------
     def _lower(self):
+        """Graph -> buffers + fused ops. The network's input, outputs and network-level concats get their buffers first (a
+        concat's members are produced long before it); then every block, in forward order, by the rule of its kind."""
         g = self.g
-        bc = g.base_channels
-        c1, c2, c3, c4 = bc, 2 * bc, 4 * bc, 8 * bc
-        H, W = g.in_h, g.in_w
-        images = self.buf("images", H, W, 3, BUF_F32_NCHW_IN, BUF_INPUT)
-        outs = {}
-        for name, s in zip(OUTPUT_NAMES, (4, 4, 8, 8, 16, 16)):
-            c = g.num_classes if name.endswith("cls") else 4
-            outs[name] = self.buf(name, H // s, W // s, c, BUF_F32_PLANAR, BUF_OUTPUT)
-
-        # concat buffers of the neck (orders: model.py:257,260,264,267)
-        fpn1 = self.buf("neck.cat_fpn1", H // 8, W // 8, c3 + c3)      # [p4_up | p3]
-        fpn2 = self.buf("neck.cat_fpn2", H // 4, W // 4, c2 + c2)      # [p3_up | p2]
-        pan1 = self.buf("neck.cat_pan1", H // 8, W // 8, c2 + c3)      # [p2_down | p3_fused]
-        pan2 = self.buf("neck.cat_pan2", H // 16, W // 16, c3 + c4)    # [p3_down | p4 (pre-SPPF)]
-        p2, p3, p4 = View(fpn2, c2, c2), View(fpn1, c3, c3), View(pan2, c3, c4)
-        p3_fused = View(pan1, c2, c3)
-
-        # Backbone (model.py:205-219)
-        stem = self.view("backbone.stem", H // 2, W // 2, c1)
-        w, b = fold_bn(self.sd, "backbone.stem")
-        op = Op(OP_STEM, "backbone.stem", images, 3, 3, 2, 1, None, (H, W), (H // 2, W // 2))
-        seg = Seg("backbone.stem", 0, c1, stem, 0, n_pad=c1)
-        seg.w_raw, seg.fold, seg.bias = w.reshape(c1, 27), np.ones(c1), b      # stem: folded fp32 [O][(c,kh,kw)]
-        op.segs.append(seg)
-        self.ops.append(op)
-        s1 = self.view("backbone.stage1_conv", H // 4, W // 4, c2)
-        self.conv([("backbone.stage1_conv", 0, s1, 0)], stem.buf, c1, 3, 2)
-        if g.lite_p2:
-            self.conv([("backbone.stage1_block", 0, p2, 0)], s1.buf, c2, 3)
-        else:
-            self.c3k2("backbone.stage1_block", s1, p2, 1)
-        s2 = self.view("backbone.stage2_conv", H // 8, W // 8, c3)
-        self.conv([("backbone.stage2_conv", p2.coff, s2, 0)], p2.buf, c2, 3, 2)
-        self.c3k2("backbone.stage2_c3k2", s2, p3, 2)
-        s3 = self.view("backbone.stage3_conv", H // 16, W // 16, c4)
-        self.conv([("backbone.stage3_conv", p3.coff, s3, 0)], p3.buf, c3, 3, 2)
-        self.c3k2("backbone.stage3_c3k2", s3, p4, 2)
-        # SPPF_DLA (model.py:113-132)
-        hid = c4 // 2
-        sp = self.buf("backbone.sppf.cat", H // 16, W // 16, 4 * hid)
-        self.conv([("backbone.sppf.cv1", p4.coff, View(sp, 0, hid), 0)], p4.buf, c4, 1)
-        pool = Op(OP_SPPF_POOL, "backbone.sppf.pool1+pool2+pool3", sp, hid, 5, 1, 0, None,
-                  (H // 16, W // 16), (H // 16, W // 16))
-        pool.segs.append(Seg("backbone.sppf.pool", 0, 3 * hid, View(sp, hid, 3 * hid)))
-        self.ops.append(pool)
-        p4_sppf = self.view("backbone.sppf", H // 16, W // 16, c4)
-        self.conv([("backbone.sppf.cv2", 0, p4_sppf, 0)], sp, 4 * hid, 1)
-
-        # Neck (model.py:252-269)
-        self.conv([("neck.lateral_p3", 0, View(fpn1, 0, c3), SEG_UP2)], p4_sppf.buf, c4, 1)
-        self.c3k2("neck.fpn_c3k2_1", View(fpn1, 0, 2 * c3), p3_fused, 1)
-        self.conv([("neck.lateral_p2", p3_fused.coff, View(fpn2, 0, c2), SEG_UP2)], p3_fused.buf, c3, 1)
-        p2_fused = self.view("p2_fused", H // 4, W // 4, c2)
-        self.c3k2("neck.fpn_c3k2_2", View(fpn2, 0, 2 * c2), p2_fused, 1)
-        self.conv([("neck.down1", 0, View(pan1, 0, c2), 0)], p2_fused.buf, c2, 3, 2)
-        p3_out = self.view("p3_out", H // 8, W // 8, c3)
-        self.c3k2("neck.pan_c3k2_1", View(pan1, 0, c2 + c3), p3_out, 1)
-        self.conv([("neck.down2", 0, View(pan2, 0, c3), 0)], p3_out.buf, c3, 3, 2)
-        p4_out = self.view("p4_out", H // 16, W // 16, c4)
-        self.c3k2("neck.pan_c3k2_2", View(pan2, 0, c3 + c4), p4_out, 1)
-
-        # Heads (model.py:361-365)
-        self.head("head_p2", p2_fused, outs["p2_cls"], outs["p2_reg"])
-        self.head("head_p3", p3_out, outs["p3_cls"], outs["p3_reg"])
-        self.head("head_p4", p4_out, outs["p4_cls"], outs["p4_reg"])
+        self.at: Dict[int, View] = {-1: View(self.buf("images", g.in_h, g.in_w, 3, BUF_F32_NCHW_IN, BUF_INPUT), 0, 3)}
+        for name, n in zip(OUTPUT_NAMES, (g.nodes[i] for i in g.outputs)):
+            self.at[n.idx] = View(self.buf(name, n.h, n.w, n.c, BUF_F32_PLANAR, BUF_OUTPUT), 0, n.c)
+        inner = {i for blk in g.blocks for i in blk.nodes}
+        for n in g.nodes:
+            if n.kind == "cat" and n.idx not in inner:
+                self._cat(n.idx)
+        for blk in g.blocks:
+            getattr(self, blk.kind)(blk)
 
     # ---- INT8 pass (generic over the op table) ----------------------------------------------------
     def _quantize_pass(self):
