@@ -141,6 +141,52 @@ int unina_infer_async(unina_engine_t *e, const float *d_images_nchw, float conf_
 int unina_postprocess_async(unina_engine_t *e, float conf_threshold, float iou_threshold, float conformal_q,
                             GpuDetection *d_out, int *d_out_count, hipStream_t stream);
 
+/* ------------------------------------------------------------------ sliced inference (auto_labeler.py:124-199, 255-271)
+ * A high-resolution camera frame resized whole to the network input loses its small objects (1920 px -> 640 px: a 12 px cone
+ * arrives as 4 px). The reference's answer is SAHI_Wrapper: network-sized tiles with 20 % overlap, the detector on each, the
+ * boxes shifted back (map_boxes_to_global) and one global per-class NMS at 0.45. Here: one frame graph per tile, enqueued back
+ * to back into engine-owned device slots -- a tile is a pointer offset into the camera frame, nothing is copied -- and one merge
+ * on the GPU, all on one stream with no host round-trip in between. Boxes come back in CAMERA-FRAME pixels.
+ *
+ * Merge semantics: the engine's own on the union of the tiles' records mapped to the frame -- stable sort
+ * by confidence descending, ties by enumeration index t * MAX_DETECTIONS + i (tile-major), the MAX_DETECTIONS best kept,
+ * sequential greedy class-aware NMS at IoU > merge_iou (+1e-6f denominator), only a strictly lower confidence is suppressed;
+ * output compact and sorted, valid = 1, _pad = 0. Mapping, fp32, each step rounded: X = x * ((float)w / (float)net_w) + (float)x0
+ * (for a network-sized tile the scale is 1.0f and the map is the reference's offset add). Confidences must lie in [0, 1]. */
+#define UNINA_MAX_TILES 64
+typedef struct { int x, y, w, h; } unina_tile;   /* region of the camera frame, pixels */
+
+/* Host only, no engine, no device: the slices of SAHI_Wrapper.get_slices (auto_labeler.py:132-154), in its order, with exact
+ * repeats dropped (first occurrence kept): the reference yields the last row / column twice where the stride does not divide
+ * the frame (h = 1080, slice 640, stride 512: y = 0, 440, 440), and since equal confidences never suppress each other a repeated
+ * tile would double every one of its detections. stride = (int)(slice * (1 - overlap)) in double, as the reference computes it.
+ * A frame no larger than the slice in both dimensions is one tile, the whole frame; one smaller in one dimension gives
+ * non-square tiles. Returns the number of tiles and writes at most `cap` of them (out may be NULL when cap is 0);
+ * < 0: -error code (non-positive sizes, a stride below 1). */
+int unina_slice_tiles(int frame_w, int frame_h, int slice_w, int slice_h, float overlap_w, float overlap_h,
+                      unina_tile *out, int cap);
+
+/* Camera frame -> merged detections in frame pixels. Synchronous; host `out` / `out_count` as unina_infer (delivered through the
+ * same pinned block and completion word). Per tile: unina_infer_bgra's frame on d_bgra + y * pitch + 4 * x with the tile's
+ * width and height (a tile of any size is resized to the network input), thresholds conf / iou / conformal_q as there; then the
+ * merge at merge_iou. d_bgra / src_pitch: as unina_infer_bgra. UNINA_ERR_ARG: null pointer, n_tiles outside
+ * 1..UNINA_MAX_TILES, a tile that is empty or not inside the frame, bad pitch. */
+int unina_infer_tiled_bgra(unina_engine_t *e, const uint8_t *d_bgra, int src_width, int src_height, int src_pitch,
+                           const unina_tile *tiles, int n_tiles, const NormParams *norm, float conf_threshold,
+                           float iou_threshold, float conformal_q, float merge_iou, GpuDetection *out, int *out_count,
+                           hipStream_t stream);
+/* The same, results on the device (d_out: MAX_DETECTIONS records, d_out_count: one int), nothing synchronised
+ * (unina_infer_async's role). */
+int unina_infer_tiled_bgra_async(unina_engine_t *e, const uint8_t *d_bgra, int src_width, int src_height, int src_pitch,
+                                 const unina_tile *tiles, int n_tiles, const NormParams *norm, float conf_threshold,
+                                 float iou_threshold, float conformal_q, float merge_iou, GpuDetection *d_out,
+                                 int *d_out_count, hipStream_t stream);
+/* The merge alone, on slots already on the device: d_slots[n_tiles][MAX_DETECTIONS] (16-byte aligned), d_counts[n_tiles]
+ * (what unina_postprocess_async is to unina_infer_async). Only a tile's x, y, w, h enter (offset and scale). It uses the
+ * handle's post-process workspace, so it is ordered like any other call on the handle: behind the previous one on `stream`. */
+int unina_merge_tiles_async(unina_engine_t *e, const GpuDetection *d_slots, const int *d_counts, const unina_tile *tiles,
+                            int n_tiles, float merge_iou, GpuDetection *d_out, int *d_out_count, hipStream_t stream);
+
 /* ------------------------------------------------------------------ data mining (active_learning.py, mine_data.py)
  * The reference's third consumer of the forward graph: the active-learning loop pushes an unlabeled image set through the
  * detector and keeps, per image, a difficulty score and an embedding, then picks a diverse subset. These calls run BEHIND the

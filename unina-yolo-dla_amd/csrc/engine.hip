@@ -135,6 +135,9 @@ struct unina_engine {
   // engine has none, graph (B)), and the partial / staging workspace allocated by the first mining call
   int embed_op = -1;
   float* d_mine_ws = nullptr;
+  // sliced inference: UNINA_MAX_TILES detection slots ([tile][MAX_DETECTIONS] records, then the counts), allocated by the first
+  // tiled call
+  GpuDetection* d_tile_slots = nullptr;
   std::string err;
 };
 
@@ -1508,7 +1511,7 @@ void unina_unload_engine(unina_engine_t* e) {
   (void)hipSetDevice(e->device);
   drop_graph(e);
   if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
-  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws};
+  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws, e->d_tile_slots};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (e->h_result) (void)hipHostFree(e->h_result);
@@ -1603,9 +1606,13 @@ int unina_infer_async(unina_engine_t* e, const float* d_images, float conf, floa
   return unina_postprocess_async(e, conf, iou, q, d_out, d_out_count, stream);
 }
 
-int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou, float q, GpuDetection* out,
-                int* out_count, hipStream_t stream) {
-  if (!e || !out || !out_count) return UNINA_ERR_ARG;
+}  // extern "C"
+
+namespace {
+// The synchronous delivery of unina_infer and unina_infer_tiled_bgra: `enqueue(d_out, d_count)` enqueues the work whose LAST
+// post-process launch writes the records and the count there (and signals e->done_flag, which is set around the call).
+template <typename Enqueue>
+int infer_sync(unina_engine* e, Enqueue enqueue, GpuDetection* out, int* out_count, hipStream_t stream) {
   // The post-process writes its compacted output (write-only: count + n records) straight into the pinned, device-mapped
   // host block: no D2H copy command (a blit-kernel launch of its own, and all 1024 slots) on the latency path.
   // UNINA_HOST_RESULT=0 restores the device buffer + copy.
@@ -1624,7 +1631,7 @@ int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou,
     }
     static const bool timing = getenv("UNINA_TIMING") != nullptr;
     const auto ta = std::chrono::steady_clock::now();
-    int rc = unina_infer_async(e, d_images, conf, iou, q, e->h_result_dev->det, &e->h_result_dev->count, stream);
+    int rc = enqueue(e->h_result_dev->det, &e->h_result_dev->count);
     e->done_flag = nullptr;
     if (rc != UNINA_OK) return rc;
     const auto tb = std::chrono::steady_clock::now();
@@ -1656,7 +1663,7 @@ int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou,
       ++e->t_calls;
     }
   } else {
-    int rc = unina_infer_async(e, d_images, conf, iou, q, e->d_result->det, &e->d_result->count, stream);
+    int rc = enqueue(e->d_result->det, &e->d_result->count);
     if (rc != UNINA_OK) return rc;
     HIPCHK(e, hipMemcpyAsync(e->h_result, e->d_result, sizeof(DeviceResult), hipMemcpyDeviceToHost, stream));
     HIPCHK(e, hipStreamSynchronize(stream));
@@ -1666,6 +1673,16 @@ int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou,
   if (!copied) memcpy(out, e->h_result->det, sizeof(GpuDetection) * (size_t)n);   // (the UNINA_TIMING branch has copied them already)
   *out_count = n;
   return UNINA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou, float q, GpuDetection* out,
+                int* out_count, hipStream_t stream) {
+  if (!e || !out || !out_count) return UNINA_ERR_ARG;
+  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) { return unina_infer_async(e, d_images, conf, iou, q, d_out, d_count, stream); },
+                    out, out_count, stream);
 }
 
 // ---- data mining (active_learning.py:31-99, 234-305): scores and embedding behind the raw-head forward ----
@@ -1795,6 +1812,34 @@ int unina_serial_latency(unina_engine_t* e, const float* const* d_frames, int n_
   return UNINA_OK;
 }
 
+// Points every eager stem op at a pitched BGRA frame (src_kind 1: the network's size, 2: resized) / back at the fp32 tensor.
+// Returns the number of stem ops.
+static int point_stems_at_camera(unina_engine* e, const uint8_t* d_bgra, int w, int h, int pitch, const NormParams& norm) {
+  int nstem = 0;
+  for (size_t k = 0; k < e->ops.size(); ++k) {
+    PlannedOp& op = e->ops[k];
+    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
+    op.sp.src_kind = (w == op.sp.W && h == op.sp.H) ? 1 : 2;
+    op.sp.cam = d_bgra;
+    op.sp.cam_w = w;
+    op.sp.cam_h = h;
+    op.sp.cam_pitch = pitch;
+    op.sp.norm = norm;
+    ++nstem;
+  }
+  return nstem;
+}
+static void restore_stems(unina_engine* e) {
+  for (size_t k = 0; k < e->ops.size(); ++k) {
+    PlannedOp& op = e->ops[k];
+    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
+    op.sp.src_kind = 0;
+    op.sp.cam = nullptr;
+    op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = 0;
+    memset(&op.sp.norm, 0, sizeof op.sp.norm);
+  }
+}
+
 // Camera frame -> detections: unina_infer with the pre-process (preprocess.hip: BGRA -> RGB, optional half-pixel-centre
 // bilinear resize, normalise) computed inside the stem kernel instead of written to an fp32 tensor by one launch and
 // read back by the next (4 B/px in instead of 12 B/px out + 12 B/px in, one launch less). Same arithmetic, so the
@@ -1810,31 +1855,162 @@ int unina_infer_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, in
     int rc = plan(e);
     if (rc != UNINA_OK) return rc;
   }
-  int nstem = 0;
-  for (size_t k = 0; k < e->ops.size(); ++k) {
-    PlannedOp& op = e->ops[k];
-    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    op.sp.src_kind = (src_width == op.sp.W && src_height == op.sp.H) ? 1 : 2;
-    op.sp.cam = d_bgra;
-    op.sp.cam_w = src_width;
-    op.sp.cam_h = src_height;
-    op.sp.cam_pitch = src_pitch;
-    op.sp.norm = *norm;
-    ++nstem;
-  }
-  if (!nstem) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+  if (!point_stems_at_camera(e, d_bgra, src_width, src_height, src_pitch, *norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
   e->camera_active = true;
   const int rc = unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
   e->camera_active = false;
-  for (size_t k = 0; k < e->ops.size(); ++k) {
-    PlannedOp& op = e->ops[k];
-    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    op.sp.src_kind = 0;
-    op.sp.cam = nullptr;
-    op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = 0;
-    memset(&op.sp.norm, 0, sizeof op.sp.norm);
-  }
+  restore_stems(e);
   return rc;
+}
+
+// ---- sliced inference (auto_labeler.py:124-199, 255-271): T frame graphs into T device slots, one merge ----
+// The overlap ratio as the reference's arithmetic sees it: Python computes int(slice * (1 - 0.2)) in double, and 0.2f widened to
+// double is 0.20000000298, which turns 640 * 0.8 = 512 into 511. The float is therefore read as the shortest decimal that names
+// it (0.2f -> "0.2" -> the double 0.2), which is what the caller wrote.
+static double ratio_as_written(float r) {
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    snprintf(buf, sizeof buf, "%.*g", prec, (double)r);
+    const double d = strtod(buf, nullptr);
+    if ((float)d == r) return d;
+  }
+  return (double)r;
+}
+
+int unina_slice_tiles(int frame_w, int frame_h, int slice_w, int slice_h, float overlap_w, float overlap_h, unina_tile* out, int cap) {
+  if (frame_w <= 0 || frame_h <= 0 || slice_w <= 0 || slice_h <= 0 || cap < 0 || (cap > 0 && !out)) return -UNINA_ERR_ARG;
+  if (!(overlap_w == overlap_w) || !(overlap_h == overlap_h)) return -UNINA_ERR_ARG;
+  int n = 0;
+  auto emit = [&](int x, int y, int w, int h) {
+    if (n < cap) out[n] = unina_tile{x, y, w, h};
+    ++n;
+  };
+  if (frame_h <= slice_h && frame_w <= slice_w) {   // "Handle small images" (:139-141): the whole frame
+    emit(0, 0, frame_w, frame_h);
+    return n;
+  }
+  const double sh = (double)slice_h * (1.0 - ratio_as_written(overlap_h)), sw = (double)slice_w * (1.0 - ratio_as_written(overlap_w));
+  if (!(sh >= 1.0 && sh < 2147483648.0 && sw >= 1.0 && sw < 2147483648.0)) return -UNINA_ERR_ARG;   // (range() needs a positive step)
+  const int stride_h = (int)sh, stride_w = (int)sw;
+  // start / extent of the slice that range() step `pos` gives along one axis (:146-151), and whether an earlier step gave the same
+  auto axis = [](int len, int slice, int stride, std::vector<int>* start, std::vector<int>* extent, std::vector<char>* first) {
+    for (long long pos = 0; pos < len; pos += stride) {
+      const int end = (int)(pos + slice < len ? pos + slice : len);
+      const int st = end - slice > 0 ? end - slice : 0;
+      bool seen = false;
+      for (int s : *start) seen = seen || s == st;
+      start->push_back(st);
+      extent->push_back(end - st);
+      first->push_back(!seen);
+    }
+  };
+  std::vector<int> xs, xw, ys, yh;
+  std::vector<char> xf, yf;
+  axis(frame_h, slice_h, stride_h, &ys, &yh, &yf);
+  axis(frame_w, slice_w, stride_w, &xs, &xw, &xf);
+  for (size_t j = 0; j < ys.size(); ++j)
+    for (size_t i = 0; i < xs.size(); ++i)
+      if (yf[j] && xf[i]) emit(xs[i], ys[j], xw[i], yh[j]);   // (a slice repeats exactly when its row or its column does)
+  return n;
+}
+
+// offset and scale of every tile, fp32 (include/unina_mi355.h at "sliced inference"); checks the tile list against the frame
+// when frame_w > 0
+static int fill_tile_maps(unina_engine* e, const char* who, const unina_tile* tiles, int n_tiles, int frame_w, int frame_h, TileGatherParams* g) {
+  if (!tiles || n_tiles < 1 || n_tiles > UNINA_MAX_TILES) return fail(e, UNINA_ERR_ARG, "%s: need 1..%d tiles, got %d", who, UNINA_MAX_TILES, tiles ? n_tiles : 0);
+  static_assert(UNINA_MAX_TILES == kMaxTiles64, "the gather kernel's tile table");
+  for (int t = 0; t < n_tiles; ++t) {
+    const unina_tile& r = tiles[t];
+    if (r.w <= 0 || r.h <= 0 || r.x < 0 || r.y < 0 ||
+        (frame_w > 0 && ((long long)r.x + r.w > frame_w || (long long)r.y + r.h > frame_h)))
+      return fail(e, UNINA_ERR_ARG, "%s: tile %d (x %d, y %d, %d x %d) is empty or not inside the frame", who, t, r.x, r.y, r.w, r.h);
+    g->map[t] = TileMap{(float)r.w / (float)e->h.in_w, (float)r.h / (float)e->h.in_h, (float)r.x, (float)r.y};
+  }
+  g->n_tiles = n_tiles;
+  return UNINA_OK;
+}
+
+// gather + the frame's own NMS launch on the handle's workspace; `done`: the synchronous form's completion word (or nullptr)
+static int enqueue_merge(unina_engine* e, TileGatherParams* g, const GpuDetection* d_slots, const int* d_counts, float merge_iou,
+                         GpuDetection* d_out, int* d_out_count, unsigned int* done, unsigned int done_value, hipStream_t stream) {
+  PostParams pp;
+  memset(&pp, 0, sizeof pp);
+  post_bind_workspace(&pp, e->d_post_ws);
+  pp.mode = 2;
+  pp.cand = e->d_cand;
+  pp.iou_thr = merge_iou;
+  pp.eoff[2] = g->n_tiles * MAX_DETECTIONS;   // (the NMS launch sizes its enumeration-index split by eoff[2] + gw[2] * gh[2])
+  pp.out = d_out;
+  pp.out_count = d_out_count;
+  pp.out_candidates = &e->d_result->candidates;
+  pp.done_flag = done;
+  pp.done_value = done_value;
+  g->slots = d_slots;
+  g->counts = d_counts;
+  g->cand = pp.cand;
+  g->ws_ke = pp.ws_ke;
+  g->ws_hist = pp.ws_hist;
+  g->ws_total = pp.ws_total;
+  HIPCHK(e, merge_tiles_launch(*g, pp, stream));
+  return UNINA_OK;
+}
+
+int unina_merge_tiles_async(unina_engine_t* e, const GpuDetection* d_slots, const int* d_counts, const unina_tile* tiles, int n_tiles,
+                            float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_slots || !d_counts || !d_out || !d_out_count || ((uintptr_t)d_slots & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_counts & 3))
+    return fail(e, UNINA_ERR_ARG, "unina_merge_tiles_async: null / misaligned pointer");
+  TileGatherParams g;
+  int rc = fill_tile_maps(e, "unina_merge_tiles_async", tiles, n_tiles, 0, 0, &g);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  return enqueue_merge(e, &g, d_slots, d_counts, merge_iou, d_out, d_out_count, nullptr, 0, stream);
+}
+
+int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
+                                 const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
+                                 float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
+  if (src_width <= 0 || src_height <= 0 || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_bgra & 3))
+    return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: bad frame geometry");
+  TileGatherParams g;
+  int rc = fill_tile_maps(e, "unina_infer_tiled_bgra", tiles, n_tiles, src_width, src_height, &g);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->plan_dirty) {
+    rc = plan(e);
+    if (rc != UNINA_OK) return rc;
+  }
+  constexpr size_t kSlotBytes = sizeof(GpuDetection) * MAX_DETECTIONS;
+  if (!e->d_tile_slots) HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_tile_slots), UNINA_MAX_TILES * (kSlotBytes + sizeof(int))));
+  int* d_counts = reinterpret_cast<int*>(e->d_tile_slots + (size_t)UNINA_MAX_TILES * MAX_DETECTIONS);
+  // the tiles' frames signal nothing: the completion word of the synchronous form belongs to the merge
+  unsigned int* const done = e->done_flag;
+  e->done_flag = nullptr;
+  e->camera_active = true;
+  for (int t = 0; t < n_tiles && rc == UNINA_OK; ++t) {
+    const unina_tile& r = tiles[t];
+    if (!point_stems_at_camera(e, d_bgra + (size_t)r.y * src_pitch + (size_t)r.x * 4, r.w, r.h, src_pitch, *norm))
+      rc = fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+    else
+      rc = unina_infer_async(e, nullptr, conf, iou, q, e->d_tile_slots + (size_t)t * MAX_DETECTIONS, d_counts + t, stream);
+  }
+  e->camera_active = false;
+  restore_stems(e);
+  e->done_flag = done;
+  if (rc != UNINA_OK) return rc;
+  return enqueue_merge(e, &g, e->d_tile_slots, d_counts, merge_iou, d_out, d_out_count, done, e->done_value, stream);
+}
+
+int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
+                           const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
+                           float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null result pointer");
+  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
+    return unina_infer_tiled_bgra_async(e, d_bgra, src_width, src_height, src_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
+  }, out, out_count, stream);
 }
 
 int unina_debug_post_stamps(unina_engine_t* e, long long* out8) {

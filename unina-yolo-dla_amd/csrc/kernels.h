@@ -354,4 +354,24 @@ hipError_t post_init();   // the post-process table, the step-wise API's kernels
 hipError_t postprocess_launch(const PostParams& p, hipStream_t stream);
 int postprocess_desc(const PostParams& p, LaunchDesc out[2]);   // number of launches (1 or 2), or -1 on error
 
+// Sliced inference (unina_merge_tiles_async): the detection slots of up to kMaxTiles tiles of one camera frame -> ONE candidate
+// list in frame pixels (tile_gather_kernel, one workgroup per tile), in exactly the form launch 1 of the two-launch post-process
+// leaves behind (cand with the enumeration index in _pad, ws_ke, ws_hist, ws_total); the frame's own launch 2 (post_nms_kernel)
+// then merges it. Enumeration index of record i of tile t: t * MAX_DETECTIONS + i (tile-major).
+constexpr int kMaxTiles64 = 64;                       // == UNINA_MAX_TILES; kMaxTiles64 * MAX_DETECTIONS candidates fit the compact list
+struct TileMap { float sx, sy, ox, oy; };             // frame = tile * (sx, sy) + (ox, oy): fp32, multiply and add rounded separately
+struct TileGatherParams {
+  const GpuDetection* slots;   // [n_tiles][MAX_DETECTIONS]
+  const int* counts;           // [n_tiles] (clamped to 0..MAX_DETECTIONS on the device)
+  GpuDetection* cand;          // the handle's workspace, as PostParams
+  uint2* ws_ke;
+  int* ws_hist;
+  int* ws_total;
+  int n_tiles;
+  TileMap map[kMaxTiles64];
+};
+// gather + post_nms_kernel on `stream`. `nms`: a PostParams with the workspace bound and out / out_count / iou_thr (and the
+// optional done_flag) set; its decode fields are not read.
+hipError_t merge_tiles_launch(const TileGatherParams& g, const PostParams& nms, hipStream_t stream);
+
 }  // namespace unina

@@ -1208,6 +1208,39 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
   signal_done(p, tid);
 }
 
+// ---- sliced inference: the detection slots of T tiles of one camera frame -> the compact candidate list, in frame pixels ----
+// One workgroup per tile. Record i of tile t is mapped to the frame (multiply, then add: two roundings per coordinate, the scale
+// is 1.0f for a network-sized tile and the map is then the reference's plain offset add, auto_labeler.py:158-165), takes the
+// enumeration index t * MAX_DETECTIONS + i and goes where post_decode_kernel's tail would have put it: a run of the list
+// reserved with one atomic per workgroup, its key in ws_ke, its confidence in the histogram. post_nms_kernel does the rest.
+// The slot is compact (records 0..count), so a record's place in the run is its index: no ranking. ws_total / ws_hist are zero
+// at rest (the previous post_nms_kernel on this stream reset them with plain stores; this launch is a later kernel).
+__global__ __launch_bounds__(kPost2Block) void tile_gather_kernel(const TileGatherParams g) {
+  int& s_base = *reinterpret_cast<int*>(post_smem);   // (dynamic LDS like every kernel of the table: 16 bytes)
+  const int t = blockIdx.x, tid = threadIdx.x;
+  int cnt = g.counts[t];
+  cnt = cnt < 0 ? 0 : (cnt > kMaxDet ? kMaxDet : cnt);      // (a count is never trusted with the workspace's bounds)
+  if (tid == 0) s_base = cnt ? __hip_atomic_fetch_add(g.ws_total, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+  __syncthreads();
+  const int base = s_base;
+  const TileMap m = g.map[t];
+  // a record is 32 bytes: two 16-byte loads / stores per lane, consecutive lanes on consecutive records
+  const uint4* src = reinterpret_cast<const uint4*>(g.slots + (size_t)t * kMaxDet);
+  uint4* dst = reinterpret_cast<uint4*>(g.cand + base);
+  for (int i = tid; i < cnt; i += kPost2Block) {
+    const uint4 bx = src[2 * i], rest = src[2 * i + 1];      // (x1, y1, x2, y2), (confidence, class, valid, _pad)
+    const float x1 = __uint_as_float(bx.x) * m.sx + m.ox, y1 = __uint_as_float(bx.y) * m.sy + m.oy;
+    const float x2 = __uint_as_float(bx.z) * m.sx + m.ox, y2 = __uint_as_float(bx.w) * m.sy + m.oy;
+    const unsigned eidx = (unsigned)(t * kMaxDet + i);
+    dst[2 * i] = make_uint4(__float_as_uint(x1), __float_as_uint(y1), __float_as_uint(x2), __float_as_uint(y2));
+    dst[2 * i + 1] = make_uint4(rest.x, rest.y, rest.z, eidx);
+    g.ws_ke[base + i] = make_uint2(rest.x, eidx);
+    int bin = conf_bin(__uint_as_float(rest.x));              // a confidence lies in [0, 1]; anything else still lands in a bin
+    bin = bin < 0 ? 0 : bin;
+    atomicAdd(&g.ws_hist[bin], 1);
+  }
+}
+
 int post_num_blocks(const int gw[3], const int gh[3]) {
   const int cells = gw[0] * gh[0] + gw[1] * gh[1] + gw[2] * gh[2];
   return (cells + kPostBlock - 1) / kPostBlock;
@@ -1325,7 +1358,7 @@ __global__ __launch_bounds__(kPostBlock) void compact_valid_kernel(const GpuDete
 }
 
 // The post-process table: the engine's forms and the step-wise API's kernels.
-enum { kPostOne = 0, kPostDecode, kPostNms };
+enum { kPostOne = 0, kPostDecode, kPostNms, kStepDecode, kStepNms, kStepCompact, kTileGather };
 const struct { const char* name; const void* fn; } kPostKernelTable[] = {
     {"postprocess_kernel", reinterpret_cast<const void*>(&postprocess_kernel)},
     {"post_decode_kernel", reinterpret_cast<const void*>(&post_decode_kernel)},
@@ -1333,6 +1366,7 @@ const struct { const char* name; const void* fn; } kPostKernelTable[] = {
     {"decode_head_append_kernel", reinterpret_cast<const void*>(&decode_head_append_kernel)},
     {"nms_inplace_kernel", reinterpret_cast<const void*>(&nms_inplace_kernel)},
     {"compact_valid_kernel", reinterpret_cast<const void*>(&compact_valid_kernel)},
+    {"tile_gather_kernel", reinterpret_cast<const void*>(&tile_gather_kernel)},
 };
 
 }  // namespace
@@ -1367,6 +1401,20 @@ hipError_t postprocess_launch(const PostParams& p, hipStream_t stream) {
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t merge_tiles_launch(const TileGatherParams& g, const PostParams& nms, hipStream_t stream) {
+  static_assert((size_t)kMaxTiles64 * kMaxDet <= kListCap, "every record of every tile must fit the compact list");
+  if (g.n_tiles < 1 || g.n_tiles > kMaxTiles64 || !nms.ws_full || !nms.out || !nms.out_count) return hipErrorInvalidValue;
+  TileGatherParams gcopy = g;
+  void* gargs[] = {&gcopy};
+  hipError_t e = launch_desc(LaunchDesc{kPostKernelTable[kTileGather].fn, dim3(g.n_tiles), dim3(kT2), 16, kPostKernelTable[kTileGather].name},
+                             gargs, stream);
+  if (e != hipSuccess) return e;
+  PostParams ncopy = nms;
+  void* nargs[] = {&ncopy};
+  return launch_desc(LaunchDesc{kPostKernelTable[kPostNms].fn, dim3(kMaxTiles), dim3(kTN), (unsigned)sizeof(SmemN), kPostKernelTable[kPostNms].name},
+                     nargs, stream);
 }
 
 }  // namespace unina

@@ -37,6 +37,15 @@ class NormParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("mean_r", "mean_g", "mean_b", "std_r", "std_g", "std_b")]
 
 
+class Tile(C.Structure):
+    """unina_tile: a region of the camera frame, pixels."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "w", "h")]
+
+
+def _tile_array(tiles):
+    return (Tile * len(tiles))(*[Tile(*map(int, t)) for t in tiles])
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -50,6 +59,7 @@ ABI_SYMBOLS = [
     "unina_last_error", "unina_op_count", "unina_get_op_info", "unina_profile_ops", "unina_profile_post", "unina_debug_read_buffer",
     "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_serial_latency",
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
+    "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
@@ -102,6 +112,13 @@ def load_library() -> C.CDLL:
     L.unina_debug_dual_timeline.argtypes = [vp, ci, C.POINTER(C.c_longlong), ci, vp]
     L.unina_debug_block_stamps.argtypes = [vp, ci, C.POINTER(C.c_longlong), vp]
     L.unina_serial_latency.argtypes = [vp, C.POINTER(vp), ci, ci, cf, cf, cf, C.POINTER(C.c_double), vp]
+    # sliced inference (csrc/postprocess.hip: tile_gather_kernel)
+    L.unina_slice_tiles.argtypes = [ci, ci, ci, ci, cf, cf, C.POINTER(Tile), ci]
+    L.unina_infer_tiled_bgra.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf, vp,
+                                         C.POINTER(ci), vp]
+    L.unina_infer_tiled_bgra_async.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf, vp,
+                                               vp, vp]
+    L.unina_merge_tiles_async.argtypes = [vp, vp, vp, C.POINTER(Tile), ci, cf, vp, vp, vp]
     # data mining (csrc/mining.hip)
     L.unina_embedding_dim.argtypes = [vp]
     L.unina_mine_async.argtypes = [vp, vp, vp, vp, vp]
@@ -274,6 +291,50 @@ class Engine:
         self._check(self.L.unina_infer_bgra(self.h, frame.data_ptr(), width, height, pitch, C.byref(norm), conf_thr, iou_thr,
                                             conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
         return out[:n.value].copy()
+
+    def default_tiles(self, width: int, height: int):
+        """The reference's default slicing (20 % overlap) at the engine's input size, exact repeats dropped."""
+        from . import slicing
+        return slicing.get_slices(height, width, self.height, self.width)
+
+    def infer_tiled_bgra(self, frame, width: int, height: int, pitch: int, tiles=None, norm: Optional[NormParams] = None,
+                         conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, merge_iou: float = 0.45,
+                         out=None, stream=None):
+        """Sliced inference (auto_labeler.py:124-199): the detector on every tile (x, y, w, h) of the camera frame -- a tile is
+        a pointer offset, nothing is copied -- and one merge on the GPU; boxes in CAMERA-FRAME pixels. `tiles=None` slices
+        with the reference's defaults for the engine's input size. `out=None`: synchronous, returns the kept detections
+        (DET_DTYPE); `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if tiles is None:
+            tiles = self.default_tiles(width, height)
+        arr = _tile_array(tiles)
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_tiled_bgra_async(self.h, frame.data_ptr(), width, height, pitch, arr, len(tiles),
+                                                            C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou, base + 32,
+                                                            base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_tiled_bgra(self.h, frame.data_ptr(), width, height, pitch, arr, len(tiles), C.byref(norm),
+                                                  conf_thr, iou_thr, conformal_q, merge_iou, host.ctypes.data, C.byref(n),
+                                                  _stream_ptr(stream)))
+        return host[:n.value].copy()
+
+    def merge_tiles(self, slots, counts, tiles, merge_iou: float = 0.45, out=None, stream=None):
+        """The merge alone (unina_merge_tiles_async): `slots` int32 CUDA tensor [T, 8 * MAX_DETECTIONS] (records), `counts`
+        int32 CUDA tensor [T], `tiles` [(x, y, w, h)]. Asynchronous; returns `out` (int32 result tensor as infer_async's;
+        Engine.unpack reads it)."""
+        torch = _torch()
+        for t in (slots, counts):
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+        assert slots.numel() >= len(tiles) * 8 * MAX_DETECTIONS and counts.numel() >= len(tiles)
+        out = self._det_buf if out is None else out
+        base = out.data_ptr()
+        self._check(self.L.unina_merge_tiles_async(self.h, slots.data_ptr(), counts.data_ptr(), _tile_array(tiles), len(tiles),
+                                                   merge_iou, base + 32, base, _stream_ptr(stream)))
+        return out
 
     def infer_async(self, images, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1,
                     out=None, stream=None):
@@ -504,3 +565,16 @@ def calibrate_amax(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, de
         return _export.calibrate(per_frame(), percentile, method)
     finally:
         eng.close()
+
+
+def slice_tiles(frame_w: int, frame_h: int, slice_w: int = 640, slice_h: int = 640, overlap_w: float = 0.2,
+                overlap_h: float = 0.2, cap: Optional[int] = None):
+    """unina_slice_tiles through the C ABI (host only, no device): (count, [(x, y, w, h)] -- at most `cap` of them)."""
+    L = load_library()
+    n = L.unina_slice_tiles(frame_w, frame_h, slice_w, slice_h, overlap_w, overlap_h, None, 0)
+    if n < 0:
+        raise EngineError(f"unina_slice_tiles failed [{ERRORS.get(-n, -n)}]")
+    cap = n if cap is None else cap
+    arr = (Tile * max(cap, 1))()
+    n = L.unina_slice_tiles(frame_w, frame_h, slice_w, slice_h, overlap_w, overlap_h, arr, cap)
+    return n, [(t.x, t.y, t.w, t.h) for t in arr[:min(n, cap)]]
