@@ -229,6 +229,30 @@ int unina_mine_heads_async(unina_engine_t *e, float *d_scores8, hipStream_t stre
 int unina_kcenter(const float *d_embeddings, int n, int dim, int k, int first_index, int *d_selected, float *d_min_dist,
                   hipStream_t stream);
 
+/* ------------------------------------------------------------------ INT8 calibration (qat.py:171-220, train.py:809)
+ * The collection half of the reference's calibrate_model, on the device. An fp16 tensor has at most 32 768 distinct |x| (the
+ * sign bit drops out, 15 bits remain), so a table "how many elements carry each 15-bit pattern" is a LOSSLESS summary of it for
+ * everything a calibrator does with |x|: export.HistogramCalibrator.collect_counts folds a frame's table into bit-identical
+ * histograms, edges and ranges to folding the tensor. counts[bits & 0x7fff] += 1 per element: +0 and -0 share bin 0, Inf / NaN
+ * patterns are counted like any other (values are not interpreted). Counts are exact integers: two runs give the same bytes and
+ * a table sums to its element count (below 2^32 per buffer per frame). These calls run BEHIND the raw-head forward
+ * (unina_enqueue's launch sequence); the frame path (unina_infer*) is untouched by them. */
+#define UNINA_CALIB_BINS 32768
+/* No engine handle (unina_kcenter's role): value-count table of n fp16 elements on the device. d_half and d_counts 16-byte
+ * aligned (UNINA_ERR_ARG otherwise, and for NULL / n == 0); the call zeroes d_counts itself; nothing is synchronised. */
+int unina_abs_histogram_f16(const void *d_half, size_t n, uint32_t *d_counts, hipStream_t stream);
+/* The buffers a calibration covers: every kBufF16Nhwc buffer of the engine file, in file order. */
+int unina_calib_buffer_count(const unina_engine_t *e);                    /* < 0: -error code */
+int unina_calib_buffer_name(const unina_engine_t *e, int i, char *name, size_t cap);
+/* Tables of the buffers as they stand now: d_counts[count][UNINA_CALIB_BINS], 16-byte aligned, zeroed by the call; every
+ * buffer in ONE launch (what unina_mine_heads_async is to unina_mine_async). UNINA_ERR_UNSUPPORTED: the engine's precision is
+ * not fp16 (calibration runs on the fp16 engine). UNINA_ERR_STATE: unina_fusion_groups(e) > 0 -- fused launches do not write
+ * their internal buffers, call unina_set_fusion(e, 0) first. A refused call enqueues nothing. */
+int unina_calib_buffers_async(unina_engine_t *e, uint32_t *d_counts, hipStream_t stream);
+/* Forward (unina_enqueue's launch sequence) + the tables, enqueued on `stream`; d_images_nchw as unina_infer (NULL = current
+ * binding). Nothing is synchronised. */
+int unina_calib_async(unina_engine_t *e, const float *d_images_nchw, uint32_t *d_counts, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "calib.h"
 #include "engine_format.h"
 #include "kernels.h"
 #include "mining.h"
@@ -25,7 +26,7 @@
 using namespace unina;
 
 hipError_t unina::kernels_init() {
-  for (hipError_t (*init)() : {conv_init, c3k2_init, head_init, pair_init, block_dual_init, stem_pool_init, post_init}) {
+  for (hipError_t (*init)() : {conv_init, c3k2_init, head_init, pair_init, block_dual_init, stem_pool_init, post_init, calib_init}) {
     const hipError_t e = init();
     if (e != hipSuccess) return e;
   }
@@ -138,6 +139,11 @@ struct unina_engine {
   // sliced inference: UNINA_MAX_TILES detection slots ([tile][MAX_DETECTIONS] records, then the counts), allocated by the first
   // tiled call
   GpuDetection* d_tile_slots = nullptr;
+  // INT8 calibration (calib.hip): the kBufF16Nhwc buffers in file order and their descriptor table on the device, built by the
+  // first calibration call (those buffers live in the arena: their addresses never change)
+  std::vector<int> calib_bufs;
+  CalibDesc* d_calib_tab = nullptr;
+  unsigned calib_grid = 0;
   std::string err;
 };
 
@@ -1511,7 +1517,7 @@ void unina_unload_engine(unina_engine_t* e) {
   (void)hipSetDevice(e->device);
   drop_graph(e);
   if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
-  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws, e->d_tile_slots};
+  void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws, e->d_tile_slots, e->d_calib_tab};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (e->h_result) (void)hipHostFree(e->h_result);
@@ -1793,6 +1799,82 @@ int unina_mine(unina_engine_t* e, const float* d_images, float* scores8, float* 
   HIPCHK(e, hipMemcpy(scores8, stage, sizeof(float) * UNINA_MINE_SCORES, hipMemcpyDeviceToHost));
   if (embed) HIPCHK(e, hipMemcpy(embed, stage + UNINA_MINE_SCORES, sizeof(float) * (size_t)mp.c, hipMemcpyDeviceToHost));
   return UNINA_OK;
+}
+
+// ---- INT8 calibration (qat.py:171-220): |x| value-count tables of the fp16 activation buffers, behind the raw-head forward ----
+static bool is_calib_buffer(const Buffer& b) { return b.d.dtype == kBufF16Nhwc; }
+
+int unina_calib_buffer_count(const unina_engine_t* e) {
+  if (!e) return -UNINA_ERR_ARG;
+  int n = 0;
+  for (const Buffer& b : e->bufs) n += is_calib_buffer(b);
+  return n;
+}
+
+int unina_calib_buffer_name(const unina_engine_t* e, int i, char* name, size_t cap) {
+  if (!e || !name || cap == 0 || i < 0) return UNINA_ERR_ARG;
+  for (const Buffer& b : e->bufs) {
+    if (!is_calib_buffer(b) || i--) continue;
+    const size_t len = strnlen(b.d.name, sizeof b.d.name);
+    if (len + 1 > cap) return UNINA_ERR_ARG;
+    memcpy(name, b.d.name, len);
+    name[len] = 0;
+    return UNINA_OK;
+  }
+  return UNINA_ERR_ARG;
+}
+
+// What every calibration call checks before it enqueues anything -- the engine first (a caller sizes its table from
+// unina_calib_buffer_count, which is 0 for an fp32 / STRICT engine), then the table pointer -- and the descriptor table (built
+// once per handle).
+static int calib_prepare(unina_engine* e, const char* who, uint32_t* d_counts) {
+  if (e->h.precision != kFp16) return fail(e, UNINA_ERR_UNSUPPORTED, "%s: calibration runs on the fp16 engine (this one has precision %u)", who, e->h.precision);
+  if (unina_fusion_groups(e) > 0)
+    return fail(e, UNINA_ERR_STATE, "%s: %d fused launches do not write their internal buffers; call unina_set_fusion(e, 0) first", who, unina_fusion_groups(e));
+  if (!d_counts || ((uintptr_t)d_counts & 15)) return fail(e, UNINA_ERR_ARG, "%s: null / misaligned table pointer", who);
+  if (e->d_calib_tab) return UNINA_OK;
+  std::vector<CalibDesc> tab;
+  for (size_t i = 0; i < e->bufs.size(); ++i) {
+    const Buffer& b = e->bufs[i];
+    if (!is_calib_buffer(b)) continue;
+    if (!b.ptr || ((uintptr_t)b.ptr & 15)) return fail(e, UNINA_ERR_STATE, "%s: buffer '%s' has no 16-byte aligned address", who, b.d.name);
+    tab.push_back(CalibDesc{b.ptr, (unsigned long long)b.d.h * b.d.w * b.d.c, (unsigned)tab.size(), 0, 0, 0});
+    e->calib_bufs.push_back((int)i);
+  }
+  if (tab.empty()) return fail(e, UNINA_ERR_UNSUPPORTED, "%s: the engine has no fp16 activation buffer", who);
+  e->calib_grid = calib_plan(tab.data(), (int)tab.size());
+  if (!e->calib_grid) return fail(e, UNINA_ERR_HIP, "%s: calib_plan failed (device query)", who);
+  HIPCHK(e, hipMalloc(&e->d_calib_tab, sizeof(CalibDesc) * tab.size()));
+  HIPCHK(e, hipMemcpy(e->d_calib_tab, tab.data(), sizeof(CalibDesc) * tab.size(), hipMemcpyHostToDevice));
+  return UNINA_OK;
+}
+
+static int calib_enqueue(unina_engine* e, uint32_t* d_counts, hipStream_t stream) {
+  const int count = (int)e->calib_bufs.size();
+  HIPCHK(e, hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * (size_t)count * UNINA_CALIB_BINS, stream));
+  HIPCHK(e, calib_launch_table(e->d_calib_tab, count, e->calib_grid, d_counts, stream));
+  return UNINA_OK;
+}
+
+int unina_calib_buffers_async(unina_engine_t* e, uint32_t* d_counts, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  HIPCHK(e, hipSetDevice(e->device));
+  const int rc = calib_prepare(e, "unina_calib_buffers_async", d_counts);
+  return rc != UNINA_OK ? rc : calib_enqueue(e, d_counts, stream);
+}
+
+int unina_calib_async(unina_engine_t* e, const float* d_images, uint32_t* d_counts, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  HIPCHK(e, hipSetDevice(e->device));
+  int rc = calib_prepare(e, "unina_calib_async", d_counts);   // before any launch: a refused call enqueues nothing
+  if (rc != UNINA_OK) return rc;
+  if (d_images) {
+    rc = unina_set_tensor_address(e, "images", const_cast<float*>(d_images));
+    if (rc != UNINA_OK) return rc;
+  }
+  rc = unina_enqueue(e, stream);   // the raw-head forward, unfused: every activation buffer is written
+  if (rc != UNINA_OK) return rc;
+  return calib_enqueue(e, d_counts, stream);
 }
 
 // `n_calls` serial unina_infer calls over a ring of `n_ring` input frames, each timed on the host's steady clock from entry to

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
     "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
+    "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -125,6 +126,12 @@ def load_library() -> C.CDLL:
     L.unina_mine.argtypes = [vp, vp, vp, vp, vp]
     L.unina_mine_heads_async.argtypes = [vp, vp, vp]
     L.unina_kcenter.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
+    # INT8 calibration (csrc/calib.hip)
+    L.unina_abs_histogram_f16.argtypes = [vp, C.c_size_t, vp, vp]
+    L.unina_calib_buffer_count.argtypes = [vp]
+    L.unina_calib_buffer_name.argtypes = [vp, ci, C.c_char_p, C.c_size_t]
+    L.unina_calib_buffers_async.argtypes = [vp, vp, vp]
+    L.unina_calib_async.argtypes = [vp, vp, vp, vp]
     # multi-GPU: RCCL gather of detection slots behind the C ABI (csrc/comm.hip)
     L.unina_comm_unique_id.argtypes = [vp]
     L.unina_comm_init.argtypes = [C.POINTER(vp), vp, ci, ci, ci]
@@ -400,6 +407,44 @@ class Engine:
         self._check(self.L.unina_mine_heads_async(self.h, out.data_ptr(), _stream_ptr(stream)))
         return out.cpu().numpy()
 
+    # -- INT8 calibration (csrc/calib.hip: |x| value-count tables of the fp16 activation buffers) ----------------
+    def calib_buffer_names(self) -> List[str]:
+        """The buffers a calibration covers (every fp16 activation buffer of the engine file, in file order): the row
+        order of calib_counts()."""
+        if getattr(self, "_calib_names", None) is None:
+            n = self.L.unina_calib_buffer_count(self.h)
+            if n < 0:
+                raise EngineError(f"[{ERRORS.get(-n, -n)}] unina_calib_buffer_count")
+            names = []
+            for i in range(n):
+                buf = C.create_string_buffer(64)
+                self._check(self.L.unina_calib_buffer_name(self.h, i, buf, len(buf)))
+                names.append(buf.value.decode())
+            self._calib_names = names
+        return list(self._calib_names)
+
+    def calib_counts_async(self, images, out, stream=None) -> None:
+        """Asynchronous: forward of `images` (None: no forward, the buffers as they stand) + the value-count tables into
+        the CUDA int32 tensor `out` ([n_buf, 32768], the bits are uint32 counts). Fusion must be off (set_fusion(False))."""
+        torch = _torch()
+        n = len(self.calib_buffer_names())
+        assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n * _export.CALIB_BINS
+        if images is None:
+            self._check(self.L.unina_calib_buffers_async(self.h, out.data_ptr(), _stream_ptr(stream)))
+        else:
+            self._check(self.L.unina_calib_async(self.h, self._checked_images_ptr(images), out.data_ptr(), _stream_ptr(stream)))
+
+    def calib_counts(self, images=None) -> np.ndarray:
+        """Value-count tables of every calibration buffer, synchronous: uint32 [n_buf, 32768], row i = how many elements of
+        buffer calib_buffer_names()[i] carry each 15-bit fp16 pattern (bits & 0x7fff). `images`: a frame to run first
+        (raw-head forward); None = the buffers as they stand."""
+        torch = _torch()
+        n = len(self.calib_buffer_names())
+        out = torch.empty((max(n, 1), _export.CALIB_BINS), dtype=torch.int32, device=torch.device("cuda", self.device))
+        self.calib_counts_async(images, out)
+        torch.cuda.synchronize(self.device)
+        return out[:n].cpu().numpy().view(np.uint32)
+
     @staticmethod
     def unpack(buf) -> np.ndarray:
         """int32 result tensor (see infer_async) -> structured ndarray of the kept detections."""
@@ -543,12 +588,52 @@ def kcenter(embeddings, k: int, first_index: int, stream=None) -> np.ndarray:
         return sel.cpu().numpy()[:k].astype(np.int64)
 
 
+def abs_histogram_f16(tensor, stream=None) -> np.ndarray:
+    """unina_abs_histogram_f16: the |x| value-count table (uint32 [32768]) of a contiguous CUDA fp16 tensor, synchronous."""
+    L = load_library()
+    torch = _torch()
+    assert tensor.is_cuda and tensor.dtype == torch.float16 and tensor.is_contiguous()
+    with torch.cuda.device(tensor.device):
+        out = torch.empty(_export.CALIB_BINS, dtype=torch.int32, device=tensor.device)
+        rc = L.unina_abs_histogram_f16(tensor.data_ptr(), tensor.numel(), out.data_ptr(), _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_abs_histogram_f16 failed [{ERRORS.get(rc, rc)}] (n={tensor.numel()}, address {tensor.data_ptr():#x})")
+        torch.cuda.synchronize(tensor.device)
+        return out.cpu().numpy().view(np.uint32)
+
+
+def calibrate_amax_device(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, device: int = 0,
+                          percentile: Optional[float] = None, method: Optional[str] = None, specs=None):
+    """calibrate_amax with the collection on the GPU: same arguments, same dict, float for float. Per frame the engine
+    counts, for every fp16 activation buffer, how many elements carry each of the 32 768 |x| patterns (csrc/calib.hip, one
+    launch behind the forward); only those tables cross to the host, where export.calibrate_counts folds them exactly as
+    export.calibrate folds the tensors. method None / "max" WITH a percentile is not offered (ValueError; np.percentile
+    needs the raw tensor: calibrate_amax)."""
+    torch = _torch()
+    if specs is None and method in (None, "max") and percentile is not None:
+        raise ValueError('method "max" with a per-frame percentile needs the raw tensors: use calibrate_amax')
+    eng = Engine.from_state_dict(sd, graph, device)
+    eng.set_fusion(False)          # every internal buffer must be written: the tables cover them all
+    try:
+        names = eng.calib_buffer_names()
+
+        def per_frame():
+            for x in frames:
+                yield eng.calib_counts(torch.from_numpy(np.ascontiguousarray(x)).cuda(device))
+        if specs is not None:
+            return _export.calibrate_counts_all(per_frame(), names, specs)
+        return _export.calibrate_counts(per_frame(), names, percentile, method)
+    finally:
+        eng.close()
+
+
 def calibrate_amax(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, device: int = 0,
                    percentile: Optional[float] = None, method: Optional[str] = None, specs=None):
     """INT8 calibration on the GPU (the role of qat.py:171-220 `calibrate_model`, 30 batches in train.py:809): runs the
     fp16 engine over `frames` (iterable of [1,3,H,W] fp32 ndarrays) and records, per activation buffer, the
     (percentile of the) absolute maximum, or -- `method` = "entropy" | "mse" | "percentile" -- the range a |x| histogram over
     all frames selects (export.HistogramCalibrator: the reference's QuantDescriptor(calib_method="histogram"), qat.py:91-126).
+    calibrate_amax_device above returns the same dict with the per-buffer collection on the GPU instead of read_buffer.
     Feed the result to from_state_dict(..., precision=INT8, amax=...)."""
     torch = _torch()
     b = _export.EngineBuilder(sd, graph)

@@ -24,6 +24,7 @@ Graph (A): 67 reference convs -> 50 conv ops + stem + pool = 52 ops; graph (B): 
 from __future__ import annotations
 
 import math
+import os
 import struct
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -524,7 +525,20 @@ class HistogramCalibrator:
         self.edges: Optional[np.ndarray] = None
 
     def collect(self, x: np.ndarray) -> None:
-        a = np.abs(np.asarray(x, dtype=np.float32)).reshape(-1)
+        self._fold(np.abs(np.asarray(x, dtype=np.float32)).reshape(-1), None)
+
+    def collect_counts(self, counts: np.ndarray) -> None:
+        """Folds one frame given as its |x| value-count table (CALIB_BINS entries: how many elements carry each 15-bit
+        fp16 pattern, Engine.calib_counts / unina_abs_histogram_f16) exactly as `collect` folds the frame's tensor: the
+        values are the fp16 numbers of the non-empty patterns as float32, each weighted by its count, through the same
+        np.histogram calls, restart and growth rules. Counts are integers below 2^53, so the float64 weighted sums are
+        exact and hist / edges come out bit-identical. A non-finite pattern (Inf / NaN, 0x7c00 and above) with a count
+        raises ValueError."""
+        a, w = pattern_values(counts)
+        self._fold(a, w)
+
+    def _fold(self, a: np.ndarray, weights: Optional[np.ndarray]) -> None:
+        """a: |x| values, float32, flat; weights: None (every value once) or a float64 count per value."""
         amax = float(a.max()) if a.size else 0.0
         if self.hist is not None and self.edges[-1] <= 1e-6 and amax > self.edges[-1]:
             # everything seen so far was (numerically) zero -- a dead buffer on the first frames: its range (0, 1e-8) must not be
@@ -535,7 +549,7 @@ class HistogramCalibrator:
             zeros = 0.0
         if self.hist is None:
             amax = max(amax, 1e-8)
-            self.hist, self.edges = np.histogram(a, bins=self.num_bins, range=(0.0, amax))
+            self.hist, self.edges = np.histogram(a, bins=self.num_bins, range=(0.0, amax), weights=weights)
             self.hist = self.hist.astype(np.float64)
             self.hist[0] += zeros
             return
@@ -544,7 +558,7 @@ class HistogramCalibrator:
             extra = int(np.ceil((amax - self.edges[-1]) / width))
             self.edges = np.concatenate([self.edges, self.edges[-1] + width * np.arange(1, extra + 1)])
             self.hist = np.concatenate([self.hist, np.zeros(extra)])
-        h, _ = np.histogram(a, bins=self.edges)
+        h, _ = np.histogram(a, bins=self.edges, weights=weights)
         self.hist += h
 
     # -- range selection ------------------------------------------------------------------------------
@@ -608,6 +622,22 @@ class HistogramCalibrator:
         return float(self.edges[arg])
 
 
+CALIB_BINS = 32768                 # include/unina_mi355.h UNINA_CALIB_BINS: fp16 patterns with the sign bit dropped
+_FIRST_NON_FINITE = 0x7c00         # +Inf; every pattern above it is a NaN
+
+
+def pattern_values(counts: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """One |x| value-count table -> (the fp16 numbers of its non-empty patterns as float32, ascending; their counts as
+    float64). ValueError for a table of another length or one that counts an Inf / NaN pattern."""
+    c = np.asarray(counts).reshape(-1)
+    if c.size != CALIB_BINS:
+        raise ValueError(f"a value-count table has {CALIB_BINS} entries, got {c.size}")
+    nz = np.flatnonzero(c)
+    if nz.size and nz[-1] >= _FIRST_NON_FINITE:
+        raise ValueError(f"the table counts {int(c[_FIRST_NON_FINITE:].sum())} non-finite fp16 values (Inf / NaN): the buffer cannot be calibrated")
+    return nz.astype(np.uint16).view(np.float16).astype(np.float32), c[nz].astype(np.float64)
+
+
 def calibrate(named_buffers_per_frame, percentile: Optional[float] = None, method: Optional[str] = None) -> Dict[str, float]:
     """The build's own activation calibrator (the reference's lives in NVIDIA pytorch-quantization, qat.py:129-220,
     which is not available: parity unpinned). Input: an iterable of {buffer name: ndarray} (one dict per
@@ -645,6 +675,58 @@ def calibrate_all(named_buffers_per_frame, specs) -> Dict[str, Dict[str, float]]
     for label, (method, pct) in specs.items():
         out[label] = dict(mx) if method == "max" else {n: c.amax(method, 99.99 if pct is None else pct) for n, c in cals.items()}
     return out
+
+
+def _table_max(counts: np.ndarray) -> float:
+    a, _w = pattern_values(counts)
+    return float(a[-1]) if a.size else 0.0
+
+
+def calibrate_counts(tables_per_frame, names, percentile: Optional[float] = None, method: Optional[str] = None) -> Dict[str, float]:
+    """`calibrate` on |x| value-count tables: tables_per_frame is an iterable of [len(names), CALIB_BINS] integer arrays
+    (one per calibration frame, Engine.calib_counts), names the buffer of each row. Same ranges as `calibrate` on the
+    tensors the tables were counted from, float for float (HistogramCalibrator.collect_counts).
+      method None / "max" : the value of the largest non-empty pattern over all frames. With a `percentile` it is NOT
+                            offered: np.percentile's interpolation over the raw tensor is not reproduced from a table
+                            (ValueError; engine.calibrate_amax computes that one);
+      "entropy" | "mse" | "percentile" : as `calibrate`."""
+    names = list(names)
+    if method in (None, "max"):
+        if percentile is not None:
+            raise ValueError('method "max" with a per-frame percentile needs the raw tensors (np.percentile interpolates between '
+                             "elements): use engine.calibrate_amax for it")
+        amax: Dict[str, float] = {}
+        for tables in tables_per_frame:
+            for name, row in zip(names, _rows(tables, names)):
+                amax[name] = max(amax.get(name, 0.0), _table_max(row))
+        return amax
+    cals: Dict[str, HistogramCalibrator] = {}
+    for tables in tables_per_frame:
+        for name, row in zip(names, _rows(tables, names)):
+            cals.setdefault(name, HistogramCalibrator()).collect_counts(row)
+    return {name: c.amax(method, 99.99 if percentile is None else percentile) for name, c in cals.items()}
+
+
+def calibrate_counts_all(tables_per_frame, names, specs) -> Dict[str, Dict[str, float]]:
+    """`calibrate_all` on value-count tables: one pass, several range selections, specs = {label: (method, percentile | None)}."""
+    names = list(names)
+    cals: Dict[str, HistogramCalibrator] = {}
+    mx: Dict[str, float] = {}
+    for tables in tables_per_frame:
+        for name, row in zip(names, _rows(tables, names)):
+            cals.setdefault(name, HistogramCalibrator()).collect_counts(row)
+            mx[name] = max(mx.get(name, 0.0), _table_max(row))
+    out = {}
+    for label, (method, pct) in specs.items():
+        out[label] = dict(mx) if method == "max" else {n: c.amax(method, 99.99 if pct is None else pct) for n, c in cals.items()}
+    return out
+
+
+def _rows(tables, names):
+    t = np.asarray(tables)
+    if t.shape != (len(names), CALIB_BINS):
+        raise ValueError(f"expected tables of shape {(len(names), CALIB_BINS)}, got {t.shape}")
+    return t
 
 
 def export_engine(sd: Dict[str, np.ndarray], path: str, graph: Optional[Graph] = None,
@@ -701,3 +783,92 @@ def read_engine_header(path: str) -> dict:
     return dict(version=version, precision=precision, in_c=in_c, in_h=in_h, in_w=in_w, num_classes=nc,
                 n_buffers=n_buf, n_ops=n_ops, n_heads=n_heads, strides=(s0, s1, s2), blob_bytes=blob, macs=macs,
                 model_base_channels=model_bc)
+
+
+# ---- command line: weights file -> engine file (export_trt.py's `python export_trt.py --weights ... --output ...`) ----
+PRECISIONS = {"fp16": FP16, "strict": STRICT, "fp32": FP32, "int8": INT8}
+CALIBRATORS = ("max", "entropy", "mse", "percentile")
+
+
+def load_weights(path: str) -> Dict[str, np.ndarray]:
+    """A .unsd file (statedict.py), or a .pt / .pth checkpoint read with torch's weights-only (non-executing) loader: a
+    state_dict, or a dict holding one under "state_dict" / "model"; a `module.` prefix, BatchNorm counters and quantizer
+    entries are dropped (statedict.from_qat_checkpoint's name rules)."""
+    from . import statedict
+    if path.lower().endswith(".unsd"):
+        return statedict.load(path)
+    import torch
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    for key in ("state_dict", "model"):
+        if isinstance(ck, dict) and isinstance(ck.get(key), dict):
+            ck = ck[key]
+    weights, _quant = statedict.from_qat_checkpoint({k: v.numpy() for k, v in ck.items() if hasattr(v, "numpy")})
+    return weights
+
+
+def graph_for(sd: Dict[str, np.ndarray], in_h: int, in_w: int) -> Graph:
+    """The Graph a state_dict belongs to, read off its own tensors: variant by key names, width from the stem, class count
+    from a cls head's output conv, lite_p2 from the P2 stage being one ConvBlock."""
+    from . import statedict
+    variant = statedict.detect_variant(sd)
+    stem = "backbone.stem.conv.weight" if variant == "A" else "stem.conv.weight"
+    cls = "head_p3.cls_branch.2.weight" if variant == "A" else "head_p3_cls.2.weight"
+    if cls not in sd:
+        raise ValueError(f"state_dict has no {cls!r}")
+    return Graph(num_classes=int(sd[cls].shape[0]), base_channels=int(sd[stem].shape[0]),
+                 lite_p2=variant == "A" and "backbone.stage1_block.conv.weight" in sd, in_h=in_h, in_w=in_w, variant=variant)
+
+
+def cli_parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m unina_yolo_dla_amd.export",
+                                 description="weights file -> .une engine file for libunina_mi355.so")
+    ap.add_argument("--weights", required=True, help=".unsd (statedict.py), or a .pt / .pth state_dict (loaded weights-only)")
+    ap.add_argument("--out", required=True, help="engine file to write (.une)")
+    ap.add_argument("--precision", default="fp16", choices=sorted(PRECISIONS))
+    ap.add_argument("--size", type=int, nargs=2, default=(640, 640), metavar=("H", "W"), help="network input size")
+    ap.add_argument("--calib-dir", help="int8: folder of calibration images (or .npy frames), read as mine.load_frame does")
+    ap.add_argument("--calib-frames", type=int, default=30, help="int8: number of frames taken from --calib-dir (sorted order)")
+    ap.add_argument("--calibrator", default="entropy", choices=CALIBRATORS, help="int8: range selection")
+    ap.add_argument("--percentile", type=float, default=None, help='int8, --calibrator percentile: default 99.99')
+    ap.add_argument("--device", type=int, default=0, help="int8: GPU the calibration runs on")
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = cli_parser()
+    args = ap.parse_args(argv)
+    precision = PRECISIONS[args.precision]
+    if precision == INT8 and not args.calib_dir:
+        ap.error("--precision int8 needs --calib-dir")
+    if precision != INT8 and args.calib_dir:
+        ap.error("--calib-dir is only used with --precision int8")
+    if args.percentile is not None and args.calibrator != "percentile":
+        ap.error("--percentile goes with --calibrator percentile")
+    if args.calib_frames < 1:
+        ap.error("--calib-frames must be at least 1")
+    try:
+        sd = load_weights(args.weights)
+        g = graph_for(sd, args.size[0], args.size[1])
+    except (OSError, ValueError, KeyError) as e:
+        ap.error(f"{args.weights}: {e}")
+    amax = None
+    if precision == INT8:
+        from . import mine
+        files = mine.list_files(args.calib_dir)[:args.calib_frames] if os.path.isdir(args.calib_dir) else []
+        if not files:
+            ap.error(f"--calib-dir {args.calib_dir}: no images")
+        import torch  # noqa: F401  (first: the engine library then shares the HIP runtime that torch has loaded)
+        from . import engine
+        frames = (mine.load_frame(p, g.in_w, g.in_h)[None] for p in files)
+        amax = engine.calibrate_amax_device(sd, g, frames, device=args.device, percentile=args.percentile,
+                                            method=None if args.calibrator == "max" else args.calibrator)
+        print(f"calibrated {len(amax)} buffers on {len(files)} frames ({args.calibrator})")
+    b = export_engine(sd, args.out, g, precision, amax)
+    print(f"wrote {args.out}: {args.precision}, {g.in_h}x{g.in_w}, graph ({g.variant}), {len(b.ops)} ops")
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())
