@@ -132,6 +132,25 @@ int unina_infer_bgra(unina_engine_t *e, const uint8_t *d_bgra, int src_width, in
                      const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
                      GpuDetection *out, int *out_count, hipStream_t stream);
 
+/* The same for an NV12 camera frame (GpuBufferHandle::format 1; 1.5 B/px in): d_y the luma plane (y_pitch bytes per row), d_uv the
+ * interleaved U,V plane ((src_height + 1) / 2 rows of uv_pitch bytes). The arithmetic, all fp32, each operation rounded once:
+ *   tap at camera pixel (X, Y), cuda_preprocess.cu:224-241:
+ *     Yv = y[Y * y_pitch + X];  U = uv[(Y / 2) * uv_pitch + (X / 2) * 2] - 128.0f;  V = uv[... + 1] - 128.0f
+ *     r = Yv + 1.402f * V;  g = Yv - 0.344136f * U - 0.714136f * V;  b = Yv + 1.772f * U
+ *     each clamped with fmaxf(0, fminf(255, .)); the clamped values stay floats, they are never rounded to u8
+ *   a frame (or tile) of the network's size: the tap, then ((v / 255.0f) - mean) / std -- preprocess_nv12
+ *   any other size: the REFERENCE HAS NO NV12 RESIZE; this one is defined here. Coordinates, clamps and weights are those of
+ *     preprocess_bgra_resize (cuda_preprocess.cu:155-178) unchanged, the four taps are the clamped float r, g, b above instead of
+ *     u8 channels, blended per channel as w00 * t00 + w01 * t01 + w10 * t10 + w11 * t11 left to right, then normalised --
+ *     unina_preprocess_nv12_resize below. On a grey frame (every chroma byte 128) it equals the BGRA resize of B = G = R = Y.
+ * Identical results to the two-step form (preprocess_nv12 / unina_preprocess_nv12_resize, then unina_infer). Nothing is asked
+ * of the alignment of the planes or pitches (aligned ones are read with wider loads). UNINA_ERR_ARG: a null plane, a
+ * non-positive size, y_pitch < src_width, uv_pitch < src_width or < 2 * ((src_width + 1) / 2) (the last chroma pair of an
+ * odd-width row is read whole). */
+int unina_infer_nv12(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv, int src_width, int src_height, int y_pitch,
+                     int uv_pitch, const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
+                     GpuDetection *out, int *out_count, hipStream_t stream);
+
 /* Asynchronous variant: results stay on the device (d_out: MAX_DETECTIONS records, d_out_count: one int);
  * nothing is synchronised. Used to pipeline frames and to feed the RCCL gather without touching the host. */
 int unina_infer_async(unina_engine_t *e, const float *d_images_nchw, float conf_threshold, float iou_threshold,
@@ -181,6 +200,18 @@ int unina_infer_tiled_bgra_async(unina_engine_t *e, const uint8_t *d_bgra, int s
                                  const unina_tile *tiles, int n_tiles, const NormParams *norm, float conf_threshold,
                                  float iou_threshold, float conformal_q, float merge_iou, GpuDetection *d_out,
                                  int *d_out_count, hipStream_t stream);
+/* The NV12 pair: the same tiles, slots and merge on an NV12 frame (planes and pitches as unina_infer_nv12). A tile (x, y, w, h)
+ * is pre-processed as a frame of w x h whose tap (xs, ys) is read at camera pixel (x + xs, y + ys): source coordinates are
+ * tile-local, and the tile's origin enters the chroma index ((y + ys) / 2, (x + xs) / 2) -- so an NV12 tile is not a pointer
+ * offset, the origin travels to the kernel, and it may be odd. UNINA_ERR_ARG as the BGRA pair and unina_infer_nv12. */
+int unina_infer_tiled_nv12(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv, int src_width, int src_height,
+                           int y_pitch, int uv_pitch, const unina_tile *tiles, int n_tiles, const NormParams *norm,
+                           float conf_threshold, float iou_threshold, float conformal_q, float merge_iou, GpuDetection *out,
+                           int *out_count, hipStream_t stream);
+int unina_infer_tiled_nv12_async(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv, int src_width, int src_height,
+                                 int y_pitch, int uv_pitch, const unina_tile *tiles, int n_tiles, const NormParams *norm,
+                                 float conf_threshold, float iou_threshold, float conformal_q, float merge_iou,
+                                 GpuDetection *d_out, int *d_out_count, hipStream_t stream);
 /* The merge alone, on slots already on the device: d_slots[n_tiles][MAX_DETECTIONS] (16-byte aligned), d_counts[n_tiles]
  * (what unina_postprocess_async is to unina_infer_async). Only a tile's x, y, w, h enter (offset and scale). It uses the
  * handle's post-process workspace, so it is ordered like any other call on the handle: behind the previous one on `stream`. */
@@ -394,6 +425,13 @@ hipError_t preprocess_bgra(const uint8_t *d_input, float *d_output, int width, i
                            NormParams params, hipStream_t stream);
 hipError_t preprocess_nv12(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, float *d_output, int width,
                            int height, int y_pitch, int uv_pitch, NormParams params, hipStream_t stream);
+/* Not in the reference (its NV12 path cannot resize): NV12 of any size -> the dst_width x dst_height tensor, by the definition
+ * at unina_infer_nv12 above; with dst == src it is preprocess_nv12. Odd sizes are legal (chroma plane: (src_height + 1) / 2
+ * rows); hipErrorInvalidValue for a null pointer, a non-positive size, y_pitch < src_width, uv_pitch < src_width or
+ * < 2 * ((src_width + 1) / 2). */
+hipError_t unina_preprocess_nv12_resize(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, float *d_output, int src_width,
+                                        int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
+                                        NormParams params, hipStream_t stream);
 float *allocate_preprocess_buffer(int width, int height);
 void free_preprocess_buffer(float *d_buffer);
 hipStream_t create_preprocess_stream(void);

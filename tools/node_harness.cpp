@@ -4,12 +4,14 @@
 // It includes ONLY the public header (plus the HIP runtime API for the buffers the node owns, :473-483, 696-707), so
 // that the Mi355Engine shim and the three call sequences of INTEGRATION.md are compiled and run, not just documented.
 //
-//   node_harness <engine.une> <frame.bgra> <src_w> <src_h> <pitch> <mode A|B|C> <out.bin> [conf iou q]
+//   node_harness <engine.une> <frame.bgra> <src_w> <src_h> <pitch> <mode A|B|C|N> <out.bin> [conf iou q]
 //
 //   mode A: preprocess_bgra_resize -> bind seven tensors -> enqueueV3 -> reset_detection_counter, 3 x decode_yolo_head,
 //           get_detection_count, run_gpu_nms, copy_valid_detections_to_host   (the node's own sequence, :601-656)
 //   mode B: preprocess_bgra_resize -> unina_infer                              (fused path)
 //   mode C: unina_infer_bgra                                                   (camera frame in, detections out)
+//   mode N: unina_infer_nv12                                                   (the same for an NV12 buffer, format 1 of
+//           GpuBufferHandle: the file holds <src_h> luma rows, then (<src_h> + 1) / 2 chroma rows, all of <pitch> bytes)
 //
 // <out.bin>: int32 count, then count 32-byte GpuDetection records -- what the node would publish (:659-678).
 // Built by __graft_entry__.build() with hipcc, linked with -lunina_mi355; tests/test_gpu_node_harness.py runs it as a
@@ -161,6 +163,20 @@ class Node {
     return n;
   }
 
+  // INTEGRATION.md Option C for an NV12 buffer: the chroma plane follows the luma plane, same pitch
+  int processGpuBuffer_N(const GpuBufferHandle &buffer) {
+    const uint8_t *y = static_cast<const uint8_t *>(buffer.device_ptr);
+    int n = 0;
+    int rc = unina_infer_nv12(engine_.handle(), y, y + size_t(buffer.pitch) * buffer.height, buffer.width, buffer.height,
+                              buffer.pitch, buffer.pitch, &norm_params_, confidence_threshold_, iou_threshold_, conformal_q_,
+                              h_detections_.data(), &n, stream_);
+    if (rc != UNINA_OK) {
+      std::fprintf(stderr, "unina_infer_nv12: %s\n", unina_last_error(engine_.handle()));
+      return -1;
+    }
+    return n;
+  }
+
   void cleanup() {                                                                                   // :709-751
     if (stream_) hipStreamSynchronize(stream_);
     cleanup_postprocess_resources();
@@ -192,7 +208,7 @@ class Node {
 
 int main(int argc, char **argv) {
   if (argc < 8) {
-    std::fprintf(stderr, "usage: %s engine.une frame.bgra src_w src_h pitch A|B|C out.bin [conf iou q]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s engine.une frame.bgra src_w src_h pitch A|B|C|N out.bin [conf iou q]\n", argv[0]);
     return 2;
   }
   const char *engine_path = argv[1], *frame_path = argv[2], *out_path = argv[7];
@@ -200,11 +216,12 @@ int main(int argc, char **argv) {
   const char mode = argv[6][0];
   const float conf = argc > 8 ? std::atof(argv[8]) : 0.5f, iou = argc > 9 ? std::atof(argv[9]) : 0.45f,
               q = argc > 10 ? std::atof(argv[10]) : 0.1f;
-  if (src_w <= 0 || src_h <= 0 || pitch < 4 * src_w) {
+  const bool nv12 = mode == 'N';
+  if (src_w <= 0 || src_h <= 0 || pitch < (nv12 ? src_w : 4 * src_w)) {
     std::fprintf(stderr, "bad frame geometry\n");
     return 2;
   }
-  std::vector<uint8_t> frame(size_t(pitch) * src_h);
+  std::vector<uint8_t> frame(size_t(pitch) * (nv12 ? src_h + (src_h + 1) / 2 : src_h));
   FILE *f = std::fopen(frame_path, "rb");
   if (!f || std::fread(frame.data(), 1, frame.size(), f) != frame.size()) {
     std::fprintf(stderr, "cannot read %zu bytes from %s\n", frame.size(), frame_path);
@@ -220,7 +237,7 @@ int main(int argc, char **argv) {
 
   int n = -1;
   for (int rep = 0; rep < 2; ++rep) {  // twice: the second frame runs on warm state, like every frame after the first
-    n = mode == 'A' ? node.processGpuBuffer_A(buf) : mode == 'B' ? node.processGpuBuffer_B(buf) : node.processGpuBuffer_C(buf);
+    n = mode == 'A' ? node.processGpuBuffer_A(buf) : mode == 'B' ? node.processGpuBuffer_B(buf) : nv12 ? node.processGpuBuffer_N(buf) : node.processGpuBuffer_C(buf);
     if (n < 0) {
       std::fprintf(stderr, "frame dropped (mode %c)\n", mode);
       return 1;

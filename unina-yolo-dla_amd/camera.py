@@ -1,0 +1,95 @@
+"""NV12 camera frames on the host side: a numpy float32 twin of the pre-process the stem kernel computes.
+
+``nv12_to_tensor`` is to ``unina_infer_nv12`` / ``unina_infer_tiled_nv12`` / ``unina_preprocess_nv12_resize`` what
+``slicing.merge_numpy`` is to the GPU merge: the same arithmetic without a GPU, operation for operation on ``np.float32``
+in the written order, so the results agree bit for bit. The definition (include/unina_mi355.h at unina_infer_nv12):
+
+  tap at camera pixel (X, Y)      cuda_preprocess.cu:224-241
+      Yv = y[Y, X];  U = uv[Y // 2, (X // 2) * 2] - 128;  V = uv[Y // 2, (X // 2) * 2 + 1] - 128
+      r = Yv + 1.402 V;  g = Yv - 0.344136 U - 0.714136 V;  b = Yv + 1.772 U;  each clamped to [0, 255], kept as float
+  region of the output's size     the tap, then ((v / 255) - mean) / std               (preprocess_nv12)
+  any other size                  the reference has no NV12 resize; ours takes the coordinates, clamps and weights of
+                                  preprocess_bgra_resize (cuda_preprocess.cu:155-178), the four float taps blended
+                                  w00 t00 + w01 t01 + w10 t10 + w11 t11 left to right, then normalised
+  tile (x0, y0, w, h)             source coordinates tile-local (a frame of w x h), the tap read at (x0 + xs, y0 + ys):
+                                  the origin enters the chroma index, so it may be odd
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+IMAGENET = (0.485, 0.456, 0.406, 0.229, 0.224, 0.225)   # mean r, g, b, std r, g, b (cuda_preprocess.cu:73-75)
+
+_F = np.float32
+
+
+def _norm6(norm) -> Tuple[np.float32, ...]:
+    if hasattr(norm, "mean_r"):                           # engine.NormParams
+        norm = (norm.mean_r, norm.mean_g, norm.mean_b, norm.std_r, norm.std_g, norm.std_b)
+    assert len(norm) == 6
+    return tuple(_F(v) for v in norm)
+
+
+def _tap(y: np.ndarray, uv: np.ndarray, X: np.ndarray, Y: np.ndarray):
+    """Clamped float r, g, b at camera pixels (X, Y) (integer index arrays, broadcast against each other)."""
+    Yv = y[Y, X].astype(_F)
+    cx = (X // 2) * 2
+    U = uv[Y // 2, cx].astype(_F) - _F(128.0)
+    V = uv[Y // 2, cx + 1].astype(_F) - _F(128.0)
+    r = Yv + _F(1.402) * V
+    g = Yv - _F(0.344136) * U - _F(0.714136) * V
+    b = Yv + _F(1.772) * U
+    clamp = lambda v: np.maximum(_F(0.0), np.minimum(_F(255.0), v))
+    return clamp(r), clamp(g), clamp(b)
+
+
+def _axis(dst: int, src: int):
+    """Source coordinates of one axis of the resize: (lower tap, upper tap, fraction), cuda_preprocess.cu:155-170."""
+    scale = _F(src) / _F(dst)
+    s = (np.arange(dst).astype(_F) + _F(0.5)) * scale - _F(0.5)
+    s = np.maximum(_F(0.0), np.minimum(s, _F(src) - _F(1.0)))
+    i0 = s.astype(np.int32)                               # (int)sx: truncation
+    i1 = np.minimum(i0 + 1, src - 1)
+    return i0, i1, s - i0.astype(_F)
+
+
+def nv12_to_tensor(y: np.ndarray, uv: np.ndarray, dst_hw: Optional[Tuple[int, int]] = None, norm: Sequence[float] = IMAGENET,
+                   origin: Tuple[int, int] = (0, 0), region: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """NV12 frame -> float32 [3, H, W] network input, RGB planar, normalised.
+
+    y: uint8 [h, >= w] luma plane; uv: uint8 [(h + 1) // 2, >= 2 * ((w + 1) // 2)] interleaved U, V (columns beyond the frame,
+    a pitch, are ignored). origin = (x0, y0) and region = (w, h): the part of the frame to read, default the whole frame
+    right and below the origin. dst_hw = (H, W): the output size, default the region's (no resize)."""
+    y = np.asarray(y)
+    uv = np.asarray(uv)
+    assert y.dtype == np.uint8 and uv.dtype == np.uint8 and y.ndim == 2 and uv.ndim == 2
+    x0, y0 = int(origin[0]), int(origin[1])
+    sw, sh = (y.shape[1] - x0, y.shape[0] - y0) if region is None else (int(region[0]), int(region[1]))
+    if x0 < 0 or y0 < 0 or sw <= 0 or sh <= 0 or x0 + sw > y.shape[1] or y0 + sh > y.shape[0]:
+        raise ValueError(f"region {sw} x {sh} at ({x0}, {y0}) is empty or not inside the {y.shape[1]} x {y.shape[0]} frame")
+    if uv.shape[0] < (y0 + sh + 1) // 2 or uv.shape[1] < 2 * ((x0 + sw + 1) // 2):
+        raise ValueError("chroma plane too small for the region")
+    dh, dw = (sh, sw) if dst_hw is None else (int(dst_hw[0]), int(dst_hw[1]))
+    if dh <= 0 or dw <= 0:
+        raise ValueError("output size must be positive")
+    if (dh, dw) == (sh, sw):
+        r, g, b = _tap(y, uv, x0 + np.arange(sw)[None, :], y0 + np.arange(sh)[:, None])
+    else:
+        xa, xb, fx = _axis(dw, sw)
+        ya, yb, fy = _axis(dh, sh)
+        fx, fy = fx[None, :], fy[:, None]
+        one = _F(1.0)
+        w00, w01, w10, w11 = (one - fx) * (one - fy), fx * (one - fy), (one - fx) * fy, fx * fy
+        t00 = _tap(y, uv, x0 + xa[None, :], y0 + ya[:, None])
+        t01 = _tap(y, uv, x0 + xb[None, :], y0 + ya[:, None])
+        t10 = _tap(y, uv, x0 + xa[None, :], y0 + yb[:, None])
+        t11 = _tap(y, uv, x0 + xb[None, :], y0 + yb[:, None])
+        r, g, b = (w00 * t00[c] + w01 * t01[c] + w10 * t10[c] + w11 * t11[c] for c in range(3))
+    n = _norm6(norm)
+    out = np.empty((3, dh, dw), dtype=_F)
+    for c, v in enumerate((r, g, b)):
+        out[c] = ((v / _F(255.0)) - n[c]) / n[3 + c]
+        assert v.dtype == _F
+    return out

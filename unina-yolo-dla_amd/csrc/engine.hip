@@ -1894,18 +1894,32 @@ int unina_serial_latency(unina_engine_t* e, const float* const* d_frames, int n_
   return UNINA_OK;
 }
 
-// Points every eager stem op at a pitched BGRA frame (src_kind 1: the network's size, 2: resized) / back at the fp32 tensor.
-// Returns the number of stem ops.
-static int point_stems_at_camera(unina_engine* e, const uint8_t* d_bgra, int w, int h, int pitch, const NormParams& norm) {
+// A camera region as the stem reads it (GpuBufferHandle::format, perception_node.cpp:357-368). BGRA: `plane` is the region's
+// first pixel, a tile is a pointer offset. NV12: `plane` / `uv` are the planes of the WHOLE frame and (x0, y0) the region's
+// origin, which enters the chroma index.
+enum CameraFormat : int { kCamBgra = 0, kCamNv12 = 1 };
+struct CameraRegion {
+  int format;
+  const uint8_t *plane, *uv;
+  int w, h, pitch, uv_pitch, x0, y0;
+};
+
+// Points every eager stem op at a camera region (src_kind 1 / 3: the network's size, 2 / 4: resized) / back at the fp32
+// tensor. Returns the number of stem ops.
+static int point_stems_at_camera(unina_engine* e, const CameraRegion& c, const NormParams& norm) {
   int nstem = 0;
   for (size_t k = 0; k < e->ops.size(); ++k) {
     PlannedOp& op = e->ops[k];
     if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    op.sp.src_kind = (w == op.sp.W && h == op.sp.H) ? 1 : 2;
-    op.sp.cam = d_bgra;
-    op.sp.cam_w = w;
-    op.sp.cam_h = h;
-    op.sp.cam_pitch = pitch;
+    op.sp.src_kind = (c.format == kCamNv12 ? 3 : 1) + ((c.w == op.sp.W && c.h == op.sp.H) ? 0 : 1);
+    op.sp.cam = c.plane;
+    op.sp.cam_uv = c.uv;
+    op.sp.cam_w = c.w;
+    op.sp.cam_h = c.h;
+    op.sp.cam_pitch = c.pitch;
+    op.sp.cam_uv_pitch = c.uv_pitch;
+    op.sp.cam_x0 = c.x0;
+    op.sp.cam_y0 = c.y0;
     op.sp.norm = norm;
     ++nstem;
   }
@@ -1916,10 +1930,32 @@ static void restore_stems(unina_engine* e) {
     PlannedOp& op = e->ops[k];
     if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
     op.sp.src_kind = 0;
-    op.sp.cam = nullptr;
-    op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = 0;
+    op.sp.cam = op.sp.cam_uv = nullptr;
+    op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = op.sp.cam_uv_pitch = op.sp.cam_x0 = op.sp.cam_y0 = 0;
     memset(&op.sp.norm, 0, sizeof op.sp.norm);
   }
+}
+
+// unina_infer on a camera region: the stems are pointed at it for the call and back at the tensor afterwards, whatever it returns
+static int infer_camera(unina_engine* e, const CameraRegion& c, const NormParams& norm, float conf, float iou, float q,
+                        GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!point_stems_at_camera(e, c, norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+  e->camera_active = true;
+  const int rc = unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
+  e->camera_active = false;
+  restore_stems(e);
+  return rc;
+}
+
+// The NV12 frame geometry every NV12 entry point accepts: preprocess_nv12's pitch rules (y_pitch >= w, uv_pitch >= w), and
+// since the last chroma pair of an odd-width row is read whole, uv_pitch >= 2 * ((w + 1) / 2). Odd sizes are legal (the chroma
+// plane then has (h + 1) / 2 rows); nothing is asked of the alignment of the planes or the pitches.
+static int check_nv12_frame(unina_engine* e, const char* who, const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch, int uv_pitch) {
+  if (!d_y || !d_uv) return fail(e, UNINA_ERR_ARG, "%s: null %s plane", who, d_y ? "chroma" : "luma");
+  if (w <= 0 || h <= 0) return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, w, h);
+  if (y_pitch < w || uv_pitch < w || uv_pitch < 2 * ((w + 1) / 2))
+    return fail(e, UNINA_ERR_ARG, "%s: pitch too small for width %d (y_pitch %d < %d or uv_pitch %d < %d)", who, w, y_pitch, w, uv_pitch, 2 * ((w + 1) / 2));
+  return UNINA_OK;
 }
 
 // Camera frame -> detections: unina_infer with the pre-process (preprocess.hip: BGRA -> RGB, optional half-pixel-centre
@@ -1937,12 +1973,25 @@ int unina_infer_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, in
     int rc = plan(e);
     if (rc != UNINA_OK) return rc;
   }
-  if (!point_stems_at_camera(e, d_bgra, src_width, src_height, src_pitch, *norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
-  e->camera_active = true;
-  const int rc = unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
-  e->camera_active = false;
-  restore_stems(e);
-  return rc;
+  return infer_camera(e, CameraRegion{kCamBgra, d_bgra, nullptr, src_width, src_height, src_pitch, 0, 0, 0}, *norm, conf, iou, q, out, out_count, stream);
+}
+
+// NV12 camera frame -> detections: unina_infer_bgra's role for the other common camera format (cuda_preprocess.cu:206-211),
+// 1.5 B/px in. The stem computes preprocess_nv12 (a frame of the network's size) or unina_preprocess_nv12_resize (any other
+// size) per pixel, so the detections are those of the two-step form bit for bit (tests/test_gpu_nv12.py).
+int unina_infer_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
+                     int uv_pitch, const NormParams* norm, float conf, float iou, float q, GpuDetection* out, int* out_count,
+                     hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_nv12: null norm / result pointer");
+  int rc = check_nv12_frame(e, "unina_infer_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->plan_dirty) {
+    rc = plan(e);
+    if (rc != UNINA_OK) return rc;
+  }
+  return infer_camera(e, CameraRegion{kCamNv12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, 0, 0}, *norm, conf, iou, q, out, out_count, stream);
 }
 
 // ---- sliced inference (auto_labeler.py:124-199, 255-271): T frame graphs into T device slots, one merge ----
@@ -2049,15 +2098,12 @@ int unina_merge_tiles_async(unina_engine_t* e, const GpuDetection* d_slots, cons
   return enqueue_merge(e, &g, d_slots, d_counts, merge_iou, d_out, d_out_count, nullptr, 0, stream);
 }
 
-int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
-                                 const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
-                                 float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
-  if (src_width <= 0 || src_height <= 0 || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_bgra & 3))
-    return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: bad frame geometry");
+// The tiled calls' common body, behind the argument checks of the frame: one frame graph per tile into the handle's slots, one merge.
+static int infer_tiled_camera(unina_engine* e, const char* who, const CameraRegion& frame, const unina_tile* tiles, int n_tiles,
+                              const NormParams& norm, float conf, float iou, float q, float merge_iou, GpuDetection* d_out,
+                              int* d_out_count, hipStream_t stream) {
   TileGatherParams g;
-  int rc = fill_tile_maps(e, "unina_infer_tiled_bgra", tiles, n_tiles, src_width, src_height, &g);
+  int rc = fill_tile_maps(e, who, tiles, n_tiles, frame.w, frame.h, &g);
   if (rc != UNINA_OK) return rc;
   HIPCHK(e, hipSetDevice(e->device));
   if (e->plan_dirty) {
@@ -2073,7 +2119,16 @@ int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int s
   e->camera_active = true;
   for (int t = 0; t < n_tiles && rc == UNINA_OK; ++t) {
     const unina_tile& r = tiles[t];
-    if (!point_stems_at_camera(e, d_bgra + (size_t)r.y * src_pitch + (size_t)r.x * 4, r.w, r.h, src_pitch, *norm))
+    CameraRegion c = frame;
+    c.w = r.w;
+    c.h = r.h;
+    if (frame.format == kCamBgra) {
+      c.plane = frame.plane + (size_t)r.y * frame.pitch + (size_t)r.x * 4;   // a BGRA tile is a pointer offset
+    } else {
+      c.x0 = r.x;                                                            // an NV12 tile is not: the origin enters the chroma index
+      c.y0 = r.y;
+    }
+    if (!point_stems_at_camera(e, c, norm))
       rc = fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
     else
       rc = unina_infer_async(e, nullptr, conf, iou, q, e->d_tile_slots + (size_t)t * MAX_DETECTIONS, d_counts + t, stream);
@@ -2085,6 +2140,17 @@ int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int s
   return enqueue_merge(e, &g, e->d_tile_slots, d_counts, merge_iou, d_out, d_out_count, done, e->done_value, stream);
 }
 
+int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
+                                 const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
+                                 float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
+  if (src_width <= 0 || src_height <= 0 || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_bgra & 3))
+    return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: bad frame geometry");
+  return infer_tiled_camera(e, "unina_infer_tiled_bgra", CameraRegion{kCamBgra, d_bgra, nullptr, src_width, src_height, src_pitch, 0, 0, 0},
+                            tiles, n_tiles, *norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+}
+
 int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                            const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
                            float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
@@ -2092,6 +2158,29 @@ int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_wid
   if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null result pointer");
   return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
     return unina_infer_tiled_bgra_async(e, d_bgra, src_width, src_height, src_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
+  }, out, out_count, stream);
+}
+
+// The NV12 pair: the same slots, gather and merge; only the stem's source differs (StemParams::cam_x0 / cam_y0 carry the tile).
+int unina_infer_tiled_nv12_async(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height,
+                                 int y_pitch, int uv_pitch, const unina_tile* tiles, int n_tiles, const NormParams* norm,
+                                 float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count,
+                                 hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null / misaligned pointer");
+  const int rc = check_nv12_frame(e, "unina_infer_tiled_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  if (rc != UNINA_OK) return rc;
+  return infer_tiled_camera(e, "unina_infer_tiled_nv12", CameraRegion{kCamNv12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, 0, 0},
+                            tiles, n_tiles, *norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+}
+
+int unina_infer_tiled_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
+                           int uv_pitch, const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou,
+                           float q, float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null result pointer");
+  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
+    return unina_infer_tiled_nv12_async(e, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
   }, out, out_count, stream);
 }
 

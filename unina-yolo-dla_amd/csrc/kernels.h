@@ -257,10 +257,14 @@ constexpr int kHeadWsTH = 13;
 struct StemParams {
   int dtype;           // DType of dst
   int src_kind;        // 0: fp32 planar tensor `src`; 1: BGRA u8 camera frame of the network's size; 2: BGRA u8 frame of
-                       // cam_w x cam_h, bilinear-resized to W x H -- 1 / 2 compute the pre-process (preprocess.hip, same
-                       // arithmetic) on the fly instead of reading a tensor it would have written (unina_infer_bgra)
-  const unsigned char* cam;   // src_kind 1 / 2: pitched BGRA
-  int cam_w, cam_h, cam_pitch;
+                       // cam_w x cam_h, bilinear-resized to W x H; 3: NV12 region of the network's size; 4: NV12 region of
+                       // cam_w x cam_h, bilinear-resized -- 1..4 compute the pre-process (preprocess.hip, same arithmetic) on
+                       // the fly instead of reading a tensor it would have written (unina_infer_bgra / unina_infer_nv12)
+  const unsigned char* cam;   // src_kind 1 / 2: pitched BGRA (of the region); 3 / 4: the luma plane of the WHOLE frame
+  const unsigned char* cam_uv;   // src_kind 3 / 4: the interleaved chroma plane of the whole frame
+  int cam_w, cam_h, cam_pitch, cam_uv_pitch;   // size of the region the stem reads; pitches in bytes
+  int cam_x0, cam_y0;  // src_kind 3 / 4: the region's origin in the frame. It enters the chroma index ((y0 + y) / 2,
+                       // (x0 + x) / 2), so an NV12 tile cannot be a pointer offset the way a BGRA tile is; may be odd
   NormParams norm;
   const float* src;    // [3][H][W]
   const float* w;      // [Co][27], (c,kh,kw)

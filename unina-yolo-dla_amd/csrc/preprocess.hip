@@ -5,6 +5,9 @@
 //   plain BGRA   :99-128   u8 BGRA (pitched) -> fp32 RGB planar, ((v/255) - mean)/std
 //   BGRA resize  :144-204  half-pixel-centre bilinear, clamp to [0, src-1], same normalise
 //   NV12         :212-253  BT.601 (1.402 / 0.344136 / 0.714136 / 1.772), clamp, normalise
+//   NV12 resize  (ours: the reference has none) the BGRA resize's coordinates, clamps and weights; the four taps are the
+//                clamped FLOAT r, g, b of the NV12 conversion (never rounded to u8), blended w00*t00 + w01*t01 + w10*t10 +
+//                w11*t11 left to right, then normalised. unina_infer_nv12's in-stem form (stem_pool.hip) equals it.
 // The DATA MOVEMENT is not the reference's one-thread-per-pixel form: all three are HBM-bound byte movers (4 B/px in,
 // 12 B/px out), so ONE kernel template, thread = FOUR consecutive output pixels of a row: the no-resize paths read the
 // quad with one 16-byte load (BGRA) or one dword of luma + one dword of chroma (NV12: 2 chroma pairs for 4 pixels), every
@@ -20,7 +23,7 @@
 
 namespace {
 
-enum Mode : int { kPlain = 0, kResize = 1, kNv12 = 2 };
+enum Mode : int { kPlain = 0, kResize = 1, kNv12 = 2, kNv12Resize = 3 };
 
 struct PreParams {
   const uint8_t* in;      // BGRA (plain / resize) or the Y plane (NV12)
@@ -58,15 +61,47 @@ __device__ __forceinline__ void resize_pixel(const PreParams& q, int dx, int dy,
   normalise(r, g, b, q.norm, o);
 }
 
-// BT.601 (cuda_preprocess.cu:229-247)
-__device__ __forceinline__ void nv12_pixel(float Y, float U, float V, const NormParams& n, float (&o)[3]) {
-  float r = Y + 1.402f * V;
-  float g = Y - 0.344136f * U - 0.714136f * V;
-  float b = Y + 1.772f * U;
+// BT.601 (cuda_preprocess.cu:229-241); the clamped values stay floats
+__device__ __forceinline__ void nv12_rgb(float Y, float U, float V, float& r, float& g, float& b) {
+  r = Y + 1.402f * V;
+  g = Y - 0.344136f * U - 0.714136f * V;
+  b = Y + 1.772f * U;
   r = fmaxf(0.0f, fminf(255.0f, r));
   g = fmaxf(0.0f, fminf(255.0f, g));
   b = fmaxf(0.0f, fminf(255.0f, b));
+}
+__device__ __forceinline__ void nv12_pixel(float Y, float U, float V, const NormParams& n, float (&o)[3]) {   // (:229-247)
+  float r, g, b;
+  nv12_rgb(Y, U, V, r, g, b);
   normalise(r, g, b, n, o);
+}
+
+// one NV12 tap (cuda_preprocess.cu:224-241)
+__device__ __forceinline__ void nv12_tap(const PreParams& q, int x, int y, float& r, float& g, float& b) {
+  const float Y = q.in[(size_t)y * q.pitch + x];
+  const uint8_t* c = q.uv + (size_t)(y / 2) * q.uv_pitch + (size_t)(x / 2) * 2;
+  nv12_rgb(Y, c[0] - 128.0f, c[1] - 128.0f, r, g, b);
+}
+
+// one output pixel of the NV12 resize: resize_pixel's coordinates and weights on float taps (see the file header)
+__device__ __forceinline__ void nv12_resize_pixel(const PreParams& q, int dx, int dy, float (&o)[3]) {
+  const float scale_x = (float)q.sw / q.dw, scale_y = (float)q.sh / q.dh;
+  float sx = (dx + 0.5f) * scale_x - 0.5f, sy = (dy + 0.5f) * scale_y - 0.5f;
+  sx = fmaxf(0.0f, fminf(sx, q.sw - 1.0f));
+  sy = fmaxf(0.0f, fminf(sy, q.sh - 1.0f));
+  const int x0 = (int)sx, y0 = (int)sy;
+  const int x1 = min(x0 + 1, q.sw - 1), y1 = min(y0 + 1, q.sh - 1);
+  const float fx = sx - x0, fy = sy - y0;
+  const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
+  float r00, g00, b00, r01, g01, b01, r10, g10, b10, r11, g11, b11;
+  nv12_tap(q, x0, y0, r00, g00, b00);
+  nv12_tap(q, x1, y0, r01, g01, b01);
+  nv12_tap(q, x0, y1, r10, g10, b10);
+  nv12_tap(q, x1, y1, r11, g11, b11);
+  const float r = w00 * r00 + w01 * r01 + w10 * r10 + w11 * r11;
+  const float g = w00 * g00 + w01 * g01 + w10 * g10 + w11 * g11;
+  const float b = w00 * b00 + w01 * b01 + w10 * b10 + w11 * b11;
+  normalise(r, g, b, q.norm, o);
 }
 
 template <int MODE>
@@ -101,6 +136,10 @@ __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams q
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (i < n) resize_pixel(q, x + i, y, o[i]);
+    } else if constexpr (MODE == kNv12Resize) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < n) nv12_resize_pixel(q, x + i, y, o[i]);
     } else {
       unsigned char yy[4], uu[4];
       const uint8_t* yrow = q.in + (size_t)y * q.pitch + x;
@@ -182,6 +221,20 @@ hipError_t preprocess_nv12(const uint8_t* d_y_plane, const uint8_t* d_uv_plane, 
     return hipErrorInvalidValue;
   PreParams q = {d_y_plane, d_uv_plane, d_output, width, height, y_pitch, uv_pitch, width, height, params};
   return launch_quads<kNv12>(q, stream);
+}
+
+// NV12 of any size -> the dst_width x dst_height tensor (the file header defines the resize; the reference has none). At
+// dst == src it is preprocess_nv12, launch included. Odd sizes are legal: the chroma plane then has (src_height + 1) / 2 rows,
+// and the last pair of an odd-width row is read whole, hence uv_pitch >= 2 * ((src_width + 1) / 2).
+hipError_t unina_preprocess_nv12_resize(const uint8_t* d_y_plane, const uint8_t* d_uv_plane, float* d_output, int src_width,
+                                        int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
+                                        NormParams params, hipStream_t stream) {
+  if (!d_y_plane || !d_uv_plane || !d_output || src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0 ||
+      y_pitch < src_width || uv_pitch < src_width || uv_pitch < 2 * ((src_width + 1) / 2))
+    return hipErrorInvalidValue;
+  PreParams q = {d_y_plane, d_uv_plane, d_output, src_width, src_height, y_pitch, uv_pitch, dst_width, dst_height, params};
+  if (dst_width == src_width && dst_height == src_height) return launch_quads<kNv12>(q, stream);
+  return launch_quads<kNv12Resize>(q, stream);
 }
 
 float* allocate_preprocess_buffer(int width, int height) {  // nullptr on failure (cuda_preprocess.cu:395-405)

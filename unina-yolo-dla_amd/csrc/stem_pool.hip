@@ -35,14 +35,48 @@ template <> struct StemOut<s16_t> {
 // pixel's CO/2 contiguous NHWC channels.
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
+// ((v / 255) - mean) / std per channel, as preprocess.hip's normalise
+__device__ __forceinline__ void cam_normalise(const StemParams& p, float r, float g, float b, float (&rgb)[3]) {
+#pragma clang fp contract(off)
+  rgb[0] = ((r / 255.0f) - p.norm.mean_r) / p.norm.std_r;
+  rgb[1] = ((g / 255.0f) - p.norm.mean_g) / p.norm.std_g;
+  rgb[2] = ((b / 255.0f) - p.norm.mean_b) / p.norm.std_b;
+}
+
+// BT.601 of one NV12 sample (preprocess.hip's nv12_pixel, cuda_preprocess.cu:229-241): the clamped values stay floats, they
+// are never rounded to u8.
+__device__ __forceinline__ void nv12_rgb(float Y, float U, float V, float& r, float& g, float& b) {
+#pragma clang fp contract(off)
+  r = Y + 1.402f * V;
+  g = Y - 0.344136f * U - 0.714136f * V;
+  b = Y + 1.772f * U;
+  r = fmaxf(0.0f, fminf(255.0f, r));
+  g = fmaxf(0.0f, fminf(255.0f, g));
+  b = fmaxf(0.0f, fminf(255.0f, b));
+}
+
+// The NV12 tap at pixel (xs, ys) of the region: camera pixel (cam_x0 + xs, cam_y0 + ys), whose chroma pair lies at row
+// (cam_y0 + ys) / 2, bytes 2 * ((cam_x0 + xs) / 2) and + 1 of the chroma plane (cuda_preprocess.cu:224-227).
+__device__ __forceinline__ void nv12_tap(const StemParams& p, int xs, int ys, float& r, float& g, float& b) {
+#pragma clang fp contract(off)
+  const int X = p.cam_x0 + xs, Y = p.cam_y0 + ys;
+  const float Yv = p.cam[(size_t)Y * p.cam_pitch + X];
+  const unsigned char* c = p.cam_uv + (size_t)(Y / 2) * p.cam_uv_pitch + (size_t)(X / 2) * 2;
+  nv12_rgb(Yv, c[0] - 128.0f, c[1] - 128.0f, r, g, b);
+}
+
 // Network-input pixel (y, x) of a camera frame: the arithmetic of preprocess.hip (cuda_preprocess.cu:99-128 plain BGRA,
-// :144-204 half-pixel-centre bilinear resize), expression trees rounded exactly as written there.
+// :144-204 half-pixel-centre bilinear resize, :212-253 NV12), expression trees rounded exactly as written there. The NV12
+// resize (src_kind 4) is this project's definition, the reference has none: the coordinates, clamps and weights of the BGRA
+// resize, the four taps being the clamped float r, g, b of nv12_tap instead of u8 channels.
 __device__ __forceinline__ void camera_pixel(const StemParams& p, int y, int x, float (&rgb)[3]) {
 #pragma clang fp contract(off)
   float r, g, b;
   if (p.src_kind == 1) {
     const uchar4 px = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y * p.cam_pitch + (size_t)x * 4);  // B,G,R,A
     r = (float)px.z; g = (float)px.y; b = (float)px.x;
+  } else if (p.src_kind == 3) {
+    nv12_tap(p, x, y, r, g, b);
   } else {
     const int sw = p.cam_w, sh = p.cam_h;
     const float scale_x = (float)sw / p.W, scale_y = (float)sh / p.H;
@@ -53,17 +87,26 @@ __device__ __forceinline__ void camera_pixel(const StemParams& p, int y, int x, 
     const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
     const float fx = sx - x0, fy = sy - y0;
     const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
-    const uchar4 p00 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x0 * 4);
-    const uchar4 p01 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x1 * 4);
-    const uchar4 p10 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x0 * 4);
-    const uchar4 p11 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x1 * 4);
-    r = w00 * p00.z + w01 * p01.z + w10 * p10.z + w11 * p11.z;
-    g = w00 * p00.y + w01 * p01.y + w10 * p10.y + w11 * p11.y;
-    b = w00 * p00.x + w01 * p01.x + w10 * p10.x + w11 * p11.x;
+    if (p.src_kind == 2) {
+      const uchar4 p00 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x0 * 4);
+      const uchar4 p01 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x1 * 4);
+      const uchar4 p10 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x0 * 4);
+      const uchar4 p11 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x1 * 4);
+      r = w00 * p00.z + w01 * p01.z + w10 * p10.z + w11 * p11.z;
+      g = w00 * p00.y + w01 * p01.y + w10 * p10.y + w11 * p11.y;
+      b = w00 * p00.x + w01 * p01.x + w10 * p10.x + w11 * p11.x;
+    } else {
+      float r00, g00, b00, r01, g01, b01, r10, g10, b10, r11, g11, b11;
+      nv12_tap(p, x0, y0, r00, g00, b00);
+      nv12_tap(p, x1, y0, r01, g01, b01);
+      nv12_tap(p, x0, y1, r10, g10, b10);
+      nv12_tap(p, x1, y1, r11, g11, b11);
+      r = w00 * r00 + w01 * r01 + w10 * r10 + w11 * r11;
+      g = w00 * g00 + w01 * g01 + w10 * g10 + w11 * g11;
+      b = w00 * b00 + w01 * b01 + w10 * b10 + w11 * b11;
+    }
   }
-  rgb[0] = ((r / 255.0f) - p.norm.mean_r) / p.norm.std_r;
-  rgb[1] = ((g / 255.0f) - p.norm.mean_g) / p.norm.std_g;
-  rgb[2] = ((b / 255.0f) - p.norm.mean_b) / p.norm.std_b;
+  cam_normalise(p, r, g, b, rgb);
 }
 
 template <typename T, int CO>
@@ -195,6 +238,56 @@ __global__ __launch_bounds__(kStemNT) void stem_tile_kernel(const StemParams p) 
       }
       *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = val;
     }
+  } else if (p.src_kind == 3) {
+    // NV12 region of the network's size, four footprint pixels per thread as preprocess_quads_kernel<kNv12> reads them: W and
+    // ix0 are multiples of 4, so a quad lies wholly inside its row or wholly outside. A dword of luma and a dword of chroma
+    // (two U,V pairs) cover it where the addresses are 4-byte aligned -- the same answer for every quad of the frame, it
+    // depends on the pitches, the plane addresses and the region's origin only -- and byte loads otherwise.
+    const bool wide_y = (p.cam_pitch & 3) == 0 && (((uintptr_t)p.cam + (unsigned)p.cam_x0) & 3) == 0;
+    const bool wide_c = (p.cam_uv_pitch & 3) == 0 && (p.cam_x0 & 1) == 0 && (((uintptr_t)p.cam_uv + (unsigned)p.cam_x0) & 3) == 0;
+    for (int v = tid; v < kStemPR * (kStemPW / 4); v += kStemNT) {
+      const int r = v / (kStemPW / 4), q = v - r * (kStemPW / 4);
+      const int iy = iy0 + r, ix = ix0 + 4 * q;
+      float o[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix + 3 < p.W) {
+        const int X = p.cam_x0 + ix, Y = p.cam_y0 + iy;
+        const unsigned char* yrow = p.cam + (size_t)Y * p.cam_pitch + X;
+        const unsigned char* crow = p.cam_uv + (size_t)(Y / 2) * p.cam_uv_pitch;
+        unsigned char yy[4], uu[4], vv[4];
+        if (wide_y) {
+          const unsigned yw = *reinterpret_cast<const unsigned*>(yrow);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) yy[i] = (unsigned char)(yw >> (8 * i));
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) yy[i] = yrow[i];
+        }
+        if (wide_c) {   // X is even: the pairs of pixels X, X + 1 | X + 2, X + 3
+          const unsigned cw = *reinterpret_cast<const unsigned*>(crow + X);
+          uu[0] = uu[1] = (unsigned char)cw;
+          vv[0] = vv[1] = (unsigned char)(cw >> 8);
+          uu[2] = uu[3] = (unsigned char)(cw >> 16);
+          vv[2] = vv[3] = (unsigned char)(cw >> 24);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const unsigned char* c = crow + (size_t)((X + i) / 2) * 2;
+            uu[i] = c[0];
+            vv[i] = c[1];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma clang fp contract(off)
+          float cr, cg, cb;
+          nv12_rgb((float)yy[i], uu[i] - 128.0f, vv[i] - 128.0f, cr, cg, cb);
+          cam_normalise(p, cr, cg, cb, o[i]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+    }
   } else {
     // camera frame: every footprint pixel is pre-processed once, as preprocess.hip would have written it
     for (int e = tid; e < kStemPR * kStemPW; e += kStemNT) {
@@ -311,8 +404,9 @@ const StemKernel kStemKernels[] = {STEM(half_t, kF16, "f16", 32), STEM(half_t, k
 hipError_t stem_desc(const StemParams& p, LaunchDesc* out) {
   if (!p.wt) return hipErrorInvalidValue;
   static const bool legacy = getenv("UNINA_STEM_V1") && getenv("UNINA_STEM_V1")[0] == '1';   // the one-thread-per-pixel form
-  // The form depends on the SHAPE only, never on the pointer of the frame at hand: the captured frame graph's stem node is
-  // re-pointed per frame (hipGraphExecKernelNodeSetParams) and must keep its function, grid and block. The tiled kernel's aligned
+  // The form depends on the SHAPE only, never on the pointer of the frame at hand nor on its source kind (tensor, BGRA, NV12;
+  // whole frame or tile): the captured frame graph's stem node is re-pointed per frame and per tile
+  // (hipGraphExecKernelNodeSetParams) and must keep its function, grid, block and LDS size. The tiled kernel's aligned
   // 16-byte row loads need W % 4 == 0 and a 16-byte aligned tensor -- which unina_set_tensor_address / unina_infer guarantee
   // (they refuse any other address with UNINA_ERR_ARG).
   const bool tiled = !legacy && (p.W & 3) == 0 && p.dst_ld == p.Co;

@@ -55,11 +55,12 @@ _lib: Optional[C.CDLL] = None
 # every symbol include/unina_mi355.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "unina_load_engine", "unina_unload_engine", "unina_engine_input_dims", "unina_set_tensor_address",
-    "unina_tensor_address", "unina_enqueue", "unina_infer", "unina_infer_bgra", "unina_infer_async", "unina_postprocess_async",
+    "unina_tensor_address", "unina_enqueue", "unina_infer", "unina_infer_bgra", "unina_infer_nv12", "unina_infer_async", "unina_postprocess_async",
     "unina_last_error", "unina_op_count", "unina_get_op_info", "unina_profile_ops", "unina_profile_post", "unina_debug_read_buffer",
     "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_serial_latency",
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
     "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
+    "unina_infer_tiled_nv12", "unina_infer_tiled_nv12_async", "unina_preprocess_nv12_resize",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -91,6 +92,7 @@ def load_library() -> C.CDLL:
     L.unina_infer.argtypes = [vp, vp, cf, cf, cf, vp, C.POINTER(ci), vp]
     L.unina_infer_async.argtypes = [vp, vp, cf, cf, cf, vp, vp, vp]
     L.unina_infer_bgra.argtypes = [vp, vp, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, vp, C.POINTER(ci), vp]
+    L.unina_infer_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, vp, C.POINTER(ci), vp]
     L.unina_postprocess_async.argtypes = [vp, cf, cf, cf, vp, vp, vp]
     L.unina_last_error.argtypes = [vp]
     L.unina_last_error.restype = C.c_char_p
@@ -119,6 +121,10 @@ def load_library() -> C.CDLL:
                                          C.POINTER(ci), vp]
     L.unina_infer_tiled_bgra_async.argtypes = [vp, vp, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf, vp,
                                                vp, vp]
+    L.unina_infer_tiled_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf, vp,
+                                         C.POINTER(ci), vp]
+    L.unina_infer_tiled_nv12_async.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf,
+                                               vp, vp, vp]
     L.unina_merge_tiles_async.argtypes = [vp, vp, vp, C.POINTER(Tile), ci, cf, vp, vp, vp]
     # data mining (csrc/mining.hip)
     L.unina_embedding_dim.argtypes = [vp]
@@ -148,6 +154,7 @@ def load_library() -> C.CDLL:
     L.preprocess_bgra_resize.argtypes = [vp, vp, ci, ci, ci, ci, ci, NormParams, vp]
     L.preprocess_bgra.argtypes = [vp, vp, ci, ci, ci, NormParams, vp]
     L.preprocess_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, NormParams, vp]
+    L.unina_preprocess_nv12_resize.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, NormParams, vp]   # (ours: the reference's NV12 path cannot resize)
     L.allocate_preprocess_buffer.restype = vp
     L.allocate_preprocess_buffer.argtypes = [ci, ci]
     L.free_preprocess_buffer.argtypes = [vp]
@@ -174,6 +181,11 @@ def _stream_ptr(stream) -> int:
     if stream is None:
         stream = _torch().cuda.current_stream()
     return stream if isinstance(stream, int) else stream.cuda_stream
+
+
+def _ptr(t):
+    """Device address of a CUDA tensor; None stays None (the ABI answers a null plane with UNINA_ERR_ARG)."""
+    return None if t is None else t.data_ptr()
 
 
 class Engine:
@@ -298,6 +310,41 @@ class Engine:
         self._check(self.L.unina_infer_bgra(self.h, frame.data_ptr(), width, height, pitch, C.byref(norm), conf_thr, iou_thr,
                                             conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
         return out[:n.value].copy()
+
+    def infer_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, norm: Optional[NormParams] = None,
+                   conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, stream=None):
+        """NV12 camera frame (uint8 CUDA tensors: luma plane `y`, interleaved chroma plane `uv` of (height + 1) // 2 rows)
+        -> detections, the pre-process inside the stem kernel (unina_infer_nv12; camera.nv12_to_tensor is its numpy twin)."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        out = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, C.byref(norm), conf_thr,
+                                            iou_thr, conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
+        return out[:n.value].copy()
+
+    def infer_tiled_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, tiles=None,
+                         norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1,
+                         merge_iou: float = 0.45, out=None, stream=None):
+        """infer_tiled_bgra on an NV12 frame: the tile's origin goes to the stem kernel (it enters the chroma index, so it may
+        be odd). `tiles`, `out` and the result as there."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if tiles is None:
+            tiles = self.default_tiles(width, height)
+        arr = _tile_array(tiles)
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_tiled_nv12_async(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, arr,
+                                                            len(tiles), C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou,
+                                                            base + 32, base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_tiled_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, arr, len(tiles),
+                                                  C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou, host.ctypes.data,
+                                                  C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
 
     def default_tiles(self, width: int, height: int):
         """The reference's default slicing (20 % overlap) at the engine's input size, exact repeats dropped."""
