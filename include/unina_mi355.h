@@ -151,6 +151,56 @@ int unina_infer_nv12(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv,
                      int uv_pitch, const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
                      GpuDetection *out, int *out_count, hipStream_t stream);
 
+/* ------------------------------------------------------------------ letterboxed camera frames
+ * unina_infer_bgra / unina_infer_nv12 STRETCH the frame to the network input: 1920 x 1080 into 640 x 640 squeezes every object
+ * 1.78 x narrower than the model was trained on. These calls keep the aspect ratio instead: the frame is resized into an inner
+ * rectangle of the network input, the rest is padded, and the boxes can come back in the camera's own pixels -- all inside the
+ * frame graph (the stem kernel computes the letterboxed pixel, the post-process maps the kept records where it writes them).
+ * Everything below is THIS PROJECT'S definition. Parity with Ultralytics' LetterBox / cv2.resize is unpinned: cv2 blends u8 in
+ * fixed point and rounds to u8, here the blended values stay floats.
+ *
+ * Geometry (unina_letterbox_geometry; host only, no engine, no device -- unina_slice_tiles' role), all in double:
+ *   r = min((double)dst_h / src_h, (double)dst_w / src_w)
+ *   new_w = round(src_w * r), new_h = round(src_h * r), each at least 1
+ *   left = round((dst_w - new_w) / 2.0 - 0.1), top = round((dst_h - new_h) / 2.0 - 0.1); right / bottom padding: what remains
+ *   round = round-half-to-even (Python's round, nearbyint in the default rounding mode): 5 x 128 into 64 x 64 has r = 0.5 and
+ *   new_w = round(2.5) = 2. 1920 x 1080 into 640 x 640: 640 x 360 at (0, 140). Returns 0, or -UNINA_ERR_ARG (non-positive size, NULL).
+ * Network-input pixel (x, y):
+ *   inside the inner rectangle (left <= x < left + new_w, top <= y < top + new_h):
+ *     (new_w, new_h) == (src_w, src_h): the plain tap at (x - left, y - top), as preprocess_bgra / preprocess_nv12;
+ *     otherwise preprocess_bgra_resize / unina_preprocess_nv12_resize evaluated for a destination of new_w x new_h at
+ *     (x - left, y - top): scale_x = (float)src_w / (float)new_w, coordinates, clamps, weights and the left-to-right blend unchanged
+ *   outside: r = g = b = (float)pad_value (Ultralytics pads with 114)
+ *   both then ((v / 255.0f) - mean) / std. So the inner rectangle of a letterboxed tensor equals the resize of the frame to
+ *   new_w x new_h bit for bit, and the conv's zero padding outside the network input stays zero.
+ * Box map, map_boxes: 0 = records in network pixels, as unina_infer; 1 = camera pixels. Decode, conformal dilation and NMS always
+ * run in network pixels; only the KEPT records are mapped, both corners, fp32, each step rounded separately:
+ *   X = (x - (float)left) * ((float)src_w / (float)new_w)      Y = (y - (float)top) * ((float)src_h / (float)new_h)
+ * NOTHING IS CLAMPED to the frame (the engine clamps nowhere): a box over the padding maps to coordinates outside the camera. */
+typedef struct { int new_w, new_h, left, top; } unina_letterbox;
+int unina_letterbox_geometry(int src_w, int src_h, int dst_w, int dst_h, unina_letterbox *out);
+
+/* unina_infer_bgra / unina_infer_nv12 with the letterbox above in place of the stretch: same arguments and argument checks, plus
+ * pad_value and map_boxes (0 / 1, anything else UNINA_ERR_ARG). Synchronous, delivered as unina_infer delivers (pinned block +
+ * completion word: no D2H copy, no stream synchronisation, no extra launch for the map). A refused call enqueues nothing; the
+ * stems and the map flag are restored whatever the call returns. With map_boxes = 0 the results equal
+ * unina_preprocess_letterbox_* + unina_infer bit for bit; a frame of the network's size is unina_infer_bgra / unina_infer_nv12. */
+int unina_infer_letterbox_bgra(unina_engine_t *e, const uint8_t *d_bgra, int src_width, int src_height, int src_pitch,
+                               const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
+                               float pad_value, int map_boxes, GpuDetection *out, int *out_count, hipStream_t stream);
+int unina_infer_letterbox_nv12(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv, int src_width, int src_height,
+                               int y_pitch, int uv_pitch, const NormParams *norm, float conf_threshold, float iou_threshold,
+                               float conformal_q, float pad_value, int map_boxes, GpuDetection *out, int *out_count,
+                               hipStream_t stream);
+/* The same, results on the device (d_out: MAX_DETECTIONS records, 16-byte aligned; d_out_count: one int), nothing synchronised. */
+int unina_infer_letterbox_bgra_async(unina_engine_t *e, const uint8_t *d_bgra, int src_width, int src_height, int src_pitch,
+                                     const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
+                                     float pad_value, int map_boxes, GpuDetection *d_out, int *d_out_count, hipStream_t stream);
+int unina_infer_letterbox_nv12_async(unina_engine_t *e, const uint8_t *d_y, const uint8_t *d_uv, int src_width, int src_height,
+                                     int y_pitch, int uv_pitch, const NormParams *norm, float conf_threshold, float iou_threshold,
+                                     float conformal_q, float pad_value, int map_boxes, GpuDetection *d_out, int *d_out_count,
+                                     hipStream_t stream);
+
 /* Asynchronous variant: results stay on the device (d_out: MAX_DETECTIONS records, d_out_count: one int);
  * nothing is synchronised. Used to pipeline frames and to feed the RCCL gather without touching the host. */
 int unina_infer_async(unina_engine_t *e, const float *d_images_nchw, float conf_threshold, float iou_threshold,
@@ -432,6 +482,16 @@ hipError_t preprocess_nv12(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, 
 hipError_t unina_preprocess_nv12_resize(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, float *d_output, int src_width,
                                         int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
                                         NormParams params, hipStream_t stream);
+/* The letterbox as a step of its own (the definition at unina_letterbox_geometry above): camera frame -> the dst_width x
+ * dst_height tensor, resized into the inner rectangle, pad_value around it. Arguments as preprocess_bgra_resize /
+ * unina_preprocess_nv12_resize plus pad_value; hipErrorInvalidValue for what those refuse, and for a BGRA pitch or address that
+ * is not a multiple of 4. */
+hipError_t unina_preprocess_letterbox_bgra(const uint8_t *d_input, float *d_output, int src_width, int src_height,
+                                           int src_pitch, int dst_width, int dst_height, float pad_value, NormParams params,
+                                           hipStream_t stream);
+hipError_t unina_preprocess_letterbox_nv12(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, float *d_output, int src_width,
+                                           int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
+                                           float pad_value, NormParams params, hipStream_t stream);
 float *allocate_preprocess_buffer(int width, int height);
 void free_preprocess_buffer(float *d_buffer);
 hipStream_t create_preprocess_stream(void);

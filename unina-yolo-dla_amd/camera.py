@@ -1,4 +1,5 @@
-"""NV12 camera frames on the host side: a numpy float32 twin of the pre-process the stem kernel computes.
+"""Camera frames on the host side: numpy float32 twins of the pre-process the stem kernel computes (NV12, and the letterbox
+of both camera formats with its box map).
 
 ``nv12_to_tensor`` is to ``unina_infer_nv12`` / ``unina_infer_tiled_nv12`` / ``unina_preprocess_nv12_resize`` what
 ``slicing.merge_numpy`` is to the GPU merge: the same arithmetic without a GPU, operation for operation on ``np.float32``
@@ -13,6 +14,12 @@ in the written order, so the results agree bit for bit. The definition (include/
                                   w00 t00 + w01 t01 + w10 t10 + w11 t11 left to right, then normalised
   tile (x0, y0, w, h)             source coordinates tile-local (a frame of w x h), the tap read at (x0 + xs, y0 + ys):
                                   the origin enters the chroma index, so it may be odd
+
+``letterbox_bgra_to_tensor`` / ``letterbox_nv12_to_tensor`` / ``unmap_boxes`` are the twins of ``unina_preprocess_letterbox_*`` /
+``unina_infer_letterbox_*`` (include/unina_mi355.h at unina_letterbox_geometry): the frame resized -- or, where the inner
+rectangle has the frame's size, tapped -- into ``mine.letterbox_geometry``'s rectangle by the forms above evaluated for a
+destination of new_w x new_h, ``pad_value`` around it, one normalise for both; kept boxes back to camera pixels as
+``(x - left) * (src_w / new_w)``, each step rounded to float32, nothing clamped.
 """
 from __future__ import annotations
 
@@ -74,6 +81,11 @@ def nv12_to_tensor(y: np.ndarray, uv: np.ndarray, dst_hw: Optional[Tuple[int, in
     dh, dw = (sh, sw) if dst_hw is None else (int(dst_hw[0]), int(dst_hw[1]))
     if dh <= 0 or dw <= 0:
         raise ValueError("output size must be positive")
+    return _normalise(_nv12_rgb(y, uv, x0, y0, sw, sh, dh, dw), norm)
+
+
+def _nv12_rgb(y, uv, x0: int, y0: int, sw: int, sh: int, dh: int, dw: int):
+    """Float r, g, b [dh, dw] of the region before the normalisation: the tap, or the resize's blend of four taps."""
     if (dh, dw) == (sh, sw):
         r, g, b = _tap(y, uv, x0 + np.arange(sw)[None, :], y0 + np.arange(sh)[:, None])
     else:
@@ -87,9 +99,79 @@ def nv12_to_tensor(y: np.ndarray, uv: np.ndarray, dst_hw: Optional[Tuple[int, in
         t10 = _tap(y, uv, x0 + xa[None, :], y0 + yb[:, None])
         t11 = _tap(y, uv, x0 + xb[None, :], y0 + yb[:, None])
         r, g, b = (w00 * t00[c] + w01 * t01[c] + w10 * t10[c] + w11 * t11[c] for c in range(3))
+    return r, g, b
+
+
+def _normalise(rgb, norm) -> np.ndarray:
+    """((v / 255) - mean) / std per channel: float32 [3, H, W]."""
     n = _norm6(norm)
-    out = np.empty((3, dh, dw), dtype=_F)
-    for c, v in enumerate((r, g, b)):
-        out[c] = ((v / _F(255.0)) - n[c]) / n[3 + c]
+    out = np.empty((3,) + rgb[0].shape, dtype=_F)
+    for c, v in enumerate(rgb):
         assert v.dtype == _F
+        out[c] = ((v / _F(255.0)) - n[c]) / n[3 + c]
+    return out
+
+
+def _bgra_rgb(img: np.ndarray, dh: int, dw: int):
+    """Float r, g, b [dh, dw] of a BGRA frame [h, w, 4] before the normalisation: the u8 channels (preprocess_bgra), or
+    preprocess_bgra_resize's blend w00 p00 + w01 p01 + w10 p10 + w11 p11 left to right (cuda_preprocess.cu:155-198)."""
+    sh, sw = img.shape[:2]
+    if (dh, dw) == (sh, sw):
+        return tuple(img[..., c].astype(_F) for c in (2, 1, 0))
+    xa, xb, fx = _axis(dw, sw)
+    ya, yb, fy = _axis(dh, sh)
+    fx, fy = fx[None, :], fy[:, None]
+    one = _F(1.0)
+    w00, w01, w10, w11 = (one - fx) * (one - fy), fx * (one - fy), (one - fx) * fy, fx * fy
+    p00, p01 = img[ya[:, None], xa[None, :]], img[ya[:, None], xb[None, :]]
+    p10, p11 = img[yb[:, None], xa[None, :]], img[yb[:, None], xb[None, :]]
+    return tuple(w00 * p00[..., c].astype(_F) + w01 * p01[..., c].astype(_F) + w10 * p10[..., c].astype(_F) + w11 * p11[..., c].astype(_F)
+                 for c in (2, 1, 0))
+
+
+def _letterbox(inner_rgb, src_w: int, src_h: int, dst_hw, pad_value: float, norm) -> np.ndarray:
+    from .mine import letterbox_geometry
+    dh, dw = int(dst_hw[0]), int(dst_hw[1])
+    if src_w <= 0 or src_h <= 0 or dh <= 0 or dw <= 0:
+        raise ValueError("frame and output sizes must be positive")
+    new_w, new_h, left, top = letterbox_geometry(src_w, src_h, dw, dh)
+    canvas = [np.full((dh, dw), _F(pad_value), dtype=_F) for _ in range(3)]
+    for plane, v in zip(canvas, inner_rgb(new_h, new_w)):
+        plane[top:top + new_h, left:left + new_w] = v
+    return _normalise(canvas, norm)
+
+
+def letterbox_bgra_to_tensor(img: np.ndarray, dst_hw: Tuple[int, int], pad_value: float = 114.0,
+                             norm: Sequence[float] = IMAGENET) -> np.ndarray:
+    """BGRA frame uint8 [h, w, 4] -> float32 [3, H, W]: unina_preprocess_letterbox_bgra / the stem of
+    unina_infer_letterbox_bgra, bit for bit."""
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 4
+    return _letterbox(lambda nh, nw: _bgra_rgb(img, nh, nw), img.shape[1], img.shape[0], dst_hw, pad_value, norm)
+
+
+def letterbox_nv12_to_tensor(y: np.ndarray, uv: np.ndarray, dst_hw: Tuple[int, int], pad_value: float = 114.0,
+                             norm: Sequence[float] = IMAGENET) -> np.ndarray:
+    """NV12 frame (planes as nv12_to_tensor takes them, the whole frame) -> float32 [3, H, W]: unina_preprocess_letterbox_nv12 /
+    the stem of unina_infer_letterbox_nv12, bit for bit."""
+    y = np.asarray(y)
+    uv = np.asarray(uv)
+    assert y.dtype == np.uint8 and uv.dtype == np.uint8 and y.ndim == 2 and uv.ndim == 2
+    sh, sw = y.shape
+    if uv.shape[0] < (sh + 1) // 2 or uv.shape[1] < 2 * ((sw + 1) // 2):
+        raise ValueError("chroma plane too small for the frame")
+    return _letterbox(lambda nh, nw: _nv12_rgb(y, uv, 0, 0, sw, sh, nh, nw), sw, sh, dst_hw, pad_value, norm)
+
+
+def unmap_boxes(dets: np.ndarray, src_w: int, src_h: int, dst_w: int, dst_h: int) -> np.ndarray:
+    """Records in network pixels -> a copy in camera pixels: what map_boxes = 1 does where the post-process writes the kept
+    records. X = (x - float32(left)) * (float32(src_w) / float32(new_w)), each step rounded to float32; no clamp."""
+    from .mine import letterbox_geometry
+    new_w, new_h, left, top = letterbox_geometry(src_w, src_h, dst_w, dst_h)
+    sx, sy = _F(src_w) / _F(new_w), _F(src_h) / _F(new_h)
+    out = np.array(dets, copy=True)
+    for k, off, sc in (("x1", left, sx), ("y1", top, sy), ("x2", left, sx), ("y2", top, sy)):
+        v = (out[k].astype(_F) - _F(off)) * sc
+        assert v.dtype == _F
+        out[k] = v
     return out

@@ -109,6 +109,9 @@ struct unina_engine {
   unsigned int result_seq = 0;           // unina_infer calls so far
   unsigned int* done_flag = nullptr;     // set around unina_infer's launch: the post-process signals completion there
   unsigned int done_value = 0;
+  // set around a letterboxed call with map_boxes = 1: the post-process maps the kept records to camera pixels (PostParams::map_*)
+  int map_boxes = 0;
+  float map_left = 0.f, map_top = 0.f, map_sx = 0.f, map_sy = 0.f;
   int post_blocks = 0;
   // graph
   bool use_graph = true;
@@ -1302,6 +1305,13 @@ int fill_post_params(unina_engine* e, PostParams* pp, float conf, float iou, flo
   pp->stamps = getenv("UNINA_POST_STAMPS") ? reinterpret_cast<long long*>(e->d_result->pad_stamps) : nullptr;
   pp->done_flag = e->done_flag;
   pp->done_value = e->done_value;
+  if (e->map_boxes) {
+    pp->map_boxes = 1;
+    pp->map_left = e->map_left;
+    pp->map_top = e->map_top;
+    pp->map_sx = e->map_sx;
+    pp->map_sy = e->map_sy;
+  }
   return UNINA_OK;
 }
 
@@ -1902,6 +1912,10 @@ struct CameraRegion {
   int format;
   const uint8_t *plane, *uv;
   int w, h, pitch, uv_pitch, x0, y0;
+  // letterboxed (unina_infer_letterbox_*): the frame goes into the inner rectangle of the network input, `pad` around it
+  int letterbox = 0;
+  unina_letterbox box = {0, 0, 0, 0};
+  float pad = 0.f;
 };
 
 // Points every eager stem op at a camera region (src_kind 1 / 3: the network's size, 2 / 4: resized) / back at the fp32
@@ -1912,6 +1926,17 @@ static int point_stems_at_camera(unina_engine* e, const CameraRegion& c, const N
     PlannedOp& op = e->ops[k];
     if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
     op.sp.src_kind = (c.format == kCamNv12 ? 3 : 1) + ((c.w == op.sp.W && c.h == op.sp.H) ? 0 : 1);
+    op.sp.in_x0 = op.sp.in_y0 = op.sp.in_w = op.sp.in_h = 0;
+    op.sp.pad_value = 0.f;
+    // an inner rectangle that is the whole network input is the plain resize (or tap): kinds 1..4 and their fast paths
+    if (c.letterbox && !(c.box.new_w == op.sp.W && c.box.new_h == op.sp.H)) {
+      op.sp.src_kind = c.format == kCamNv12 ? 6 : 5;
+      op.sp.in_x0 = c.box.left;
+      op.sp.in_y0 = c.box.top;
+      op.sp.in_w = c.box.new_w;
+      op.sp.in_h = c.box.new_h;
+      op.sp.pad_value = c.pad;
+    }
     op.sp.cam = c.plane;
     op.sp.cam_uv = c.uv;
     op.sp.cam_w = c.w;
@@ -1932,6 +1957,8 @@ static void restore_stems(unina_engine* e) {
     op.sp.src_kind = 0;
     op.sp.cam = op.sp.cam_uv = nullptr;
     op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = op.sp.cam_uv_pitch = op.sp.cam_x0 = op.sp.cam_y0 = 0;
+    op.sp.in_x0 = op.sp.in_y0 = op.sp.in_w = op.sp.in_h = 0;
+    op.sp.pad_value = 0.f;
     memset(&op.sp.norm, 0, sizeof op.sp.norm);
   }
 }
@@ -1992,6 +2019,89 @@ int unina_infer_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv,
     if (rc != UNINA_OK) return rc;
   }
   return infer_camera(e, CameraRegion{kCamNv12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, 0, 0}, *norm, conf, iou, q, out, out_count, stream);
+}
+
+// ---- letterboxed camera frames (include/unina_mi355.h at unina_letterbox_geometry) ----
+// The body of the four calls, behind the argument checks of the frame: the stems are pointed at the letterboxed frame and the
+// post-process is told the box map for the call; both are put back afterwards, whatever it returns. Nothing is enqueued before
+// the last check has passed.
+static int infer_letterbox(unina_engine* e, const char* who, CameraRegion c, const NormParams& norm, float conf, float iou, float q,
+                           float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (map_boxes != 0 && map_boxes != 1) return fail(e, UNINA_ERR_ARG, "%s: map_boxes must be 0 or 1, got %d", who, map_boxes);
+  if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
+  if (unina_letterbox_geometry(c.w, c.h, (int)e->h.in_w, (int)e->h.in_h, &c.box) != UNINA_OK)
+    return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, c.w, c.h);
+  c.letterbox = 1;
+  c.pad = pad_value;
+  HIPCHK(e, hipSetDevice(e->device));
+  if (e->plan_dirty) {
+    const int rc = plan(e);
+    if (rc != UNINA_OK) return rc;
+  }
+  if (!point_stems_at_camera(e, c, norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+  e->camera_active = true;
+  if (map_boxes) {
+    e->map_boxes = 1;
+    e->map_left = (float)c.box.left;
+    e->map_top = (float)c.box.top;
+    e->map_sx = (float)c.w / (float)c.box.new_w;
+    e->map_sy = (float)c.h / (float)c.box.new_h;
+  }
+  const int rc = async ? unina_infer_async(e, nullptr, conf, iou, q, out, out_count, stream)
+                       : unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
+  e->map_boxes = 0;
+  e->camera_active = false;
+  restore_stems(e);
+  return rc;
+}
+
+static int letterbox_bgra(unina_engine* e, const char* who, const uint8_t* d_bgra, int w, int h, int pitch, const NormParams* norm,
+                          float conf, float iou, float q, float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count,
+                          hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!d_bgra || !norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null frame / norm / result pointer", who);
+  if (w <= 0 || h <= 0 || pitch < 4 * w || (pitch & 3) || ((uintptr_t)d_bgra & 3)) return fail(e, UNINA_ERR_ARG, "%s: bad frame geometry", who);
+  return infer_letterbox(e, who, CameraRegion{kCamBgra, d_bgra, nullptr, w, h, pitch, 0, 0, 0}, *norm, conf, iou, q, pad_value, map_boxes,
+                         async, out, out_count, stream);
+}
+
+static int letterbox_nv12(unina_engine* e, const char* who, const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch,
+                          int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes, bool async,
+                          GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
+  const int rc = check_nv12_frame(e, who, d_y, d_uv, w, h, y_pitch, uv_pitch);
+  if (rc != UNINA_OK) return rc;
+  return infer_letterbox(e, who, CameraRegion{kCamNv12, d_y, d_uv, w, h, y_pitch, uv_pitch, 0, 0}, *norm, conf, iou, q, pad_value,
+                         map_boxes, async, out, out_count, stream);
+}
+
+int unina_infer_letterbox_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
+                               const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
+                               GpuDetection* out, int* out_count, hipStream_t stream) {
+  return letterbox_bgra(e, "unina_infer_letterbox_bgra", d_bgra, src_width, src_height, src_pitch, norm, conf, iou, q, pad_value,
+                        map_boxes, false, out, out_count, stream);
+}
+
+int unina_infer_letterbox_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
+                                     const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
+                                     GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return letterbox_bgra(e, "unina_infer_letterbox_bgra_async", d_bgra, src_width, src_height, src_pitch, norm, conf, iou, q, pad_value,
+                        map_boxes, true, d_out, d_out_count, stream);
+}
+
+int unina_infer_letterbox_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
+                               int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
+                               GpuDetection* out, int* out_count, hipStream_t stream) {
+  return letterbox_nv12(e, "unina_infer_letterbox_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, norm, conf, iou, q,
+                        pad_value, map_boxes, false, out, out_count, stream);
+}
+
+int unina_infer_letterbox_nv12_async(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height,
+                                     int y_pitch, int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value,
+                                     int map_boxes, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return letterbox_nv12(e, "unina_infer_letterbox_nv12_async", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, norm, conf, iou, q,
+                        pad_value, map_boxes, true, d_out, d_out_count, stream);
 }
 
 // ---- sliced inference (auto_labeler.py:124-199, 255-271): T frame graphs into T device slots, one merge ----

@@ -442,6 +442,18 @@ __device__ void sort_and_nms(Smem& s, int n, float iou_thr, long long* stamps = 
 
 }  // namespace
 
+// The box map of a letterboxed frame (unina_infer_letterbox_*, map_boxes = 1): network pixels -> camera pixels, applied to a KEPT
+// record on its way out -- into the device buffer or the pinned host block alike -- so decode, dilation and NMS have run in
+// network pixels. fp32, subtract and multiply rounded separately, no clamp. The flag is a kernel argument: off, nothing runs.
+__device__ __forceinline__ void map_box(const PostParams& p, GpuDetection& d) {
+#pragma clang fp contract(off)
+  if (!p.map_boxes) return;
+  d.x1 = (d.x1 - p.map_left) * p.map_sx;
+  d.y1 = (d.y1 - p.map_top) * p.map_sy;
+  d.x2 = (d.x2 - p.map_left) * p.map_sx;
+  d.y2 = (d.y2 - p.map_top) * p.map_sy;
+}
+
 // Host hand-off without a stream synchronisation: when the outputs live in pinned host memory, the last block publishes
 // them at system scope and then stores the caller's sequence number; the host spins on that word (engine.hip unina_infer).
 __device__ __forceinline__ void signal_done(const PostParams& p, int tid) {
@@ -543,7 +555,11 @@ __global__ __launch_bounds__(kPostBlock) void postprocess_kernel(const PostParam
   const bool kept = tid < n && !((s.removed[tid >> 6] >> (tid & 63)) & 1ull);
   int nkept;
   const int opos = block_rank(kept, s, &nkept);
-  if (kept) p.out[opos] = get(s, tid, 1);
+  if (kept) {
+    GpuDetection d = get(s, tid, 1);
+    map_box(p, d);
+    p.out[opos] = d;
+  }
   if (tid == 0) {
     *p.out_count = nkept;
     if (p.out_candidates) *p.out_candidates = total;
@@ -1190,6 +1206,7 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
       d.class_id = ce_class(cc2[q].y);
       d.valid = 1;
       d._pad = 0;
+      map_box(p, d);
       p.out[s.list[0][rk[q]]] = d;
     }
   }

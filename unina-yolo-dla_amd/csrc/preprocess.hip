@@ -14,6 +14,7 @@
 // path writes one 16-byte store per output plane (a wave: 1 KiB contiguous per plane per instruction instead of 256 B),
 // and a flat grid-stride loop over the quads replaces the 2-D grid. Row tails (width % 4) and unaligned tensors fall back to
 // scalar accesses inside the same kernel. Built with -ffp-contract=off so the expression trees round exactly as written.
+#include <cmath>
 #include <cstdio>
 #include <hip/hip_runtime.h>
 
@@ -23,7 +24,7 @@
 
 namespace {
 
-enum Mode : int { kPlain = 0, kResize = 1, kNv12 = 2, kNv12Resize = 3 };
+enum Mode : int { kPlain = 0, kResize = 1, kNv12 = 2, kNv12Resize = 3, kLetterbox = 4, kNv12Letterbox = 5 };
 
 struct PreParams {
   const uint8_t* in;      // BGRA (plain / resize) or the Y plane (NV12)
@@ -31,8 +32,10 @@ struct PreParams {
   float* out;             // [3][dh][dw]
   int sw, sh, pitch;      // source size / pitch (NV12: luma pitch)
   int uv_pitch;
-  int dw, dh;             // output size (== source size except for kResize)
+  int dw, dh;             // output size (== source size except for the resizing and the letterbox modes)
   NormParams norm;
+  int lb_left, lb_top, lb_w, lb_h;   // letterbox modes: the inner rectangle of the output
+  float pad;                         // ... and r = g = b outside it
 };
 
 __device__ __forceinline__ void normalise(float r, float g, float b, const NormParams& p, float (&o)[3]) {
@@ -104,6 +107,37 @@ __device__ __forceinline__ void nv12_resize_pixel(const PreParams& q, int dx, in
   normalise(r, g, b, q.norm, o);
 }
 
+// one output pixel of a letterboxed frame: the pad value outside the inner rectangle; inside it the plain tap (the rectangle has
+// the frame's size) or the resize evaluated for a destination of lb_w x lb_h, at the rectangle's own coordinates
+template <int MODE>
+__device__ __forceinline__ void letterbox_pixel(const PreParams& q, int dx, int dy, float (&o)[3]) {
+  const int xi = dx - q.lb_left, yi = dy - q.lb_top;
+  if ((unsigned)xi >= (unsigned)q.lb_w || (unsigned)yi >= (unsigned)q.lb_h) {
+    normalise(q.pad, q.pad, q.pad, q.norm, o);
+    return;
+  }
+  const bool plain = q.lb_w == q.sw && q.lb_h == q.sh;
+  PreParams in = q;
+  in.dw = q.lb_w;
+  in.dh = q.lb_h;
+  if constexpr (MODE == kLetterbox) {
+    if (plain) {
+      const uchar4 px = *reinterpret_cast<const uchar4*>(q.in + (size_t)yi * q.pitch + (size_t)xi * 4);   // B,G,R,A
+      normalise((float)px.z, (float)px.y, (float)px.x, q.norm, o);
+    } else {
+      resize_pixel(in, xi, yi, o);
+    }
+  } else {
+    if (plain) {
+      float r, g, b;
+      nv12_tap(q, xi, yi, r, g, b);
+      normalise(r, g, b, q.norm, o);
+    } else {
+      nv12_resize_pixel(in, xi, yi, o);
+    }
+  }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams q) {
   const int qpr = (q.dw + 3) >> 2;                         // quads per output row
@@ -140,6 +174,10 @@ __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams q
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (i < n) nv12_resize_pixel(q, x + i, y, o[i]);
+    } else if constexpr (MODE == kLetterbox || MODE == kNv12Letterbox) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < n) letterbox_pixel<MODE>(q, x + i, y, o[i]);
     } else {
       unsigned char yy[4], uu[4];
       const uint8_t* yrow = q.in + (size_t)y * q.pitch + x;
@@ -235,6 +273,45 @@ hipError_t unina_preprocess_nv12_resize(const uint8_t* d_y_plane, const uint8_t*
   PreParams q = {d_y_plane, d_uv_plane, d_output, src_width, src_height, y_pitch, uv_pitch, dst_width, dst_height, params};
   if (dst_width == src_width && dst_height == src_height) return launch_quads<kNv12>(q, stream);
   return launch_quads<kNv12Resize>(q, stream);
+}
+
+// Host only. Python's round() is round-half-to-even: nearbyint in the default rounding mode (lround rounds halves away from zero:
+// 5 x 128 into 64 x 64 has r = 0.5 and new_w = round(2.5) = 2, not 3).
+int unina_letterbox_geometry(int src_w, int src_h, int dst_w, int dst_h, unina_letterbox* out) {
+  if (!out || src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return -UNINA_ERR_ARG;
+  const double rh = (double)dst_h / src_h, rw = (double)dst_w / src_w;
+  const double r = rh < rw ? rh : rw;
+  int new_w = (int)nearbyint(src_w * r), new_h = (int)nearbyint(src_h * r);
+  if (new_w < 1) new_w = 1;
+  if (new_h < 1) new_h = 1;
+  out->new_w = new_w;
+  out->new_h = new_h;
+  out->left = (int)nearbyint((dst_w - new_w) / 2.0 - 0.1);
+  out->top = (int)nearbyint((dst_h - new_h) / 2.0 - 0.1);
+  return UNINA_OK;
+}
+
+hipError_t unina_preprocess_letterbox_bgra(const uint8_t* d_input, float* d_output, int src_width, int src_height, int src_pitch,
+                                           int dst_width, int dst_height, float pad_value, NormParams params, hipStream_t stream) {
+  unina_letterbox lb;
+  if (!d_input || !d_output || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_input & 3) ||
+      unina_letterbox_geometry(src_width, src_height, dst_width, dst_height, &lb) != UNINA_OK)
+    return hipErrorInvalidValue;
+  PreParams q = {d_input, nullptr, d_output, src_width, src_height, src_pitch, 0, dst_width, dst_height, params,
+                 lb.left, lb.top, lb.new_w, lb.new_h, pad_value};
+  return launch_quads<kLetterbox>(q, stream);
+}
+
+hipError_t unina_preprocess_letterbox_nv12(const uint8_t* d_y_plane, const uint8_t* d_uv_plane, float* d_output, int src_width,
+                                           int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
+                                           float pad_value, NormParams params, hipStream_t stream) {
+  unina_letterbox lb;
+  if (!d_y_plane || !d_uv_plane || !d_output || unina_letterbox_geometry(src_width, src_height, dst_width, dst_height, &lb) != UNINA_OK ||
+      y_pitch < src_width || uv_pitch < src_width || uv_pitch < 2 * ((src_width + 1) / 2))
+    return hipErrorInvalidValue;
+  PreParams q = {d_y_plane, d_uv_plane, d_output, src_width, src_height, y_pitch, uv_pitch, dst_width, dst_height, params,
+                 lb.left, lb.top, lb.new_w, lb.new_h, pad_value};
+  return launch_quads<kNv12Letterbox>(q, stream);
 }
 
 float* allocate_preprocess_buffer(int width, int height) {  // nullptr on failure (cuda_preprocess.cu:395-405)

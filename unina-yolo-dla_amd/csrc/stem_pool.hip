@@ -69,17 +69,33 @@ __device__ __forceinline__ void nv12_tap(const StemParams& p, int xs, int ys, fl
 // :144-204 half-pixel-centre bilinear resize, :212-253 NV12), expression trees rounded exactly as written there. The NV12
 // resize (src_kind 4) is this project's definition, the reference has none: the coordinates, clamps and weights of the BGRA
 // resize, the four taps being the clamped float r, g, b of nv12_tap instead of u8 channels.
+// Letterboxed frames (src_kind 5 BGRA, 6 NV12; include/unina_mi355.h at unina_infer_letterbox_bgra): inside the inner rectangle
+// the pixel is that of kind 1..4 for a destination of in_w x in_h at (x - in_x0, y - in_y0), outside it r = g = b = pad_value.
+// The kind, the destination size and the offset are kernel arguments: they are re-based in scalar registers under a wave-uniform
+// branch, so kinds 1..4 run the instructions they ran before; only the inside test is per pixel (lanes outside skip the taps).
 __device__ __forceinline__ void camera_pixel(const StemParams& p, int y, int x, float (&rgb)[3]) {
 #pragma clang fp contract(off)
   float r, g, b;
-  if (p.src_kind == 1) {
+  int kind = p.src_kind, dw = p.W, dh = p.H;
+  bool inside = true;
+  if (kind >= 5) {
+    dw = p.in_w;
+    dh = p.in_h;
+    x -= p.in_x0;
+    y -= p.in_y0;
+    inside = (unsigned)x < (unsigned)dw && (unsigned)y < (unsigned)dh;
+    kind = (kind == 5 ? 1 : 3) + ((dw == p.cam_w && dh == p.cam_h) ? 0 : 1);
+  }
+  if (!inside) {
+    r = g = b = p.pad_value;
+  } else if (kind == 1) {
     const uchar4 px = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y * p.cam_pitch + (size_t)x * 4);  // B,G,R,A
     r = (float)px.z; g = (float)px.y; b = (float)px.x;
-  } else if (p.src_kind == 3) {
+  } else if (kind == 3) {
     nv12_tap(p, x, y, r, g, b);
   } else {
     const int sw = p.cam_w, sh = p.cam_h;
-    const float scale_x = (float)sw / p.W, scale_y = (float)sh / p.H;
+    const float scale_x = (float)sw / dw, scale_y = (float)sh / dh;
     float sx = (x + 0.5f) * scale_x - 0.5f, sy = (y + 0.5f) * scale_y - 0.5f;
     sx = fmaxf(0.0f, fminf(sx, sw - 1.0f));
     sy = fmaxf(0.0f, fminf(sy, sh - 1.0f));
@@ -87,7 +103,7 @@ __device__ __forceinline__ void camera_pixel(const StemParams& p, int y, int x, 
     const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
     const float fx = sx - x0, fy = sy - y0;
     const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
-    if (p.src_kind == 2) {
+    if (kind == 2) {
       const uchar4 p00 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x0 * 4);
       const uchar4 p01 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x1 * 4);
       const uchar4 p10 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x0 * 4);

@@ -42,6 +42,11 @@ class Tile(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x", "y", "w", "h")]
 
 
+class Letterbox(C.Structure):
+    """unina_letterbox: the inner rectangle of a letterboxed frame in the network input."""
+    _fields_ = [(n, C.c_int) for n in ("new_w", "new_h", "left", "top")]
+
+
 def _tile_array(tiles):
     return (Tile * len(tiles))(*[Tile(*map(int, t)) for t in tiles])
 
@@ -61,6 +66,8 @@ ABI_SYMBOLS = [
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
     "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
     "unina_infer_tiled_nv12", "unina_infer_tiled_nv12_async", "unina_preprocess_nv12_resize",
+    "unina_letterbox_geometry", "unina_infer_letterbox_bgra", "unina_infer_letterbox_nv12", "unina_infer_letterbox_bgra_async",
+    "unina_infer_letterbox_nv12_async", "unina_preprocess_letterbox_bgra", "unina_preprocess_letterbox_nv12",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -126,6 +133,15 @@ def load_library() -> C.CDLL:
     L.unina_infer_tiled_nv12_async.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(Tile), ci, C.POINTER(NormParams), cf, cf, cf, cf,
                                                vp, vp, vp]
     L.unina_merge_tiles_async.argtypes = [vp, vp, vp, C.POINTER(Tile), ci, cf, vp, vp, vp]
+    # letterboxed camera frames (csrc/stem_pool.hip: src_kind 5 / 6; csrc/postprocess.hip: map_box)
+    L.unina_letterbox_geometry.argtypes = [ci, ci, ci, ci, C.POINTER(Letterbox)]
+    L.unina_infer_letterbox_bgra.argtypes = [vp, vp, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, cf, ci, vp, C.POINTER(ci), vp]
+    L.unina_infer_letterbox_bgra_async.argtypes = [vp, vp, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, cf, ci, vp, vp, vp]
+    L.unina_infer_letterbox_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, cf, ci, vp,
+                                             C.POINTER(ci), vp]
+    L.unina_infer_letterbox_nv12_async.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, cf, ci, vp, vp, vp]
+    L.unina_preprocess_letterbox_bgra.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, NormParams, vp]
+    L.unina_preprocess_letterbox_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, NormParams, vp]
     # data mining (csrc/mining.hip)
     L.unina_embedding_dim.argtypes = [vp]
     L.unina_mine_async.argtypes = [vp, vp, vp, vp, vp]
@@ -322,6 +338,47 @@ class Engine:
         self._check(self.L.unina_infer_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, C.byref(norm), conf_thr,
                                             iou_thr, conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
         return out[:n.value].copy()
+
+    def infer_letterbox_bgra(self, frame, width: int, height: int, pitch: int, norm: Optional[NormParams] = None,
+                             conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, pad_value: float = 114.0,
+                             map_boxes: bool = True, out=None, stream=None):
+        """infer_bgra without the stretch: the frame keeps its aspect ratio inside the network input (letterbox_geometry),
+        `pad_value` around it, all computed in the stem kernel. map_boxes: boxes back in CAMERA pixels (mapped where the
+        post-process writes them; camera.unmap_boxes is the numpy twin), False: network pixels. `out=None`: synchronous,
+        returns the kept detections; `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_letterbox_bgra_async(self.h, _ptr(frame), width, height, pitch, C.byref(norm), conf_thr,
+                                                                iou_thr, conformal_q, pad_value, int(map_boxes), base + 32, base,
+                                                                _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_letterbox_bgra(self.h, _ptr(frame), width, height, pitch, C.byref(norm), conf_thr, iou_thr,
+                                                      conformal_q, pad_value, int(map_boxes), host.ctypes.data, C.byref(n),
+                                                      _stream_ptr(stream)))
+        return host[:n.value].copy()
+
+    def infer_letterbox_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, norm: Optional[NormParams] = None,
+                             conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, pad_value: float = 114.0,
+                             map_boxes: bool = True, out=None, stream=None):
+        """infer_letterbox_bgra for an NV12 frame (planes and pitches as infer_nv12)."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_letterbox_nv12_async(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch,
+                                                                C.byref(norm), conf_thr, iou_thr, conformal_q, pad_value,
+                                                                int(map_boxes), base + 32, base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_letterbox_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, C.byref(norm),
+                                                      conf_thr, iou_thr, conformal_q, pad_value, int(map_boxes), host.ctypes.data,
+                                                      C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
 
     def infer_tiled_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, tiles=None,
                          norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1,
@@ -697,6 +754,16 @@ def calibrate_amax(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, de
         return _export.calibrate(per_frame(), percentile, method)
     finally:
         eng.close()
+
+
+def letterbox_geometry(src_w: int, src_h: int, dst_w: int, dst_h: int):
+    """unina_letterbox_geometry through the C ABI (host only, no device): (new_w, new_h, left, top)."""
+    L = load_library()
+    box = Letterbox()
+    rc = L.unina_letterbox_geometry(src_w, src_h, dst_w, dst_h, C.byref(box))
+    if rc:
+        raise EngineError(f"unina_letterbox_geometry failed [{ERRORS.get(-rc, -rc)}] ({src_w} x {src_h} into {dst_w} x {dst_h})")
+    return box.new_w, box.new_h, box.left, box.top
 
 
 def slice_tiles(frame_w: int, frame_h: int, slice_w: int = 640, slice_h: int = 640, overlap_w: float = 0.2,

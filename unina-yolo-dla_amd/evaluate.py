@@ -14,6 +14,10 @@ Frames: ``.npy`` holding the network tensor itself (fp32 ``[3,H,W]``, H x W = th
 frame (uint8 ``[h,w,4]`` BGRA / ``[h,w,3]`` RGB, any size: resized + normalised on the GPU by the stem kernel, i.e.
 ``unina_infer_bgra``), and ``.png`` / ``.jpg`` when Pillow is importable. Detections come back in network pixels; the
 records written to predictions.json are scaled to the image's own pixels, as Ultralytics writes them.
+
+By default a camera frame is STRETCHED to the network input (``unina_infer_bgra``). ``--letterbox`` keeps its aspect ratio, as
+``YOLO.val`` does: ``unina_infer_letterbox_bgra`` with pad 114 and ``map_boxes=1``, so the records come back in the image's own
+pixels from the GPU and the host rescale is skipped for them.
 """
 from __future__ import annotations
 
@@ -76,12 +80,13 @@ class EngineDetector:
     """frame -> detections through the C ABI. fp32 [3,H,W] frames go to unina_infer; uint8 camera frames are packed to
     BGRA and go to unina_infer_bgra (pre-process inside the stem kernel, perception_node.cpp:601-656 as one call)."""
 
-    def __init__(self, engine_path: str, device: int = 0, autotune: bool = True):
+    def __init__(self, engine_path: str, device: int = 0, autotune: bool = True, letterbox: bool = False):
         from .engine import Engine
         self.eng = Engine(engine_path, device)
         if autotune:
             self.eng.autotune()
         self.width, self.height = self.eng.width, self.eng.height
+        self.letterbox = letterbox          # uint8 frames: letterboxed in the stem, boxes returned in the frame's own pixels
 
     def __call__(self, frame: np.ndarray, conf: float, iou: float, q: float) -> np.ndarray:
         import torch
@@ -94,6 +99,8 @@ class EngineDetector:
             else:
                 bgra = np.ascontiguousarray(frame)
             cam = torch.from_numpy(bgra.reshape(h, w * 4)).to(dev)
+            if self.letterbox:
+                return self.eng.infer_letterbox_bgra(cam, w, h, w * 4, None, conf, iou, q, 114.0, True)
             return self.eng.infer_bgra(cam, w, h, w * 4, None, conf, iou, q)
         x = np.ascontiguousarray(frame, dtype=np.float32).reshape(1, 3, self.height, self.width)
         return self.eng.infer(torch.from_numpy(x).to(dev), conf, iou, q)
@@ -105,14 +112,15 @@ class EngineDetector:
 def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], root: str, imgsz: int = 640,
              conf: float = 0.5, iou: float = 0.45, conformal_q: float = 0.1, out_dir: Optional[str] = None,
              net_size: Optional[Tuple[int, int]] = None, conformal_alpha: Optional[float] = None,
-             conformal_conf: float = 0.001) -> Dict[str, object]:
+             conformal_conf: float = 0.001, camera_pixels: bool = False) -> Dict[str, object]:
     """eval.py:18-138 over `detect` (frame, conf, iou, q) -> GpuDetection records in network pixels.
 
     Writes <out_dir>/predictions.json (eval.py:58-61 schema, boxes in the image's own pixels), computes
     SmallObjectMetric(size_threshold=15, image_size=imgsz) exactly as eval.py:74,96-131 does, and -- with
     `conformal_alpha` -- the conformal quantile of train.py:299-520 from a second pass at a very low confidence
     threshold (train.py:403) without dilation. Returns {'small_object': {...}, 'conformal': {...} | None,
-    'predictions': [...], 'images': n}."""
+    'predictions': [...], 'images': n}. camera_pixels: `detect` returns the records of uint8 camera frames in the frame's own
+    pixels already (a letterboxing detector with the box map on): no host rescale for them."""
     files = list_frames(root)
     if not files:
         raise FileNotFoundError(f"no frames (*.npy / *.png / *.jpg) under {root}")
@@ -123,7 +131,9 @@ def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], ro
         stem = os.path.splitext(os.path.basename(path))[0]
         frame = load_frame(path)
         w, h = frame_size(frame)
-        if frame.dtype == np.uint8:                                   # camera frame: detections come back in network pixels
+        if frame.dtype == np.uint8 and camera_pixels:                 # camera frame, boxes mapped back on the GPU
+            nw, nh = w, h
+        elif frame.dtype == np.uint8:                                 # camera frame: detections come back in network pixels
             if net_size is None:
                 raise ValueError("uint8 camera frames need net_size=(width, height) of the engine input")
             nw, nh = net_size
@@ -171,11 +181,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--alpha", type=float, default=0.10)
     ap.add_argument("--out-dir", default="runs/eval")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--letterbox", action="store_true",
+                    help="uint8 camera frames keep their aspect ratio (pad 114) instead of being stretched; boxes mapped back on the GPU")
     a = ap.parse_args(argv)
-    det = EngineDetector(a.engine, a.device)
+    det = EngineDetector(a.engine, a.device, letterbox=a.letterbox)
     try:
         res = evaluate(det, a.data, a.imgsz, a.conf, a.iou, a.conformal_q, a.out_dir, (det.width, det.height),
-                       a.alpha if a.conformal else None)
+                       a.alpha if a.conformal else None, camera_pixels=a.letterbox)
     finally:
         det.close()
     print(f"{res['images']} images, {len(res['predictions'])} predictions -> {os.path.join(a.out_dir, 'predictions.json')}")

@@ -10,6 +10,10 @@ Images are read with PIL: letterbox to the engine's input size with grey 114, RG
 describes. PARITY OF THE IMAGE LOADING IS UNPINNED: the reference uses Ultralytics' ``LetterBox`` and ``cv2.resize``,
 neither of which is available to this build's tests, so resampled pixels may differ from the reference's in the last bits.
 ``.npy`` files holding a ready ``[3,H,W]`` fp32 frame are taken as they are (and are the pinned path).
+
+``--device-letterbox`` moves the letterbox to the GPU: an image file is uploaded as BGRA ``uint8`` (4 B/px instead of a 12 B/px
+fp32 tensor) and letterboxed there by ``unina_preprocess_letterbox_bgra`` with mean 0 / std 1, i.e. the same ``/255`` frame, by
+this project's own resize definition (include/unina_mi355.h at unina_letterbox_geometry) instead of PIL's.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ def letterbox_geometry(src_w: int, src_h: int, dst_w: int, dst_h: int) -> Tuple[
     """(new_w, new_h, left, top): the aspect-preserving resize and the centred paste position of a letterbox
     (LetterBox(auto=False, center=True): ratio = min(dst/src), unpadded size rounded, padding split with -0.1 / +0.1 rounding)."""
     r = min(dst_h / src_h, dst_w / src_w)
-    new_w, new_h = int(round(src_w * r)), int(round(src_h * r))
+    new_w, new_h = max(1, int(round(src_w * r))), max(1, int(round(src_h * r)))   # (a strip thinner than half a pixel keeps one)
     dw, dh = (dst_w - new_w) / 2, (dst_h - new_h) / 2
     return new_w, new_h, int(round(dw - 0.1)), int(round(dh - 0.1))
 
@@ -50,6 +54,41 @@ def load_frame(path: str, width: int, height: int) -> np.ndarray:
     return np.ascontiguousarray(canvas.transpose(2, 0, 1)).astype(np.float32) / 255.0
 
 
+def load_bgra(path: str) -> np.ndarray:
+    """The image file as uint8 [h, w, 4] BGRA (alpha 255), nothing resized: what --device-letterbox uploads."""
+    from PIL import Image
+    rgb = np.asarray(Image.open(path).convert("RGB"))
+    out = np.full(rgb.shape[:2] + (4,), 255, dtype=np.uint8)
+    out[..., 0], out[..., 1], out[..., 2] = rgb[..., 2], rgb[..., 1], rgb[..., 0]
+    return out
+
+
+class DeviceLetterbox:
+    """load_frame's letterbox on the GPU: BGRA uint8 up, unina_preprocess_letterbox_bgra (pad 114, mean 0 / std 1) into a CUDA
+    fp32 [1,3,H,W] tensor that the mining calls take as it is (mining._device_frame passes a CUDA tensor through), on the
+    same stream. .npy frames are the network tensor already and go the usual way."""
+
+    def __init__(self, engine):
+        self.eng = engine
+        self.norm = engine.L.create_norm_params(0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
+
+    def __call__(self, path: str):
+        import torch
+        e = self.eng
+        if path.lower().endswith(".npy"):
+            return load_frame(path, e.width, e.height)
+        bgra = load_bgra(path)
+        h, w = bgra.shape[:2]
+        dev = torch.device("cuda", e.device)
+        cam = torch.from_numpy(bgra.reshape(h, w * 4)).to(dev)
+        out = torch.empty((1, 3, e.height, e.width), dtype=torch.float32, device=dev)
+        rc = e.L.unina_preprocess_letterbox_bgra(cam.data_ptr(), out.data_ptr(), w, h, w * 4, e.width, e.height, 114.0, self.norm,
+                                                 torch.cuda.current_stream(dev).cuda_stream)
+        if rc:
+            raise RuntimeError(f"{path}: unina_preprocess_letterbox_bgra failed ({rc}) for a {w} x {h} image")
+        return out
+
+
 def list_files(root: str) -> List[str]:
     out = []
     for d, _dirs, files in os.walk(root):
@@ -68,7 +107,11 @@ def run(engine, args) -> dict:
     if args.limit > 0 and args.limit < len(files):
         files = files[:args.limit]
         print(f"    Limited to {args.limit} images.")
-    frames = (load_frame(p, engine.width, engine.height) for p in files)
+    if getattr(args, "device_letterbox", False):
+        on_device = DeviceLetterbox(engine)
+        frames = (on_device(p) for p in files)
+    else:
+        frames = (load_frame(p, engine.width, engine.height) for p in files)
     k = 6 + mining.MODES.index(args.mode)
     if args.coreset > 0:
         sc, emb, paths = mining.mine_frames(engine, frames, files)
@@ -100,6 +143,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--coreset", type=int, default=0, help="also select this many diverse samples (k-center greedy)")
     ap.add_argument("--coreset-output", default="coreset.json")
     ap.add_argument("--seed", type=int, default=0, help="seed of the k-center start point")
+    ap.add_argument("--device-letterbox", action="store_true",
+                    help="letterbox image files on the GPU (BGRA uint8 upload + unina_preprocess_letterbox_bgra) instead of with PIL")
     return ap
 
 
