@@ -310,6 +310,44 @@ int unina_mine_heads_async(unina_engine_t *e, float *d_scores8, hipStream_t stre
 int unina_kcenter(const float *d_embeddings, int n, int dim, int k, int first_index, int *d_selected, float *d_min_dist,
                   hipStream_t stream);
 
+/* K-means coreset (coreset_selection_kmeans, active_learning.py:166-211) on device data; no engine handle. The reference
+ * fits scikit-learn's MiniBatchKMeans, whose trajectory and RNG stream cannot be reproduced; the clustering here is FULL-BATCH
+ * LLOYD by this build's own specification, the selection (unina_nearest_rows) is the reference's loop line for line.
+ * One iteration = |c_j|^2 -> assign -> update -> inertia:
+ *   assign  : label[i] = argmin_j |c_j|^2 - 2 <x_i, c_j>, the dot products on the f32-input MFMA (a d-ordered fp32 fma
+ *             chain); the LOWEST index wins exact ties.
+ *   update  : c_j = (sum of its member rows in ascending row index, fp32) / count_j; a cluster WITHOUT members keeps its
+ *             previous centroid.
+ *   inertia : sum_i sum_d (x_id - c_{label_i,d})^2 with the updated centroids, in double, fixed order -> history[iteration].
+ * All max_iter iterations are enqueued by the call, no host round-trip: an iteration whose assignment changes no label is
+ * completed and sets a device flag that makes every kernel behind it return at once (labels are compared from the call's
+ * second iteration on, so a call executes at least two iterations before it can report convergence, max_iter permitting).
+ * Fixed reduction orders, no float atomics: two runs give identical bytes, and one call of max_iter = T gives the bytes of T
+ * chained calls of max_iter = 1.
+ *   d_embeddings : device, fp32 [n, dim] row-major, 16-byte aligned, dim % 4 == 0
+ *   d_init_rows  : device, k row indices: the start centroids are those rows; NULL: d_centroids holds the start
+ *   d_centroids  : device, fp32 [k, dim], 16-byte aligned, in/out        d_labels : device, n ints, out
+ *   d_inertia_history : device, max_iter doubles or NULL; entries of iterations that were not executed are NaN
+ *   d_iters      : device, one int: iterations executed, bit 30 (UNINA_KMEANS_CONVERGED) set when converged
+ *   d_workspace  : device, unina_kmeans_workspace_bytes(n, dim, k) bytes, 16-byte aligned; or NULL: the call allocates it and
+ *                  then returns only when the loop has finished. With a workspace nothing is synchronised.
+ * UNINA_ERR_ARG: null / misaligned pointer, dim % 4 != 0, k < 1, k > n, max_iter < 1 (unina_kmeans_workspace_bytes: 0).
+ * An init row outside [0, n) is found ON THE DEVICE (the indices live there): the call returns UNINA_OK, *d_iters becomes -1
+ * and centroids, labels and history are left untouched. */
+#define UNINA_KMEANS_CONVERGED (1 << 30)
+size_t unina_kmeans_workspace_bytes(int n, int dim, int k);
+int unina_kmeans(const float *d_embeddings, int n, int dim, int k, const int *d_init_rows, int max_iter, float *d_centroids,
+                 int *d_labels, double *d_inertia_history, int *d_iters, void *d_workspace, hipStream_t stream);
+/* The selection loop (active_learning.py:203-209): for each of the k centroids IN ORDER the row with the smallest
+ * sqrt(sum (a-b)^2) (unina_kcenter's direct form) among the rows not chosen by an earlier centroid, the lowest index winning
+ * ties (numpy's argmin); the next step reads the chosen index from device memory, so the k steps run without a host
+ * round-trip.
+ *   d_selected  : device, k ints (one row per centroid, in centroid order)
+ *   d_workspace : device, n floats, or NULL: allocated by the call, which then returns only when finished
+ * UNINA_ERR_ARG: null / misaligned pointer (16 bytes for the two matrices), dim % 4 != 0, k < 1, k > n. */
+int unina_nearest_rows(const float *d_embeddings, int n, int dim, const float *d_centroids, int k, int *d_selected,
+                       float *d_workspace, hipStream_t stream);
+
 /* ------------------------------------------------------------------ INT8 calibration (qat.py:171-220, train.py:809)
  * The collection half of the reference's calibrate_model, on the device. An fp16 tensor has at most 32 768 distinct |x| (the
  * sign bit drops out, 15 bits remain), so a table "how many elements carry each 15-bit pattern" is a LOSSLESS summary of it for

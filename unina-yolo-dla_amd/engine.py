@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "unina_letterbox_geometry", "unina_infer_letterbox_bgra", "unina_infer_letterbox_nv12", "unina_infer_letterbox_bgra_async",
     "unina_infer_letterbox_nv12_async", "unina_preprocess_letterbox_bgra", "unina_preprocess_letterbox_nv12",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
+    "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
@@ -148,6 +149,11 @@ def load_library() -> C.CDLL:
     L.unina_mine.argtypes = [vp, vp, vp, vp, vp]
     L.unina_mine_heads_async.argtypes = [vp, vp, vp]
     L.unina_kcenter.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
+    # k-means coreset (csrc/kmeans.hip)
+    L.unina_kmeans_workspace_bytes.restype = C.c_size_t
+    L.unina_kmeans_workspace_bytes.argtypes = [ci, ci, ci]
+    L.unina_kmeans.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.unina_nearest_rows.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     # INT8 calibration (csrc/calib.hip)
     L.unina_abs_histogram_f16.argtypes = [vp, C.c_size_t, vp, vp]
     L.unina_calib_buffer_count.argtypes = [vp]
@@ -689,6 +695,82 @@ def kcenter(embeddings, k: int, first_index: int, stream=None) -> np.ndarray:
         rc = L.unina_kcenter(embeddings.data_ptr(), n, d, k, first_index, sel.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
         if rc:
             raise EngineError(f"unina_kcenter failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, k={k}, first_index={first_index})")
+        return sel.cpu().numpy()[:k].astype(np.int64)
+
+
+KMEANS_CONVERGED = 1 << 30   # include/unina_mi355.h UNINA_KMEANS_CONVERGED
+
+
+def _device_matrix(torch, x, device=None):
+    """[rows, cols] fp32 contiguous CUDA tensor: a tensor is used in place, an ndarray is uploaded."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        x = x.cuda() if device is None else x.to(device)
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
+    return x
+
+
+def kmeans(embeddings, k: int, init_rows=None, centroids=None, max_iter: int = 100, stream=None):
+    """Full-batch Lloyd k-means on the GPU (unina_kmeans, csrc/kmeans.hip): all `max_iter` iterations are enqueued by one
+    call and a device flag ends the loop once an assignment changes no label. Start centroids: the rows `init_rows` (k
+    indices) or the [k, D] matrix `centroids` (exactly one of the two). `embeddings`: [N,D] fp32, a CUDA tensor (used in
+    place) or an ndarray (uploaded). Returns (centroids [k,D] fp32, labels [N] int64, inertia_history [iters] float64, iters,
+    converged), all on the host."""
+    L = load_library()
+    torch = _torch()
+    if (init_rows is None) == (centroids is None):
+        raise ValueError("give the start as init_rows or as centroids, not both")
+    embeddings = _device_matrix(torch, embeddings)
+    n, d = embeddings.shape
+    dev = embeddings.device
+    with torch.cuda.device(dev):
+        if centroids is None:
+            init = torch.from_numpy(np.ascontiguousarray(init_rows, dtype=np.int32).reshape(-1)).to(dev)
+            if init.numel() != k:
+                raise ValueError(f"init_rows holds {init.numel()} indices, k = {k}")
+            cen = torch.zeros((k, d), dtype=torch.float32, device=dev)
+        else:
+            init = None
+            cen = _device_matrix(torch, centroids, dev).clone()
+            if tuple(cen.shape) != (k, d):
+                raise ValueError(f"centroids of shape {tuple(cen.shape)}, expected {(k, d)}")
+        labels = torch.zeros(n, dtype=torch.int32, device=dev)
+        hist = torch.zeros(max(max_iter, 1), dtype=torch.float64, device=dev)
+        iters = torch.zeros(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(int(L.unina_kmeans_workspace_bytes(n, d, k)), 16), dtype=torch.uint8, device=dev)
+        rc = L.unina_kmeans(embeddings.data_ptr(), n, d, k, init.data_ptr() if init is not None else None, max_iter, cen.data_ptr(),
+                            labels.data_ptr(), hist.data_ptr(), iters.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_kmeans failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, k={k}, max_iter={max_iter})")
+        if stream is not None:
+            torch.cuda.synchronize(dev)   # (the copies below run on the current stream, the loop on `stream`)
+        it = int(iters.cpu()[0])
+        if it < 0:
+            raise EngineError(f"unina_kmeans: an init row lies outside [0, {n})")
+        done = it & (KMEANS_CONVERGED - 1)
+        return (cen.cpu().numpy(), labels.cpu().numpy().astype(np.int64), hist.cpu().numpy()[:done].copy(), done,
+                bool(it & KMEANS_CONVERGED))
+
+
+def nearest_rows(embeddings, centroids, stream=None) -> np.ndarray:
+    """For each centroid in order, the index of the nearest row not chosen by an earlier centroid (unina_nearest_rows: the
+    selection loop of coreset_selection_kmeans, active_learning.py:203-209). Tensors or ndarrays, as kmeans()."""
+    L = load_library()
+    torch = _torch()
+    embeddings = _device_matrix(torch, embeddings)
+    centroids = _device_matrix(torch, centroids, embeddings.device)
+    n, d = embeddings.shape
+    k = centroids.shape[0]
+    if centroids.shape[1] != d:
+        raise ValueError(f"centroids of shape {tuple(centroids.shape)} for embeddings of dimension {d}")
+    with torch.cuda.device(embeddings.device):
+        sel = torch.zeros(max(k, 1), dtype=torch.int32, device=embeddings.device)
+        ws = torch.empty(n, dtype=torch.float32, device=embeddings.device)
+        rc = L.unina_nearest_rows(embeddings.data_ptr(), n, d, centroids.data_ptr(), k, sel.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_nearest_rows failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, centroids {tuple(centroids.shape)})")
+        if stream is not None:
+            torch.cuda.synchronize(embeddings.device)
         return sel.cpu().numpy()[:k].astype(np.int64)
 
 

@@ -2,9 +2,11 @@
 
     python -m unina_yolo_dla_amd.mine --engine m.une --data <dir> --output difficulty_map.json [--limit N]
                                       [--mode entropy|loc_var] [--coreset K --coreset-output coreset.json]
+                                      [--coreset-method kcenter|kmeans]
 
 Writes ``{path: score}`` (``indent=2``, the reference's schema) and prints the five most uncertain images; with
-``--coreset K`` it also pools the embeddings and writes the K paths the k-center greedy selection picks.
+``--coreset K`` it also pools the embeddings and writes the K paths the k-center greedy selection picks (the list itself, as
+before), or with ``--coreset-method kmeans`` ``{"method": "kmeans", "paths": [...]}``: the K paths nearest to k-means centroids.
 
 Images are read with PIL: letterbox to the engine's input size with grey 114, RGB, ``/255`` -- what mine_data.py:77-81
 describes. PARITY OF THE IMAGE LOADING IS UNPINNED: the reference uses Ultralytics' ``LetterBox`` and ``cv2.resize``,
@@ -125,10 +127,12 @@ def run(engine, args) -> dict:
     for path, score in sorted(scores.items(), key=lambda kv: kv[1], reverse=True)[:5]:
         print(f"  {os.path.basename(path)}: {score:.4f}")
     if args.coreset > 0:
-        chosen = mining.coreset_selection_kcenter(emb, paths, args.coreset, seed=args.seed, device=getattr(args, "device_kcenter", None))
+        method = getattr(args, "coreset_method", "kcenter")
+        chosen = mining.coreset_selection(emb, paths, args.coreset, method=method, seed=args.seed, device=getattr(args, "device_kcenter", None))
         with open(args.coreset_output, "w") as f:
-            json.dump(chosen, f, indent=2)
-        print(f">>> Coreset: {len(chosen)} paths -> {args.coreset_output}")
+            # k-center writes the bare list it has always written; another method names itself beside its paths
+            json.dump(chosen if method == "kcenter" else {"method": method, "paths": chosen}, f, indent=2)
+        print(f">>> Coreset ({method}): {len(chosen)} paths -> {args.coreset_output}")
     return scores
 
 
@@ -142,7 +146,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--mode", default="entropy", choices=("entropy", "loc_var"))
     ap.add_argument("--coreset", type=int, default=0, help="also select this many diverse samples (k-center greedy)")
     ap.add_argument("--coreset-output", default="coreset.json")
-    ap.add_argument("--seed", type=int, default=0, help="seed of the k-center start point")
+    ap.add_argument("--coreset-method", default="kcenter", choices=("kcenter", "kmeans"),
+                    help="kcenter: k-center greedy; kmeans: the samples nearest to k-means centroids (for large sets)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the k-center start point / of the k-means++ starts")
     ap.add_argument("--device-letterbox", action="store_true",
                     help="letterbox image files on the GPU (BGRA uint8 upload + unina_preprocess_letterbox_bgra) instead of with PIL")
     return ap

@@ -6,11 +6,15 @@ Same names and return types as the reference:
   query_uncertain_samples ........ ActiveLearner.query_uncertain_samples     active_learning.py:307-331
   extract_backbone_embeddings .... extract_backbone_embeddings               active_learning.py:31-99
   coreset_selection_kcenter ...... coreset_selection_kcenter                 active_learning.py:104-163
+  coreset_selection_kmeans ....... coreset_selection_kmeans                  active_learning.py:166-211
+  coreset_selection .............. ActiveLearner.coreset_selection           active_learning.py:327-360
 
-The GPU work is hand-written HIP behind the C ABI (csrc/mining.hip: ``unina_mine`` / ``unina_kcenter``). The pure-numpy
-twins ``difficulty_from_heads`` and ``kcenter_numpy`` restate the reference's arithmetic; they are what the CPU tests pin
-to the reference's recorded results and they run without a GPU. Not covered: the kmeans coreset variant
-(active_learning.py:166-211, scikit-learn), the copy-paste augmenter, graph (B) models (no ``.backbone``).
+The GPU work is hand-written HIP behind the C ABI (csrc/mining.hip: ``unina_mine`` / ``unina_kcenter``; csrc/kmeans.hip:
+``unina_kmeans`` / ``unina_nearest_rows``). The pure-numpy twins ``difficulty_from_heads``, ``kcenter_numpy``,
+``kmeans_numpy`` and ``nearest_rows_numpy`` restate the arithmetic; they are what the CPU tests pin to the reference's
+recorded results and they run without a GPU. The kmeans variant clusters by full-batch Lloyd from k-means++ starts (the
+reference's MiniBatchKMeans trajectory cannot be reproduced: DESIGN.md 9b); its selection loop is the reference's.
+Not covered: the copy-paste augmenter, graph (B) models (no ``.backbone``).
 """
 from __future__ import annotations
 
@@ -142,3 +146,132 @@ def coreset_selection_kcenter(embeddings: np.ndarray, paths: Sequence[str], targ
     else:
         sel = kcenter_numpy(embeddings, target_size, first)
     return [paths[int(i)] for i in sel]
+
+
+# ---- the kmeans coreset variant ---------------------------------------------------------------------------------------
+def kmeans_pp_init(embeddings: np.ndarray, k: int, seed: Optional[int]) -> np.ndarray:
+    """k-means++ start (Arthur & Vassilvitskii 2007): `k` distinct row indices, the first uniform, each next one drawn with
+    probability proportional to the squared distance to the nearest row chosen so far. float64, O(n k dim), all draws from
+    ``np.random.RandomState(seed)``: numpy's global state is not touched. When every remaining row coincides with a chosen
+    one, the lowest unchosen index is taken."""
+    x = np.asarray(embeddings, dtype=np.float64)
+    n = x.shape[0]
+    if not 1 <= k <= n:
+        raise ValueError("need 1 <= k <= n")
+    rng = np.random.RandomState(seed)
+    rows = [int(rng.randint(n))]
+    d2 = ((x - x[rows[0]]) ** 2).sum(axis=1)
+    d2[rows[0]] = 0.0
+    for _ in range(1, k):
+        total = d2.sum()
+        if total > 0:
+            nxt = int(np.searchsorted(np.cumsum(d2), rng.random_sample() * total, side="right"))
+            nxt = min(nxt, n - 1)
+            if d2[nxt] == 0:                                    # (rounding at the end of the cumulative sum)
+                nxt = int(np.argmax(d2))
+        else:
+            chosen = np.zeros(n, dtype=bool)
+            chosen[rows] = True
+            nxt = int(np.argmin(chosen))
+        rows.append(nxt)
+        d2 = np.minimum(d2, ((x - x[nxt]) ** 2).sum(axis=1))
+        d2[nxt] = 0.0
+    return np.asarray(rows, dtype=np.int64)
+
+
+def kmeans_numpy(embeddings: np.ndarray, k: int, init_rows=None, max_iter: int = 100, centroids=None):
+    """float64 twin of the device loop (csrc/kmeans.hip), same rules, same outputs. Per iteration: label = argmin_j
+    |c_j|^2 - 2 <x, c_j> (lowest index on ties); c_j = mean of its members, a cluster without members keeps its centroid;
+    inertia = sum (x - c_label)^2 with the new centroids. An iteration whose assignment changes no label is completed and
+    is the last; labels are compared from the second iteration on. Returns (centroids, labels, inertia_history [iters],
+    iters, converged)."""
+    x = np.asarray(embeddings, dtype=np.float64)
+    n = x.shape[0]
+    if (init_rows is None) == (centroids is None):
+        raise ValueError("give the start as init_rows or as centroids, not both")
+    if init_rows is not None:
+        init_rows = np.asarray(init_rows, dtype=np.int64).reshape(-1)
+        if init_rows.min() < 0 or init_rows.max() >= n:
+            raise ValueError(f"an init row lies outside [0, {n})")
+        c = x[init_rows].copy()
+    else:
+        c = np.array(centroids, dtype=np.float64)
+    if c.shape != (k, x.shape[1]) or not 1 <= k <= n or max_iter < 1:
+        raise ValueError("need k start centroids, 1 <= k <= n and max_iter >= 1")
+    labels = np.full(n, -1, dtype=np.int64)
+    history: List[float] = []
+    converged = False
+    for _ in range(max_iter):
+        cn = (c * c).sum(axis=1)[None, :]
+        new = np.concatenate([np.argmin(cn - 2.0 * (x[r:r + 8192] @ c.T), axis=1) for r in range(0, n, 8192)])   # (row blocks: memory)
+        changed = int((new != labels).sum())
+        labels = new
+        order = np.argsort(labels, kind="stable")
+        counts = np.bincount(labels, minlength=k)
+        starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        live = counts > 0
+        sums = np.add.reduceat(x[order], starts[live], axis=0)
+        c[live] = sums / counts[live][:, None]
+        history.append(float(((x - c[labels]) ** 2).sum()))
+        if changed == 0:
+            converged = True
+            break
+    return c, labels, np.asarray(history, dtype=np.float64), len(history), converged
+
+
+def nearest_rows_numpy(embeddings: np.ndarray, centroids: np.ndarray) -> np.ndarray:
+    """The reference's selection loop (active_learning.py:203-209): one row index per centroid, in centroid order."""
+    embeddings = np.asarray(embeddings)
+    selected: List[int] = []
+    for centroid in np.asarray(centroids):
+        distances = np.linalg.norm(embeddings - centroid, axis=1)
+        distances[selected] = np.inf
+        selected.append(int(np.argmin(distances)))
+    return np.asarray(selected, dtype=np.int64)
+
+
+def coreset_selection_kmeans(embeddings: np.ndarray, paths: Sequence[str], target_size: int, seed: Optional[int] = None,
+                             device: Optional[bool] = None, n_init: int = 3, max_iter: int = 100) -> List[str]:
+    """The paths nearest to `target_size` k-means centroids. `n_init` Lloyd runs from k-means++ starts (seeds `seed`,
+    `seed + 1`, ...; seed=None draws fresh entropy per start); the run with the lowest final inertia is kept, the first one
+    on a tie; then the reference's selection loop. `device`: True = the GPU kernels (unina_kmeans / unina_nearest_rows),
+    False = numpy, None = the GPU when one is visible."""
+    n = embeddings.shape[0]
+    if n == 0:
+        raise ValueError("FATAL: Cannot perform Coreset Selection on empty dataset.")
+    if target_size > n:
+        return list(paths)
+    if target_size < 1 or n_init < 1:
+        raise ValueError("need target_size >= 1 and n_init >= 1")
+    if device is None:
+        try:
+            import torch
+            device = torch.cuda.is_available()
+        except ImportError:
+            device = False
+    host = np.asarray(embeddings)
+    if device:
+        import torch
+        from . import engine
+        data = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).cuda()   # one upload for every start
+        fit, pick = engine.kmeans, engine.nearest_rows
+    else:
+        data, fit, pick = host, kmeans_numpy, nearest_rows_numpy
+    best, best_inertia = None, np.inf
+    for i in range(n_init):
+        init = kmeans_pp_init(host, target_size, None if seed is None else seed + i)
+        cen, _, hist, _, _ = fit(data, target_size, init_rows=init, max_iter=max_iter)
+        if best is None or hist[-1] < best_inertia:
+            best, best_inertia = cen, hist[-1]
+    return [paths[int(i)] for i in pick(data, best)]
+
+
+def coreset_selection(embeddings: np.ndarray, paths: Sequence[str], target_size: int, method: str = "kcenter",
+                      seed: Optional[int] = None, device: Optional[bool] = None) -> List[str]:
+    """The dispatcher of ActiveLearner.coreset_selection (active_learning.py:352-359) on given embeddings. An unknown
+    method is an error here (the reference runs k-center for anything that is not "kmeans")."""
+    if method == "kmeans":
+        return coreset_selection_kmeans(embeddings, paths, target_size, seed=seed, device=device)
+    if method == "kcenter":
+        return coreset_selection_kcenter(embeddings, paths, target_size, seed=seed, device=device)
+    raise ValueError('method must be "kcenter" or "kmeans"')
