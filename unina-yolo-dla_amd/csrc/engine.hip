@@ -1904,74 +1904,86 @@ int unina_serial_latency(unina_engine_t* e, const float* const* d_frames, int n_
   return UNINA_OK;
 }
 
-// A camera region as the stem reads it (GpuBufferHandle::format, perception_node.cpp:357-368). BGRA: `plane` is the region's
-// first pixel, a tile is a pointer offset. NV12: `plane` / `uv` are the planes of the WHOLE frame and (x0, y0) the region's
-// origin, which enters the chroma index.
-enum CameraFormat : int { kCamBgra = 0, kCamNv12 = 1 };
-struct CameraRegion {
-  int format;
-  const uint8_t *plane, *uv;
-  int w, h, pitch, uv_pitch, x0, y0;
-  // letterboxed (unina_infer_letterbox_*): the frame goes into the inner rectangle of the network input, `pad` around it
-  int letterbox = 0;
-  unina_letterbox box = {0, 0, 0, 0};
-  float pad = 0.f;
-};
+// A camera region as an entry point describes it (GpuBufferHandle::format, perception_node.cpp:357-368): a CameraSource
+// (camera_source.h) whose kind, destination and inner rectangle point_stems_at_camera fills in per stem. BGRA: uv == nullptr.
+static CameraSource camera_region(const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, const NormParams& norm) {
+  CameraSource c = {};
+  c.plane = plane;
+  c.uv = uv;
+  c.w = w;
+  c.h = h;
+  c.pitch = pitch;
+  c.uv_pitch = uv_pitch;
+  c.norm = norm;
+  return c;
+}
 
-// Points every eager stem op at a camera region (src_kind 1 / 3: the network's size, 2 / 4: resized) / back at the fp32
-// tensor. Returns the number of stem ops.
-static int point_stems_at_camera(unina_engine* e, const CameraRegion& c, const NormParams& norm) {
+// The kind of source a region of w x h is for a network input of net_w x net_h, stretched (lb == nullptr) or letterboxed into *lb.
+// An inner rectangle that is the whole network input is the plain resize (or tap): the unboxed kinds and their fast paths.
+static int camera_kind(bool nv12, int w, int h, int net_w, int net_h, const unina_letterbox* lb) {
+  if (lb && !(lb->new_w == net_w && lb->new_h == net_h)) return nv12 ? kSrcNv12Letterbox : kSrcBgraLetterbox;
+  const bool tap = w == net_w && h == net_h;
+  return nv12 ? (tap ? kSrcNv12Tap : kSrcNv12Resize) : (tap ? kSrcBgraTap : kSrcBgraResize);
+}
+
+// Points every eager stem op at a camera region / back at the fp32 tensor. Returns the number of stem ops.
+static int point_stems_at_camera(unina_engine* e, const CameraSource& region, const unina_letterbox* lb = nullptr, float pad = 0.f) {
   int nstem = 0;
   for (size_t k = 0; k < e->ops.size(); ++k) {
     PlannedOp& op = e->ops[k];
     if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    op.sp.src_kind = (c.format == kCamNv12 ? 3 : 1) + ((c.w == op.sp.W && c.h == op.sp.H) ? 0 : 1);
-    op.sp.in_x0 = op.sp.in_y0 = op.sp.in_w = op.sp.in_h = 0;
-    op.sp.pad_value = 0.f;
-    // an inner rectangle that is the whole network input is the plain resize (or tap): kinds 1..4 and their fast paths
-    if (c.letterbox && !(c.box.new_w == op.sp.W && c.box.new_h == op.sp.H)) {
-      op.sp.src_kind = c.format == kCamNv12 ? 6 : 5;
-      op.sp.in_x0 = c.box.left;
-      op.sp.in_y0 = c.box.top;
-      op.sp.in_w = c.box.new_w;
-      op.sp.in_h = c.box.new_h;
-      op.sp.pad_value = c.pad;
+    CameraSource c = region;
+    c.dst_w = op.sp.W;
+    c.dst_h = op.sp.H;
+    c.kind = camera_kind(c.uv != nullptr, c.w, c.h, c.dst_w, c.dst_h, lb);
+    if (c.kind == kSrcBgraLetterbox || c.kind == kSrcNv12Letterbox) {
+      c.in_x0 = lb->left;
+      c.in_y0 = lb->top;
+      c.in_w = lb->new_w;
+      c.in_h = lb->new_h;
+      c.pad = pad;
     }
-    op.sp.cam = c.plane;
-    op.sp.cam_uv = c.uv;
-    op.sp.cam_w = c.w;
-    op.sp.cam_h = c.h;
-    op.sp.cam_pitch = c.pitch;
-    op.sp.cam_uv_pitch = c.uv_pitch;
-    op.sp.cam_x0 = c.x0;
-    op.sp.cam_y0 = c.y0;
-    op.sp.norm = norm;
+    op.sp.cam = c;
     ++nstem;
   }
   return nstem;
 }
 static void restore_stems(unina_engine* e) {
-  for (size_t k = 0; k < e->ops.size(); ++k) {
-    PlannedOp& op = e->ops[k];
-    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    op.sp.src_kind = 0;
-    op.sp.cam = op.sp.cam_uv = nullptr;
-    op.sp.cam_w = op.sp.cam_h = op.sp.cam_pitch = op.sp.cam_uv_pitch = op.sp.cam_x0 = op.sp.cam_y0 = 0;
-    op.sp.in_x0 = op.sp.in_y0 = op.sp.in_w = op.sp.in_h = 0;
-    op.sp.pad_value = 0.f;
-    memset(&op.sp.norm, 0, sizeof op.sp.norm);
-  }
+  for (size_t k = 0; k < e->ops.size(); ++k)
+    if (is_eager(e, k) && e->ops[k].d.kind == kOpStem) e->ops[k].sp.cam = CameraSource{};
 }
 
-// unina_infer on a camera region: the stems are pointed at it for the call and back at the tensor afterwards, whatever it returns
-static int infer_camera(unina_engine* e, const CameraRegion& c, const NormParams& norm, float conf, float iou, float q,
-                        GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!point_stems_at_camera(e, c, norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+// The engine's device current and its plan up to date: what every camera entry point needs before it touches the stems
+static int make_ready(unina_engine* e) {
+  HIPCHK(e, hipSetDevice(e->device));
+  return e->plan_dirty ? plan(e) : UNINA_OK;
+}
+
+// unina_infer / unina_infer_async on a camera region, stretched or (lb) letterboxed with the post-process told the box map for the
+// call (map_boxes): the stems are pointed at the region and back at the tensor afterwards, whatever the call returns
+static int infer_camera(unina_engine* e, const CameraSource& c, const unina_letterbox* lb, float pad_value, int map_boxes, bool async,
+                        float conf, float iou, float q, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!point_stems_at_camera(e, c, lb, pad_value)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
   e->camera_active = true;
-  const int rc = unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
+  if (lb && map_boxes) {
+    e->map_boxes = 1;
+    e->map_left = (float)lb->left;
+    e->map_top = (float)lb->top;
+    e->map_sx = (float)c.w / (float)lb->new_w;
+    e->map_sy = (float)c.h / (float)lb->new_h;
+  }
+  const int rc = async ? unina_infer_async(e, nullptr, conf, iou, q, out, out_count, stream)
+                       : unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
+  e->map_boxes = 0;
   e->camera_active = false;
   restore_stems(e);
   return rc;
+}
+
+// The frame geometry every BGRA entry point accepts: whole pixels are read as dwords, so the pitch and the address are multiples of 4
+static int check_bgra_frame(unina_engine* e, const char* who, const uint8_t* d_bgra, int w, int h, int pitch) {
+  if (w <= 0 || h <= 0 || pitch < 4 * w || (pitch & 3) || ((uintptr_t)d_bgra & 3)) return fail(e, UNINA_ERR_ARG, "%s: bad frame geometry", who);
+  return UNINA_OK;
 }
 
 // The NV12 frame geometry every NV12 entry point accepts: preprocess_nv12's pitch rules (y_pitch >= w, uv_pitch >= w), and
@@ -1985,22 +1997,19 @@ static int check_nv12_frame(unina_engine* e, const char* who, const uint8_t* d_y
   return UNINA_OK;
 }
 
-// Camera frame -> detections: unina_infer with the pre-process (preprocess.hip: BGRA -> RGB, optional half-pixel-centre
+// Camera frame -> detections: unina_infer with the pre-process (camera_source.h: BGRA -> RGB, optional half-pixel-centre
 // bilinear resize, normalise) computed inside the stem kernel instead of written to an fp32 tensor by one launch and
-// read back by the next (4 B/px in instead of 12 B/px out + 12 B/px in, one launch less). Same arithmetic, so the
+// read back by the next (4 B/px in instead of 12 B/px out + 12 B/px in, one launch less). The same functions, so the
 // detections are those of preprocess_bgra[_resize] + unina_infer bit for bit (tests/test_gpu_preprocess.py).
 int unina_infer_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                      const NormParams* norm, float conf, float iou, float q, GpuDetection* out, int* out_count,
                      hipStream_t stream) {
   if (!e || !d_bgra || !norm || !out || !out_count) return UNINA_ERR_ARG;
-  if (src_width <= 0 || src_height <= 0 || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_bgra & 3))
-    return fail(e, UNINA_ERR_ARG, "unina_infer_bgra: bad frame geometry");
-  HIPCHK(e, hipSetDevice(e->device));
-  if (e->plan_dirty) {
-    int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  return infer_camera(e, CameraRegion{kCamBgra, d_bgra, nullptr, src_width, src_height, src_pitch, 0, 0, 0}, *norm, conf, iou, q, out, out_count, stream);
+  int rc = check_bgra_frame(e, "unina_infer_bgra", d_bgra, src_width, src_height, src_pitch);
+  if (rc == UNINA_OK) rc = make_ready(e);
+  if (rc != UNINA_OK) return rc;
+  return infer_camera(e, camera_region(d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), nullptr, 0.f, 0, false, conf, iou, q,
+                      out, out_count, stream);
 }
 
 // NV12 camera frame -> detections: unina_infer_bgra's role for the other common camera format (cuda_preprocess.cu:206-211),
@@ -2012,47 +2021,24 @@ int unina_infer_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv,
   if (!e) return UNINA_ERR_ARG;
   if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_nv12: null norm / result pointer");
   int rc = check_nv12_frame(e, "unina_infer_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  if (rc == UNINA_OK) rc = make_ready(e);
   if (rc != UNINA_OK) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (e->plan_dirty) {
-    rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  return infer_camera(e, CameraRegion{kCamNv12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, 0, 0}, *norm, conf, iou, q, out, out_count, stream);
+  return infer_camera(e, camera_region(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), nullptr, 0.f, 0, false, conf, iou, q,
+                      out, out_count, stream);
 }
 
 // ---- letterboxed camera frames (include/unina_mi355.h at unina_letterbox_geometry) ----
-// The body of the four calls, behind the argument checks of the frame: the stems are pointed at the letterboxed frame and the
-// post-process is told the box map for the call; both are put back afterwards, whatever it returns. Nothing is enqueued before
-// the last check has passed.
-static int infer_letterbox(unina_engine* e, const char* who, CameraRegion c, const NormParams& norm, float conf, float iou, float q,
-                           float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+// The body of the four calls, behind the argument checks of the frame. Nothing is enqueued before the last check has passed.
+static int infer_letterbox(unina_engine* e, const char* who, const CameraSource& c, float conf, float iou, float q, float pad_value,
+                           int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+  unina_letterbox lb;
   if (map_boxes != 0 && map_boxes != 1) return fail(e, UNINA_ERR_ARG, "%s: map_boxes must be 0 or 1, got %d", who, map_boxes);
   if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
-  if (unina_letterbox_geometry(c.w, c.h, (int)e->h.in_w, (int)e->h.in_h, &c.box) != UNINA_OK)
+  if (unina_letterbox_geometry(c.w, c.h, (int)e->h.in_w, (int)e->h.in_h, &lb) != UNINA_OK)
     return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, c.w, c.h);
-  c.letterbox = 1;
-  c.pad = pad_value;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (e->plan_dirty) {
-    const int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  if (!point_stems_at_camera(e, c, norm)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
-  e->camera_active = true;
-  if (map_boxes) {
-    e->map_boxes = 1;
-    e->map_left = (float)c.box.left;
-    e->map_top = (float)c.box.top;
-    e->map_sx = (float)c.w / (float)c.box.new_w;
-    e->map_sy = (float)c.h / (float)c.box.new_h;
-  }
-  const int rc = async ? unina_infer_async(e, nullptr, conf, iou, q, out, out_count, stream)
-                       : unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
-  e->map_boxes = 0;
-  e->camera_active = false;
-  restore_stems(e);
-  return rc;
+  const int rc = make_ready(e);
+  if (rc != UNINA_OK) return rc;
+  return infer_camera(e, c, &lb, pad_value, map_boxes, async, conf, iou, q, out, out_count, stream);
 }
 
 static int letterbox_bgra(unina_engine* e, const char* who, const uint8_t* d_bgra, int w, int h, int pitch, const NormParams* norm,
@@ -2060,9 +2046,10 @@ static int letterbox_bgra(unina_engine* e, const char* who, const uint8_t* d_bgr
                           hipStream_t stream) {
   if (!e) return UNINA_ERR_ARG;
   if (!d_bgra || !norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null frame / norm / result pointer", who);
-  if (w <= 0 || h <= 0 || pitch < 4 * w || (pitch & 3) || ((uintptr_t)d_bgra & 3)) return fail(e, UNINA_ERR_ARG, "%s: bad frame geometry", who);
-  return infer_letterbox(e, who, CameraRegion{kCamBgra, d_bgra, nullptr, w, h, pitch, 0, 0, 0}, *norm, conf, iou, q, pad_value, map_boxes,
-                         async, out, out_count, stream);
+  const int rc = check_bgra_frame(e, who, d_bgra, w, h, pitch);
+  if (rc != UNINA_OK) return rc;
+  return infer_letterbox(e, who, camera_region(d_bgra, nullptr, w, h, pitch, 0, *norm), conf, iou, q, pad_value, map_boxes, async, out,
+                         out_count, stream);
 }
 
 static int letterbox_nv12(unina_engine* e, const char* who, const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch,
@@ -2072,8 +2059,8 @@ static int letterbox_nv12(unina_engine* e, const char* who, const uint8_t* d_y, 
   if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
   const int rc = check_nv12_frame(e, who, d_y, d_uv, w, h, y_pitch, uv_pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, CameraRegion{kCamNv12, d_y, d_uv, w, h, y_pitch, uv_pitch, 0, 0}, *norm, conf, iou, q, pad_value,
-                         map_boxes, async, out, out_count, stream);
+  return infer_letterbox(e, who, camera_region(d_y, d_uv, w, h, y_pitch, uv_pitch, *norm), conf, iou, q, pad_value, map_boxes, async, out,
+                         out_count, stream);
 }
 
 int unina_infer_letterbox_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
@@ -2209,17 +2196,14 @@ int unina_merge_tiles_async(unina_engine_t* e, const GpuDetection* d_slots, cons
 }
 
 // The tiled calls' common body, behind the argument checks of the frame: one frame graph per tile into the handle's slots, one merge.
-static int infer_tiled_camera(unina_engine* e, const char* who, const CameraRegion& frame, const unina_tile* tiles, int n_tiles,
-                              const NormParams& norm, float conf, float iou, float q, float merge_iou, GpuDetection* d_out,
+static int infer_tiled_camera(unina_engine* e, const char* who, const CameraSource& frame, const unina_tile* tiles, int n_tiles,
+                              float conf, float iou, float q, float merge_iou, GpuDetection* d_out,
                               int* d_out_count, hipStream_t stream) {
   TileGatherParams g;
   int rc = fill_tile_maps(e, who, tiles, n_tiles, frame.w, frame.h, &g);
   if (rc != UNINA_OK) return rc;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (e->plan_dirty) {
-    rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
+  rc = make_ready(e);
+  if (rc != UNINA_OK) return rc;
   constexpr size_t kSlotBytes = sizeof(GpuDetection) * MAX_DETECTIONS;
   if (!e->d_tile_slots) HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_tile_slots), UNINA_MAX_TILES * (kSlotBytes + sizeof(int))));
   int* d_counts = reinterpret_cast<int*>(e->d_tile_slots + (size_t)UNINA_MAX_TILES * MAX_DETECTIONS);
@@ -2229,16 +2213,16 @@ static int infer_tiled_camera(unina_engine* e, const char* who, const CameraRegi
   e->camera_active = true;
   for (int t = 0; t < n_tiles && rc == UNINA_OK; ++t) {
     const unina_tile& r = tiles[t];
-    CameraRegion c = frame;
+    CameraSource c = frame;
     c.w = r.w;
     c.h = r.h;
-    if (frame.format == kCamBgra) {
+    if (!frame.uv) {
       c.plane = frame.plane + (size_t)r.y * frame.pitch + (size_t)r.x * 4;   // a BGRA tile is a pointer offset
     } else {
       c.x0 = r.x;                                                            // an NV12 tile is not: the origin enters the chroma index
       c.y0 = r.y;
     }
-    if (!point_stems_at_camera(e, c, norm))
+    if (!point_stems_at_camera(e, c))
       rc = fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
     else
       rc = unina_infer_async(e, nullptr, conf, iou, q, e->d_tile_slots + (size_t)t * MAX_DETECTIONS, d_counts + t, stream);
@@ -2255,10 +2239,10 @@ int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int s
                                  float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
   if (!e) return UNINA_ERR_ARG;
   if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
-  if (src_width <= 0 || src_height <= 0 || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_bgra & 3))
-    return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: bad frame geometry");
-  return infer_tiled_camera(e, "unina_infer_tiled_bgra", CameraRegion{kCamBgra, d_bgra, nullptr, src_width, src_height, src_pitch, 0, 0, 0},
-                            tiles, n_tiles, *norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  const int rc = check_bgra_frame(e, "unina_infer_tiled_bgra", d_bgra, src_width, src_height, src_pitch);
+  if (rc != UNINA_OK) return rc;
+  return infer_tiled_camera(e, "unina_infer_tiled_bgra", camera_region(d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), tiles, n_tiles,
+                            conf, iou, q, merge_iou, d_out, d_out_count, stream);
 }
 
 int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
@@ -2271,7 +2255,7 @@ int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_wid
   }, out, out_count, stream);
 }
 
-// The NV12 pair: the same slots, gather and merge; only the stem's source differs (StemParams::cam_x0 / cam_y0 carry the tile).
+// The NV12 pair: the same slots, gather and merge; only the stem's source differs (CameraSource::x0 / y0 carry the tile).
 int unina_infer_tiled_nv12_async(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height,
                                  int y_pitch, int uv_pitch, const unina_tile* tiles, int n_tiles, const NormParams* norm,
                                  float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count,
@@ -2280,8 +2264,8 @@ int unina_infer_tiled_nv12_async(unina_engine_t* e, const uint8_t* d_y, const ui
   if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null / misaligned pointer");
   const int rc = check_nv12_frame(e, "unina_infer_tiled_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, "unina_infer_tiled_nv12", CameraRegion{kCamNv12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, 0, 0},
-                            tiles, n_tiles, *norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  return infer_tiled_camera(e, "unina_infer_tiled_nv12", camera_region(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), tiles, n_tiles,
+                            conf, iou, q, merge_iou, d_out, d_out_count, stream);
 }
 
 int unina_infer_tiled_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,

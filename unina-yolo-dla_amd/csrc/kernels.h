@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/unina_mi355.h"
+#include "camera_source.h"
 
 namespace unina {
 
@@ -256,20 +257,7 @@ constexpr int kHeadWsTH = 13;
 // ------------------------------------------------------------------------------------------------
 struct StemParams {
   int dtype;           // DType of dst
-  int src_kind;        // 0: fp32 planar tensor `src`; 1: BGRA u8 camera frame of the network's size; 2: BGRA u8 frame of
-                       // cam_w x cam_h, bilinear-resized to W x H; 3: NV12 region of the network's size; 4: NV12 region of
-                       // cam_w x cam_h, bilinear-resized -- 1..4 compute the pre-process (preprocess.hip, same arithmetic) on
-                       // the fly instead of reading a tensor it would have written (unina_infer_bgra / unina_infer_nv12);
-                       // 5: BGRA u8 frame of cam_w x cam_h, LETTERBOXED: resized (or, at in_w x in_h == cam_w x cam_h, tapped) into
-                       // the inner rectangle, pad_value around it; 6: the same for an NV12 frame (unina_infer_letterbox_*)
-  const unsigned char* cam;   // src_kind 1 / 2: pitched BGRA (of the region); 3 / 4: the luma plane of the WHOLE frame
-  const unsigned char* cam_uv;   // src_kind 3 / 4: the interleaved chroma plane of the whole frame
-  int cam_w, cam_h, cam_pitch, cam_uv_pitch;   // size of the region the stem reads; pitches in bytes
-  int cam_x0, cam_y0;  // src_kind 3 / 4: the region's origin in the frame. It enters the chroma index ((y0 + y) / 2,
-                       // (x0 + x) / 2), so an NV12 tile cannot be a pointer offset the way a BGRA tile is; may be odd
-  int in_x0, in_y0, in_w, in_h;   // src_kind 5 / 6: the inner rectangle of the network input (unina_letterbox: left, top, new_w, new_h)
-  float pad_value;     // src_kind 5 / 6: r = g = b of every pixel outside it, before the normalisation
-  NormParams norm;
+  CameraSource cam;    // what the stem reads: the tensor `src` (kSrcTensor) or a camera frame, pre-processed per pixel (camera_source.h)
   const float* src;    // [3][H][W]
   const float* w;      // [Co][27], (c,kh,kw)
   const float* wt;     // the same weights transposed to [27][Co] (prepared at load): wave-uniform scalar loads in the stem kernel

@@ -1,5 +1,6 @@
 // stem_pool.hip -- the non-GEMM ops of the forward graph (gfx950).
-//   stem_conv_kernel   : backbone.stem  (model.py:175: ConvBlock(3, c1, k=3, s=2)) reading the fp32 NCHW image
+//   stem_conv_kernel   : backbone.stem  (model.py:175: ConvBlock(3, c1, k=3, s=2)) reading the fp32 NCHW image, or computing it
+//                        per pixel from a camera frame: camera_source.h holds that definition, shared with preprocess.hip
 //   sppf_pool_kernel   : SPPF_DLA's three chained MaxPool2d(5,1,2)  (model.py:125,129-131)
 //   upsample2x_kernel  : Upsample(scale_factor=2, nearest)  (model.py:145-147), standalone form
 #include "kernels.h"
@@ -35,96 +36,6 @@ template <> struct StemOut<s16_t> {
 // pixel's CO/2 contiguous NHWC channels.
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
-// ((v / 255) - mean) / std per channel, as preprocess.hip's normalise
-__device__ __forceinline__ void cam_normalise(const StemParams& p, float r, float g, float b, float (&rgb)[3]) {
-#pragma clang fp contract(off)
-  rgb[0] = ((r / 255.0f) - p.norm.mean_r) / p.norm.std_r;
-  rgb[1] = ((g / 255.0f) - p.norm.mean_g) / p.norm.std_g;
-  rgb[2] = ((b / 255.0f) - p.norm.mean_b) / p.norm.std_b;
-}
-
-// BT.601 of one NV12 sample (preprocess.hip's nv12_pixel, cuda_preprocess.cu:229-241): the clamped values stay floats, they
-// are never rounded to u8.
-__device__ __forceinline__ void nv12_rgb(float Y, float U, float V, float& r, float& g, float& b) {
-#pragma clang fp contract(off)
-  r = Y + 1.402f * V;
-  g = Y - 0.344136f * U - 0.714136f * V;
-  b = Y + 1.772f * U;
-  r = fmaxf(0.0f, fminf(255.0f, r));
-  g = fmaxf(0.0f, fminf(255.0f, g));
-  b = fmaxf(0.0f, fminf(255.0f, b));
-}
-
-// The NV12 tap at pixel (xs, ys) of the region: camera pixel (cam_x0 + xs, cam_y0 + ys), whose chroma pair lies at row
-// (cam_y0 + ys) / 2, bytes 2 * ((cam_x0 + xs) / 2) and + 1 of the chroma plane (cuda_preprocess.cu:224-227).
-__device__ __forceinline__ void nv12_tap(const StemParams& p, int xs, int ys, float& r, float& g, float& b) {
-#pragma clang fp contract(off)
-  const int X = p.cam_x0 + xs, Y = p.cam_y0 + ys;
-  const float Yv = p.cam[(size_t)Y * p.cam_pitch + X];
-  const unsigned char* c = p.cam_uv + (size_t)(Y / 2) * p.cam_uv_pitch + (size_t)(X / 2) * 2;
-  nv12_rgb(Yv, c[0] - 128.0f, c[1] - 128.0f, r, g, b);
-}
-
-// Network-input pixel (y, x) of a camera frame: the arithmetic of preprocess.hip (cuda_preprocess.cu:99-128 plain BGRA,
-// :144-204 half-pixel-centre bilinear resize, :212-253 NV12), expression trees rounded exactly as written there. The NV12
-// resize (src_kind 4) is this project's definition, the reference has none: the coordinates, clamps and weights of the BGRA
-// resize, the four taps being the clamped float r, g, b of nv12_tap instead of u8 channels.
-// Letterboxed frames (src_kind 5 BGRA, 6 NV12; include/unina_mi355.h at unina_infer_letterbox_bgra): inside the inner rectangle
-// the pixel is that of kind 1..4 for a destination of in_w x in_h at (x - in_x0, y - in_y0), outside it r = g = b = pad_value.
-// The kind, the destination size and the offset are kernel arguments: they are re-based in scalar registers under a wave-uniform
-// branch, so kinds 1..4 run the instructions they ran before; only the inside test is per pixel (lanes outside skip the taps).
-__device__ __forceinline__ void camera_pixel(const StemParams& p, int y, int x, float (&rgb)[3]) {
-#pragma clang fp contract(off)
-  float r, g, b;
-  int kind = p.src_kind, dw = p.W, dh = p.H;
-  bool inside = true;
-  if (kind >= 5) {
-    dw = p.in_w;
-    dh = p.in_h;
-    x -= p.in_x0;
-    y -= p.in_y0;
-    inside = (unsigned)x < (unsigned)dw && (unsigned)y < (unsigned)dh;
-    kind = (kind == 5 ? 1 : 3) + ((dw == p.cam_w && dh == p.cam_h) ? 0 : 1);
-  }
-  if (!inside) {
-    r = g = b = p.pad_value;
-  } else if (kind == 1) {
-    const uchar4 px = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y * p.cam_pitch + (size_t)x * 4);  // B,G,R,A
-    r = (float)px.z; g = (float)px.y; b = (float)px.x;
-  } else if (kind == 3) {
-    nv12_tap(p, x, y, r, g, b);
-  } else {
-    const int sw = p.cam_w, sh = p.cam_h;
-    const float scale_x = (float)sw / dw, scale_y = (float)sh / dh;
-    float sx = (x + 0.5f) * scale_x - 0.5f, sy = (y + 0.5f) * scale_y - 0.5f;
-    sx = fmaxf(0.0f, fminf(sx, sw - 1.0f));
-    sy = fmaxf(0.0f, fminf(sy, sh - 1.0f));
-    const int x0 = (int)sx, y0 = (int)sy;
-    const int x1 = min(x0 + 1, sw - 1), y1 = min(y0 + 1, sh - 1);
-    const float fx = sx - x0, fy = sy - y0;
-    const float w00 = (1.0f - fx) * (1.0f - fy), w01 = fx * (1.0f - fy), w10 = (1.0f - fx) * fy, w11 = fx * fy;
-    if (kind == 2) {
-      const uchar4 p00 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x0 * 4);
-      const uchar4 p01 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y0 * p.cam_pitch + (size_t)x1 * 4);
-      const uchar4 p10 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x0 * 4);
-      const uchar4 p11 = *reinterpret_cast<const uchar4*>(p.cam + (size_t)y1 * p.cam_pitch + (size_t)x1 * 4);
-      r = w00 * p00.z + w01 * p01.z + w10 * p10.z + w11 * p11.z;
-      g = w00 * p00.y + w01 * p01.y + w10 * p10.y + w11 * p11.y;
-      b = w00 * p00.x + w01 * p01.x + w10 * p10.x + w11 * p11.x;
-    } else {
-      float r00, g00, b00, r01, g01, b01, r10, g10, b10, r11, g11, b11;
-      nv12_tap(p, x0, y0, r00, g00, b00);
-      nv12_tap(p, x1, y0, r01, g01, b01);
-      nv12_tap(p, x0, y1, r10, g10, b10);
-      nv12_tap(p, x1, y1, r11, g11, b11);
-      r = w00 * r00 + w01 * r01 + w10 * r10 + w11 * r11;
-      g = w00 * g00 + w01 * g01 + w10 * g10 + w11 * g11;
-      b = w00 * b00 + w01 * b01 + w10 * b10 + w11 * b11;
-    }
-  }
-  cam_normalise(p, r, g, b, rgb);
-}
-
 template <typename T, int CO>
 __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
   constexpr int CH = CO / 2;  // channels per thread
@@ -142,7 +53,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
   const int oy = m / p.Wo, ox = m - oy * p.Wo;
   float x[27];
   const size_t plane = (size_t)p.H * p.W;
-  if (p.src_kind == 0) {
+  if (p.cam.kind == kSrcTensor) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -156,7 +67,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
         }
       }
   } else {
-    // camera frame: the network-input pixel (iy, ix) is computed as preprocess.hip would have written it
+    // camera frame: the network-input pixel (ix, iy) as camera_source.h defines it
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
       const int iy = oy * 2 + kh - 1;
@@ -164,7 +75,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
       for (int kw = 0; kw < 3; ++kw) {
         const int ix = ox * 2 + kw - 1;
         float rgb[3] = {0.f, 0.f, 0.f};
-        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p, iy, ix, rgb);
+        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p.cam, p.cam.kind, ix, iy, rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) x[(c * 3 + kh) * 3 + kw] = rgb[c];
       }
@@ -233,7 +144,7 @@ __global__ __launch_bounds__(kStemNT) void stem_tile_kernel(const StemParams p) 
   const int iy0 = 2 * ty0 - 1, ix0 = 2 * tx0 - 4;               // image coordinates of patch (row 0, column 0)
   for (int i = tid; i < 27 * CO / 4; i += kStemNT) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(p.wt)[i];
   if (tid < CO) wl[27 * CO + tid] = p.bias[tid];
-  if (p.src_kind == 0) {
+  if (p.cam.kind == kSrcTensor) {
     const size_t plane = (size_t)p.H * p.W;
     constexpr int NV = 3 * kStemPR * (kStemPW / 4);
     for (int v = tid; v < NV; v += kStemNT) {
@@ -254,63 +165,27 @@ __global__ __launch_bounds__(kStemNT) void stem_tile_kernel(const StemParams p) 
       }
       *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = val;
     }
-  } else if (p.src_kind == 3) {
-    // NV12 region of the network's size, four footprint pixels per thread as preprocess_quads_kernel<kNv12> reads them: W and
-    // ix0 are multiples of 4, so a quad lies wholly inside its row or wholly outside. A dword of luma and a dword of chroma
-    // (two U,V pairs) cover it where the addresses are 4-byte aligned -- the same answer for every quad of the frame, it
-    // depends on the pitches, the plane addresses and the region's origin only -- and byte loads otherwise.
-    const bool wide_y = (p.cam_pitch & 3) == 0 && (((uintptr_t)p.cam + (unsigned)p.cam_x0) & 3) == 0;
-    const bool wide_c = (p.cam_uv_pitch & 3) == 0 && (p.cam_x0 & 1) == 0 && (((uintptr_t)p.cam_uv + (unsigned)p.cam_x0) & 3) == 0;
+  } else if (p.cam.kind == kSrcNv12Tap) {
+    // NV12 region of the network's size, four footprint pixels per thread (nv12_quad, as preprocess_quads_kernel reads them): W
+    // and ix0 are multiples of 4, so a quad lies wholly inside its row or wholly outside
+    bool wide_y, wide_c;
+    nv12_quad_alignment(p.cam, wide_y, wide_c);
     for (int v = tid; v < kStemPR * (kStemPW / 4); v += kStemNT) {
       const int r = v / (kStemPW / 4), q = v - r * (kStemPW / 4);
       const int iy = iy0 + r, ix = ix0 + 4 * q;
       float o[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-      if (iy >= 0 && iy < p.H && ix >= 0 && ix + 3 < p.W) {
-        const int X = p.cam_x0 + ix, Y = p.cam_y0 + iy;
-        const unsigned char* yrow = p.cam + (size_t)Y * p.cam_pitch + X;
-        const unsigned char* crow = p.cam_uv + (size_t)(Y / 2) * p.cam_uv_pitch;
-        unsigned char yy[4], uu[4], vv[4];
-        if (wide_y) {
-          const unsigned yw = *reinterpret_cast<const unsigned*>(yrow);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) yy[i] = (unsigned char)(yw >> (8 * i));
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) yy[i] = yrow[i];
-        }
-        if (wide_c) {   // X is even: the pairs of pixels X, X + 1 | X + 2, X + 3
-          const unsigned cw = *reinterpret_cast<const unsigned*>(crow + X);
-          uu[0] = uu[1] = (unsigned char)cw;
-          vv[0] = vv[1] = (unsigned char)(cw >> 8);
-          uu[2] = uu[3] = (unsigned char)(cw >> 16);
-          vv[2] = vv[3] = (unsigned char)(cw >> 24);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const unsigned char* c = crow + (size_t)((X + i) / 2) * 2;
-            uu[i] = c[0];
-            vv[i] = c[1];
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma clang fp contract(off)
-          float cr, cg, cb;
-          nv12_rgb((float)yy[i], uu[i] - 128.0f, vv[i] - 128.0f, cr, cg, cb);
-          cam_normalise(p, cr, cg, cb, o[i]);
-        }
-      }
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix + 3 < p.W) nv12_quad(p.cam, p.cam.x0 + ix, p.cam.y0 + iy, 4, false, wide_y, wide_c, o);
 #pragma unroll
       for (int c = 0; c < 3; ++c)
         *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
     }
   } else {
-    // camera frame: every footprint pixel is pre-processed once, as preprocess.hip would have written it
+    // camera frame: every footprint pixel is pre-processed once (camera_source.h)
     for (int e = tid; e < kStemPR * kStemPW; e += kStemNT) {
       const int r = e / kStemPW, j = e - r * kStemPW;
       const int iy = iy0 + r, ix = ix0 + j;
       float rgb[3] = {0.f, 0.f, 0.f};
-      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p, iy, ix, rgb);
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p.cam, p.cam.kind, ix, iy, rgb);
 #pragma unroll
       for (int c = 0; c < 3; ++c) patch[(c * kStemPR + r) * kStemPW + j] = rgb[c];
     }
