@@ -372,6 +372,74 @@ int unina_calib_buffers_async(unina_engine_t *e, uint32_t *d_counts, hipStream_t
  * binding). Nothing is synchronised. */
 int unina_calib_async(unina_engine_t *e, const float *d_images_nchw, uint32_t *d_counts, hipStream_t stream);
 
+/* ------------------------------------------------------------------ evaluation (eval.py:18-138, train.py:299-520)
+ * Scoring detections against labels where the records already are: one small launch per image (csrc/evalmatch.hip: one
+ * workgroup of 11 waves), enqueued behind the frame that produced the records (unina_infer_async and the camera / letterbox /
+ * tiled _async calls); no engine handle. Only counters, conformal scores and per-detection true-positive masks cross to the
+ * host, once per data set (unina_eval_read). The HOST code is the definition, decision for decision and bit for bit:
+ *   UNINA_EVAL_SMALL     metrics.SmallObjectMetric.update on the rows evaluate() builds from the records: x * sx / y * sy in fp32,
+ *                        x2 - x1 in fp32 (detections_to_coco), then double: centre format normalised by width / height, small =
+ *                        w * imgsz < size_threshold and h * imgsz < size_threshold (both strict), TP at best IoU >= iou_threshold,
+ *                        FP only for a small prediction, FN = small labels left unmatched; an image without a small label
+ *                        counts nothing
+ *   UNINA_EVAL_CONFORMAL metrics.conformal_quantile's matcher on the records scaled by cx / cy in fp32 (to imgsz pixels) and the
+ *                        labels converted with the ONE size imgsz: a pair is a candidate if iou > best and iou >= 0.5; every match
+ *                        appends the score 1 - best_iou (double), in the host's order
+ *   UNINA_EVAL_AP        the same matcher at the ten thresholds t_j = (10 + j) / 20.0, j = 0..9 (metrics.ap_rows_numpy): one row
+ *                        per record, in matching order, bit j of tp_mask = matched at t_j; and the labels counted per class
+ * Matching order: greater confidence first, equal confidences by record index (np.argsort(-confidence, kind="stable")); the
+ * records need not arrive sorted. Among labels of equal IoU the lowest index wins. Every launch handles one image: at most
+ * UNINA_EVAL_MAX_LABELS labels, at most MAX_DETECTIONS records, the count read from device memory. Integer counters, fixed
+ * append order (one workgroup per launch, launches stream-ordered): two runs give identical bytes. */
+#define UNINA_EVAL_SMALL 1u
+#define UNINA_EVAL_CONFORMAL 2u
+#define UNINA_EVAL_AP 4u
+#define UNINA_EVAL_MAX_LABELS 256
+#define UNINA_EVAL_MAX_CLASSES 256
+typedef struct unina_eval unina_eval_t;
+typedef struct {
+  float sx, sy;            /* SMALL: record -> pixels of the image itself (evaluate(): w / net_w, h / net_h)                */
+  float cx, cy;            /* CONFORMAL / AP: record -> imgsz pixels (evaluate(): imgsz / net_w, imgsz / net_h)              */
+  int width, height;       /* the image's own size: what the labels are normalised to (eval.py:96-108)                       */
+  int imgsz;               /* SmallObjectMetric.image_size and conformal_quantile's imgsz                                     */
+  double size_threshold;   /* SmallObjectMetric.size_threshold (15)                                                           */
+  double iou_threshold;    /* SmallObjectMetric.iou_threshold (0.5), > 0                                                      */
+} unina_eval_params;
+typedef struct {
+  float confidence;
+  int class_id;
+  unsigned tp_mask;
+} unina_eval_row;
+typedef struct {
+  long long tp, fp, fn;                /* SmallObjectMetric's accumulators                                                    */
+  unsigned long long n_scores, n_rows; /* TRUE totals since the last reset, also where a list ran past its capacity           */
+  int overflow;                        /* bit 0: scores past max_scores, bit 1: rows past max_rows (the excess is dropped)    */
+  int guard_intact;                    /* 1: the canary words the handle keeps behind both lists still hold their pattern     */
+  long long label_counts[UNINA_EVAL_MAX_CLASSES]; /* AP: labels per class id in [0, num_classes)                              */
+} unina_eval_result;
+
+/* Host only: no HIP call; the device memory (counters, max_scores doubles, max_rows rows) is allocated -- and zeroed -- by the
+ * first reset / update / read, on that call's stream, which then fails with UNINA_ERR_HIP where there is no device.
+ * UNINA_ERR_ARG: NULL out, negative device_id, num_classes outside 1..UNINA_EVAL_MAX_CLASSES. */
+int unina_eval_create(int device_id, int num_classes, size_t max_scores, size_t max_rows, unina_eval_t **out);
+/* Waits for the device, frees. NULL is a no-op. */
+void unina_eval_destroy(unina_eval_t *ev);
+/* Zeroes counters and list lengths, enqueued on `stream`. */
+int unina_eval_reset_async(unina_eval_t *ev, hipStream_t stream);
+/* One image, enqueued on `stream`; nothing is synchronised.
+ *   d_dets / d_count : device, MAX_DETECTIONS records / one int, as unina_infer_async writes them (*d_count is clamped to
+ *                      0..MAX_DETECTIONS on the device)
+ *   d_labels         : device, double [n_labels, 5] rows cls, xc, yc, w, h (normalised); may be NULL when n_labels == 0
+ *   what             : mask of UNINA_EVAL_*; all parts of one call see the same records
+ * UNINA_ERR_ARG, before any HIP call: NULL ev / d_dets / d_count / p, n_labels outside 0..UNINA_EVAL_MAX_LABELS, d_labels NULL
+ * with labels, `what` zero or with unknown bits, a non-positive size, iou_threshold <= 0, a misaligned pointer. */
+int unina_eval_update_async(unina_eval_t *ev, const GpuDetection *d_dets, const int *d_count, const double *d_labels,
+                            int n_labels, const unina_eval_params *p, unsigned what, hipStream_t stream);
+/* Synchronises `stream`, then copies out the counters and min(n_scores, max_scores, score_cap) scores /
+ * min(n_rows, max_rows, row_cap) rows (scores / rows may be NULL when their cap is 0). */
+int unina_eval_read(unina_eval_t *ev, unina_eval_result *res, double *scores, size_t score_cap, unina_eval_row *rows,
+                    size_t row_cap, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

@@ -30,6 +30,7 @@ UNITS = {
     "mining.hip": ["-ffp-contract=off"],        # scores / pool / k-center round as the reference's fp32 expressions are written
     "kmeans.hip": ["-ffp-contract=off"],        # k-means coreset: fused operations only where fmaf is written (the tests' bounds count roundings)
     "calib.hip": [],                     # |x| value-count tables for INT8 calibration: integer counts only
+    "evalmatch.hip": ["-ffp-contract=off"],     # detections against labels: every comparison must decide as the host's numpy code does
     "engine.hip": [],
     "comm.hip": [],                             # host code only: RCCL all-gather of detection slots, librccl loaded on first use
 }

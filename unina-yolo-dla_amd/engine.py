@@ -47,6 +47,25 @@ class Letterbox(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("new_w", "new_h", "left", "top")]
 
 
+EVAL_SMALL, EVAL_CONFORMAL, EVAL_AP = 1, 2, 4   # include/unina_mi355.h UNINA_EVAL_*
+EVAL_MAX_LABELS = 256
+EVAL_MAX_CLASSES = 256
+EVAL_ROW_DTYPE = np.dtype([("confidence", "<f4"), ("class_id", "<i4"), ("tp_mask", "<u4")])   # unina_eval_row
+
+
+class EvalParams(C.Structure):
+    """unina_eval_params."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_int), ("height", C.c_int),
+                ("imgsz", C.c_int), ("size_threshold", C.c_double), ("iou_threshold", C.c_double)]
+
+
+class EvalResult(C.Structure):
+    """unina_eval_result."""
+    _fields_ = [("tp", C.c_longlong), ("fp", C.c_longlong), ("fn", C.c_longlong), ("n_scores", C.c_ulonglong),
+                ("n_rows", C.c_ulonglong), ("overflow", C.c_int), ("guard_intact", C.c_int),
+                ("label_counts", C.c_longlong * EVAL_MAX_CLASSES)]
+
+
 def _tile_array(tiles):
     return (Tile * len(tiles))(*[Tile(*map(int, t)) for t in tiles])
 
@@ -71,6 +90,7 @@ ABI_SYMBOLS = [
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
+    "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -160,6 +180,13 @@ def load_library() -> C.CDLL:
     L.unina_calib_buffer_name.argtypes = [vp, ci, C.c_char_p, C.c_size_t]
     L.unina_calib_buffers_async.argtypes = [vp, vp, vp]
     L.unina_calib_async.argtypes = [vp, vp, vp, vp]
+    # evaluation (csrc/evalmatch.hip)
+    L.unina_eval_create.argtypes = [ci, ci, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.unina_eval_destroy.argtypes = [vp]
+    L.unina_eval_destroy.restype = None
+    L.unina_eval_reset_async.argtypes = [vp, vp]
+    L.unina_eval_update_async.argtypes = [vp, vp, vp, vp, ci, C.POINTER(EvalParams), C.c_uint, vp]
+    L.unina_eval_read.argtypes = [vp, C.POINTER(EvalResult), vp, C.c_size_t, vp, C.c_size_t, vp]
     # multi-GPU: RCCL gather of detection slots behind the C ABI (csrc/comm.hip)
     L.unina_comm_unique_id.argtypes = [vp]
     L.unina_comm_init.argtypes = [C.POINTER(vp), vp, ci, ci, ci]
@@ -836,6 +863,61 @@ def calibrate_amax(sd: Dict[str, np.ndarray], graph: Optional[Graph], frames, de
         return _export.calibrate(per_frame(), percentile, method)
     finally:
         eng.close()
+
+
+class DeviceEval:
+    """unina_eval_*: detections scored against labels on the GPU (csrc/evalmatch.hip), one launch per image behind the frame
+    that produced the records. `max_scores` / `max_rows`: capacity of the conformal-score and AP-row lists."""
+
+    def __init__(self, num_classes: int, max_scores: int, max_rows: int, device: int = 0):
+        self.L = load_library()
+        self.device, self.num_classes, self.max_scores, self.max_rows = device, num_classes, max_scores, max_rows
+        self.h = C.c_void_p()
+        rc = self.L.unina_eval_create(device, num_classes, max_scores, max_rows, C.byref(self.h))
+        if rc:
+            raise EngineError(f"unina_eval_create failed [{ERRORS.get(rc, rc)}] (num_classes={num_classes})")
+        self._labels = []      # label tensors of the updates in flight (kept until the next read / reset)
+
+    def _check(self, rc: int, what: str):
+        if rc:
+            raise EngineError(f"{what} failed [{ERRORS.get(rc, rc)}]")
+
+    def reset(self, stream=None) -> None:
+        self._check(self.L.unina_eval_reset_async(self.h, _stream_ptr(stream)), "unina_eval_reset_async")
+
+    def update(self, det_buf, labels, params: EvalParams, what: int, stream=None) -> None:
+        """One image, asynchronous. det_buf: int32 CUDA tensor as infer_async's (word 0 = count, records from word 8);
+        labels: [M,5] rows cls, xc, yc, w, h (ndarray: uploaded as float64; or a float64 CUDA tensor)."""
+        torch = _torch()
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float64).reshape(-1, 5)).to(det_buf.device)
+        assert labels.is_cuda and labels.dtype == torch.float64 and labels.is_contiguous()
+        self._labels.append(labels)
+        base = det_buf.data_ptr()
+        n = labels.shape[0]
+        self._check(self.L.unina_eval_update_async(self.h, base + 32, base, labels.data_ptr() if n else None, n, C.byref(params),
+                                                   what, _stream_ptr(stream)), f"unina_eval_update_async ({n} labels)")
+
+    def read(self, stream=None):
+        """Synchronises; returns (EvalResult, scores float64 [n], rows EVAL_ROW_DTYPE [m]) -- the lists as far as they fit."""
+        res = EvalResult()
+        scores = np.empty(self.max_scores, dtype=np.float64)
+        rows = np.zeros(self.max_rows, dtype=EVAL_ROW_DTYPE)
+        self._check(self.L.unina_eval_read(self.h, C.byref(res), scores.ctypes.data, scores.size, rows.ctypes.data, rows.size,
+                                           _stream_ptr(stream)), "unina_eval_read")
+        self._labels.clear()
+        return res, scores[:min(res.n_scores, self.max_scores)].copy(), rows[:min(res.n_rows, self.max_rows)].copy()
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.unina_eval_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def letterbox_geometry(src_w: int, src_h: int, dst_w: int, dst_h: int):

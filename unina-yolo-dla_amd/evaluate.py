@@ -18,6 +18,12 @@ records written to predictions.json are scaled to the image's own pixels, as Ult
 By default a camera frame is STRETCHED to the network input (``unina_infer_bgra``). ``--letterbox`` keeps its aspect ratio, as
 ``YOLO.val`` does: ``unina_infer_letterbox_bgra`` with pad 114 and ``map_boxes=1``, so the records come back in the image's own
 pixels from the GPU and the host rescale is skipped for them.
+
+``--device-metrics`` scores the detections against the labels on the GPU (csrc/evalmatch.hip through ``unina_eval_*``): the
+records stay on the device (``unina_infer_async`` and its kin), one small launch per image follows the frame on its stream,
+and counters, conformal scores and AP rows come back once, after the last image. Same numbers as the host loops of
+``metrics.py``, which remain the definition. ``--map`` adds ``map50`` / ``map50_95`` (``metrics.mean_average_precision``: this
+project's own COCO-style definition, parity with the reference's ``model.val`` unpinned) from the low-confidence pass.
 """
 from __future__ import annotations
 
@@ -86,19 +92,52 @@ class EngineDetector:
         if autotune:
             self.eng.autotune()
         self.width, self.height = self.eng.width, self.eng.height
+        self.num_classes, self.device = self.eng.num_classes, self.eng.device
         self.letterbox = letterbox          # uint8 frames: letterboxed in the stem, boxes returned in the frame's own pixels
+
+    @staticmethod
+    def _bgra(frame: np.ndarray) -> np.ndarray:
+        h, w = frame.shape[:2]
+        if frame.shape[2] == 3:                                      # RGB -> BGRA
+            bgra = np.empty((h, w, 4), dtype=np.uint8)
+            bgra[..., 0], bgra[..., 1], bgra[..., 2], bgra[..., 3] = frame[..., 2], frame[..., 1], frame[..., 0], 255
+        else:
+            bgra = np.ascontiguousarray(frame)
+        return bgra.reshape(h, w * 4)
+
+    def device_records(self, frame: np.ndarray, conf: float, iou: float, q: float):
+        """__call__ with the records left on the device: the int32 CUDA tensor of Engine.infer_async (word 0 = count, records
+        from word 8), enqueued on the current stream, nothing synchronised. The tensor is the engine's own and is rewritten
+        by the next call; work enqueued on the same stream in between reads it in order. Stretched camera frames take the
+        two-step form of unina_infer_bgra (preprocess_bgra[_resize], then unina_infer_async: identical results)."""
+        import torch
+        dev = torch.device("cuda", self.eng.device)
+        if frame.dtype == np.uint8:
+            h, w = frame.shape[:2]
+            self._cam = cam = torch.from_numpy(self._bgra(frame)).to(dev)
+            if self.letterbox:
+                return self.eng.infer_letterbox_bgra(cam, w, h, w * 4, None, conf, iou, q, 114.0, True, out=self.eng._det_buf)
+            L = self.eng.L
+            if getattr(self, "_tensor", None) is None:
+                self._tensor = torch.empty((1, 3, self.height, self.width), dtype=torch.float32, device=dev)
+            norm, stream = L.create_norm_params_imagenet(), torch.cuda.current_stream().cuda_stream
+            if (w, h) == (self.width, self.height):
+                rc = L.preprocess_bgra(cam.data_ptr(), self._tensor.data_ptr(), w, h, w * 4, norm, stream)
+            else:
+                rc = L.preprocess_bgra_resize(cam.data_ptr(), self._tensor.data_ptr(), w, h, w * 4, self.width, self.height, norm, stream)
+            if rc:
+                raise RuntimeError(f"pre-process of a {w} x {h} camera frame failed (hipError {rc})")
+            return self.eng.infer_async(self._tensor, conf, iou, q)
+        x = np.ascontiguousarray(frame, dtype=np.float32).reshape(1, 3, self.height, self.width)
+        self._frame = torch.from_numpy(x).to(dev)
+        return self.eng.infer_async(self._frame, conf, iou, q)
 
     def __call__(self, frame: np.ndarray, conf: float, iou: float, q: float) -> np.ndarray:
         import torch
         dev = torch.device("cuda", self.eng.device)
         if frame.dtype == np.uint8:
             h, w = frame.shape[:2]
-            if frame.shape[2] == 3:                                  # RGB -> BGRA
-                bgra = np.empty((h, w, 4), dtype=np.uint8)
-                bgra[..., 0], bgra[..., 1], bgra[..., 2], bgra[..., 3] = frame[..., 2], frame[..., 1], frame[..., 0], 255
-            else:
-                bgra = np.ascontiguousarray(frame)
-            cam = torch.from_numpy(bgra.reshape(h, w * 4)).to(dev)
+            cam = torch.from_numpy(self._bgra(frame)).to(dev)
             if self.letterbox:
                 return self.eng.infer_letterbox_bgra(cam, w, h, w * 4, None, conf, iou, q, 114.0, True)
             return self.eng.infer_bgra(cam, w, h, w * 4, None, conf, iou, q)
@@ -112,7 +151,8 @@ class EngineDetector:
 def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], root: str, imgsz: int = 640,
              conf: float = 0.5, iou: float = 0.45, conformal_q: float = 0.1, out_dir: Optional[str] = None,
              net_size: Optional[Tuple[int, int]] = None, conformal_alpha: Optional[float] = None,
-             conformal_conf: float = 0.001, camera_pixels: bool = False) -> Dict[str, object]:
+             conformal_conf: float = 0.001, camera_pixels: bool = False, device_metrics: bool = False,
+             map_metrics: bool = False) -> Dict[str, object]:
     """eval.py:18-138 over `detect` (frame, conf, iou, q) -> GpuDetection records in network pixels.
 
     Writes <out_dir>/predictions.json (eval.py:58-61 schema, boxes in the image's own pixels), computes
@@ -120,13 +160,26 @@ def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], ro
     `conformal_alpha` -- the conformal quantile of train.py:299-520 from a second pass at a very low confidence
     threshold (train.py:403) without dilation. Returns {'small_object': {...}, 'conformal': {...} | None,
     'predictions': [...], 'images': n}. camera_pixels: `detect` returns the records of uint8 camera frames in the frame's own
-    pixels already (a letterboxing detector with the box map on): no host rescale for them."""
+    pixels already (a letterboxing detector with the box map on): no host rescale for them.
+
+    map_metrics: also 'map50' / 'map50_95' (metrics.mean_average_precision) from the low-confidence pass, which then runs
+    whether or not `conformal_alpha` is given. device_metrics: the matching runs on the GPU (unina_eval_*): `detect` must be an
+    EngineDetector (device_records, num_classes, device); the records of the main pass are still copied out for
+    predictions.json, the low-confidence pass copies nothing, and every number equals the host path's. An image may then carry
+    at most engine.EVAL_MAX_LABELS labels."""
     files = list_frames(root)
     if not files:
         raise FileNotFoundError(f"no frames (*.npy / *.png / *.jpg) under {root}")
     records: List[dict] = []
     so = metrics.SmallObjectMetric(size_threshold=15, image_size=imgsz)           # eval.py:74
     conf_dets, conf_labels = [], []
+    low_pass = conformal_alpha is not None or map_metrics
+    dev_eval = None
+    if device_metrics:
+        from . import engine
+        dev_eval = engine.DeviceEval(detect.num_classes, len(files) * engine.EVAL_MAX_LABELS if conformal_alpha is not None else 0,
+                                     len(files) * engine.MAX_DETECTIONS if map_metrics else 0, detect.device)
+        dev_eval.reset()
     for path in files:
         stem = os.path.splitext(os.path.basename(path))[0]
         frame = load_frame(path)
@@ -140,15 +193,26 @@ def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], ro
         else:                                                         # the network tensor itself
             nw, nh = w, h
         sx, sy = w / nw, h / nh
-        dets = detect(frame, conf, iou, conformal_q)
+        labels = read_labels(label_path(path))
+        if dev_eval is not None:
+            params = engine.EvalParams(sx, sy, imgsz / nw, imgsz / nh, w, h, imgsz, so.size_threshold, so.iou_threshold)
+            buf = detect.device_records(frame, conf, iou, conformal_q)
+            dev_eval.update(buf, labels, params, engine.EVAL_SMALL)
+            dets = engine.Engine.unpack(buf)
+        else:
+            dets = detect(frame, conf, iou, conformal_q)
         scaled = dets.copy()
         scaled["x1"], scaled["x2"] = dets["x1"] * sx, dets["x2"] * sx
         scaled["y1"], scaled["y2"] = dets["y1"] * sy, dets["y2"] * sy
         recs = metrics.detections_to_coco(scaled, stem)
         records += recs
-        labels = read_labels(label_path(path))
+        if dev_eval is not None:
+            if low_pass:
+                what = (engine.EVAL_CONFORMAL if conformal_alpha is not None else 0) | (engine.EVAL_AP if map_metrics else 0)
+                dev_eval.update(detect.device_records(frame, conformal_conf, iou, 0.0), labels, params, what)
+            continue
         so.update([metrics.coco_to_metric_rows(recs, w, h)], [labels])           # eval.py:96-108, 124
-        if conformal_alpha is not None:
+        if low_pass:
             d0 = detect(frame, conformal_conf, iou, 0.0)
             # conformal_quantile converts labels with ONE size (train.py:346-352): hand it boxes in imgsz pixels
             c = d0.copy()
@@ -160,9 +224,28 @@ def evaluate(detect: Callable[[np.ndarray, float, float, float], np.ndarray], ro
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "predictions.json"), "w") as f:
             json.dump(records, f)
+    if dev_eval is not None:
+        try:
+            res, scores, rows = dev_eval.read()
+        finally:
+            dev_eval.close()
+        if res.overflow:
+            raise RuntimeError(f"device metric lists overflowed (flags {res.overflow}): {res.n_scores} scores, {res.n_rows} rows")
+        so.true_positives, so.false_positives, so.false_negatives = int(res.tp), int(res.fp), int(res.fn)
+        label_counts = list(res.label_counts[:detect.num_classes])
+    elif map_metrics:
+        rows = np.concatenate([metrics.ap_rows_numpy(d, l, imgsz) for d, l in zip(conf_dets, conf_labels)])
+        label_counts = {}
+        for l in conf_labels:
+            for c in l[:, 0]:
+                if c >= 0:
+                    label_counts[int(c)] = label_counts.get(int(c), 0) + 1
     result: Dict[str, object] = {"images": len(files), "predictions": records, "small_object": so.compute(), "conformal": None}
+    if map_metrics:
+        result.update(metrics.mean_average_precision(rows, label_counts))
     if conformal_alpha is not None:
-        result["conformal"] = metrics.conformal_quantile(conf_dets, conf_labels, conformal_alpha, imgsz)
+        result["conformal"] = (metrics.conformal_from_scores(scores, conformal_alpha) if dev_eval is not None
+                               else metrics.conformal_quantile(conf_dets, conf_labels, conformal_alpha, imgsz))
         if out_dir:
             with open(os.path.join(out_dir, "conformal_params.json"), "w") as f:     # train.py:506-520 writes the same keys
                 json.dump(result["conformal"], f, indent=2)
@@ -183,16 +266,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--letterbox", action="store_true",
                     help="uint8 camera frames keep their aspect ratio (pad 114) instead of being stretched; boxes mapped back on the GPU")
+    ap.add_argument("--device-metrics", action="store_true",
+                    help="match detections against labels on the GPU (unina_eval_*); same numbers, no per-image host loops")
+    ap.add_argument("--map", action="store_true", help="also report map50 / map50_95 from the low-confidence pass (this project's definition)")
     a = ap.parse_args(argv)
     det = EngineDetector(a.engine, a.device, letterbox=a.letterbox)
     try:
         res = evaluate(det, a.data, a.imgsz, a.conf, a.iou, a.conformal_q, a.out_dir, (det.width, det.height),
-                       a.alpha if a.conformal else None, camera_pixels=a.letterbox)
+                       a.alpha if a.conformal else None, camera_pixels=a.letterbox, device_metrics=a.device_metrics,
+                       map_metrics=a.map)
     finally:
         det.close()
     print(f"{res['images']} images, {len(res['predictions'])} predictions -> {os.path.join(a.out_dir, 'predictions.json')}")
     for k, v in res["small_object"].items():                                      # eval.py:128-131
         print(f"    {k}: {v}")
+    if a.map:
+        print(f"    map50: {res['map50']:.6f}  map50_95: {res['map50_95']:.6f}  (own COCO-style definition, unpinned against model.val)")
     if res["conformal"]:
         print(f"    q_hat: {res['conformal']['q_hat']:.6f}  ({res['conformal']['num_calibration_samples']} matched boxes)")
     return 0

@@ -127,10 +127,82 @@ def conformal_quantile(dets_per_image: Sequence[np.ndarray], labels_per_image: S
             if best >= 0:
                 matched.add(best)
                 scores.append(1.0 - best_iou)
-    if not scores:
+    return conformal_from_scores(scores, alpha)
+
+
+def conformal_from_scores(scores: Sequence[float], alpha: float = 0.10) -> Dict[str, float]:
+    """train.py:492-520 on the nonconformity scores 1 - IoU of the matched boxes, in matching order (conformal_quantile's
+    list, or the one unina_eval_read returns)."""
+    if len(scores) == 0:
         raise ValueError("conformal calibration failed: no matched predictions")          # train.py:492-496
     s = np.asarray(scores)
     q = float(np.quantile(s, 1 - alpha))
     return {"alpha": alpha, "coverage_target": 1 - alpha, "q_hat": q, "dilation_factor": q,
             "num_calibration_samples": len(scores), "mean_nonconformity": float(s.mean()),
             "std_nonconformity": float(s.std())}
+
+
+AP_THRESHOLDS = tuple((10 + j) / 20.0 for j in range(10))              # 0.50, 0.55 .. 0.95 (COCO's IoU thresholds)
+AP_ROW_DTYPE = np.dtype([("confidence", "<f4"), ("class_id", "<i4"), ("tp_mask", "<u4")])   # unina_eval_row
+
+
+def ap_rows_numpy(dets: np.ndarray, labels: np.ndarray, imgsz: int = 640) -> np.ndarray:
+    """One image's detections against its labels at the ten IoU thresholds AP_THRESHOLDS: conformal_quantile's matching loop
+    (same boxes, same conversions, same arithmetic, a pair is a candidate if iou > best and iou >= t) run once per threshold,
+    each with its own matched set. Returns one AP_ROW_DTYPE row per detection, in matching order (stable descending
+    confidence); bit j of tp_mask = the detection found a label at AP_THRESHOLDS[j]. The host twin of waves 1..10 of
+    csrc/evalmatch.hip."""
+    labels = np.asarray(labels, dtype=np.float64).reshape(-1, 5)
+    gts = [((l[1] - l[3] / 2) * imgsz, (l[2] - l[4] / 2) * imgsz, (l[1] + l[3] / 2) * imgsz, (l[2] + l[4] / 2) * imgsz)
+           for l in labels]
+    dets = dets[np.argsort(-dets["confidence"], kind="stable")]
+    rows = np.zeros(len(dets), dtype=AP_ROW_DTYPE)
+    rows["confidence"], rows["class_id"] = dets["confidence"], dets["class_id"]
+    for j, t in enumerate(AP_THRESHOLDS):
+        matched = set()
+        for k, d in enumerate(dets):
+            box = (d["x1"], d["y1"], d["x2"], d["y2"])
+            best_iou, best = 0.0, -1
+            for gi, (g, l) in enumerate(zip(gts, labels)):
+                if gi in matched or int(l[0]) != int(d["class_id"]):
+                    continue
+                iou = _box_iou_xyxy(box, g)
+                if iou > best_iou and iou >= t:
+                    best_iou, best = iou, gi
+            if best >= 0:
+                matched.add(best)
+                rows["tp_mask"][k] |= np.uint32(1 << j)
+    return rows
+
+
+def mean_average_precision(rows: np.ndarray, label_counts) -> Dict[str, float]:
+    """mAP50 and mAP50-95 from AP rows (ap_rows_numpy / unina_eval_read, all images concatenated) and the number of labels per
+    class (`label_counts[c]`, a sequence indexed by class id or a dict). Per class with labels and per threshold j: rows of
+    the class sorted by confidence (stable, descending), cumulative TP / FP, recall = TP / labels, precision = TP / (TP + FP)
+    made monotone from the right, AP = mean of the precision at the 101 recall points 0, 0.01 .. 1 (the precision at the first
+    row whose recall reaches the point; 0 where none does). map50 = mean over those classes of AP at j = 0, map50_95 = mean
+    over classes and the ten thresholds; both 0.0 when no class has labels.
+
+    This is THIS PROJECT'S COCO-style definition. The reference reports the two numbers from ultralytics' model.val
+    (eval.py:21-40), which is not available to pin against: parity with it is UNPINNED, as for the INT8 engine. In
+    particular the matching rule is conformal_quantile's greedy one, not ultralytics'."""
+    counts = dict(label_counts) if isinstance(label_counts, dict) else dict(enumerate(label_counts))
+    classes = sorted(int(c) for c, n in counts.items() if n > 0)
+    if not classes:
+        return {"map50": 0.0, "map50_95": 0.0}
+    rows = np.asarray(rows, dtype=AP_ROW_DTYPE)
+    points = np.linspace(0.0, 1.0, 101)
+    ap = np.zeros((len(classes), len(AP_THRESHOLDS)))
+    for ci, c in enumerate(classes):
+        r = rows[rows["class_id"] == c]
+        r = r[np.argsort(-r["confidence"], kind="stable")]
+        if len(r) == 0:
+            continue
+        for j in range(len(AP_THRESHOLDS)):
+            tp = ((r["tp_mask"] >> np.uint32(j)) & np.uint32(1)).astype(np.float64)
+            ctp, cfp = np.cumsum(tp), np.cumsum(1.0 - tp)
+            recall = ctp / float(counts[c])
+            precision = np.maximum.accumulate((ctp / (ctp + cfp))[::-1])[::-1]
+            at = np.searchsorted(recall, points, side="left")
+            ap[ci, j] = np.where(at < len(r), precision[np.minimum(at, len(r) - 1)], 0.0).mean()
+    return {"map50": float(ap[:, 0].mean()), "map50_95": float(ap.mean())}
