@@ -524,6 +524,9 @@ int unina_debug_dual_timeline(unina_engine_t* e, int op_index, long long* out, i
  * 6 b1.cv1, 7 last bottleneck, 8 cv3, 9 output stored, 10 tail conv, 11 drained), [14] / [15] = 100 MHz clock at end / entry.
  * Only the 40x40-level blocks have twins (UNINA_ERR_HIP otherwise). */
 int unina_debug_block_stamps(unina_engine_t *e, int op_index, long long *out16, hipStream_t stream);
+/* Debug, read-only: which heads' output convs the decode launch of unina_infer computes itself (folded), as the frame stands
+ * now: bit h (0 = P2, 1 = P3, 2 = P4) set = that head is not read from its planes. Negative error code for a null handle. */
+int unina_debug_folded_heads(unina_engine_t *e);
 
 /* Library/build identification: "unina_mi355 <version> gfx950". */
 const char *unina_version(void);

@@ -458,3 +458,98 @@ PER_OP_TOPOLOGIES = (("B-32x32", dict(variant="B", in_h=32, in_w=32)), ("B-96x16
                      ("lite_p2", dict(lite_p2=True, in_h=80, in_w=112)), ("base16", dict(base_channels=16, in_h=80, in_w=112)),
                      ("classes1", dict(num_classes=1, in_h=80, in_w=112)), ("classes7", dict(num_classes=7, in_h=80, in_w=112)),
                      ("classes20", dict(num_classes=20, in_h=80, in_w=112)))
+
+
+# ---- the frame as launched (fusion on): which ops can be held teacher-forced on the frame's OWN buffers ----------------
+# With fusion on, a fused group keeps its intermediates in LDS: their buffers are not written, so most ops of the table have
+# no stored input or output to be checked against. What stays checkable is every op whose source, shortcut and destination
+# slices all reach memory in that frame: the launches outside any group (the P3 / P4 head layers among them, which then run
+# as dual launches) and the convs at a group's edge. Group membership is read from op_infos(): the engine names an absorbed
+# op's kernel "(fused into op N)" / "(dual launch with op N)" (engine.hip absorb_info).
+def launched_groups(infos):
+    """op_infos() of an engine with fusion on -> ({leader: [ops fused into its launch]}, {leader: [ops sharing its dual launch]})."""
+    import re
+    groups, duals = {}, {}
+    for i, o in enumerate(infos):
+        m = re.fullmatch(r"\((fused into|dual launch with) op (\d+)\)", o["kernel"])
+        if m:
+            (groups if m.group(1) == "fused into" else duals).setdefault(int(m.group(2)), []).append(i)
+    return groups, duals
+
+
+def launched_kernel(infos, oi):
+    """The kernel that computes op oi in the frame: its own, or that of the launch that absorbed it."""
+    import re
+    k = infos[oi]["kernel"]
+    m = re.fullmatch(r"\((?:fused into|dual launch with) op (\d+)\)", k)
+    return launched_kernel(infos, int(m.group(1))) if m else k
+
+
+def op_reads(op):
+    """[(buffer index, c0, c1)] of the slices op reads: per segment its source slice and its shortcut slice."""
+    if op.kind == export.OP_QUANT:
+        out = [(op.src_buf, 0, op.segs[0].n_count)]
+    elif op.kind == export.OP_STEM:
+        out = [(op.src_buf, 0, op.cin)]
+    else:
+        out = [(op.src_buf, s.src_coff, s.src_coff + op.cin) for s in op.segs]
+    if op.res is not None:
+        out += [(op.res.buf, op.res.coff, op.res.coff + s.n_count) for s in op.segs]
+    return out
+
+
+def op_writes(op):
+    return [(s.dst.buf, s.dst.coff, s.dst.coff + s.n_count) for s in op.segs]
+
+
+def written_when_launched(builder, infos):
+    """{buffer name: bool mask over its channels} -- what the frame with fusion on writes to memory (the input image counts as
+    written). An op outside every fused group writes its slices. Inside a group (engine.hip op_regions): a slice reaches memory
+    when an op outside the group reads it or it is a network output -- a block's cv3, its tail conv and its int8 twin, a head's
+    planes; the pre-conv's and the bottlenecks' tensors stay in LDS --, and both convs of a conv pair store theirs (the pooled
+    maps of an SPPF pool inside the pair do not)."""
+    groups, _ = launched_groups(infos)
+    leader = {m: L for L, ms in groups.items() for m in ms}
+    leader.update({L: L for L in groups})
+    mask = [np.zeros(b[3], dtype=bool) for b in builder.buffers]
+    for i, b in enumerate(builder.buffers):
+        if b[5] & export.BUF_INPUT:
+            mask[i][:] = True
+    reads = [op_reads(op) for op in builder.ops]
+    for oi, op in enumerate(builder.ops):
+        L = leader.get(oi)
+        for (buf, c0, c1) in op_writes(op):
+            if L is None:
+                w = True
+            elif infos[L]["kernel"].startswith("conv_pair"):
+                w = op.kind == export.OP_CONV
+            else:
+                inside = {L, *groups[L]}
+                w = bool(builder.buffers[buf][5] & export.BUF_OUTPUT) or any(
+                    rb == buf and r0 < c1 and c0 < r1 for k, rs in enumerate(reads) if k not in inside for (rb, r0, r1) in rs)
+            if w:
+                mask[buf][c0:c1] = True
+    return {b[0]: m for b, m in zip(builder.buffers, mask)}
+
+
+def launched_ops(builder, infos, written=None):
+    """Indices of the ops whose source, shortcut and destination slices are all written by the frame with fusion on: the ops
+    per_op_bounds(only_op=...) can evaluate on that frame's own buffers."""
+    written = written_when_launched(builder, infos) if written is None else written
+    names = [b[0] for b in builder.buffers]
+    return [oi for oi, op in enumerate(builder.ops)
+            if all(written[names[buf]][c0:c1].all() for (buf, c0, c1) in op_reads(op) + op_writes(op))]
+
+
+def head_ops(builder, levels=("p3", "p4")):
+    """{level: [op index of the .0, .1 and .2 layer pair]} -- the op whose two slices carry head_<level>.cls_branch.<j> and
+    head_<level>.reg_branch.<j> (graph.py's names)."""
+    out = {}
+    for lv in levels:
+        out[lv] = []
+        for j in range(3):
+            want = {f"head_{lv}.cls_branch.{j}", f"head_{lv}.reg_branch.{j}"}
+            hit = [oi for oi, op in enumerate(builder.ops) if {s.module for s in op.segs} == want]
+            assert len(hit) == 1, (lv, j, hit)
+            out[lv].append(hit[0])
+    return out

@@ -622,6 +622,8 @@ def same_head(a, b, name):
     """fp16 engines, fused frame vs per-op table: the P2 head must agree bit for bit; the P3 / P4 heads run their two 3x3
     layers on the chunked weights-stationary pair kernel in the fused frame (chunk-major sum order, conv_igemm.hip
     conv3x3_wsc_body: last-bit differences of fp16 outputs) and agree within 5e-3."""
+    # (5e-3 is a sanity bound between two forms. The sharp checks of the pair launches and of the folded output convs are in
+    #  tests/test_gpu_launched_heads.py: the float64 bound of every element, and bytes against the same bodies launched singly.)
     if name.startswith("p2_"):
         assert np.array_equal(a, b), name
     else:

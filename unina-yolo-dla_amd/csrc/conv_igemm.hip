@@ -1426,8 +1426,9 @@ const DualKind kDual[kDualKinds] = {
     {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_s16<regq s16,8x16,64,128 | regq s16,8x8,64,256>", conv_dual_head3x3_s16, false, -1},
     {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, WS_S16_PAIR, conv_dual_head3x3_ws_s16, true, kDualWsS16Stamped},
     {kCfgWs8x16n64c128, kCfgWs4x16n64c256, 256, "conv_dual_head3x3_ws_small<ws 8x16,64,128/2 | ws 4x16,64,256/4, 2 per CU>", conv_dual_head3x3_ws_small, true, -1},
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, WS_PAIR, conv_dual_head3x3_ws_stamped, true, -1},
-    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, WS_S16_PAIR, conv_dual_head3x3_ws_s16_stamped, true, -1},
+    // (the debug twins carry names of their own: an op info that showed one would say so)
+    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws_stamped<ws 16x16,64,128/2 | ws 8x16,64,256/4>", conv_dual_head3x3_ws_stamped, true, -1},
+    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, "conv_dual_head3x3_ws_s16_stamped<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>", conv_dual_head3x3_ws_s16_stamped, true, -1},
 };
 #undef WS_PAIR
 #undef WS_S16_PAIR

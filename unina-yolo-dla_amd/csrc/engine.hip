@@ -2566,6 +2566,17 @@ int unina_profile_post(unina_engine_t* e, int iters, float conf, float iou, floa
   return rc;
 }
 
+int unina_debug_folded_heads(unina_engine_t* e) {
+  if (!e) return -UNINA_ERR_ARG;
+  if (e->plan_dirty && plan(e) != UNINA_OK) return -UNINA_ERR_STATE;
+  PostParams pp;   // exactly what unina_infer_async hands to the frame's post-process
+  fill_post_params(e, &pp, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
+  int mask = 0;
+  for (int h = 0; h < 3; ++h)
+    if (pp.mode == 2 && pp.h1[h] != nullptr) mask |= 1 << h;
+  return mask;
+}
+
 int unina_debug_read_buffer(unina_engine_t* e, const char* name, float* host_out, size_t capacity, int* c, int* h, int* w) {
   if (!e || !name) return UNINA_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));

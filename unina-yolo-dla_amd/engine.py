@@ -81,7 +81,7 @@ ABI_SYMBOLS = [
     "unina_load_engine", "unina_unload_engine", "unina_engine_input_dims", "unina_set_tensor_address",
     "unina_tensor_address", "unina_enqueue", "unina_infer", "unina_infer_bgra", "unina_infer_nv12", "unina_infer_async", "unina_postprocess_async",
     "unina_last_error", "unina_op_count", "unina_get_op_info", "unina_profile_ops", "unina_profile_post", "unina_debug_read_buffer",
-    "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_serial_latency",
+    "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_debug_folded_heads", "unina_serial_latency",
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
     "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
     "unina_infer_tiled_nv12", "unina_infer_tiled_nv12_async", "unina_preprocess_nv12_resize",
@@ -142,6 +142,7 @@ def load_library() -> C.CDLL:
     L.unina_debug_dual_stamps.argtypes = [vp, ci, C.POINTER(C.c_longlong), vp]
     L.unina_debug_dual_timeline.argtypes = [vp, ci, C.POINTER(C.c_longlong), ci, vp]
     L.unina_debug_block_stamps.argtypes = [vp, ci, C.POINTER(C.c_longlong), vp]
+    L.unina_debug_folded_heads.argtypes = [vp]
     L.unina_serial_latency.argtypes = [vp, C.POINTER(vp), ci, ci, cf, cf, cf, C.POINTER(C.c_double), vp]
     # sliced inference (csrc/postprocess.hip: tile_gather_kernel)
     L.unina_slice_tiles.argtypes = [ci, ci, ci, ci, cf, cf, C.POINTER(Tile), ci]
@@ -677,6 +678,13 @@ class Engine:
         if n <= 0:
             raise RuntimeError(f"unina_debug_dual_timeline: error {-n}")
         return np.array(buf[:2 * n + 2], dtype=np.int64).reshape(n + 1, 2)
+
+    def folded_heads(self) -> List[bool]:
+        """Per head (P2, P3, P4): does the decode launch of infer() compute its output convs itself (unina_debug_folded_heads)?"""
+        m = self.L.unina_debug_folded_heads(self.h)
+        if m < 0:
+            raise EngineError(f"[{ERRORS.get(-m, -m)}] unina_debug_folded_heads")
+        return [bool(m >> h & 1) for h in range(3)]
 
     def conv_configs(self) -> List[str]:
         return [self.L.unina_conv_config_name(i).decode() for i in range(self.L.unina_conv_config_count())]
