@@ -268,6 +268,68 @@ int unina_infer_tiled_nv12_async(unina_engine_t *e, const uint8_t *d_y, const ui
 int unina_merge_tiles_async(unina_engine_t *e, const GpuDetection *d_slots, const int *d_counts, const unina_tile *tiles,
                             int n_tiles, float merge_iou, GpuDetection *d_out, int *d_out_count, hipStream_t stream);
 
+/* ------------------------------------------------------------------ frame descriptor: every camera format through one call
+ * The transport message declares four formats (GpuBufferPtr.msg:24-27: 0 BGRA, 1 NV12, 2 RGB, 3 RGBA) and the node copies the
+ * code into GpuBufferHandle::format (perception_node.cpp:362, 558) -- then calls preprocess_bgra_resize whatever it says
+ * (:601-604). Here the code travels with the frame: one descriptor, one family of calls, and the formats cameras deliver where no
+ * converter sits in front of the node (packed 4:2:2 from GMSL / USB cameras, raw 8-bit Bayer from machine-vision cameras).
+ * Formats 0 and 1 through these calls ARE unina_infer_bgra / unina_infer_nv12 and their relatives: the same kernel paths, the
+ * same bytes. All arithmetic below is fp32, each operation rounded once, never contracted; tap values stay floats, they are never
+ * rounded to u8. Frame pixel (X, Y) is pixel (xs, ys) of a region (the whole frame, or a tile) whose origin is (x0, y0).
+ *   RGB / RGBA   r, g, b = bytes 0, 1, 2 of the 3- / 4-byte pixel at plane[0] + Y * pitch + 3 X (4 X), converted to float;
+ *                everything else as BGRA. A tile is a pointer offset (3 * x for RGB, hence nothing is asked of its alignment).
+ *   YUYV / UYVY  pair = plane[0] + Y * pitch + 4 * (X / 2)
+ *                YUYV: Yv = pair[2 * (X & 1)],     U = pair[1] - 128.0f, V = pair[3] - 128.0f
+ *                UYVY: Yv = pair[1 + 2 * (X & 1)], U = pair[0] - 128.0f, V = pair[2] - 128.0f
+ *                then the BT.601 conversion and clamp of unina_infer_nv12 above, unchanged (cuda_preprocess.cu:229-241). The
+ *                origin enters the pair index and may be odd: as for NV12 a tile is not a pointer offset.
+ *   Bayer        8-bit mosaic, BILINEAR demosaic. THIS PROJECT'S definition, as the letterbox is: parity with cv2.cvtColor's
+ *                demosaic is unpinned (cv2 rounds to u8, here the interpolated values stay floats). The pattern names the colours
+ *                of (X & 1, Y & 1) = (0,0), (1,0), (0,1), (1,1): RGGB is R G / G B. raw(X, Y) reads the FRAME with reflect-101 at
+ *                the frame's borders (-1 -> 1, W -> W - 2), which keeps the colour phase; a tile reads its neighbours from the
+ *                frame, not from a crop, so its pixels are the full-frame demosaic's pixels. At a site its own colour is raw(X, Y).
+ *                R or B site: G = (raw(X,Y-1) + raw(X-1,Y) + raw(X+1,Y) + raw(X,Y+1)) * 0.25f
+ *                             opposite colour = (raw(X-1,Y-1) + raw(X+1,Y-1) + raw(X-1,Y+1) + raw(X+1,Y+1)) * 0.25f
+ *                G site:      the colour on its row = (raw(X-1,Y) + raw(X+1,Y)) * 0.5f
+ *                             the colour on its column = (raw(X,Y-1) + raw(X,Y+1)) * 0.5f
+ *                Every sum is an integer of at most 1020 and every factor a power of two: the values are exact.
+ *   geometry     a region of the destination's size: the tap above, then ((v / 255.0f) - mean) / std. Any other size: the
+ *                coordinates, clamps, weights and left-to-right blend of preprocess_bgra_resize on four float taps, as the NV12
+ *                resize. Letterbox: exactly as for BGRA / NV12 (unina_letterbox_geometry above).
+ * Frame geometry, UNINA_ERR_ARG otherwise (pitch = pitch[0]; sizes positive; plane[0] not NULL):
+ *   BGRA / RGBA  pitch >= 4 * width, pitch and plane[0] multiples of 4        NV12   as unina_infer_nv12 (plane[1], pitch[1]: chroma)
+ *   RGB          pitch >= 3 * width                                           Bayer  pitch >= width, width >= 2, height >= 2,
+ *                                                                                    pitch * height < 4 GiB
+ *   YUYV / UYVY  pitch >= 4 * ((width + 1) / 2) (the last pair of an odd-width row is read whole)
+ * Nothing else is asked of the alignment (aligned 4:2:2 and Bayer frames are read with wider loads). A format code outside 0..9
+ * is UNINA_ERR_ARG. */
+typedef enum { UNINA_FMT_BGRA = 0, UNINA_FMT_NV12 = 1, UNINA_FMT_RGB = 2, UNINA_FMT_RGBA = 3,   /* GpuBufferPtr.msg:24-27 */
+               UNINA_FMT_YUYV = 4, UNINA_FMT_UYVY = 5,
+               UNINA_FMT_BAYER_RGGB = 6, UNINA_FMT_BAYER_BGGR = 7, UNINA_FMT_BAYER_GRBG = 8, UNINA_FMT_BAYER_GBRG = 9 } unina_pixel_format;
+typedef struct { int format, width, height; const uint8_t *plane[2]; int pitch[2]; } unina_frame;   /* plane[1] / pitch[1]: NV12 chroma, else NULL / 0 */
+
+/* unina_infer_bgra / unina_infer_nv12 for any format: semantics, delivery and the rest of the argument checks are theirs. A
+ * refused call enqueues nothing and leaves the handle intact. Identical results to unina_preprocess_frame + unina_infer. */
+int unina_infer_frame(unina_engine_t *e, const unina_frame *frame, const NormParams *norm, float conf_threshold,
+                      float iou_threshold, float conformal_q, GpuDetection *out, int *out_count, hipStream_t stream);
+int unina_infer_frame_async(unina_engine_t *e, const unina_frame *frame, const NormParams *norm, float conf_threshold,
+                            float iou_threshold, float conformal_q, GpuDetection *d_out, int *d_out_count, hipStream_t stream);
+/* unina_infer_letterbox_bgra / _nv12 [_async] for any format (pad_value, map_boxes as there). */
+int unina_infer_letterbox_frame(unina_engine_t *e, const unina_frame *frame, const NormParams *norm, float conf_threshold,
+                                float iou_threshold, float conformal_q, float pad_value, int map_boxes, GpuDetection *out,
+                                int *out_count, hipStream_t stream);
+int unina_infer_letterbox_frame_async(unina_engine_t *e, const unina_frame *frame, const NormParams *norm, float conf_threshold,
+                                      float iou_threshold, float conformal_q, float pad_value, int map_boxes,
+                                      GpuDetection *d_out, int *d_out_count, hipStream_t stream);
+/* unina_infer_tiled_bgra / _nv12 [_async] for any format: the same tiles, slots and merge. BGRA, RGB and RGBA tiles are pointer
+ * offsets; for the other formats the tile's origin travels to the kernel (and may be odd). */
+int unina_infer_tiled_frame(unina_engine_t *e, const unina_frame *frame, const unina_tile *tiles, int n_tiles,
+                            const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
+                            float merge_iou, GpuDetection *out, int *out_count, hipStream_t stream);
+int unina_infer_tiled_frame_async(unina_engine_t *e, const unina_frame *frame, const unina_tile *tiles, int n_tiles,
+                                  const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,
+                                  float merge_iou, GpuDetection *d_out, int *d_out_count, hipStream_t stream);
+
 /* ------------------------------------------------------------------ data mining (active_learning.py, mine_data.py)
  * The reference's third consumer of the forward graph: the active-learning loop pushes an unlabeled image set through the
  * detector and keeps, per image, a difficulty score and an embedding, then picks a diverse subset. These calls run BEHIND the
@@ -601,6 +663,14 @@ hipError_t unina_preprocess_letterbox_bgra(const uint8_t *d_input, float *d_outp
 hipError_t unina_preprocess_letterbox_nv12(const uint8_t *d_y_plane, const uint8_t *d_uv_plane, float *d_output, int src_width,
                                            int src_height, int y_pitch, int uv_pitch, int dst_width, int dst_height,
                                            float pad_value, NormParams params, hipStream_t stream);
+/* The pre-process of a unina_frame as a step of its own (the definitions at unina_pixel_format above): `region` (NULL: the whole
+ * frame) of the frame -> the dst_w x dst_h tensor, tapped where the region has that size, resized otherwise; and the letterbox of
+ * the whole frame. Formats 0 and 1 run the kernels of the calls above. 0, or UNINA_ERR_ARG (what the frame checks refuse, a NULL
+ * pointer, a non-positive size, a region that is empty or not inside the frame), or UNINA_ERR_HIP. */
+int unina_preprocess_frame(const unina_frame *frame, const unina_tile *region, float *d_output, int dst_width, int dst_height,
+                           const NormParams *params, hipStream_t stream);
+int unina_preprocess_letterbox_frame(const unina_frame *frame, float *d_output, int dst_width, int dst_height, float pad_value,
+                                     const NormParams *params, hipStream_t stream);
 float *allocate_preprocess_buffer(int width, int height);
 void free_preprocess_buffer(float *d_buffer);
 hipStream_t create_preprocess_stream(void);

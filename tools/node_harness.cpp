@@ -4,7 +4,7 @@
 // It includes ONLY the public header (plus the HIP runtime API for the buffers the node owns, :473-483, 696-707), so
 // that the Mi355Engine shim and the three call sequences of INTEGRATION.md are compiled and run, not just documented.
 //
-//   node_harness <engine.une> <frame.bgra> <src_w> <src_h> <pitch> <mode A|B|C|N> <out.bin> [conf iou q]
+//   node_harness <engine.une> <frame.bgra> <src_w> <src_h> <pitch> <mode A|B|C|N|F<code>> <out.bin> [conf iou q]
 //
 //   mode A: preprocess_bgra_resize -> bind seven tensors -> enqueueV3 -> reset_detection_counter, 3 x decode_yolo_head,
 //           get_detection_count, run_gpu_nms, copy_valid_detections_to_host   (the node's own sequence, :601-656)
@@ -12,6 +12,10 @@
 //   mode C: unina_infer_bgra                                                   (camera frame in, detections out)
 //   mode N: unina_infer_nv12                                                   (the same for an NV12 buffer, format 1 of
 //           GpuBufferHandle: the file holds <src_h> luma rows, then (<src_h> + 1) / 2 chroma rows, all of <pitch> bytes)
+//   mode F<code>: unina_infer_frame on a unina_frame built from the handle, <code> the message's `format` (GpuBufferPtr.msg:24-27:
+//           0 BGRA, 1 NV12, 2 RGB, 3 RGBA) or one of this engine's own (4 YUYV, 5 UYVY, 6..9 Bayer RGGB / BGGR / GRBG / GBRG): the
+//           dispatch on GpuBufferHandle::format that the reference node lacks (it copies the code, :362, 558, and then calls
+//           preprocess_bgra_resize whatever it says, :601-604). The file holds <src_h> rows of <pitch> bytes (NV12: as mode N).
 //
 // <out.bin>: int32 count, then count 32-byte GpuDetection records -- what the node would publish (:659-678).
 // Built by __graft_entry__.build() with hipcc, linked with -lunina_mi355; tests/test_gpu_node_harness.py runs it as a
@@ -68,6 +72,7 @@ class Mi355Engine {
 struct GpuBufferHandle {  // perception_node.cpp:357-368 (the camera buffer the SDK hands over)
   void *device_ptr;
   int width, height, pitch;
+  int format;             // GpuBufferPtr.msg:24-27 (0 BGRA, 1 NV12, 2 RGB, 3 RGBA), or a unina_pixel_format beyond them
 };
 
 class Node {
@@ -177,6 +182,22 @@ class Node {
     return n;
   }
 
+  // INTEGRATION.md Option C for a buffer of ANY format: the handle's format code travels with the frame
+  int processGpuBuffer_F(const GpuBufferHandle &buffer) {
+    const uint8_t *p = static_cast<const uint8_t *>(buffer.device_ptr);
+    const bool nv12 = buffer.format == UNINA_FMT_NV12;
+    const unina_frame frame = {buffer.format, buffer.width, buffer.height, {p, nv12 ? p + size_t(buffer.pitch) * buffer.height : nullptr},
+                               {buffer.pitch, nv12 ? buffer.pitch : 0}};
+    int n = 0;
+    int rc = unina_infer_frame(engine_.handle(), &frame, &norm_params_, confidence_threshold_, iou_threshold_, conformal_q_,
+                               h_detections_.data(), &n, stream_);
+    if (rc != UNINA_OK) {
+      std::fprintf(stderr, "unina_infer_frame: %s\n", unina_last_error(engine_.handle()));
+      return -1;
+    }
+    return n;
+  }
+
   void cleanup() {                                                                                   // :709-751
     if (stream_) hipStreamSynchronize(stream_);
     cleanup_postprocess_resources();
@@ -208,7 +229,7 @@ class Node {
 
 int main(int argc, char **argv) {
   if (argc < 8) {
-    std::fprintf(stderr, "usage: %s engine.une frame.bgra src_w src_h pitch A|B|C|N out.bin [conf iou q]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s engine.une frame.bgra src_w src_h pitch A|B|C|N|F<format> out.bin [conf iou q]\n", argv[0]);
     return 2;
   }
   const char *engine_path = argv[1], *frame_path = argv[2], *out_path = argv[7];
@@ -216,8 +237,13 @@ int main(int argc, char **argv) {
   const char mode = argv[6][0];
   const float conf = argc > 8 ? std::atof(argv[8]) : 0.5f, iou = argc > 9 ? std::atof(argv[9]) : 0.45f,
               q = argc > 10 ? std::atof(argv[10]) : 0.1f;
-  const bool nv12 = mode == 'N';
-  if (src_w <= 0 || src_h <= 0 || pitch < (nv12 ? src_w : 4 * src_w)) {
+  const int format = mode == 'F' ? std::atoi(argv[6] + 1) : mode == 'N' ? 1 : 0;
+  const bool nv12 = mode == 'N' || (mode == 'F' && format == UNINA_FMT_NV12);
+  if (mode == 'F' && (argv[6][1] < '0' || argv[6][1] > '9')) {
+    std::fprintf(stderr, "mode F needs a format code, e.g. F4\n");
+    return 2;
+  }
+  if (src_w <= 0 || src_h <= 0 || pitch < (mode == 'F' ? 1 : nv12 ? src_w : 4 * src_w)) {   // (mode F: the engine checks the pitch)
     std::fprintf(stderr, "bad frame geometry\n");
     return 2;
   }
@@ -231,13 +257,17 @@ int main(int argc, char **argv) {
 
   Node node;
   if (!node.configure(engine_path, conf, iou, q)) return 1;
-  GpuBufferHandle buf{nullptr, src_w, src_h, pitch};
+  GpuBufferHandle buf{nullptr, src_w, src_h, pitch, format};
   HIP_CHECK(hipMalloc(&buf.device_ptr, frame.size()));
   HIP_CHECK(hipMemcpy(buf.device_ptr, frame.data(), frame.size(), hipMemcpyHostToDevice));
 
   int n = -1;
   for (int rep = 0; rep < 2; ++rep) {  // twice: the second frame runs on warm state, like every frame after the first
-    n = mode == 'A' ? node.processGpuBuffer_A(buf) : mode == 'B' ? node.processGpuBuffer_B(buf) : nv12 ? node.processGpuBuffer_N(buf) : node.processGpuBuffer_C(buf);
+    n = mode == 'A'   ? node.processGpuBuffer_A(buf)
+        : mode == 'B' ? node.processGpuBuffer_B(buf)
+        : mode == 'F' ? node.processGpuBuffer_F(buf)
+        : nv12        ? node.processGpuBuffer_N(buf)
+                      : node.processGpuBuffer_C(buf);
     if (n < 0) {
       std::fprintf(stderr, "frame dropped (mode %c)\n", mode);
       return 1;
@@ -249,7 +279,7 @@ int main(int argc, char **argv) {
   std::fwrite(&count, sizeof(count), 1, o);
   std::fwrite(node.detections().data(), sizeof(GpuDetection), size_t(n), o);
   std::fclose(o);
-  std::printf("mode %c: %dx%d -> %dx%d, %d detections\n", mode, src_w, src_h, node.width(), node.height(), n);
+  std::printf("mode %s: %dx%d -> %dx%d, %d detections\n", argv[6], src_w, src_h, node.width(), node.height(), n);
   HIP_CHECK(hipFree(buf.device_ptr));
   node.cleanup();
   return 0;

@@ -1904,26 +1904,16 @@ int unina_serial_latency(unina_engine_t* e, const float* const* d_frames, int n_
   return UNINA_OK;
 }
 
-// A camera region as an entry point describes it (GpuBufferHandle::format, perception_node.cpp:357-368): a CameraSource
-// (camera_source.h) whose kind, destination and inner rectangle point_stems_at_camera fills in per stem. BGRA: uv == nullptr.
-static CameraSource camera_region(const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, const NormParams& norm) {
-  CameraSource c = {};
-  c.plane = plane;
-  c.uv = uv;
-  c.w = w;
-  c.h = h;
-  c.pitch = pitch;
-  c.uv_pitch = uv_pitch;
-  c.norm = norm;
-  return c;
+// A camera region as a format-named entry point describes it (GpuBufferHandle::format, perception_node.cpp:357-368): a CameraSource
+// (camera_source.h) whose kind, destination and inner rectangle point_stems_at_camera fills in per stem. The caller names its format.
+static CameraSource camera_region(int format, const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, const NormParams& norm) {
+  const unina_frame f = {format, w, h, {plane, uv}, {pitch, uv_pitch}};
+  return frame_source(f, norm);
 }
 
-// The kind of source a region of w x h is for a network input of net_w x net_h, stretched (lb == nullptr) or letterboxed into *lb.
-// An inner rectangle that is the whole network input is the plain resize (or tap): the unboxed kinds and their fast paths.
-static int camera_kind(bool nv12, int w, int h, int net_w, int net_h, const unina_letterbox* lb) {
-  if (lb && !(lb->new_w == net_w && lb->new_h == net_h)) return nv12 ? kSrcNv12Letterbox : kSrcBgraLetterbox;
-  const bool tap = w == net_w && h == net_h;
-  return nv12 ? (tap ? kSrcNv12Tap : kSrcNv12Resize) : (tap ? kSrcBgraTap : kSrcBgraResize);
+// The kind of source a region is for a network input of net_w x net_h: frame_kind (camera_source.h), by the region's FORMAT.
+static int camera_kind(const CameraSource& c, int net_w, int net_h, const unina_letterbox* lb) {
+  return frame_kind(c.format, c.w, c.h, net_w, net_h, lb);
 }
 
 // Points every eager stem op at a camera region / back at the fp32 tensor. Returns the number of stem ops.
@@ -1935,8 +1925,8 @@ static int point_stems_at_camera(unina_engine* e, const CameraSource& region, co
     CameraSource c = region;
     c.dst_w = op.sp.W;
     c.dst_h = op.sp.H;
-    c.kind = camera_kind(c.uv != nullptr, c.w, c.h, c.dst_w, c.dst_h, lb);
-    if (c.kind == kSrcBgraLetterbox || c.kind == kSrcNv12Letterbox) {
+    c.kind = camera_kind(c, c.dst_w, c.dst_h, lb);
+    if (c.kind == kSrcBgraLetterbox || c.kind == kSrcNv12Letterbox || c.kind == kSrcFrameLetterbox) {
       c.in_x0 = lb->left;
       c.in_y0 = lb->top;
       c.in_w = lb->new_w;
@@ -2008,7 +1998,7 @@ int unina_infer_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, in
   int rc = check_bgra_frame(e, "unina_infer_bgra", d_bgra, src_width, src_height, src_pitch);
   if (rc == UNINA_OK) rc = make_ready(e);
   if (rc != UNINA_OK) return rc;
-  return infer_camera(e, camera_region(d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), nullptr, 0.f, 0, false, conf, iou, q,
+  return infer_camera(e, camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), nullptr, 0.f, 0, false, conf, iou, q,
                       out, out_count, stream);
 }
 
@@ -2023,7 +2013,7 @@ int unina_infer_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv,
   int rc = check_nv12_frame(e, "unina_infer_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
   if (rc == UNINA_OK) rc = make_ready(e);
   if (rc != UNINA_OK) return rc;
-  return infer_camera(e, camera_region(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), nullptr, 0.f, 0, false, conf, iou, q,
+  return infer_camera(e, camera_region(UNINA_FMT_NV12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), nullptr, 0.f, 0, false, conf, iou, q,
                       out, out_count, stream);
 }
 
@@ -2048,7 +2038,7 @@ static int letterbox_bgra(unina_engine* e, const char* who, const uint8_t* d_bgr
   if (!d_bgra || !norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null frame / norm / result pointer", who);
   const int rc = check_bgra_frame(e, who, d_bgra, w, h, pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, camera_region(d_bgra, nullptr, w, h, pitch, 0, *norm), conf, iou, q, pad_value, map_boxes, async, out,
+  return infer_letterbox(e, who, camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, w, h, pitch, 0, *norm), conf, iou, q, pad_value, map_boxes, async, out,
                          out_count, stream);
 }
 
@@ -2059,7 +2049,7 @@ static int letterbox_nv12(unina_engine* e, const char* who, const uint8_t* d_y, 
   if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
   const int rc = check_nv12_frame(e, who, d_y, d_uv, w, h, y_pitch, uv_pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, camera_region(d_y, d_uv, w, h, y_pitch, uv_pitch, *norm), conf, iou, q, pad_value, map_boxes, async, out,
+  return infer_letterbox(e, who, camera_region(UNINA_FMT_NV12, d_y, d_uv, w, h, y_pitch, uv_pitch, *norm), conf, iou, q, pad_value, map_boxes, async, out,
                          out_count, stream);
 }
 
@@ -2213,15 +2203,8 @@ static int infer_tiled_camera(unina_engine* e, const char* who, const CameraSour
   e->camera_active = true;
   for (int t = 0; t < n_tiles && rc == UNINA_OK; ++t) {
     const unina_tile& r = tiles[t];
-    CameraSource c = frame;
-    c.w = r.w;
-    c.h = r.h;
-    if (!frame.uv) {
-      c.plane = frame.plane + (size_t)r.y * frame.pitch + (size_t)r.x * 4;   // a BGRA tile is a pointer offset
-    } else {
-      c.x0 = r.x;                                                            // an NV12 tile is not: the origin enters the chroma index
-      c.y0 = r.y;
-    }
+    // (a BGRA / RGB / RGBA tile is a pointer offset; an NV12, 4:2:2 or Bayer tile is not: its origin travels to the kernel)
+    const CameraSource c = frame_region(frame, r.x, r.y, r.w, r.h);
     if (!point_stems_at_camera(e, c))
       rc = fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
     else
@@ -2241,7 +2224,7 @@ int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int s
   if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
   const int rc = check_bgra_frame(e, "unina_infer_tiled_bgra", d_bgra, src_width, src_height, src_pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, "unina_infer_tiled_bgra", camera_region(d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), tiles, n_tiles,
+  return infer_tiled_camera(e, "unina_infer_tiled_bgra", camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), tiles, n_tiles,
                             conf, iou, q, merge_iou, d_out, d_out_count, stream);
 }
 
@@ -2264,7 +2247,7 @@ int unina_infer_tiled_nv12_async(unina_engine_t* e, const uint8_t* d_y, const ui
   if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null / misaligned pointer");
   const int rc = check_nv12_frame(e, "unina_infer_tiled_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
   if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, "unina_infer_tiled_nv12", camera_region(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), tiles, n_tiles,
+  return infer_tiled_camera(e, "unina_infer_tiled_nv12", camera_region(UNINA_FMT_NV12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), tiles, n_tiles,
                             conf, iou, q, merge_iou, d_out, d_out_count, stream);
 }
 
@@ -2275,6 +2258,79 @@ int unina_infer_tiled_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t*
   if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null result pointer");
   return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
     return unina_infer_tiled_nv12_async(e, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
+  }, out, out_count, stream);
+}
+
+// ---- the frame descriptor: every format through one family of calls (include/unina_mi355.h at unina_pixel_format) ----
+static int check_frame(unina_engine* e, const char* who, const unina_frame* f) {
+  const char* why = frame_defect(f);
+  if (!why) return UNINA_OK;
+  if (f) return fail(e, UNINA_ERR_ARG, "%s: %s (format %d, %d x %d, pitch %d / %d)", who, why, f->format, f->width, f->height, f->pitch[0], f->pitch[1]);
+  return fail(e, UNINA_ERR_ARG, "%s: %s", who, why);
+}
+
+static int infer_frame(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, bool async, float conf, float iou,
+                       float q, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
+  if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
+  int rc = check_frame(e, who, f);
+  if (rc == UNINA_OK) rc = make_ready(e);
+  if (rc != UNINA_OK) return rc;
+  return infer_camera(e, frame_source(*f, *norm), nullptr, 0.f, 0, async, conf, iou, q, out, out_count, stream);
+}
+
+int unina_infer_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                      GpuDetection* out, int* out_count, hipStream_t stream) {
+  return infer_frame(e, "unina_infer_frame", frame, norm, false, conf, iou, q, out, out_count, stream);
+}
+
+int unina_infer_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                            GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return infer_frame(e, "unina_infer_frame_async", frame, norm, true, conf, iou, q, d_out, d_out_count, stream);
+}
+
+static int letterbox_frame(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, float conf, float iou, float q,
+                           float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
+  const int rc = check_frame(e, who, f);
+  if (rc != UNINA_OK) return rc;
+  return infer_letterbox(e, who, frame_source(*f, *norm), conf, iou, q, pad_value, map_boxes, async, out, out_count, stream);
+}
+
+int unina_infer_letterbox_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                                float pad_value, int map_boxes, GpuDetection* out, int* out_count, hipStream_t stream) {
+  return letterbox_frame(e, "unina_infer_letterbox_frame", frame, norm, conf, iou, q, pad_value, map_boxes, false, out, out_count, stream);
+}
+
+int unina_infer_letterbox_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                                      float pad_value, int map_boxes, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return letterbox_frame(e, "unina_infer_letterbox_frame_async", frame, norm, conf, iou, q, pad_value, map_boxes, true, d_out, d_out_count,
+                         stream);
+}
+
+static int tiled_frame(unina_engine* e, const char* who, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
+                       float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "%s: null / misaligned pointer", who);
+  const int rc = check_frame(e, who, frame);
+  if (rc != UNINA_OK) return rc;
+  return infer_tiled_camera(e, who, frame_source(*frame, *norm), tiles, n_tiles, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+}
+
+int unina_infer_tiled_frame_async(unina_engine_t* e, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
+                                  float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count,
+                                  hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  return tiled_frame(e, "unina_infer_tiled_frame_async", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+}
+
+int unina_infer_tiled_frame(unina_engine_t* e, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
+                            float conf, float iou, float q, float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_frame: null result pointer");
+  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
+    return tiled_frame(e, "unina_infer_tiled_frame", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
   }, out, out_count, stream);
 }
 

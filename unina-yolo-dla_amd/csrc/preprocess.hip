@@ -1,6 +1,7 @@
 // preprocess.hip -- camera-buffer pre-processing on the GPU (gfx950): the step right before the engine in the
 // reference's processGpuBuffer (perception_node.cpp:601-604), behind the reference's C API names. The ARITHMETIC per
-// pixel is defined once, in camera_source.h (plain BGRA, BGRA resize, NV12, NV12 resize, the letterbox of both formats); the
+// pixel is defined once, in camera_source.h (plain BGRA, BGRA resize, NV12, NV12 resize, RGB / RGBA / 4:2:2 / Bayer, the letterbox of
+// every format); the
 // stem kernels call the same functions, so unina_infer_bgra / _nv12 / _letterbox_*'s in-stem form equals the two-step form, and
 // both are compared bit for bit with oracle/preprocess_oracle.c and the numpy twins (camera.py).
 // The DATA MOVEMENT is not the reference's one-thread-per-pixel form: all three are HBM-bound byte movers (4 B/px in,
@@ -22,8 +23,8 @@ namespace {
 
 using namespace unina;
 
-// MODE of the kernel template: the CameraKind of the source (never kSrcTensor). kSrcBgraTap and kSrcNv12Tap have quad loads of
-// their own; the other four go through camera_pixel with the constant kind.
+// MODE of the kernel template: the CameraKind of the source (never kSrcTensor). kSrcBgraTap, kSrcNv12Tap and (for packed 4:2:2
+// and Bayer frames) kSrcFrameTap have quad loads of their own; the others go through camera_pixel with the constant kind.
 struct PreParams {
   CameraSource cam;       // the frame; cam.dst_w x cam.dst_h is the output size
   float* out;             // [3][dst_h][dst_w]
@@ -52,6 +53,8 @@ __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams p
     bool wide_y, wide_c;
     nv12_quad_alignment(q, wide_y, wide_c);
     wide_in = wide_y && wide_c;
+  } else if constexpr (MODE == kSrcFrameTap) {
+    wide_in = cam_is_yuv422(q.format) ? yuv422_quad_alignment(q) : (cam_is_bayer(q.format) && bayer_quad_alignment(q));
   }
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nquads; t += (long long)gridDim.x * blockDim.x) {
     const int y = (int)(t / qpr), x = (int)(t - (long long)y * qpr) * 4;
@@ -71,7 +74,20 @@ __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams p
 #pragma unroll
       for (int i = 0; i < 4; ++i) cam_normalise(q.norm, (float)px[i].r, (float)px[i].g, (float)px[i].b, o[i]);
     } else if constexpr (MODE == kSrcNv12Tap) {
-      nv12_quad(q, x, y, n, true, wide_in && n == 4, wide_in && n == 4, o);
+      // (the region's origin: 0 for the whole frame, where x is even by construction; a region of unina_preprocess_frame may start
+      // at an odd column, and then the chroma pairs straddle the quad)
+      nv12_quad(q, q.x0 + x, q.y0 + y, n, (q.x0 & 1) == 0, wide_in && n == 4, wide_in && n == 4, o);
+    } else if constexpr (MODE == kSrcFrameTap) {
+      // (the format is uniform over the grid; RGB / RGBA stay per pixel)
+      if (cam_is_yuv422(q.format)) {
+        yuv422_quad(q, q.format, q.x0 + x, q.y0 + y, n, wide_in && n == 4, o);
+      } else if (cam_is_bayer(q.format)) {
+        bayer_quad(q, q.format, q.x0 + x, q.y0 + y, n, wide_in && n == 4, o);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (i < n) camera_pixel(q, MODE, x + i, y, o[i]);
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -186,6 +202,52 @@ hipError_t unina_preprocess_letterbox_nv12(const uint8_t* d_y_plane, const uint8
     return hipErrorInvalidValue;
   return launch_quads<kSrcNv12Letterbox>(pre_params(kSrcNv12Letterbox, d_y_plane, d_uv_plane, src_width, src_height, y_pitch, uv_pitch, d_output,
                                                     dst_width, dst_height, params, lb, pad_value), stream);
+}
+
+// ---- a unina_frame of any format (include/unina_mi355.h at unina_pixel_format) ----
+static int launch_frame(const CameraSource& region, float* d_output, int dst_width, int dst_height, const unina_letterbox* lb, float pad_value,
+                        hipStream_t stream) {
+  PreParams q{region, d_output};
+  q.cam.dst_w = dst_width;
+  q.cam.dst_h = dst_height;
+  q.cam.kind = frame_kind(region.format, region.w, region.h, dst_width, dst_height, lb);
+  if (lb) {
+    q.cam.in_x0 = lb->left;
+    q.cam.in_y0 = lb->top;
+    q.cam.in_w = lb->new_w;
+    q.cam.in_h = lb->new_h;
+    q.cam.pad = pad_value;
+  }
+  hipError_t err = hipErrorInvalidValue;
+  switch (q.cam.kind) {
+    case kSrcBgraTap: err = launch_quads<kSrcBgraTap>(q, stream); break;
+    case kSrcBgraResize: err = launch_quads<kSrcBgraResize>(q, stream); break;
+    case kSrcNv12Tap: err = launch_quads<kSrcNv12Tap>(q, stream); break;
+    case kSrcNv12Resize: err = launch_quads<kSrcNv12Resize>(q, stream); break;
+    case kSrcBgraLetterbox: err = launch_quads<kSrcBgraLetterbox>(q, stream); break;
+    case kSrcNv12Letterbox: err = launch_quads<kSrcNv12Letterbox>(q, stream); break;
+    case kSrcFrameTap: err = launch_quads<kSrcFrameTap>(q, stream); break;
+    case kSrcFrameResize: err = launch_quads<kSrcFrameResize>(q, stream); break;
+    case kSrcFrameLetterbox: err = launch_quads<kSrcFrameLetterbox>(q, stream); break;
+  }
+  return err == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+}
+
+int unina_preprocess_frame(const unina_frame* frame, const unina_tile* region, float* d_output, int dst_width, int dst_height,
+                           const NormParams* params, hipStream_t stream) {
+  if (frame_defect(frame) || !d_output || !params || dst_width <= 0 || dst_height <= 0) return UNINA_ERR_ARG;
+  const unina_tile whole = {0, 0, frame->width, frame->height};
+  const unina_tile& r = region ? *region : whole;
+  if (r.w <= 0 || r.h <= 0 || r.x < 0 || r.y < 0 || (long long)r.x + r.w > frame->width || (long long)r.y + r.h > frame->height) return UNINA_ERR_ARG;
+  return launch_frame(frame_region(frame_source(*frame, *params), r.x, r.y, r.w, r.h), d_output, dst_width, dst_height, nullptr, 0.f, stream);
+}
+
+int unina_preprocess_letterbox_frame(const unina_frame* frame, float* d_output, int dst_width, int dst_height, float pad_value,
+                                     const NormParams* params, hipStream_t stream) {
+  unina_letterbox lb;
+  if (frame_defect(frame) || !d_output || !params || unina_letterbox_geometry(frame->width, frame->height, dst_width, dst_height, &lb) != UNINA_OK)
+    return UNINA_ERR_ARG;
+  return launch_frame(frame_source(*frame, *params), d_output, dst_width, dst_height, &lb, pad_value, stream);
 }
 
 float* allocate_preprocess_buffer(int width, int height) {  // nullptr on failure (cuda_preprocess.cu:395-405)

@@ -53,7 +53,24 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
   const int oy = m / p.Wo, ox = m - oy * p.Wo;
   float x[27];
   const size_t plane = (size_t)p.H * p.W;
-  if (p.cam.kind == kSrcTensor) {
+  if (p.cam.kind >= kSrcFrameTap) {
+    // the formats of a unina_frame beyond BGRA / NV12: ONE copy of frame_pixel (with the rolled resize) in a loop over the nine
+    // taps that is not unrolled, each result selected into its registers, so that this legacy form's other sources keep their
+    // registers and occupancy (this branch FIRST: behind the other two the register allocator gave the NV12 path six more)
+#pragma unroll
+    for (int k = 0; k < 27; ++k) x[k] = 0.f;
+#pragma unroll 1
+    for (int t = 0; t < 9; ++t) {
+      const int kh = t / 3, kw = t - 3 * kh;
+      const int iy = oy * 2 + kh - 1, ix = ox * 2 + kw - 1;
+      float rgb[3] = {0.f, 0.f, 0.f};
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) frame_pixel<true>(p.cam, p.cam.kind, ix, iy, rgb);
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c * 9 + k] = k == t ? rgb[c] : x[c * 9 + k];
+    }
+  } else if (p.cam.kind == kSrcTensor) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -75,7 +92,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
       for (int kw = 0; kw < 3; ++kw) {
         const int ix = ox * 2 + kw - 1;
         float rgb[3] = {0.f, 0.f, 0.f};
-        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p.cam, p.cam.kind, ix, iy, rgb);
+        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel_classic(p.cam, p.cam.kind, ix, iy, rgb);
 #pragma unroll
         for (int c = 0; c < 3; ++c) x[(c * 3 + kh) * 3 + kw] = rgb[c];
       }
@@ -179,13 +196,48 @@ __global__ __launch_bounds__(kStemNT) void stem_tile_kernel(const StemParams p) 
       for (int c = 0; c < 3; ++c)
         *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
     }
+  } else if (p.cam.kind == kSrcFrameTap && cam_is_yuv422(p.cam.format)) {
+    // packed 4:2:2 region of the network's size, four footprint pixels per thread as above: two pairs, each converted once
+    const bool wide = yuv422_quad_alignment(p.cam);
+    for (int v = tid; v < kStemPR * (kStemPW / 4); v += kStemNT) {
+      const int r = v / (kStemPW / 4), q = v - r * (kStemPW / 4);
+      const int iy = iy0 + r, ix = ix0 + 4 * q;
+      float o[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix + 3 < p.W) yuv422_quad(p.cam, p.cam.format, p.cam.x0 + ix, p.cam.y0 + iy, 4, wide, o);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+    }
+  } else if (p.cam.kind == kSrcFrameTap && cam_is_bayer(p.cam.format)) {
+    // Bayer region of the network's size, likewise: three rows of six bytes serve the four 3 x 3 neighbourhoods
+    const bool wide = bayer_quad_alignment(p.cam);
+    for (int v = tid; v < kStemPR * (kStemPW / 4); v += kStemNT) {
+      const int r = v / (kStemPW / 4), q = v - r * (kStemPW / 4);
+      const int iy = iy0 + r, ix = ix0 + 4 * q;
+      float o[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix + 3 < p.W) bayer_quad(p.cam, p.cam.format, p.cam.x0 + ix, p.cam.y0 + iy, 4, wide, o);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<float4*>(patch + (c * kStemPR + r) * kStemPW + 4 * q) = make_float4(o[0][c], o[1][c], o[2][c], o[3][c]);
+    }
+  } else if (p.cam.kind >= kSrcFrameTap) {
+    // the other formats and geometries of a unina_frame, per footprint pixel. (The rolled resize: four Bayer taps at once are 36
+    // byte loads in flight, more registers than the FMA loop below holds -- and this kernel sits right below an occupancy step.)
+    for (int e = tid; e < kStemPR * kStemPW; e += kStemNT) {
+      const int r = e / kStemPW, j = e - r * kStemPW;
+      const int iy = iy0 + r, ix = ix0 + j;
+      float rgb[3] = {0.f, 0.f, 0.f};
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) frame_pixel<true>(p.cam, p.cam.kind, ix, iy, rgb);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) patch[(c * kStemPR + r) * kStemPW + j] = rgb[c];
+    }
   } else {
     // camera frame: every footprint pixel is pre-processed once (camera_source.h)
     for (int e = tid; e < kStemPR * kStemPW; e += kStemNT) {
       const int r = e / kStemPW, j = e - r * kStemPW;
       const int iy = iy0 + r, ix = ix0 + j;
       float rgb[3] = {0.f, 0.f, 0.f};
-      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel(p.cam, p.cam.kind, ix, iy, rgb);
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) camera_pixel_classic(p.cam, p.cam.kind, ix, iy, rgb);
 #pragma unroll
       for (int c = 0; c < 3; ++c) patch[(c * kStemPR + r) * kStemPW + j] = rgb[c];
     }

@@ -47,6 +47,24 @@ class Letterbox(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("new_w", "new_h", "left", "top")]
 
 
+# unina_pixel_format (include/unina_mi355.h): 0..3 are GpuBufferPtr.msg's codes
+FMT_BGRA, FMT_NV12, FMT_RGB, FMT_RGBA, FMT_YUYV, FMT_UYVY, FMT_BAYER_RGGB, FMT_BAYER_BGGR, FMT_BAYER_GRBG, FMT_BAYER_GBRG = range(10)
+
+
+class Frame(C.Structure):
+    """unina_frame: a camera frame of any unina_pixel_format on the device. plane[1] / pitch[1]: the NV12 chroma plane."""
+    _fields_ = [("format", C.c_int), ("width", C.c_int), ("height", C.c_int), ("plane", C.c_void_p * 2), ("pitch", C.c_int * 2)]
+
+    @classmethod
+    def from_tensors(cls, fmt: int, width: int, height: int, plane, pitch: int, uv=None, uv_pitch: int = 0) -> "Frame":
+        """From uint8 CUDA tensors (or raw device addresses). The tensors must outlive the calls the frame is handed to."""
+        addr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        f = cls(int(fmt), int(width), int(height))
+        f.plane[0], f.plane[1] = addr(plane), addr(uv)
+        f.pitch[0], f.pitch[1] = int(pitch), int(uv_pitch)
+        return f
+
+
 EVAL_SMALL, EVAL_CONFORMAL, EVAL_AP = 1, 2, 4   # include/unina_mi355.h UNINA_EVAL_*
 EVAL_MAX_LABELS = 256
 EVAL_MAX_CLASSES = 256
@@ -87,6 +105,8 @@ ABI_SYMBOLS = [
     "unina_infer_tiled_nv12", "unina_infer_tiled_nv12_async", "unina_preprocess_nv12_resize",
     "unina_letterbox_geometry", "unina_infer_letterbox_bgra", "unina_infer_letterbox_nv12", "unina_infer_letterbox_bgra_async",
     "unina_infer_letterbox_nv12_async", "unina_preprocess_letterbox_bgra", "unina_preprocess_letterbox_nv12",
+    "unina_infer_frame", "unina_infer_frame_async", "unina_infer_letterbox_frame", "unina_infer_letterbox_frame_async",
+    "unina_infer_tiled_frame", "unina_infer_tiled_frame_async", "unina_preprocess_frame", "unina_preprocess_letterbox_frame",
     "unina_embedding_dim", "unina_mine_async", "unina_mine", "unina_mine_heads_async", "unina_kcenter",
     "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
@@ -164,6 +184,16 @@ def load_library() -> C.CDLL:
     L.unina_infer_letterbox_nv12_async.argtypes = [vp, vp, vp, ci, ci, ci, ci, C.POINTER(NormParams), cf, cf, cf, cf, ci, vp, vp, vp]
     L.unina_preprocess_letterbox_bgra.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, NormParams, vp]
     L.unina_preprocess_letterbox_nv12.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, NormParams, vp]
+    # the frame descriptor: one family of calls for every unina_pixel_format
+    fp, npp = C.POINTER(Frame), C.POINTER(NormParams)
+    L.unina_infer_frame.argtypes = [vp, fp, npp, cf, cf, cf, vp, C.POINTER(ci), vp]
+    L.unina_infer_frame_async.argtypes = [vp, fp, npp, cf, cf, cf, vp, vp, vp]
+    L.unina_infer_letterbox_frame.argtypes = [vp, fp, npp, cf, cf, cf, cf, ci, vp, C.POINTER(ci), vp]
+    L.unina_infer_letterbox_frame_async.argtypes = [vp, fp, npp, cf, cf, cf, cf, ci, vp, vp, vp]
+    L.unina_infer_tiled_frame.argtypes = [vp, fp, C.POINTER(Tile), ci, npp, cf, cf, cf, cf, vp, C.POINTER(ci), vp]
+    L.unina_infer_tiled_frame_async.argtypes = [vp, fp, C.POINTER(Tile), ci, npp, cf, cf, cf, cf, vp, vp, vp]
+    L.unina_preprocess_frame.argtypes = [fp, C.POINTER(Tile), vp, ci, ci, npp, vp]
+    L.unina_preprocess_letterbox_frame.argtypes = [fp, vp, ci, ci, cf, npp, vp]
     # data mining (csrc/mining.hip)
     L.unina_embedding_dim.argtypes = [vp]
     L.unina_mine_async.argtypes = [vp, vp, vp, vp, vp]
@@ -435,6 +465,60 @@ class Engine:
         self._check(self.L.unina_infer_tiled_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, arr, len(tiles),
                                                   C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou, host.ctypes.data,
                                                   C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
+
+    def infer_frame(self, frame: Frame, norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45,
+                    conformal_q: float = 0.1, out=None, stream=None):
+        """A camera frame of any unina_pixel_format (Frame) -> detections, the pre-process inside the stem kernel
+        (unina_infer_frame; camera.frame_to_tensor is its numpy twin). `out=None`: synchronous, returns the kept detections;
+        `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_frame_async(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, base + 32,
+                                                       base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_frame(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, host.ctypes.data,
+                                             C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
+
+    def infer_letterbox_frame(self, frame: Frame, norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45,
+                              conformal_q: float = 0.1, pad_value: float = 114.0, map_boxes: bool = True, out=None, stream=None):
+        """infer_letterbox_bgra for a Frame of any format."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_letterbox_frame_async(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q,
+                                                                 pad_value, int(map_boxes), base + 32, base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_letterbox_frame(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, pad_value,
+                                                       int(map_boxes), host.ctypes.data, C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
+
+    def infer_tiled_frame(self, frame: Frame, tiles=None, norm: Optional[NormParams] = None, conf_thr: float = 0.5,
+                          iou_thr: float = 0.45, conformal_q: float = 0.1, merge_iou: float = 0.45, out=None, stream=None):
+        """infer_tiled_bgra for a Frame of any format (BGRA / RGB / RGBA tiles are pointer offsets, the other formats send the
+        tile's origin to the stem kernel)."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if tiles is None:
+            tiles = self.default_tiles(frame.width, frame.height)
+        arr = _tile_array(tiles)
+        if out is not None:
+            base = out.data_ptr()
+            self._check(self.L.unina_infer_tiled_frame_async(self.h, C.byref(frame), arr, len(tiles), C.byref(norm), conf_thr, iou_thr,
+                                                             conformal_q, merge_iou, base + 32, base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(self.L.unina_infer_tiled_frame(self.h, C.byref(frame), arr, len(tiles), C.byref(norm), conf_thr, iou_thr,
+                                                   conformal_q, merge_iou, host.ctypes.data, C.byref(n), _stream_ptr(stream)))
         return host[:n.value].copy()
 
     def default_tiles(self, width: int, height: int):
@@ -926,6 +1010,36 @@ class DeviceEval:
             self.close()
         except Exception:
             pass
+
+
+def preprocess_frame(frame: Frame, out, region=None, norm: Optional[NormParams] = None, stream=None):
+    """unina_preprocess_frame: `region` (x, y, w, h; None: the whole frame) of a Frame -> the float32 CUDA tensor `out`
+    [..., 3, H, W], tapped where the region has the output's size, resized otherwise. Asynchronous; returns `out`."""
+    L = load_library()
+    torch = _torch()
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[-3] == 3
+    if norm is None:
+        norm = L.create_norm_params_imagenet()
+    tile = None if region is None else C.byref(Tile(*map(int, region)))
+    rc = L.unina_preprocess_frame(C.byref(frame), tile, out.data_ptr(), int(out.shape[-1]), int(out.shape[-2]), C.byref(norm),
+                                  _stream_ptr(stream))
+    if rc:
+        raise EngineError(f"unina_preprocess_frame failed [{ERRORS.get(rc, rc)}]")
+    return out
+
+
+def preprocess_letterbox_frame(frame: Frame, out, pad_value: float = 114.0, norm: Optional[NormParams] = None, stream=None):
+    """unina_preprocess_letterbox_frame: the whole Frame letterboxed into the float32 CUDA tensor `out` [..., 3, H, W]."""
+    L = load_library()
+    torch = _torch()
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[-3] == 3
+    if norm is None:
+        norm = L.create_norm_params_imagenet()
+    rc = L.unina_preprocess_letterbox_frame(C.byref(frame), out.data_ptr(), int(out.shape[-1]), int(out.shape[-2]), pad_value,
+                                            C.byref(norm), _stream_ptr(stream))
+    if rc:
+        raise EngineError(f"unina_preprocess_letterbox_frame failed [{ERRORS.get(rc, rc)}]")
+    return out
 
 
 def letterbox_geometry(src_w: int, src_h: int, dst_w: int, dst_h: int):
