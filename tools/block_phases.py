@@ -22,8 +22,12 @@ for i, o in enumerate(e.op_infos()):
     except RuntimeError:
         continue
     st = np.median(runs, axis=0)
+    life = runs[:, 11] - runs[:, 0]                                  # entry -> drained of each run, in shader ticks
+    landed = runs[:, 1] - runs[:, 0]
     clk = (st[11] - st[0]) / max((st[14] - st[15]) * 10.0, 1.0)     # shader ticks per ns (s_memtime runs at 100 MHz x ?)
     print(f"op {i}: {o['name']}  [{o['kernel']}]  mid workgroup, median of 7: {(st[14] - st[15]) * 0.01:.2f} us entry -> drained")
+    print(f"   life {np.median(life):.0f} ticks (min {life.min():.0f} .. max {life.max():.0f}); entry -> patch landed {np.median(landed):.0f} "
+          f"(min {landed.min():.0f} .. max {landed.max():.0f})")
     prev = st[0]
     for k in range(1, 12):
         if st[k] == 0:

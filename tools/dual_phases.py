@@ -29,8 +29,10 @@ for i, o in enumerate(ops):
             ghz = (s[4] - s[0]) / max(1, s[6] - s[5]) * 0.1
             r.append([s[1] - s[0], s[2] - s[1], s[3] - s[2], s[4] - s[3], s[4] - s[0], ghz, (s[6] - s[5]) * 0.01])
         rows.append(r)
-    med = np.median(np.array(rows), axis=0)
+    rows = np.array(rows)
+    med = np.median(rows, axis=0)
     for h, tag in enumerate(("A (P3, 16x16 px x 64 ch, K 1152)", "B (P4, 8x16 px x 64 ch, K 2304)")):
         m = med[h]
-        print(f"{i:3d} {o['name'][:26] + ' ' + tag:58s} {o['ms'] * 1e3:7.2f} | {m[0]:6.0f} {m[1]:6.0f} {m[2]:7.0f} {m[3]:6.0f} {m[4]:7.0f} {m[5]:5.2f} {m[6]:6.2f}")
+        print(f"{i:3d} {o['name'][:26] + ' ' + tag:58s} {o['ms'] * 1e3:7.2f} | {m[0]:6.0f} {m[1]:6.0f} {m[2]:7.0f} {m[3]:6.0f} {m[4]:7.0f} {m[5]:5.2f} {m[6]:6.2f}"
+              f"   (issue min {rows[:, h, 0].min():.0f} .. max {rows[:, h, 0].max():.0f}, total min {rows[:, h, 4].min():.0f} .. max {rows[:, h, 4].max():.0f})")
 e.close()

@@ -48,9 +48,16 @@ struct C3k2Plan {
 // compiler's counted s_waitcnt vmcnt keeps D loads in flight across every step boundary.
 // E = EltH (fp16 engines and carve-outs) or EltI8 (INT8 engines: every tensor of the block is an int8 code image with
 // its per-tensor scale; the epilogues re-quantise exactly as the per-op kernels do, conv_igemm.hip conv_epilogue).
+// Prologue (LDS-DMA path): the wave requests its share of the patch, the constants and then the first D weight blocks, and waits
+// with a COUNTED s_waitcnt for the first two groups only (request_schedule.h: N = D loads, 2 x D for the split type, at most 16
+// in any instantiation), so step 0 starts when q[0] lands instead of when q[D - 1] does. The wait has to be one the compiler
+// sees (wait_vmcnt_seen, mfma_common.h): behind an asm wait it drained the queue itself, vmcnt(0), at the constants' commit.
+// Stamps of the mid workgroup, parent -> this form, same box, medians of 7 in two alternating passes (profiles/r04):
+// entry -> barrier 4 920 / 4 870 -> 4 100 / 4 040 ticks (stage-3 block), 6 380 / 6 390 -> 5 540 / 5 420 (down2 + pan_c3k2_2);
+// workgroup life 30 830 / 30 680 -> 29 950 / 29 840 and 27 670 / 27 580 -> 27 030 / 26 960 ticks.
 template <int H_, int TH, int TW, int NB, int CIN, int NW, int D, int TAIL = 0, typename E = EltH, int CPRE = 0, int CX = CIN, bool STAMPS = false>
 __device__ __forceinline__ void c3k2_fused_body(const C3k2Params& p, int bid, unsigned char* smem) {
-  // debug twin: shader-clock stamp k of the mid workgroup (0 entry, 1 patch + first weights landed, then one per step, the
+  // debug twin: shader-clock stamp k of the mid workgroup (0 entry, 1 patch + constants landed and published, then one per step, the
   // output store and the tail), slot 15 = the 100 MHz wall clock at entry, 14 at the end
   auto stamp = [&](int k) {
     if constexpr (STAMPS) {
@@ -131,9 +138,17 @@ __device__ __forceinline__ void c3k2_fused_body(const C3k2Params& p, int bid, un
   } else {
     load_patch<TH + 2 * NB, R0W, CIN, NT, E>(smem + p.off_x, p.src, p.src_ld, p.H, p.W, ty0 - NB, tx0 - NB, p.zeros, wid, lane, p.src_lo, lds_lo);
   }
-  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  // issue order = program order (pinned): patch DMA, constants, then the D weight blocks. The counted wait below retires the
+  // first two groups only (request_schedule.h): the weight queue stays in flight across consts_commit and the barrier, and
+  // step 0's own counted waits pick up q[0]. The split type's 2 x D loads are counted the same way.
+  __builtin_amdgcn_sched_barrier(0);
   consts_issue<NT>(cregs, p.bias, p.n_bias);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed (LDS-DMA is not tracked by the compiler)
+  __builtin_amdgcn_sched_barrier(0);
+  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  __builtin_amdgcn_sched_barrier(0);
+  constexpr int NWAIT = sched::prologue_wait(D, ST::total(), E::WBLK);
+  static_assert(sched::prologue_wait_fits(D, ST::total(), E::WBLK), "the weight queue's loads must fit the vmcnt field");
+  wait_vmcnt_seen<NWAIT>();   // this wave's share of the patch and the constants have landed (LDS-DMA is not tracked by the compiler)
   consts_commit<NT>(cregs, bias_lds, p.n_bias);
   lds_barrier();
 
@@ -443,9 +458,16 @@ __device__ __forceinline__ void head_fused_body(const HeadParams& p, int bid, un
   lds_barrier();
 #else
   load_patch<R0H, R0W, C, NT>(smem + p.off_x, p.src, p.src_ld, p.H, p.W, ty0 - 2, tx0 - 2, p.zeros, wid, lane);
-  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  // patch DMA, constants, then the weight queue, in program order; the counted wait leaves the D weight loads in flight
+  // (c3k2_fused_body's prologue, request_schedule.h)
+  __builtin_amdgcn_sched_barrier(0);
   consts_issue<NT>(cregs, p.bias, p.n_bias);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed
+  __builtin_amdgcn_sched_barrier(0);
+  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  __builtin_amdgcn_sched_barrier(0);
+  constexpr int NWAIT = sched::prologue_wait(D, ST::total(), EltH::WBLK);
+  static_assert(sched::prologue_wait_fits(D, ST::total(), EltH::WBLK), "the weight queue's loads must fit the vmcnt field");
+  wait_vmcnt_seen<NWAIT>();   // this wave's share of the patch and the constants have landed
   consts_commit<NT>(cregs, bias_lds, p.n_bias);
   lds_barrier();
 

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "mfma_common.h"
+#include "request_schedule.h"
 
 namespace unina {
 namespace dev {
@@ -341,7 +342,8 @@ __device__ __forceinline__ int img_at(const Img& im, int row, int n) {   // byte
 
 // Per-channel constants (biases ...) global -> LDS in two halves, so that their loads are IN FLIGHT together with the
 // patch DMA and the first weight blocks instead of in front of them: consts_issue() right after those are issued
-// (branch-free: clamped index, every lane loads), consts_commit() after the s_waitcnt vmcnt(0) that the patch needs anyway.
+// (branch-free: clamped index, every lane loads), consts_commit() after the counted s_waitcnt that the patch needs anyway
+// (the constants are requested BEHIND the patch and IN FRONT of the weight queue: request_schedule.h).
 // n is a multiple of 4, at most 4 * kConstVecs * NT floats; the array is 16-byte aligned.
 constexpr int kConstVecs = 4;
 template <int NT>
@@ -365,8 +367,9 @@ __device__ __forceinline__ void consts_commit(const floatx4 (&v)[kConstVecs], fl
 }
 
 // Input patch -> LDS image by LDS-DMA: 16-byte slot s = (region pixel r of an RH x RW region whose origin is image
-// pixel (y0, x0), chunk cs); out-of-image pixels read the zero page. NT threads; every wave must afterwards wait
-// vmcnt(0) (its own DMAs) and pass a barrier before anyone reads the image.
+// pixel (y0, x0), chunk cs); out-of-image pixels read the zero page. NT threads; every wave must afterwards wait for
+// its own DMAs (vmcnt(0), or a counted vmcnt that leaves only younger loads in flight) and pass a barrier before anyone reads
+// the image.
 // EltS: the lo plane (src_lo bytes behind the hi plane in HBM) lands lds_lo bytes behind the hi image.
 template <int RH, int RW, int CIN, int NT, typename E = EltH>
 __device__ __forceinline__ void load_patch(unsigned char* lds_img, const void* src_, int src_ld, int H, int W, int y0,

@@ -86,9 +86,16 @@ __global__ __launch_bounds__(NW * 64) void conv_pair_kernel(const PairParams p) 
     load_patch<RH, RW, CXP, NT, E>(smem + p.off_r, p.src, p.src_ld, p.H, p.W, ty0 - 6, tx0 - 6, p.zeros, wid, lane);
   else
     load_patch<TH, TW, C0, NT, E>(smem + p.off_x, p.src, p.src_ld, p.H, p.W, ty0, tx0, p.zeros, wid, lane, p.src_lo, lds_lo);
-  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  // patch DMA, constants, then the weight queue, in program order; the counted wait leaves the D weight loads (2 x D for the
+  // split type) in flight across the barrier (c3k2_fused_body's prologue, request_schedule.h)
+  __builtin_amdgcn_sched_barrier(0);
   consts_issue<NT>(cregs, p.bias, p.n_bias);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed
+  __builtin_amdgcn_sched_barrier(0);
+  static_for<0, D>([&](auto gc) { wq_fetch<ST, D, decltype(gc)::value>(q, wbase, wid); });
+  __builtin_amdgcn_sched_barrier(0);
+  constexpr int NWAIT = sched::prologue_wait(D, ST::total(), E::WBLK);
+  static_assert(sched::prologue_wait_fits(D, ST::total(), E::WBLK), "the weight queue's loads must fit the vmcnt field");
+  wait_vmcnt_seen<NWAIT>();   // this wave's share of the patch and the constants have landed
   consts_commit<NT>(cregs, cst, p.n_bias);
   lds_barrier();
 

@@ -34,6 +34,23 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// The same wait as an instruction the COMPILER sees (its waitcnt pass reads an s_waitcnt that is already in the code, not one
+// inside an asm statement), together with lgkmcnt(0). It matters where LDS-DMA and ordinary loads are in flight together: an
+// LDS-DMA is a global-segment instruction that writes LDS, so the compiler books it on BOTH counters and, as long as it believes
+// one outstanding on either, waits vmcnt(0) before the next use of any ordinary load's result -- which drains loads that were
+// meant to stay in flight behind this wait (seen in the ISA: vmcnt(0) at the constants' commit with the asm form, and, with a
+// visible vmcnt(N) alone, still vmcnt(0) at the first MFMA). After this form it knows that every LDS-DMA has landed and goes
+// on counting the N loads behind it. Use it where nothing of consequence is outstanding on lgkmcnt (a prologue).
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_seen() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  // gfx9 s_waitcnt immediate: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14; expcnt at its maximum = no wait
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (0 << 8) | ((N >> 4) << 14));
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+
 // "At most n stages of LPT DMA instructions each may still be in flight" for a run-time (wave-uniform) n: the
 // s_waitcnt immediate must be a constant, so the pipeline head / tail dispatch over the few possible values.
 template <int LPT>
