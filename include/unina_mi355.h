@@ -502,6 +502,47 @@ int unina_eval_update_async(unina_eval_t *ev, const GpuDetection *d_dets, const 
 int unina_eval_read(unina_eval_t *ev, unina_eval_result *res, double *scores, size_t score_cap, unina_eval_row *rows,
                     size_t row_cap, hipStream_t stream);
 
+/* ------------------------------------------------------------------ 3-D localisation (perception_node.cpp:545-550: the camera
+ * delivers a depth map on the GPU beside every colour frame)
+ * Kept records + a depth plane + pinhole intrinsics -> one 3-D point per record, in the camera frame (x right, y down, z
+ * forward, metres): one launch (csrc/locate.hip) enqueued behind whichever _async call produced the records; no engine handle,
+ * nothing is synchronised, the depth map never crosses to the host. localize.locate_numpy is the definition, decision for
+ * decision and bit for bit. Everything is fp32, each operation rounded once, never contracted; the divide is correctly rounded.
+ *   window   X1 = x1 * sx, X2 = x2 * sx, Y1 = y1 * sy, Y2 = y2 * sy (record -> depth-map pixels; pixel i covers [i, i + 1))
+ *            uc = 0.5f * (X1 + X2), vc = 0.5f * (Y1 + Y2); hw = (0.5f * shrink) * (X2 - X1), hh = (0.5f * shrink) * (Y2 - Y1)
+ *            columns floorf(uc - hw) .. floorf(uc + hw) clipped to 0 .. width - 1, rows floorf(vc - hh) .. floorf(vc + hh) clipped
+ *            to 0 .. height - 1. Emptiness is decided in float, integers are formed after the clip. EMPTY: a non-finite X1, X2,
+ *            Y1, Y2 or window bound, X2 < X1, Y2 < Y1, or a window wholly off the map (last bound < 0 or first bound > size - 1).
+ *            A degenerate box (X2 == X1) still covers the one column under its centre.
+ *            An empty window writes an ALL-ZERO record (n_samples = 0, valid = 0, u = v = 0).
+ *   grid     integers: nx = u1 - u0 + 1, stride = (nx + max_side - 1) / max_side, sampled columns u0 + i * stride <= u1; rows
+ *            likewise, each axis with its own stride. n_samples = columns * rows <= max_side * max_side <= 65 536.
+ *   sample   UNINA_DEPTH_F32: valid if the raw float is finite; UNINA_DEPTH_U16: valid if raw != 0. In both z = (float)raw * unit
+ *            must satisfy min_depth <= z <= max_depth. So NaN, +-inf, negatives, -0.0 and 0 are holes, and since min_depth > 0
+ *            every valid float is positive: its bit pattern orders as an unsigned integer.
+ *   depth    the LOWER MEDIAN: the valid sample of rank (n_valid - 1) / 2 in ascending raw order (np.sort(raw)[(n - 1) // 2]); an
+ *            actual sample, nothing is averaged. Found by counting (radix select on the raw bits), so exact and run-to-run
+ *            identical. Z = (float)raw_median * unit.
+ *   point    x = ((uc - cx) * Z) / fx, y = ((vc - cy) * Z) / fy, z = Z; u = uc, v = vc (depth-map pixels)
+ *   valid    1 iff n_valid >= max(1, min_valid); otherwise x = y = z = 0 (u, v, n_valid, n_samples stay)
+ * Records 0 .. count - 1 are processed whatever their `valid` field says (the _async calls write them compact, valid = 1);
+ * *d_count is clamped to 0..MAX_DETECTIONS on the device; the slots at and beyond it are written as all-zero bytes, so all
+ * MAX_DETECTIONS outputs are defined after every launch. */
+#define UNINA_DEPTH_F32 0   /* float32, e.g. ZED MEASURE::DEPTH; NaN / +-inf = hole */
+#define UNINA_DEPTH_U16 1   /* uint16, e.g. ROS 16UC1 millimetres; 0 = hole         */
+typedef struct { int format, width, height, pitch; const void *plane; float unit; } unina_depth;  /* pitch: bytes per row; unit: raw -> metres */
+typedef struct { float fx, fy, cx, cy; } unina_pinhole;   /* rectified image, depth-map pixels */
+typedef struct { float sx, sy, shrink, min_depth, max_depth; int max_side, min_valid; } unina_locate_params;
+typedef struct { float x, y, z, u, v; int n_valid, n_samples, valid; } unina_cone3d;   /* 32 bytes, index-aligned with the records */
+/*   d_dets / d_count : device, MAX_DETECTIONS records (16-byte aligned) / one int, as the _async calls write them
+ *   depth->plane     : device; d_out : device, MAX_DETECTIONS unina_cone3d, 16-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer (plane included); an unknown format; a size that is not positive (or above
+ * 16 777 216); a pitch below width * element size or not a multiple of the element size; plane not aligned to its element; d_out
+ * or d_dets not 16-byte aligned; fx, fy, unit, sx or sy not finite and positive; cx or cy not finite; shrink outside (0, 1];
+ * max_side outside 1..256; min_valid < 0; not 0 < min_depth < max_depth < inf. */
+int unina_locate_async(const GpuDetection *d_dets, const int *d_count, const unina_depth *depth, const unina_pinhole *cam,
+                       const unina_locate_params *p, unina_cone3d *d_out, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

@@ -31,6 +31,7 @@ UNITS = {
     "kmeans.hip": ["-ffp-contract=off"],        # k-means coreset: fused operations only where fmaf is written (the tests' bounds count roundings)
     "calib.hip": [],                     # |x| value-count tables for INT8 calibration: integer counts only
     "evalmatch.hip": ["-ffp-contract=off"],     # detections against labels: every comparison must decide as the host's numpy code does
+    "locate.hip": ["-ffp-contract=off"],        # detections -> 3-D points: window, validity and back-projection round as localize.locate_numpy's fp32 scalars do
     "engine.hip": [],
     "comm.hip": [],                             # host code only: RCCL all-gather of detection slots, librccl loaded on first use
 }

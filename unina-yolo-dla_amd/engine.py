@@ -84,6 +84,29 @@ class EvalResult(C.Structure):
                 ("label_counts", C.c_longlong * EVAL_MAX_CLASSES)]
 
 
+DEPTH_F32, DEPTH_U16 = 0, 1   # include/unina_mi355.h UNINA_DEPTH_*
+CONE3D_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("u", "<f4"), ("v", "<f4"), ("n_valid", "<i4"),
+                         ("n_samples", "<i4"), ("valid", "<i4")])   # unina_cone3d
+assert CONE3D_DTYPE.itemsize == 32
+
+
+class Depth(C.Structure):
+    """unina_depth: a depth plane on the device; pitch in bytes, unit: raw -> metres."""
+    _fields_ = [("format", C.c_int), ("width", C.c_int), ("height", C.c_int), ("pitch", C.c_int), ("plane", C.c_void_p),
+                ("unit", C.c_float)]
+
+
+class Pinhole(C.Structure):
+    """unina_pinhole: intrinsics of the rectified image, in depth-map pixels."""
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")]
+
+
+class LocateParams(C.Structure):
+    """unina_locate_params."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("shrink", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("max_side", C.c_int), ("min_valid", C.c_int)]
+
+
 def _tile_array(tiles):
     return (Tile * len(tiles))(*[Tile(*map(int, t)) for t in tiles])
 
@@ -111,6 +134,7 @@ ABI_SYMBOLS = [
     "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
+    "unina_locate_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -218,6 +242,8 @@ def load_library() -> C.CDLL:
     L.unina_eval_reset_async.argtypes = [vp, vp]
     L.unina_eval_update_async.argtypes = [vp, vp, vp, vp, ci, C.POINTER(EvalParams), C.c_uint, vp]
     L.unina_eval_read.argtypes = [vp, C.POINTER(EvalResult), vp, C.c_size_t, vp, C.c_size_t, vp]
+    # 3-D localisation (csrc/locate.hip)
+    L.unina_locate_async.argtypes = [vp, vp, C.POINTER(Depth), C.POINTER(Pinhole), C.POINTER(LocateParams), vp, vp]
     # multi-GPU: RCCL gather of detection slots behind the C ABI (csrc/comm.hip)
     L.unina_comm_unique_id.argtypes = [vp]
     L.unina_comm_init.argtypes = [C.POINTER(vp), vp, ci, ci, ci]

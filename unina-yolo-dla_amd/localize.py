@@ -1,0 +1,166 @@
+"""Detections lifted to 3-D cone positions from a depth map (include/unina_mi355.h "3-D localisation").
+
+``locate_numpy`` is the DEFINITION: fp32 scalars throughout, one rounding per operation, in the order the header states;
+csrc/locate.hip (through ``DeviceLocator``) returns its bytes. ``window_numpy`` is the twin of csrc/locate_window.h.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, MAX_DETECTIONS, Depth, EngineError, ERRORS, LocateParams, Pinhole,
+                     _stream_ptr, _torch, load_library)
+
+F = np.float32
+
+
+def as_pinhole(cam) -> Pinhole:
+    """(fx, fy, cx, cy) or a Pinhole -> Pinhole (the fields are rounded to fp32 once, here)."""
+    return cam if isinstance(cam, Pinhole) else Pinhole(*[float(v) for v in cam])
+
+
+def as_params(params) -> LocateParams:
+    """A LocateParams, a dict of its fields, or (sx, sy, shrink, min_depth, max_depth, max_side, min_valid)."""
+    if isinstance(params, LocateParams):
+        return params
+    if isinstance(params, dict):
+        return LocateParams(**params)
+    return LocateParams(*params)
+
+
+def _axis(c, h, n: int, max_side: int):
+    """One axis of csrc/locate_window.h: (lo, hi, stride, count) or None where the window misses the map."""
+    flo, fhi = np.floor(c - h), np.floor(c + h)
+    if not (np.isfinite(flo) and np.isfinite(fhi)):
+        return None
+    last = F(n - 1)
+    if fhi < F(0) or flo > last:
+        return None
+    lo = 0 if flo < F(0) else int(flo)
+    hi = n - 1 if fhi > last else int(fhi)
+    span = hi - lo + 1
+    stride = (span + max_side - 1) // max_side
+    return lo, hi, stride, (span - 1) // stride + 1
+
+
+def window_numpy(box, sx, sy, shrink, width: int, height: int, max_side: int):
+    """The window and sampling grid of one record: None where it is empty, else a dict u0, u1, v0, v1, stride_x, stride_y,
+    cols, rows, n_samples (ints) and uc, vc (np.float32). `box` = (x1, y1, x2, y2)."""
+    with np.errstate(all="ignore"):
+        x1, y1, x2, y2 = (F(v) for v in box)
+        sx, sy, shrink = F(sx), F(sy), F(shrink)
+        X1, X2, Y1, Y2 = x1 * sx, x2 * sx, y1 * sy, y2 * sy
+        if not (np.isfinite(X1) and np.isfinite(X2) and np.isfinite(Y1) and np.isfinite(Y2)):
+            return None
+        if X2 < X1 or Y2 < Y1:
+            return None
+        uc, vc = F(0.5) * (X1 + X2), F(0.5) * (Y1 + Y2)
+        hs = F(0.5) * shrink
+        hw, hh = hs * (X2 - X1), hs * (Y2 - Y1)
+        ax = _axis(uc, hw, width, max_side)
+        ay = _axis(vc, hh, height, max_side)
+        if ax is None or ay is None:
+            return None
+        return {"u0": ax[0], "u1": ax[1], "stride_x": ax[2], "cols": ax[3], "v0": ay[0], "v1": ay[1], "stride_y": ay[2],
+                "rows": ay[3], "n_samples": ax[3] * ay[3], "uc": uc, "vc": vc}
+
+
+def locate_numpy(dets, count: int, depth: np.ndarray, fmt: int, unit, cam, params) -> np.ndarray:
+    """dets: DET_DTYPE records; count: as the device word (clamped to 0..MAX_DETECTIONS, and to len(dets)); depth: [H, W]
+    float32 (DEPTH_F32) or uint16 (DEPTH_U16). Returns MAX_DETECTIONS CONE3D_DTYPE records, zero behind the count."""
+    cam, p = as_pinhole(cam), as_params(params)
+    want = np.float32 if fmt == DEPTH_F32 else np.uint16
+    if fmt not in (DEPTH_F32, DEPTH_U16) or depth.dtype != want or depth.ndim != 2:
+        raise ValueError(f"depth map of format {fmt} must be a 2-D {np.dtype(want).name} array")
+    height, width = depth.shape
+    unit, lo, hi = F(unit), F(p.min_depth), F(p.max_depth)
+    fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
+    out = np.zeros(MAX_DETECTIONS, dtype=CONE3D_DTYPE)
+    n = min(max(int(count), 0), MAX_DETECTIONS, len(dets))
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            d = dets[i]
+            w = window_numpy((d["x1"], d["y1"], d["x2"], d["y2"]), p.sx, p.sy, p.shrink, width, height, p.max_side)
+            if w is None:
+                continue                                                    # an empty window: the all-zero record
+            raw = depth[w["v0"]:w["v1"] + 1:w["stride_y"], w["u0"]:w["u1"] + 1:w["stride_x"]].reshape(-1)
+            assert raw.size == w["n_samples"]
+            z = raw.astype(np.float32) * unit
+            ok = (z >= lo) & (z <= hi)
+            ok &= np.isfinite(raw) if fmt == DEPTH_F32 else raw != 0
+            valid_raw = raw[ok]
+            r = out[i]
+            r["u"], r["v"], r["n_samples"], r["n_valid"] = w["uc"], w["vc"], raw.size, valid_raw.size
+            if valid_raw.size >= max(1, p.min_valid):
+                Z = F(np.sort(valid_raw)[(valid_raw.size - 1) // 2]) * unit    # the lower median, an actual sample
+                r["x"] = ((w["uc"] - cx) * Z) / fx
+                r["y"] = ((w["vc"] - cy) * Z) / fy
+                r["z"] = Z
+                r["valid"] = 1
+    return out
+
+
+class DeviceLocator:
+    """unina_locate_async (csrc/locate.hip): one launch per frame behind the call that produced the records. Holds the
+    MAX_DETECTIONS-record output buffer on the device; engine.DeviceEval's counterpart."""
+
+    def __init__(self, device: int = 0):
+        torch = _torch()
+        self.L = load_library()
+        self.out = torch.zeros(MAX_DETECTIONS * CONE3D_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
+        self._keep = None      # the depth tensor of the launch in flight
+
+    @staticmethod
+    def describe(depth_tensor, fmt=None, width=None, unit: float = 1.0) -> Depth:
+        """A CUDA tensor -> unina_depth. [H, W] float32: DEPTH_F32; [H, W] int16 / uint16: DEPTH_U16 (the bits are read as
+        unsigned); a row stride is carried as the pitch. [H, pitch_bytes] uint8 with `fmt` and `width` given: a pitched plane
+        as a camera driver hands it over."""
+        torch = _torch()
+        assert depth_tensor.is_cuda and depth_tensor.dim() == 2 and depth_tensor.stride(1) == 1
+        if depth_tensor.dtype == torch.uint8:
+            assert fmt in (DEPTH_F32, DEPTH_U16) and width is not None, "a byte plane needs its format and width"
+            return Depth(fmt, int(width), int(depth_tensor.shape[0]), int(depth_tensor.stride(0)), depth_tensor.data_ptr(), unit)
+        if depth_tensor.dtype == torch.float32:
+            f, elem = DEPTH_F32, 4
+        elif depth_tensor.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            f, elem = DEPTH_U16, 2
+        else:
+            raise EngineError(f"no depth format for a {depth_tensor.dtype} tensor")
+        assert fmt in (None, f)
+        return Depth(f, int(depth_tensor.shape[1]), int(depth_tensor.shape[0]), int(depth_tensor.stride(0)) * elem,
+                     depth_tensor.data_ptr(), unit)
+
+    def update_async(self, d_dets, d_count, depth_tensor, unit, cam, params, fmt=None, width=None, stream=None):
+        """Enqueues the launch; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and
+        the count, as the _async calls write them. Returns the output tensor (bytes; read() gives the records)."""
+        addr = lambda t: t if isinstance(t, int) else t.data_ptr()   # noqa: E731
+        depth = depth_tensor if isinstance(depth_tensor, Depth) else self.describe(depth_tensor, fmt, width, unit)
+        cam, p = as_pinhole(cam), as_params(params)
+        self._keep = depth_tensor
+        rc = self.L.unina_locate_async(addr(d_dets), addr(d_count), C.byref(depth), C.byref(cam), C.byref(p), self.out.data_ptr(),
+                                       _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_locate_async failed [{ERRORS.get(rc, rc)}]")
+        return self.out
+
+    def update_from_buffer(self, det_buf, depth_tensor, unit, cam, params, fmt=None, width=None, stream=None):
+        """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
+        base = det_buf.data_ptr()
+        return self.update_async(base + 32, base, depth_tensor, unit, cam, params, fmt, width, stream)
+
+    def read(self, stream=None) -> np.ndarray:
+        """Synchronises `stream`; returns all MAX_DETECTIONS CONE3D_DTYPE records (zero behind the count)."""
+        torch = _torch()
+        s = torch.cuda.current_stream() if stream is None else stream
+        if not isinstance(s, int):
+            with torch.cuda.stream(s):
+                host = self.out.cpu()
+        else:
+            torch.cuda.synchronize()
+            host = self.out.cpu()
+        self._keep = None
+        return host.numpy().view(CONE3D_DTYPE).copy()
+
+
+__all__ = ["locate_numpy", "window_numpy", "DeviceLocator", "as_pinhole", "as_params"]
