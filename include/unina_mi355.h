@@ -182,8 +182,8 @@ int unina_letterbox_geometry(int src_w, int src_h, int dst_w, int dst_h, unina_l
 
 /* unina_infer_bgra / unina_infer_nv12 with the letterbox above in place of the stretch: same arguments and argument checks, plus
  * pad_value and map_boxes (0 / 1, anything else UNINA_ERR_ARG). Synchronous, delivered as unina_infer delivers (pinned block +
- * completion word: no D2H copy, no stream synchronisation, no extra launch for the map). A refused call enqueues nothing; the
- * stems and the map flag are restored whatever the call returns. With map_boxes = 0 the results equal
+ * completion word: no D2H copy, no stream synchronisation, no extra launch for the map). A refused call enqueues nothing, and
+ * no call leaves anything behind in the handle: the frame, the letterbox and the map flag travel with the call. With map_boxes = 0 the results equal
  * unina_preprocess_letterbox_* + unina_infer bit for bit; a frame of the network's size is unina_infer_bgra / unina_infer_nv12. */
 int unina_infer_letterbox_bgra(unina_engine_t *e, const uint8_t *d_bgra, int src_width, int src_height, int src_pitch,
                                const NormParams *norm, float conf_threshold, float iou_threshold, float conformal_q,

@@ -528,4 +528,20 @@ inline int frame_kind(int format, int w, int h, int dst_w, int dst_h, const unin
   return (w == dst_w && h == dst_h) ? base : base + 1;     // (each Resize kind follows its Tap kind)
 }
 
+// What one launch reads: `region` as `kind` (frame_kind's answer, or the kind an entry point is defined as) for a destination of
+// dst_w x dst_h. The letterbox kinds get the inner rectangle *lb and the pad value; the others leave them zero.
+inline CameraSource launch_source(CameraSource c, int kind, int dst_w, int dst_h, const unina_letterbox* lb, float pad) {
+  c.kind = kind;
+  c.dst_w = dst_w;
+  c.dst_h = dst_h;
+  if (kind == kSrcBgraLetterbox || kind == kSrcNv12Letterbox || kind == kSrcFrameLetterbox) {
+    c.in_x0 = lb->left;
+    c.in_y0 = lb->top;
+    c.in_w = lb->new_w;
+    c.in_h = lb->new_h;
+    c.pad = pad;
+  }
+  return c;
+}
+
 }  // namespace unina

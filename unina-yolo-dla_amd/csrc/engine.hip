@@ -105,13 +105,7 @@ struct unina_engine {
   DeviceResult* d_result = nullptr;
   DeviceResult* h_result = nullptr;  // pinned
   DeviceResult* h_result_dev = nullptr;  // the same block as the device addresses it (hipHostGetDevicePointer)
-  bool camera_active = false;            // inside unina_infer_bgra: the stem reads a camera frame, "images" need not be bound
-  unsigned int result_seq = 0;           // unina_infer calls so far
-  unsigned int* done_flag = nullptr;     // set around unina_infer's launch: the post-process signals completion there
-  unsigned int done_value = 0;
-  // set around a letterboxed call with map_boxes = 1: the post-process maps the kept records to camera pixels (PostParams::map_*)
-  int map_boxes = 0;
-  float map_left = 0.f, map_top = 0.f, map_sx = 0.f, map_sy = 0.f;
+  unsigned int result_seq = 0;           // synchronous calls so far (infer_sync's completion word)
   int post_blocks = 0;
   // graph
   bool use_graph = true;
@@ -764,7 +758,35 @@ hipError_t launch_op_as(const unina_engine* e, size_t i, hipStream_t s, LaunchFo
   const hipError_t err = op_launch(e, i, f, &l, edit);
   return err != hipSuccess || !l.d.func ? err : launch_desc(l.d, l.args, s);
 }
-hipError_t launch_op(const unina_engine* e, size_t i, hipStream_t s) { return launch_op_as(e, i, s, launch_form(e, i)); }
+
+// What differs from one frame call to the next besides the thresholds and the outputs. It travels by argument from the entry point
+// to the launch; the engine and its plan hold nothing of it, before or after.
+struct FrameCall {
+  const CameraSource* region = nullptr;   // what the stems read; nullptr: the bound "images" tensor
+  const unina_letterbox* lb = nullptr;    // the region letterboxed into the network input; nullptr: stretched
+  float pad = 0.f;                        // letterbox: r = g = b outside the inner rectangle
+  bool map_boxes = false;                 // letterbox: the post-process maps the kept records to camera pixels (PostParams::map_*)
+  unsigned int* done_flag = nullptr;      // the last post-process block stores done_value there (infer_sync); nullptr: nothing is signalled
+  unsigned int done_value = 0;
+};
+
+// The stem parameters of a call: the planned ones, reading the call's region as the kind it is for this stem's input size
+StemParams call_stem(StemParams sp, const FrameCall& call) {
+  if (const CameraSource* c = call.region)
+    sp.cam = launch_source(*c, frame_kind(c->format, c->w, c->h, sp.W, sp.H, call.lb), sp.W, sp.H, call.lb, call.pad);
+  return sp;
+}
+
+// Ops that read the caller's "images" tensor (the stem) stay OUTSIDE the captured graph: a camera pipeline hands
+// over a different input buffer every frame, and re-binding must not cost a re-capture.
+bool is_eager(const unina_engine* e, size_t i) { return (int)e->ops[i].d.src_buf == e->images_buf; }
+
+// Op i as planned; in a frame call, an eager stem with the call's parameters
+hipError_t launch_op(const unina_engine* e, size_t i, hipStream_t s, const FrameCall& call = {}) {
+  const LaunchForm f = launch_form(e, i);
+  const bool stem = f == kLaunchStem && is_eager(e, i);
+  return launch_op_as(e, i, s, f, [&](OpLaunch& l) { if (stem) l.sp = call_stem(l.sp, call); });
+}
 
 // The op info's kernel, grid and block: those of op i's launch as `f`.
 void launch_info(unina_engine* e, size_t i, LaunchForm f) {
@@ -814,14 +836,10 @@ int plan(unina_engine* e) {
   return UNINA_OK;
 }
 
-// Ops that read the caller's "images" tensor (the stem) stay OUTSIDE the captured graph: a camera pipeline hands
-// over a different input buffer every frame, and re-binding must not cost a re-capture.
-bool is_eager(const unina_engine* e, size_t i) { return (int)e->ops[i].d.src_buf == e->images_buf; }
-
-int launch_all(unina_engine* e, hipStream_t s, int which = 0 /*0 all, 1 eager only, 2 graph part only*/) {
+int launch_all(unina_engine* e, hipStream_t s, int which = 0 /*0 all, 1 eager only, 2 graph part only*/, const FrameCall& call = {}) {
   for (size_t i = 0; i < e->ops.size(); ++i) {
     if ((which == 1 && !is_eager(e, i)) || (which == 2 && is_eager(e, i))) continue;
-    hipError_t err = launch_op(e, i, s);
+    hipError_t err = launch_op(e, i, s, call);
     if (err != hipSuccess) return fail(e, UNINA_ERR_HIP, "op %zu (%s): %s", i, e->ops[i].d.name, hipGetErrorString(err));
   }
   return UNINA_OK;
@@ -843,6 +861,30 @@ int capture(unina_engine* e) {
   if (rc != UNINA_OK) return rc;
   if (end != hipSuccess) return fail(e, UNINA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(end));
   HIPCHK(e, hipGraphInstantiate(&e->exec, e->graph, nullptr, nullptr, 0));
+  return UNINA_OK;
+}
+
+// Before anything is launched: the engine's device current, something for the stems to read (the bound "images" tensor, unless the
+// call brings a camera region) and the plan up to date
+int make_ready(unina_engine* e, const FrameCall& call = {}) {
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!call.region && !e->bufs[e->images_buf].ptr) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
+  bool stem = !call.region;
+  for (size_t k = 0; k < e->ops.size() && !stem; ++k) stem = is_eager(e, k) && e->ops[k].d.kind == kOpStem;
+  if (!stem) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
+  return e->plan_dirty ? plan(e) : UNINA_OK;
+}
+
+// The raw-head forward of a ready engine: the eager stems, then the captured graph of the rest (or every op, without graphs)
+int enqueue_forward(unina_engine* e, const FrameCall& call, hipStream_t stream) {
+  if (!e->use_graph) return launch_all(e, stream, 0, call);
+  if (!e->exec) {
+    int rc = capture(e);
+    if (rc != UNINA_OK) return rc;
+  }
+  int rc = launch_all(e, stream, 1, call);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipGraphLaunch(e->exec, stream));
   return UNINA_OK;
 }
 
@@ -1123,7 +1165,7 @@ hipError_t last_captured_node(hipStream_t st, hipGraphNode_t* node) {
   return hipSuccess;
 }
 
-int capture_full(unina_engine* e, const PostParams& pp) {
+int capture_full(unina_engine* e, const FrameCall& call, const PostParams& pp) {
   if (e->fexec) (void)hipGraphExecDestroy(e->fexec);
   if (e->fgraph) (void)hipGraphDestroy(e->fgraph);
   e->fexec = nullptr;
@@ -1136,7 +1178,7 @@ int capture_full(unina_engine* e, const PostParams& pp) {
   int rc = UNINA_OK;
   for (size_t j = 0; j < e->ops.size() && err == hipSuccess; ++j) {
     if (!launches_in_frame(e, j, pp)) continue;
-    err = launch_op(e, j, st);
+    err = launch_op(e, j, st, call);
     if (err != hipSuccess) {
       rc = fail(e, UNINA_ERR_HIP, "op %zu (%s): %s", j, e->ops[j].d.name, hipGetErrorString(err));
       break;
@@ -1161,7 +1203,7 @@ int capture_full(unina_engine* e, const PostParams& pp) {
   if (end != hipSuccess) return fail(e, UNINA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(end));
   if (e->stem_op < 0 || !e->stem_node || !e->post_node) return fail(e, UNINA_ERR_STATE, "full-frame graph: stem / post-process node not found");
   HIPCHK(e, hipGraphInstantiate(&e->fexec, e->fgraph, nullptr, nullptr, 0));
-  e->f_stem = e->ops[e->stem_op].sp;
+  e->f_stem = call_stem(e->ops[e->stem_op].sp, call);
   e->f_post = pp;
   return UNINA_OK;
 }
@@ -1180,20 +1222,18 @@ hipError_t set_node(hipGraphExec_t exec, hipGraphNode_t node, const LaunchDesc& 
   return hipGraphExecKernelNodeSetParams(exec, node, &np);
 }
 
-// One graph launch for the whole frame; re-points the stem / post-process nodes when their parameters changed.
-int launch_full(unina_engine* e, const PostParams& pp, hipStream_t stream) {
+// One graph launch for the whole frame; re-points the stem / post-process nodes when this call's parameters differ from the last
+// ones launched.
+int launch_full(unina_engine* e, const FrameCall& call, const PostParams& pp, hipStream_t stream) {
   if (!e->fexec) {
-    int rc = capture_full(e, pp);
+    int rc = capture_full(e, call, pp);
     if (rc != UNINA_OK) return rc;
   } else {
-    const PlannedOp& so = e->ops[e->stem_op];
-    const StemParams& sp = so.sp;
+    const StemParams sp = call_stem(e->ops[e->stem_op].sp, call);
     if (memcmp(&sp, &e->f_stem, sizeof sp)) {
       LaunchDesc d;
-      {
-        HIPCHK(e, stem_desc(sp, &d));
-        HIPCHK(e, set_node(e->fexec, e->stem_node, d, sp));
-      }
+      HIPCHK(e, stem_desc(sp, &d));
+      HIPCHK(e, set_node(e->fexec, e->stem_node, d, sp));
       e->f_stem = sp;
     }
     if (memcmp(&pp, &e->f_post, sizeof pp)) {
@@ -1258,8 +1298,8 @@ float half_bits_to_float(uint16_t h) {
   return f;
 }
 
-int fill_post_params(unina_engine* e, PostParams* pp, float conf, float iou, float q, GpuDetection* d_out, int* d_count,
-                     int* d_cand_count, bool fold = false) {
+int fill_post_params(unina_engine* e, PostParams* pp, const FrameCall& call, float conf, float iou, float q, GpuDetection* d_out,
+                     int* d_count, int* d_cand_count, bool fold = false) {
   memset(pp, 0, sizeof *pp);
   for (int i = 0; i < 3; ++i) {
     const Buffer& c = e->bufs[e->out_buf[2 * i]];
@@ -1303,15 +1343,32 @@ int fill_post_params(unina_engine* e, PostParams* pp, float conf, float iou, flo
   pp->out_count = d_count;
   pp->out_candidates = d_cand_count;
   pp->stamps = getenv("UNINA_POST_STAMPS") ? reinterpret_cast<long long*>(e->d_result->pad_stamps) : nullptr;
-  pp->done_flag = e->done_flag;
-  pp->done_value = e->done_value;
-  if (e->map_boxes) {
+  pp->done_flag = call.done_flag;
+  pp->done_value = call.done_value;
+  if (call.map_boxes && call.lb) {
     pp->map_boxes = 1;
-    pp->map_left = e->map_left;
-    pp->map_top = e->map_top;
-    pp->map_sx = e->map_sx;
-    pp->map_sy = e->map_sy;
+    pp->map_left = (float)call.lb->left;
+    pp->map_top = (float)call.lb->top;
+    pp->map_sx = (float)call.region->w / (float)call.lb->new_w;
+    pp->map_sy = (float)call.region->h / (float)call.lb->new_h;
   }
+  return UNINA_OK;
+}
+
+// One frame: forward + post-process into d_out / d_count, as one launch of the full-frame graph or as the raw-head forward and the
+// post-process behind it. The body of every inference entry point; `call` says what this frame reads and whom it signals.
+int enqueue_frame(unina_engine* e, const FrameCall& call, float conf, float iou, float q, GpuDetection* d_out, int* d_count,
+                  hipStream_t stream) {
+  if (!d_out || !d_count) return UNINA_ERR_ARG;
+  int rc = make_ready(e, call);
+  if (rc != UNINA_OK) return rc;
+  const bool full = e->full_graph && e->use_graph;
+  PostParams pp;
+  fill_post_params(e, &pp, call, conf, iou, q, d_out, d_count, &e->d_result->candidates, /*fold=*/full);
+  if (full) return launch_full(e, call, pp, stream);
+  rc = enqueue_forward(e, call, stream);
+  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, postprocess_launch(pp, stream));
   return UNINA_OK;
 }
 
@@ -1571,21 +1628,8 @@ int unina_tensor_address(const unina_engine_t* e, const char* name, void** devic
 
 int unina_enqueue(unina_engine_t* e, hipStream_t stream) {
   if (!e) return UNINA_ERR_ARG;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->bufs[e->images_buf].ptr && !e->camera_active) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
-  if (e->plan_dirty) {
-    int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  if (!e->use_graph) return launch_all(e, stream);
-  if (!e->exec) {
-    int rc = capture(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  int rc = launch_all(e, stream, 1);
-  if (rc != UNINA_OK) return rc;
-  HIPCHK(e, hipGraphLaunch(e->exec, stream));
-  return UNINA_OK;
+  const int rc = make_ready(e);
+  return rc != UNINA_OK ? rc : enqueue_forward(e, FrameCall{}, stream);
 }
 
 int unina_postprocess_async(unina_engine_t* e, float conf, float iou, float q, GpuDetection* d_out, int* d_out_count,
@@ -1593,7 +1637,7 @@ int unina_postprocess_async(unina_engine_t* e, float conf, float iou, float q, G
   if (!e || !d_out || !d_out_count) return UNINA_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));
   PostParams pp;
-  fill_post_params(e, &pp, conf, iou, q, d_out, d_out_count, &e->d_result->candidates);
+  fill_post_params(e, &pp, FrameCall{}, conf, iou, q, d_out, d_out_count, &e->d_result->candidates);
   HIPCHK(e, postprocess_launch(pp, stream));
   return UNINA_OK;
 }
@@ -1605,28 +1649,15 @@ int unina_infer_async(unina_engine_t* e, const float* d_images, float conf, floa
     int rc = unina_set_tensor_address(e, "images", const_cast<float*>(d_images));
     if (rc != UNINA_OK) return rc;
   }
-  if (e->full_graph && e->use_graph) {
-    if (!d_out || !d_out_count) return UNINA_ERR_ARG;
-    HIPCHK(e, hipSetDevice(e->device));
-    if (!e->bufs[e->images_buf].ptr && !e->camera_active) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
-    if (e->plan_dirty) {
-      int rc = plan(e);
-      if (rc != UNINA_OK) return rc;
-    }
-    PostParams pp;
-    fill_post_params(e, &pp, conf, iou, q, d_out, d_out_count, &e->d_result->candidates, /*fold=*/true);
-    return launch_full(e, pp, stream);
-  }
-  int rc = unina_enqueue(e, stream);
-  if (rc != UNINA_OK) return rc;
-  return unina_postprocess_async(e, conf, iou, q, d_out, d_out_count, stream);
+  return enqueue_frame(e, FrameCall{}, conf, iou, q, d_out, d_out_count, stream);
 }
 
 }  // extern "C"
 
 namespace {
-// The synchronous delivery of unina_infer and unina_infer_tiled_bgra: `enqueue(d_out, d_count)` enqueues the work whose LAST
-// post-process launch writes the records and the count there (and signals e->done_flag, which is set around the call).
+// The synchronous delivery of unina_infer and every synchronous camera call: `enqueue(d_out, d_count, done_flag, done_value)` enqueues
+// the work whose LAST post-process launch writes the records and the count there and then stores done_value to done_flag (nullptr:
+// the host waits for the stream instead).
 template <typename Enqueue>
 int infer_sync(unina_engine* e, Enqueue enqueue, GpuDetection* out, int* out_count, hipStream_t stream) {
   // The post-process writes its compacted output (write-only: count + n records) straight into the pinned, device-mapped
@@ -1640,15 +1671,10 @@ int infer_sync(unina_engine* e, Enqueue enqueue, GpuDetection* out, int* out_cou
   bool copied = false;
   if (host_result && e->h_result_dev) {
     unsigned int seq = 0;
-    if (host_poll) {
-      seq = ++e->result_seq ? e->result_seq : ++e->result_seq;   // never 0
-      e->done_flag = &e->h_result_dev->seq;
-      e->done_value = seq;
-    }
+    if (host_poll) seq = ++e->result_seq ? e->result_seq : ++e->result_seq;   // never 0
     static const bool timing = getenv("UNINA_TIMING") != nullptr;
     const auto ta = std::chrono::steady_clock::now();
-    int rc = enqueue(e->h_result_dev->det, &e->h_result_dev->count);
-    e->done_flag = nullptr;
+    int rc = enqueue(e->h_result_dev->det, &e->h_result_dev->count, host_poll ? &e->h_result_dev->seq : nullptr, seq);
     if (rc != UNINA_OK) return rc;
     const auto tb = std::chrono::steady_clock::now();
     if (host_poll) {
@@ -1679,7 +1705,7 @@ int infer_sync(unina_engine* e, Enqueue enqueue, GpuDetection* out, int* out_cou
       ++e->t_calls;
     }
   } else {
-    int rc = enqueue(e->d_result->det, &e->d_result->count);
+    int rc = enqueue(e->d_result->det, &e->d_result->count, nullptr, 0u);
     if (rc != UNINA_OK) return rc;
     HIPCHK(e, hipMemcpyAsync(e->h_result, e->d_result, sizeof(DeviceResult), hipMemcpyDeviceToHost, stream));
     HIPCHK(e, hipStreamSynchronize(stream));
@@ -1690,6 +1716,16 @@ int infer_sync(unina_engine* e, Enqueue enqueue, GpuDetection* out, int* out_cou
   *out_count = n;
   return UNINA_OK;
 }
+
+// One frame as `call` describes it, delivered to the host (infer_sync, whose completion word joins the call) or left on the stream
+int run_frame(unina_engine* e, FrameCall call, bool async, float conf, float iou, float q, GpuDetection* out, int* out_count, hipStream_t stream) {
+  if (async) return enqueue_frame(e, call, conf, iou, q, out, out_count, stream);
+  return infer_sync(e, [&](GpuDetection* d_out, int* d_count, unsigned int* done_flag, unsigned int done_value) {
+    call.done_flag = done_flag;
+    call.done_value = done_value;
+    return enqueue_frame(e, call, conf, iou, q, d_out, d_count, stream);
+  }, out, out_count, stream);
+}
 }  // namespace
 
 extern "C" {
@@ -1697,8 +1733,11 @@ extern "C" {
 int unina_infer(unina_engine_t* e, const float* d_images, float conf, float iou, float q, GpuDetection* out,
                 int* out_count, hipStream_t stream) {
   if (!e || !out || !out_count) return UNINA_ERR_ARG;
-  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) { return unina_infer_async(e, d_images, conf, iou, q, d_out, d_count, stream); },
-                    out, out_count, stream);
+  if (d_images) {
+    int rc = unina_set_tensor_address(e, "images", const_cast<float*>(d_images));
+    if (rc != UNINA_OK) return rc;
+  }
+  return run_frame(e, FrameCall{}, false, conf, iou, q, out, out_count, stream);
 }
 
 // ---- data mining (active_learning.py:31-99, 234-305): scores and embedding behind the raw-head forward ----
@@ -1904,181 +1943,118 @@ int unina_serial_latency(unina_engine_t* e, const float* const* d_frames, int n_
   return UNINA_OK;
 }
 
-// A camera region as a format-named entry point describes it (GpuBufferHandle::format, perception_node.cpp:357-368): a CameraSource
-// (camera_source.h) whose kind, destination and inner rectangle point_stems_at_camera fills in per stem. The caller names its format.
-static CameraSource camera_region(int format, const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, const NormParams& norm) {
-  const unina_frame f = {format, w, h, {plane, uv}, {pitch, uv_pitch}};
-  return frame_source(f, norm);
+// ---- camera frames: every entry point describes its frame as a unina_frame and its call as a FrameCall ----
+// The frame of a format-named entry point (GpuBufferHandle::format, perception_node.cpp:357-368)
+static unina_frame bgra_frame(const uint8_t* d_bgra, int w, int h, int pitch) { return {UNINA_FMT_BGRA, w, h, {d_bgra, nullptr}, {pitch, 0}}; }
+static unina_frame nv12_frame(const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch, int uv_pitch) {
+  return {UNINA_FMT_NV12, w, h, {d_y, d_uv}, {y_pitch, uv_pitch}};
 }
 
-// The kind of source a region is for a network input of net_w x net_h: frame_kind (camera_source.h), by the region's FORMAT.
-static int camera_kind(const CameraSource& c, int net_w, int net_h, const unina_letterbox* lb) {
-  return frame_kind(c.format, c.w, c.h, net_w, net_h, lb);
+// What every camera call checks before its own arguments: the pointers, the result alignment of the asynchronous forms (the
+// synchronous ones hand the post-process a buffer of the engine's) and the frame geometry of the format (frame_defect)
+static int check_frame_call(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, bool async, const GpuDetection* out,
+                            const int* out_count) {
+  if (!e) return UNINA_ERR_ARG;
+  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
+  if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
+  const char* why = frame_defect(f);
+  if (!why) return UNINA_OK;
+  if (f) return fail(e, UNINA_ERR_ARG, "%s: %s (format %d, %d x %d, pitch %d / %d)", who, why, f->format, f->width, f->height, f->pitch[0], f->pitch[1]);
+  return fail(e, UNINA_ERR_ARG, "%s: %s", who, why);
 }
 
-// Points every eager stem op at a camera region / back at the fp32 tensor. Returns the number of stem ops.
-static int point_stems_at_camera(unina_engine* e, const CameraSource& region, const unina_letterbox* lb = nullptr, float pad = 0.f) {
-  int nstem = 0;
-  for (size_t k = 0; k < e->ops.size(); ++k) {
-    PlannedOp& op = e->ops[k];
-    if (!is_eager(e, k) || op.d.kind != kOpStem) continue;
-    CameraSource c = region;
-    c.dst_w = op.sp.W;
-    c.dst_h = op.sp.H;
-    c.kind = camera_kind(c, c.dst_w, c.dst_h, lb);
-    if (c.kind == kSrcBgraLetterbox || c.kind == kSrcNv12Letterbox || c.kind == kSrcFrameLetterbox) {
-      c.in_x0 = lb->left;
-      c.in_y0 = lb->top;
-      c.in_w = lb->new_w;
-      c.in_h = lb->new_h;
-      c.pad = pad;
-    }
-    op.sp.cam = c;
-    ++nstem;
-  }
-  return nstem;
-}
-static void restore_stems(unina_engine* e) {
-  for (size_t k = 0; k < e->ops.size(); ++k)
-    if (is_eager(e, k) && e->ops[k].d.kind == kOpStem) e->ops[k].sp.cam = CameraSource{};
+// Camera frame -> detections: unina_infer with the pre-process (camera_source.h: colour conversion, optional half-pixel-centre
+// bilinear resize, normalise) computed inside the stem kernel instead of written to an fp32 tensor by one launch and read back by
+// the next (BGRA: 4 B/px in instead of 12 B/px out + 12 B/px in, one launch less). The same functions, so the detections are those
+// of the two-step form bit for bit (tests/test_gpu_preprocess.py, test_gpu_nv12.py, test_gpu_frame_formats.py).
+static int infer_plain(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, float conf, float iou, float q, bool async,
+                       GpuDetection* out, int* out_count, hipStream_t stream) {
+  const int rc = check_frame_call(e, who, f, norm, async, out, out_count);
+  if (rc != UNINA_OK) return rc;
+  const CameraSource c = frame_source(*f, *norm);
+  FrameCall call;
+  call.region = &c;
+  return run_frame(e, call, async, conf, iou, q, out, out_count, stream);
 }
 
-// The engine's device current and its plan up to date: what every camera entry point needs before it touches the stems
-static int make_ready(unina_engine* e) {
-  HIPCHK(e, hipSetDevice(e->device));
-  return e->plan_dirty ? plan(e) : UNINA_OK;
+// Letterboxed (include/unina_mi355.h at unina_letterbox_geometry). Nothing is enqueued before the last check has passed.
+static int infer_letterbox(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, float conf, float iou, float q,
+                           float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+  const int rc = check_frame_call(e, who, f, norm, async, out, out_count);
+  if (rc != UNINA_OK) return rc;
+  if (map_boxes != 0 && map_boxes != 1) return fail(e, UNINA_ERR_ARG, "%s: map_boxes must be 0 or 1, got %d", who, map_boxes);
+  unina_letterbox lb;
+  if (unina_letterbox_geometry(f->width, f->height, (int)e->h.in_w, (int)e->h.in_h, &lb) != UNINA_OK)
+    return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, f->width, f->height);
+  const CameraSource c = frame_source(*f, *norm);
+  FrameCall call;
+  call.region = &c;
+  call.lb = &lb;
+  call.pad = pad_value;
+  call.map_boxes = map_boxes != 0;
+  return run_frame(e, call, async, conf, iou, q, out, out_count, stream);
 }
 
-// unina_infer / unina_infer_async on a camera region, stretched or (lb) letterboxed with the post-process told the box map for the
-// call (map_boxes): the stems are pointed at the region and back at the tensor afterwards, whatever the call returns
-static int infer_camera(unina_engine* e, const CameraSource& c, const unina_letterbox* lb, float pad_value, int map_boxes, bool async,
-                        float conf, float iou, float q, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!point_stems_at_camera(e, c, lb, pad_value)) return fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
-  e->camera_active = true;
-  if (lb && map_boxes) {
-    e->map_boxes = 1;
-    e->map_left = (float)lb->left;
-    e->map_top = (float)lb->top;
-    e->map_sx = (float)c.w / (float)lb->new_w;
-    e->map_sy = (float)c.h / (float)lb->new_h;
-  }
-  const int rc = async ? unina_infer_async(e, nullptr, conf, iou, q, out, out_count, stream)
-                       : unina_infer(e, nullptr, conf, iou, q, out, out_count, stream);
-  e->map_boxes = 0;
-  e->camera_active = false;
-  restore_stems(e);
-  return rc;
-}
-
-// The frame geometry every BGRA entry point accepts: whole pixels are read as dwords, so the pitch and the address are multiples of 4
-static int check_bgra_frame(unina_engine* e, const char* who, const uint8_t* d_bgra, int w, int h, int pitch) {
-  if (w <= 0 || h <= 0 || pitch < 4 * w || (pitch & 3) || ((uintptr_t)d_bgra & 3)) return fail(e, UNINA_ERR_ARG, "%s: bad frame geometry", who);
-  return UNINA_OK;
-}
-
-// The NV12 frame geometry every NV12 entry point accepts: preprocess_nv12's pitch rules (y_pitch >= w, uv_pitch >= w), and
-// since the last chroma pair of an odd-width row is read whole, uv_pitch >= 2 * ((w + 1) / 2). Odd sizes are legal (the chroma
-// plane then has (h + 1) / 2 rows); nothing is asked of the alignment of the planes or the pitches.
-static int check_nv12_frame(unina_engine* e, const char* who, const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch, int uv_pitch) {
-  if (!d_y || !d_uv) return fail(e, UNINA_ERR_ARG, "%s: null %s plane", who, d_y ? "chroma" : "luma");
-  if (w <= 0 || h <= 0) return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, w, h);
-  if (y_pitch < w || uv_pitch < w || uv_pitch < 2 * ((w + 1) / 2))
-    return fail(e, UNINA_ERR_ARG, "%s: pitch too small for width %d (y_pitch %d < %d or uv_pitch %d < %d)", who, w, y_pitch, w, uv_pitch, 2 * ((w + 1) / 2));
-  return UNINA_OK;
-}
-
-// Camera frame -> detections: unina_infer with the pre-process (camera_source.h: BGRA -> RGB, optional half-pixel-centre
-// bilinear resize, normalise) computed inside the stem kernel instead of written to an fp32 tensor by one launch and
-// read back by the next (4 B/px in instead of 12 B/px out + 12 B/px in, one launch less). The same functions, so the
-// detections are those of preprocess_bgra[_resize] + unina_infer bit for bit (tests/test_gpu_preprocess.py).
 int unina_infer_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                      const NormParams* norm, float conf, float iou, float q, GpuDetection* out, int* out_count,
                      hipStream_t stream) {
-  if (!e || !d_bgra || !norm || !out || !out_count) return UNINA_ERR_ARG;
-  int rc = check_bgra_frame(e, "unina_infer_bgra", d_bgra, src_width, src_height, src_pitch);
-  if (rc == UNINA_OK) rc = make_ready(e);
-  if (rc != UNINA_OK) return rc;
-  return infer_camera(e, camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), nullptr, 0.f, 0, false, conf, iou, q,
-                      out, out_count, stream);
+  const unina_frame f = bgra_frame(d_bgra, src_width, src_height, src_pitch);
+  return infer_plain(e, "unina_infer_bgra", &f, norm, conf, iou, q, false, out, out_count, stream);
 }
 
-// NV12 camera frame -> detections: unina_infer_bgra's role for the other common camera format (cuda_preprocess.cu:206-211),
-// 1.5 B/px in. The stem computes preprocess_nv12 (a frame of the network's size) or unina_preprocess_nv12_resize (any other
-// size) per pixel, so the detections are those of the two-step form bit for bit (tests/test_gpu_nv12.py).
 int unina_infer_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
                      int uv_pitch, const NormParams* norm, float conf, float iou, float q, GpuDetection* out, int* out_count,
                      hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_nv12: null norm / result pointer");
-  int rc = check_nv12_frame(e, "unina_infer_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
-  if (rc == UNINA_OK) rc = make_ready(e);
-  if (rc != UNINA_OK) return rc;
-  return infer_camera(e, camera_region(UNINA_FMT_NV12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), nullptr, 0.f, 0, false, conf, iou, q,
-                      out, out_count, stream);
+  const unina_frame f = nv12_frame(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  return infer_plain(e, "unina_infer_nv12", &f, norm, conf, iou, q, false, out, out_count, stream);
 }
 
-// ---- letterboxed camera frames (include/unina_mi355.h at unina_letterbox_geometry) ----
-// The body of the four calls, behind the argument checks of the frame. Nothing is enqueued before the last check has passed.
-static int infer_letterbox(unina_engine* e, const char* who, const CameraSource& c, float conf, float iou, float q, float pad_value,
-                           int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
-  unina_letterbox lb;
-  if (map_boxes != 0 && map_boxes != 1) return fail(e, UNINA_ERR_ARG, "%s: map_boxes must be 0 or 1, got %d", who, map_boxes);
-  if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
-  if (unina_letterbox_geometry(c.w, c.h, (int)e->h.in_w, (int)e->h.in_h, &lb) != UNINA_OK)
-    return fail(e, UNINA_ERR_ARG, "%s: bad frame size %d x %d", who, c.w, c.h);
-  const int rc = make_ready(e);
-  if (rc != UNINA_OK) return rc;
-  return infer_camera(e, c, &lb, pad_value, map_boxes, async, conf, iou, q, out, out_count, stream);
+int unina_infer_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                      GpuDetection* out, int* out_count, hipStream_t stream) {
+  return infer_plain(e, "unina_infer_frame", frame, norm, conf, iou, q, false, out, out_count, stream);
 }
 
-static int letterbox_bgra(unina_engine* e, const char* who, const uint8_t* d_bgra, int w, int h, int pitch, const NormParams* norm,
-                          float conf, float iou, float q, float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count,
-                          hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!d_bgra || !norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null frame / norm / result pointer", who);
-  const int rc = check_bgra_frame(e, who, d_bgra, w, h, pitch);
-  if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, w, h, pitch, 0, *norm), conf, iou, q, pad_value, map_boxes, async, out,
-                         out_count, stream);
-}
-
-static int letterbox_nv12(unina_engine* e, const char* who, const uint8_t* d_y, const uint8_t* d_uv, int w, int h, int y_pitch,
-                          int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes, bool async,
-                          GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
-  const int rc = check_nv12_frame(e, who, d_y, d_uv, w, h, y_pitch, uv_pitch);
-  if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, camera_region(UNINA_FMT_NV12, d_y, d_uv, w, h, y_pitch, uv_pitch, *norm), conf, iou, q, pad_value, map_boxes, async, out,
-                         out_count, stream);
+int unina_infer_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                            GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return infer_plain(e, "unina_infer_frame_async", frame, norm, conf, iou, q, true, d_out, d_out_count, stream);
 }
 
 int unina_infer_letterbox_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                                const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
                                GpuDetection* out, int* out_count, hipStream_t stream) {
-  return letterbox_bgra(e, "unina_infer_letterbox_bgra", d_bgra, src_width, src_height, src_pitch, norm, conf, iou, q, pad_value,
-                        map_boxes, false, out, out_count, stream);
+  const unina_frame f = bgra_frame(d_bgra, src_width, src_height, src_pitch);
+  return infer_letterbox(e, "unina_infer_letterbox_bgra", &f, norm, conf, iou, q, pad_value, map_boxes, false, out, out_count, stream);
 }
 
 int unina_infer_letterbox_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                                      const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
                                      GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  return letterbox_bgra(e, "unina_infer_letterbox_bgra_async", d_bgra, src_width, src_height, src_pitch, norm, conf, iou, q, pad_value,
-                        map_boxes, true, d_out, d_out_count, stream);
+  const unina_frame f = bgra_frame(d_bgra, src_width, src_height, src_pitch);
+  return infer_letterbox(e, "unina_infer_letterbox_bgra_async", &f, norm, conf, iou, q, pad_value, map_boxes, true, d_out, d_out_count, stream);
 }
 
 int unina_infer_letterbox_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
                                int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value, int map_boxes,
                                GpuDetection* out, int* out_count, hipStream_t stream) {
-  return letterbox_nv12(e, "unina_infer_letterbox_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, norm, conf, iou, q,
-                        pad_value, map_boxes, false, out, out_count, stream);
+  const unina_frame f = nv12_frame(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  return infer_letterbox(e, "unina_infer_letterbox_nv12", &f, norm, conf, iou, q, pad_value, map_boxes, false, out, out_count, stream);
 }
 
 int unina_infer_letterbox_nv12_async(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height,
                                      int y_pitch, int uv_pitch, const NormParams* norm, float conf, float iou, float q, float pad_value,
                                      int map_boxes, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  return letterbox_nv12(e, "unina_infer_letterbox_nv12_async", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, norm, conf, iou, q,
-                        pad_value, map_boxes, true, d_out, d_out_count, stream);
+  const unina_frame f = nv12_frame(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  return infer_letterbox(e, "unina_infer_letterbox_nv12_async", &f, norm, conf, iou, q, pad_value, map_boxes, true, d_out, d_out_count, stream);
+}
+
+int unina_infer_letterbox_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                                float pad_value, int map_boxes, GpuDetection* out, int* out_count, hipStream_t stream) {
+  return infer_letterbox(e, "unina_infer_letterbox_frame", frame, norm, conf, iou, q, pad_value, map_boxes, false, out, out_count, stream);
+}
+
+int unina_infer_letterbox_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
+                                      float pad_value, int map_boxes, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
+  return infer_letterbox(e, "unina_infer_letterbox_frame_async", frame, norm, conf, iou, q, pad_value, map_boxes, true, d_out, d_out_count, stream);
 }
 
 // ---- sliced inference (auto_labeler.py:124-199, 255-271): T frame graphs into T device slots, one merge ----
@@ -2185,57 +2161,46 @@ int unina_merge_tiles_async(unina_engine_t* e, const GpuDetection* d_slots, cons
   return enqueue_merge(e, &g, d_slots, d_counts, merge_iou, d_out, d_out_count, nullptr, 0, stream);
 }
 
-// The tiled calls' common body, behind the argument checks of the frame: one frame graph per tile into the handle's slots, one merge.
-static int infer_tiled_camera(unina_engine* e, const char* who, const CameraSource& frame, const unina_tile* tiles, int n_tiles,
-                              float conf, float iou, float q, float merge_iou, GpuDetection* d_out,
-                              int* d_out_count, hipStream_t stream) {
+// The tiled calls' body: one frame per tile into the handle's slots, one merge. The tiles' frames signal nothing: the completion
+// word of the synchronous form belongs to the merge.
+static int infer_tiled(unina_engine* e, const char* who, const unina_frame* f, const unina_tile* tiles, int n_tiles, const NormParams* norm,
+                       float conf, float iou, float q, float merge_iou, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
+  int rc = check_frame_call(e, who, f, norm, async, out, out_count);
+  if (rc != UNINA_OK) return rc;
   TileGatherParams g;
-  int rc = fill_tile_maps(e, who, tiles, n_tiles, frame.w, frame.h, &g);
+  rc = fill_tile_maps(e, who, tiles, n_tiles, f->width, f->height, &g);
   if (rc != UNINA_OK) return rc;
-  rc = make_ready(e);
-  if (rc != UNINA_OK) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
   constexpr size_t kSlotBytes = sizeof(GpuDetection) * MAX_DETECTIONS;
   if (!e->d_tile_slots) HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_tile_slots), UNINA_MAX_TILES * (kSlotBytes + sizeof(int))));
   int* d_counts = reinterpret_cast<int*>(e->d_tile_slots + (size_t)UNINA_MAX_TILES * MAX_DETECTIONS);
-  // the tiles' frames signal nothing: the completion word of the synchronous form belongs to the merge
-  unsigned int* const done = e->done_flag;
-  e->done_flag = nullptr;
-  e->camera_active = true;
-  for (int t = 0; t < n_tiles && rc == UNINA_OK; ++t) {
-    const unina_tile& r = tiles[t];
-    // (a BGRA / RGB / RGBA tile is a pointer offset; an NV12, 4:2:2 or Bayer tile is not: its origin travels to the kernel)
-    const CameraSource c = frame_region(frame, r.x, r.y, r.w, r.h);
-    if (!point_stems_at_camera(e, c))
-      rc = fail(e, UNINA_ERR_STATE, "no stem op reads the input tensor");
-    else
-      rc = unina_infer_async(e, nullptr, conf, iou, q, e->d_tile_slots + (size_t)t * MAX_DETECTIONS, d_counts + t, stream);
-  }
-  e->camera_active = false;
-  restore_stems(e);
-  e->done_flag = done;
-  if (rc != UNINA_OK) return rc;
-  return enqueue_merge(e, &g, e->d_tile_slots, d_counts, merge_iou, d_out, d_out_count, done, e->done_value, stream);
+  const CameraSource frame = frame_source(*f, *norm);
+  auto enqueue = [&](GpuDetection* d_out, int* d_count, unsigned int* done_flag, unsigned int done_value) {
+    for (int t = 0; t < n_tiles; ++t) {
+      // (a BGRA / RGB / RGBA tile is a pointer offset; an NV12, 4:2:2 or Bayer tile is not: its origin travels to the kernel)
+      const CameraSource c = frame_region(frame, tiles[t].x, tiles[t].y, tiles[t].w, tiles[t].h);
+      FrameCall call;
+      call.region = &c;
+      const int rc = enqueue_frame(e, call, conf, iou, q, e->d_tile_slots + (size_t)t * MAX_DETECTIONS, d_counts + t, stream);
+      if (rc != UNINA_OK) return rc;
+    }
+    return enqueue_merge(e, &g, e->d_tile_slots, d_counts, merge_iou, d_out, d_count, done_flag, done_value, stream);
+  };
+  return async ? enqueue(out, out_count, nullptr, 0u) : infer_sync(e, enqueue, out, out_count, stream);
 }
 
 int unina_infer_tiled_bgra_async(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                                  const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
                                  float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!d_bgra || !norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null / misaligned pointer");
-  const int rc = check_bgra_frame(e, "unina_infer_tiled_bgra", d_bgra, src_width, src_height, src_pitch);
-  if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, "unina_infer_tiled_bgra", camera_region(UNINA_FMT_BGRA, d_bgra, nullptr, src_width, src_height, src_pitch, 0, *norm), tiles, n_tiles,
-                            conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  const unina_frame f = bgra_frame(d_bgra, src_width, src_height, src_pitch);
+  return infer_tiled(e, "unina_infer_tiled_bgra", &f, tiles, n_tiles, norm, conf, iou, q, merge_iou, true, d_out, d_out_count, stream);
 }
 
 int unina_infer_tiled_bgra(unina_engine_t* e, const uint8_t* d_bgra, int src_width, int src_height, int src_pitch,
                            const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou, float q,
                            float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_bgra: null result pointer");
-  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
-    return unina_infer_tiled_bgra_async(e, d_bgra, src_width, src_height, src_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
-  }, out, out_count, stream);
+  const unina_frame f = bgra_frame(d_bgra, src_width, src_height, src_pitch);
+  return infer_tiled(e, "unina_infer_tiled_bgra", &f, tiles, n_tiles, norm, conf, iou, q, merge_iou, false, out, out_count, stream);
 }
 
 // The NV12 pair: the same slots, gather and merge; only the stem's source differs (CameraSource::x0 / y0 carry the tile).
@@ -2243,95 +2208,26 @@ int unina_infer_tiled_nv12_async(unina_engine_t* e, const uint8_t* d_y, const ui
                                  int y_pitch, int uv_pitch, const unina_tile* tiles, int n_tiles, const NormParams* norm,
                                  float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count,
                                  hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null / misaligned pointer");
-  const int rc = check_nv12_frame(e, "unina_infer_tiled_nv12", d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
-  if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, "unina_infer_tiled_nv12", camera_region(UNINA_FMT_NV12, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, *norm), tiles, n_tiles,
-                            conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  const unina_frame f = nv12_frame(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  return infer_tiled(e, "unina_infer_tiled_nv12", &f, tiles, n_tiles, norm, conf, iou, q, merge_iou, true, d_out, d_out_count, stream);
 }
 
 int unina_infer_tiled_nv12(unina_engine_t* e, const uint8_t* d_y, const uint8_t* d_uv, int src_width, int src_height, int y_pitch,
                            int uv_pitch, const unina_tile* tiles, int n_tiles, const NormParams* norm, float conf, float iou,
                            float q, float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_nv12: null result pointer");
-  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
-    return unina_infer_tiled_nv12_async(e, d_y, d_uv, src_width, src_height, y_pitch, uv_pitch, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
-  }, out, out_count, stream);
-}
-
-// ---- the frame descriptor: every format through one family of calls (include/unina_mi355.h at unina_pixel_format) ----
-static int check_frame(unina_engine* e, const char* who, const unina_frame* f) {
-  const char* why = frame_defect(f);
-  if (!why) return UNINA_OK;
-  if (f) return fail(e, UNINA_ERR_ARG, "%s: %s (format %d, %d x %d, pitch %d / %d)", who, why, f->format, f->width, f->height, f->pitch[0], f->pitch[1]);
-  return fail(e, UNINA_ERR_ARG, "%s: %s", who, why);
-}
-
-static int infer_frame(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, bool async, float conf, float iou,
-                       float q, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
-  if (async && ((uintptr_t)out & 15)) return fail(e, UNINA_ERR_ARG, "%s: misaligned result pointer", who);
-  int rc = check_frame(e, who, f);
-  if (rc == UNINA_OK) rc = make_ready(e);
-  if (rc != UNINA_OK) return rc;
-  return infer_camera(e, frame_source(*f, *norm), nullptr, 0.f, 0, async, conf, iou, q, out, out_count, stream);
-}
-
-int unina_infer_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
-                      GpuDetection* out, int* out_count, hipStream_t stream) {
-  return infer_frame(e, "unina_infer_frame", frame, norm, false, conf, iou, q, out, out_count, stream);
-}
-
-int unina_infer_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
-                            GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  return infer_frame(e, "unina_infer_frame_async", frame, norm, true, conf, iou, q, d_out, d_out_count, stream);
-}
-
-static int letterbox_frame(unina_engine* e, const char* who, const unina_frame* f, const NormParams* norm, float conf, float iou, float q,
-                           float pad_value, int map_boxes, bool async, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!norm || !out || !out_count) return fail(e, UNINA_ERR_ARG, "%s: null norm / result pointer", who);
-  const int rc = check_frame(e, who, f);
-  if (rc != UNINA_OK) return rc;
-  return infer_letterbox(e, who, frame_source(*f, *norm), conf, iou, q, pad_value, map_boxes, async, out, out_count, stream);
-}
-
-int unina_infer_letterbox_frame(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
-                                float pad_value, int map_boxes, GpuDetection* out, int* out_count, hipStream_t stream) {
-  return letterbox_frame(e, "unina_infer_letterbox_frame", frame, norm, conf, iou, q, pad_value, map_boxes, false, out, out_count, stream);
-}
-
-int unina_infer_letterbox_frame_async(unina_engine_t* e, const unina_frame* frame, const NormParams* norm, float conf, float iou, float q,
-                                      float pad_value, int map_boxes, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  return letterbox_frame(e, "unina_infer_letterbox_frame_async", frame, norm, conf, iou, q, pad_value, map_boxes, true, d_out, d_out_count,
-                         stream);
-}
-
-static int tiled_frame(unina_engine* e, const char* who, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
-                       float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count, hipStream_t stream) {
-  if (!norm || !d_out || !d_out_count || ((uintptr_t)d_out & 15)) return fail(e, UNINA_ERR_ARG, "%s: null / misaligned pointer", who);
-  const int rc = check_frame(e, who, frame);
-  if (rc != UNINA_OK) return rc;
-  return infer_tiled_camera(e, who, frame_source(*frame, *norm), tiles, n_tiles, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  const unina_frame f = nv12_frame(d_y, d_uv, src_width, src_height, y_pitch, uv_pitch);
+  return infer_tiled(e, "unina_infer_tiled_nv12", &f, tiles, n_tiles, norm, conf, iou, q, merge_iou, false, out, out_count, stream);
 }
 
 int unina_infer_tiled_frame_async(unina_engine_t* e, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
                                   float conf, float iou, float q, float merge_iou, GpuDetection* d_out, int* d_out_count,
                                   hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  return tiled_frame(e, "unina_infer_tiled_frame_async", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_out_count, stream);
+  return infer_tiled(e, "unina_infer_tiled_frame_async", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, true, d_out, d_out_count, stream);
 }
 
 int unina_infer_tiled_frame(unina_engine_t* e, const unina_frame* frame, const unina_tile* tiles, int n_tiles, const NormParams* norm,
                             float conf, float iou, float q, float merge_iou, GpuDetection* out, int* out_count, hipStream_t stream) {
-  if (!e) return UNINA_ERR_ARG;
-  if (!out || !out_count) return fail(e, UNINA_ERR_ARG, "unina_infer_tiled_frame: null result pointer");
-  return infer_sync(e, [&](GpuDetection* d_out, int* d_count) {
-    return tiled_frame(e, "unina_infer_tiled_frame", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, d_out, d_count, stream);
-  }, out, out_count, stream);
+  return infer_tiled(e, "unina_infer_tiled_frame", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, false, out, out_count, stream);
 }
 
 int unina_debug_post_stamps(unina_engine_t* e, long long* out8) {
@@ -2512,13 +2408,8 @@ int unina_set_op_config(unina_engine_t* e, int op_index, int cfg) {
 // (each output element accumulates its K terms in the same order under every configuration).
 int unina_autotune(unina_engine_t* e, int iters, hipStream_t stream) {
   if (!e || iters < 1) return UNINA_ERR_ARG;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->bufs[e->images_buf].ptr && !e->camera_active) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
-  if (e->plan_dirty) {
-    int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  int rc = launch_all(e, stream);
+  int rc = make_ready(e);
+  if (rc == UNINA_OK) rc = launch_all(e, stream);
   if (rc != UNINA_OK) return rc;
   if (e->force_cfg.size() < e->ops.size()) e->force_cfg.assign(e->ops.size(), -1);
   hipEvent_t a, b;
@@ -2549,19 +2440,14 @@ int unina_autotune(unina_engine_t* e, int iters, hipStream_t stream) {
 
 int unina_profile_ops(unina_engine_t* e, int iters, float* ms_per_op, hipStream_t stream) {
   if (!e || !ms_per_op || iters < 1) return UNINA_ERR_ARG;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->bufs[e->images_buf].ptr && !e->camera_active) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
-  if (e->plan_dirty) {
-    int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
-  int rc = launch_all(e, stream);  // warm-up: every buffer holds real activations
+  int rc = make_ready(e);
+  if (rc == UNINA_OK) rc = launch_all(e, stream);  // warm-up: every buffer holds real activations
   if (rc != UNINA_OK) return rc;
   hipEvent_t a, b;
   HIPCHK(e, hipEventCreate(&a));
   HIPCHK(e, hipEventCreate(&b));
   PostParams pp;   // which head output convs the frame's decode launch computes itself (they are not launched in a frame)
-  fill_post_params(e, &pp, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
+  fill_post_params(e, &pp, FrameCall{}, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
   for (size_t i = 0; i < e->ops.size(); ++i) {
     if (!launches_in_frame(e, i, pp)) {
       ms_per_op[i] = 0.f;
@@ -2580,15 +2466,10 @@ int unina_profile_ops(unina_engine_t* e, int iters, float* ms_per_op, hipStream_
 // (0 when the post-process is one launch). Thresholds as given.
 int unina_profile_post(unina_engine_t* e, int iters, float conf, float iou, float q, float* ms2, hipStream_t stream) {
   if (!e || !ms2 || iters < 1) return UNINA_ERR_ARG;
-  HIPCHK(e, hipSetDevice(e->device));
-  if (!e->bufs[e->images_buf].ptr && !e->camera_active) return fail(e, UNINA_ERR_STATE, "tensor 'images' is not bound");
-  if (e->plan_dirty) {
-    int rc = plan(e);
-    if (rc != UNINA_OK) return rc;
-  }
+  int rc0 = make_ready(e);
+  if (rc0 != UNINA_OK) return rc0;
   PostParams pp;
-  fill_post_params(e, &pp, conf, iou, q, e->d_result->det, &e->d_result->count, &e->d_result->candidates, true);
-  pp.done_flag = nullptr;
+  fill_post_params(e, &pp, FrameCall{}, conf, iou, q, e->d_result->det, &e->d_result->count, &e->d_result->candidates, true);
   LaunchDesc d[2];
   const int npost = postprocess_desc(pp, d);
   if (npost < 1) return fail(e, UNINA_ERR_STATE, "post-process launch shape");
@@ -2626,7 +2507,7 @@ int unina_debug_folded_heads(unina_engine_t* e) {
   if (!e) return -UNINA_ERR_ARG;
   if (e->plan_dirty && plan(e) != UNINA_OK) return -UNINA_ERR_STATE;
   PostParams pp;   // exactly what unina_infer_async hands to the frame's post-process
-  fill_post_params(e, &pp, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
+  fill_post_params(e, &pp, FrameCall{}, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
   int mask = 0;
   for (int h = 0; h < 3; ++h)
     if (pp.mode == 2 && pp.h1[h] != nullptr) mask |= 1 << h;

@@ -30,12 +30,6 @@ struct PreParams {
   float* out;             // [3][dst_h][dst_w]
 };
 
-// the frame (whole: origin 0), the output size and, for the letterbox kinds, the inner rectangle
-PreParams pre_params(int kind, const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, float* out, int dw, int dh,
-                     const NormParams& norm, const unina_letterbox& lb = {0, 0, 0, 0}, float pad = 0.f) {
-  return PreParams{CameraSource{plane, uv, w, h, pitch, uv_pitch, dw, dh, norm, lb.left, lb.top, lb.new_w, lb.new_h, pad, kind, 0, 0}, out};
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void preprocess_quads_kernel(const PreParams p) {
   const CameraSource& q = p.cam;
@@ -118,6 +112,31 @@ hipError_t launch_quads(const PreParams& q, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// One launch of `region` into the dst_width x dst_height tensor as `kind` (frame_kind's answer, or the kind a reference-named entry
+// point is defined as); lb: the inner rectangle of the letterbox kinds
+hipError_t launch_frame(const CameraSource& region, int kind, float* d_output, int dst_width, int dst_height, hipStream_t stream,
+                        const unina_letterbox* lb = nullptr, float pad_value = 0.f) {
+  const PreParams q{launch_source(region, kind, dst_width, dst_height, lb, pad_value), d_output};
+  switch (kind) {
+    case kSrcBgraTap: return launch_quads<kSrcBgraTap>(q, stream);
+    case kSrcBgraResize: return launch_quads<kSrcBgraResize>(q, stream);
+    case kSrcNv12Tap: return launch_quads<kSrcNv12Tap>(q, stream);
+    case kSrcNv12Resize: return launch_quads<kSrcNv12Resize>(q, stream);
+    case kSrcBgraLetterbox: return launch_quads<kSrcBgraLetterbox>(q, stream);
+    case kSrcNv12Letterbox: return launch_quads<kSrcNv12Letterbox>(q, stream);
+    case kSrcFrameTap: return launch_quads<kSrcFrameTap>(q, stream);
+    case kSrcFrameResize: return launch_quads<kSrcFrameResize>(q, stream);
+    case kSrcFrameLetterbox: return launch_quads<kSrcFrameLetterbox>(q, stream);
+  }
+  return hipErrorInvalidValue;
+}
+int code_of(hipError_t err) { return err == hipSuccess ? UNINA_OK : UNINA_ERR_HIP; }
+
+// The whole frame of a format-named entry point (BGRA: uv == nullptr)
+CameraSource plane_source(const uint8_t* plane, const uint8_t* uv, int w, int h, int pitch, int uv_pitch, const NormParams& norm) {
+  return frame_source(unina_frame{uv ? UNINA_FMT_NV12 : UNINA_FMT_BGRA, w, h, {plane, uv}, {pitch, uv_pitch}}, norm);
+}
+
 }  // namespace
 
 extern "C" {
@@ -136,20 +155,20 @@ hipError_t preprocess_bgra_resize(const uint8_t* d_input, float* d_output, int s
                                   int dst_width, int dst_height, NormParams params, hipStream_t stream) {
   if (!d_input || !d_output || src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0 || src_pitch < 4 * src_width)
     return hipErrorInvalidValue;
-  return launch_quads<kSrcBgraResize>(pre_params(kSrcBgraResize, d_input, nullptr, src_width, src_height, src_pitch, 0, d_output, dst_width, dst_height, params), stream);
+  return launch_frame(plane_source(d_input, nullptr, src_width, src_height, src_pitch, 0, params), kSrcBgraResize, d_output, dst_width, dst_height, stream);
 }
 
 hipError_t preprocess_bgra(const uint8_t* d_input, float* d_output, int width, int height, int pitch, NormParams params,
                            hipStream_t stream) {
   if (!d_input || !d_output || width <= 0 || height <= 0 || pitch < 4 * width || (pitch & 3)) return hipErrorInvalidValue;
-  return launch_quads<kSrcBgraTap>(pre_params(kSrcBgraTap, d_input, nullptr, width, height, pitch, 0, d_output, width, height, params), stream);
+  return launch_frame(plane_source(d_input, nullptr, width, height, pitch, 0, params), kSrcBgraTap, d_output, width, height, stream);
 }
 
 hipError_t preprocess_nv12(const uint8_t* d_y_plane, const uint8_t* d_uv_plane, float* d_output, int width, int height,
                            int y_pitch, int uv_pitch, NormParams params, hipStream_t stream) {
   if (!d_y_plane || !d_uv_plane || !d_output || width <= 0 || height <= 0 || y_pitch < width || uv_pitch < width)
     return hipErrorInvalidValue;
-  return launch_quads<kSrcNv12Tap>(pre_params(kSrcNv12Tap, d_y_plane, d_uv_plane, width, height, y_pitch, uv_pitch, d_output, width, height, params), stream);
+  return launch_frame(plane_source(d_y_plane, d_uv_plane, width, height, y_pitch, uv_pitch, params), kSrcNv12Tap, d_output, width, height, stream);
 }
 
 // NV12 of any size -> the dst_width x dst_height tensor (camera_source.h defines the resize; the reference has none). At
@@ -162,9 +181,8 @@ hipError_t unina_preprocess_nv12_resize(const uint8_t* d_y_plane, const uint8_t*
       y_pitch < src_width || uv_pitch < src_width || uv_pitch < 2 * ((src_width + 1) / 2))
     return hipErrorInvalidValue;
   const bool same = dst_width == src_width && dst_height == src_height;
-  const PreParams q = pre_params(same ? kSrcNv12Tap : kSrcNv12Resize, d_y_plane, d_uv_plane, src_width, src_height, y_pitch, uv_pitch, d_output,
-                                 dst_width, dst_height, params);
-  return same ? launch_quads<kSrcNv12Tap>(q, stream) : launch_quads<kSrcNv12Resize>(q, stream);
+  return launch_frame(plane_source(d_y_plane, d_uv_plane, src_width, src_height, y_pitch, uv_pitch, params), same ? kSrcNv12Tap : kSrcNv12Resize,
+                      d_output, dst_width, dst_height, stream);
 }
 
 // Host only. Python's round() is round-half-to-even: nearbyint in the default rounding mode (lround rounds halves away from zero:
@@ -189,8 +207,8 @@ hipError_t unina_preprocess_letterbox_bgra(const uint8_t* d_input, float* d_outp
   if (!d_input || !d_output || src_pitch < 4 * src_width || (src_pitch & 3) || ((uintptr_t)d_input & 3) ||
       unina_letterbox_geometry(src_width, src_height, dst_width, dst_height, &lb) != UNINA_OK)
     return hipErrorInvalidValue;
-  return launch_quads<kSrcBgraLetterbox>(pre_params(kSrcBgraLetterbox, d_input, nullptr, src_width, src_height, src_pitch, 0, d_output, dst_width,
-                                                    dst_height, params, lb, pad_value), stream);
+  return launch_frame(plane_source(d_input, nullptr, src_width, src_height, src_pitch, 0, params), kSrcBgraLetterbox, d_output, dst_width, dst_height, stream,
+                      &lb, pad_value);
 }
 
 hipError_t unina_preprocess_letterbox_nv12(const uint8_t* d_y_plane, const uint8_t* d_uv_plane, float* d_output, int src_width,
@@ -200,46 +218,19 @@ hipError_t unina_preprocess_letterbox_nv12(const uint8_t* d_y_plane, const uint8
   if (!d_y_plane || !d_uv_plane || !d_output || unina_letterbox_geometry(src_width, src_height, dst_width, dst_height, &lb) != UNINA_OK ||
       y_pitch < src_width || uv_pitch < src_width || uv_pitch < 2 * ((src_width + 1) / 2))
     return hipErrorInvalidValue;
-  return launch_quads<kSrcNv12Letterbox>(pre_params(kSrcNv12Letterbox, d_y_plane, d_uv_plane, src_width, src_height, y_pitch, uv_pitch, d_output,
-                                                    dst_width, dst_height, params, lb, pad_value), stream);
+  return launch_frame(plane_source(d_y_plane, d_uv_plane, src_width, src_height, y_pitch, uv_pitch, params), kSrcNv12Letterbox, d_output,
+                      dst_width, dst_height, stream, &lb, pad_value);
 }
 
 // ---- a unina_frame of any format (include/unina_mi355.h at unina_pixel_format) ----
-static int launch_frame(const CameraSource& region, float* d_output, int dst_width, int dst_height, const unina_letterbox* lb, float pad_value,
-                        hipStream_t stream) {
-  PreParams q{region, d_output};
-  q.cam.dst_w = dst_width;
-  q.cam.dst_h = dst_height;
-  q.cam.kind = frame_kind(region.format, region.w, region.h, dst_width, dst_height, lb);
-  if (lb) {
-    q.cam.in_x0 = lb->left;
-    q.cam.in_y0 = lb->top;
-    q.cam.in_w = lb->new_w;
-    q.cam.in_h = lb->new_h;
-    q.cam.pad = pad_value;
-  }
-  hipError_t err = hipErrorInvalidValue;
-  switch (q.cam.kind) {
-    case kSrcBgraTap: err = launch_quads<kSrcBgraTap>(q, stream); break;
-    case kSrcBgraResize: err = launch_quads<kSrcBgraResize>(q, stream); break;
-    case kSrcNv12Tap: err = launch_quads<kSrcNv12Tap>(q, stream); break;
-    case kSrcNv12Resize: err = launch_quads<kSrcNv12Resize>(q, stream); break;
-    case kSrcBgraLetterbox: err = launch_quads<kSrcBgraLetterbox>(q, stream); break;
-    case kSrcNv12Letterbox: err = launch_quads<kSrcNv12Letterbox>(q, stream); break;
-    case kSrcFrameTap: err = launch_quads<kSrcFrameTap>(q, stream); break;
-    case kSrcFrameResize: err = launch_quads<kSrcFrameResize>(q, stream); break;
-    case kSrcFrameLetterbox: err = launch_quads<kSrcFrameLetterbox>(q, stream); break;
-  }
-  return err == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
-}
-
 int unina_preprocess_frame(const unina_frame* frame, const unina_tile* region, float* d_output, int dst_width, int dst_height,
                            const NormParams* params, hipStream_t stream) {
   if (frame_defect(frame) || !d_output || !params || dst_width <= 0 || dst_height <= 0) return UNINA_ERR_ARG;
   const unina_tile whole = {0, 0, frame->width, frame->height};
   const unina_tile& r = region ? *region : whole;
   if (r.w <= 0 || r.h <= 0 || r.x < 0 || r.y < 0 || (long long)r.x + r.w > frame->width || (long long)r.y + r.h > frame->height) return UNINA_ERR_ARG;
-  return launch_frame(frame_region(frame_source(*frame, *params), r.x, r.y, r.w, r.h), d_output, dst_width, dst_height, nullptr, 0.f, stream);
+  const int kind = frame_kind(frame->format, r.w, r.h, dst_width, dst_height, nullptr);
+  return code_of(launch_frame(frame_region(frame_source(*frame, *params), r.x, r.y, r.w, r.h), kind, d_output, dst_width, dst_height, stream));
 }
 
 int unina_preprocess_letterbox_frame(const unina_frame* frame, float* d_output, int dst_width, int dst_height, float pad_value,
@@ -247,7 +238,8 @@ int unina_preprocess_letterbox_frame(const unina_frame* frame, float* d_output, 
   unina_letterbox lb;
   if (frame_defect(frame) || !d_output || !params || unina_letterbox_geometry(frame->width, frame->height, dst_width, dst_height, &lb) != UNINA_OK)
     return UNINA_ERR_ARG;
-  return launch_frame(frame_source(*frame, *params), d_output, dst_width, dst_height, &lb, pad_value, stream);
+  const int kind = frame_kind(frame->format, frame->width, frame->height, dst_width, dst_height, &lb);
+  return code_of(launch_frame(frame_source(*frame, *params), kind, d_output, dst_width, dst_height, stream, &lb, pad_value));
 }
 
 float* allocate_preprocess_buffer(int width, int height) {  // nullptr on failure (cuda_preprocess.cu:395-405)

@@ -405,29 +405,32 @@ class Engine:
         self._check(self.L.unina_serial_latency(self.h, ptrs, len(frames), n_calls, conf_thr, iou_thr, conformal_q, lat, _stream_ptr(stream)))
         return np.array(lat[:], dtype=np.float64) * 1e-3
 
+    def _camera_call(self, symbol: str, lead, norm, tail, out, stream):
+        """One camera call of the ABI: `symbol`(handle, *lead, norm, *tail, records, count, stream). `out=None`: synchronous into a
+        host buffer, returns the kept detections; `out` = an int32 CUDA tensor as infer_async's: `symbol`_async, returns it."""
+        if norm is None:
+            norm = self.L.create_norm_params_imagenet()
+        if out is not None:
+            base = out.data_ptr()
+            self._check(getattr(self.L, symbol + "_async")(self.h, *lead, C.byref(norm), *tail, base + 32, base, _stream_ptr(stream)))
+            return out
+        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
+        n = C.c_int()
+        self._check(getattr(self.L, symbol)(self.h, *lead, C.byref(norm), *tail, host.ctypes.data, C.byref(n), _stream_ptr(stream)))
+        return host[:n.value].copy()
+
     def infer_bgra(self, frame, width: int, height: int, pitch: int, norm: Optional[NormParams] = None,
                    conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, stream=None):
         """Camera frame (uint8 CUDA tensor, pitched BGRA) -> detections: the pre-process runs inside the stem kernel
         (perception_node.cpp:601-656 as one launch sequence, no fp32 tensor in between)."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        out = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_bgra(self.h, frame.data_ptr(), width, height, pitch, C.byref(norm), conf_thr, iou_thr,
-                                            conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
-        return out[:n.value].copy()
+        return self._camera_call("unina_infer_bgra", (_ptr(frame), width, height, pitch), norm, (conf_thr, iou_thr, conformal_q), None, stream)
 
     def infer_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, norm: Optional[NormParams] = None,
                    conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, stream=None):
         """NV12 camera frame (uint8 CUDA tensors: luma plane `y`, interleaved chroma plane `uv` of (height + 1) // 2 rows)
         -> detections, the pre-process inside the stem kernel (unina_infer_nv12; camera.nv12_to_tensor is its numpy twin)."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        out = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, C.byref(norm), conf_thr,
-                                            iou_thr, conformal_q, out.ctypes.data, C.byref(n), _stream_ptr(stream)))
-        return out[:n.value].copy()
+        return self._camera_call("unina_infer_nv12", (_ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch), norm,
+                                 (conf_thr, iou_thr, conformal_q), None, stream)
 
     def infer_letterbox_bgra(self, frame, width: int, height: int, pitch: int, norm: Optional[NormParams] = None,
                              conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, pad_value: float = 114.0,
@@ -436,116 +439,47 @@ class Engine:
         `pad_value` around it, all computed in the stem kernel. map_boxes: boxes back in CAMERA pixels (mapped where the
         post-process writes them; camera.unmap_boxes is the numpy twin), False: network pixels. `out=None`: synchronous,
         returns the kept detections; `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_letterbox_bgra_async(self.h, _ptr(frame), width, height, pitch, C.byref(norm), conf_thr,
-                                                                iou_thr, conformal_q, pad_value, int(map_boxes), base + 32, base,
-                                                                _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_letterbox_bgra(self.h, _ptr(frame), width, height, pitch, C.byref(norm), conf_thr, iou_thr,
-                                                      conformal_q, pad_value, int(map_boxes), host.ctypes.data, C.byref(n),
-                                                      _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_letterbox_bgra", (_ptr(frame), width, height, pitch), norm,
+                                 (conf_thr, iou_thr, conformal_q, pad_value, int(map_boxes)), out, stream)
 
     def infer_letterbox_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, norm: Optional[NormParams] = None,
                              conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, pad_value: float = 114.0,
                              map_boxes: bool = True, out=None, stream=None):
         """infer_letterbox_bgra for an NV12 frame (planes and pitches as infer_nv12)."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_letterbox_nv12_async(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch,
-                                                                C.byref(norm), conf_thr, iou_thr, conformal_q, pad_value,
-                                                                int(map_boxes), base + 32, base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_letterbox_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, C.byref(norm),
-                                                      conf_thr, iou_thr, conformal_q, pad_value, int(map_boxes), host.ctypes.data,
-                                                      C.byref(n), _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_letterbox_nv12", (_ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch), norm,
+                                 (conf_thr, iou_thr, conformal_q, pad_value, int(map_boxes)), out, stream)
 
     def infer_tiled_nv12(self, y, uv, width: int, height: int, y_pitch: int, uv_pitch: int, tiles=None,
                          norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1,
                          merge_iou: float = 0.45, out=None, stream=None):
         """infer_tiled_bgra on an NV12 frame: the tile's origin goes to the stem kernel (it enters the chroma index, so it may
         be odd). `tiles`, `out` and the result as there."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
         if tiles is None:
             tiles = self.default_tiles(width, height)
-        arr = _tile_array(tiles)
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_tiled_nv12_async(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, arr,
-                                                            len(tiles), C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou,
-                                                            base + 32, base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_tiled_nv12(self.h, _ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, arr, len(tiles),
-                                                  C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou, host.ctypes.data,
-                                                  C.byref(n), _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_tiled_nv12", (_ptr(y), _ptr(uv), width, height, y_pitch, uv_pitch, _tile_array(tiles), len(tiles)),
+                                 norm, (conf_thr, iou_thr, conformal_q, merge_iou), out, stream)
 
     def infer_frame(self, frame: Frame, norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45,
                     conformal_q: float = 0.1, out=None, stream=None):
         """A camera frame of any unina_pixel_format (Frame) -> detections, the pre-process inside the stem kernel
         (unina_infer_frame; camera.frame_to_tensor is its numpy twin). `out=None`: synchronous, returns the kept detections;
         `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_frame_async(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, base + 32,
-                                                       base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_frame(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, host.ctypes.data,
-                                             C.byref(n), _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_frame", (C.byref(frame),), norm, (conf_thr, iou_thr, conformal_q), out, stream)
 
     def infer_letterbox_frame(self, frame: Frame, norm: Optional[NormParams] = None, conf_thr: float = 0.5, iou_thr: float = 0.45,
                               conformal_q: float = 0.1, pad_value: float = 114.0, map_boxes: bool = True, out=None, stream=None):
         """infer_letterbox_bgra for a Frame of any format."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_letterbox_frame_async(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q,
-                                                                 pad_value, int(map_boxes), base + 32, base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_letterbox_frame(self.h, C.byref(frame), C.byref(norm), conf_thr, iou_thr, conformal_q, pad_value,
-                                                       int(map_boxes), host.ctypes.data, C.byref(n), _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_letterbox_frame", (C.byref(frame),), norm,
+                                 (conf_thr, iou_thr, conformal_q, pad_value, int(map_boxes)), out, stream)
 
     def infer_tiled_frame(self, frame: Frame, tiles=None, norm: Optional[NormParams] = None, conf_thr: float = 0.5,
                           iou_thr: float = 0.45, conformal_q: float = 0.1, merge_iou: float = 0.45, out=None, stream=None):
         """infer_tiled_bgra for a Frame of any format (BGRA / RGB / RGBA tiles are pointer offsets, the other formats send the
         tile's origin to the stem kernel)."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
         if tiles is None:
             tiles = self.default_tiles(frame.width, frame.height)
-        arr = _tile_array(tiles)
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_tiled_frame_async(self.h, C.byref(frame), arr, len(tiles), C.byref(norm), conf_thr, iou_thr,
-                                                             conformal_q, merge_iou, base + 32, base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_tiled_frame(self.h, C.byref(frame), arr, len(tiles), C.byref(norm), conf_thr, iou_thr,
-                                                   conformal_q, merge_iou, host.ctypes.data, C.byref(n), _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_tiled_frame", (C.byref(frame), _tile_array(tiles), len(tiles)), norm,
+                                 (conf_thr, iou_thr, conformal_q, merge_iou), out, stream)
 
     def default_tiles(self, width: int, height: int):
         """The reference's default slicing (20 % overlap) at the engine's input size, exact repeats dropped."""
@@ -559,23 +493,10 @@ class Engine:
         a pointer offset, nothing is copied -- and one merge on the GPU; boxes in CAMERA-FRAME pixels. `tiles=None` slices
         with the reference's defaults for the engine's input size. `out=None`: synchronous, returns the kept detections
         (DET_DTYPE); `out` = an int32 CUDA tensor as infer_async's: asynchronous, returns it."""
-        if norm is None:
-            norm = self.L.create_norm_params_imagenet()
         if tiles is None:
             tiles = self.default_tiles(width, height)
-        arr = _tile_array(tiles)
-        if out is not None:
-            base = out.data_ptr()
-            self._check(self.L.unina_infer_tiled_bgra_async(self.h, frame.data_ptr(), width, height, pitch, arr, len(tiles),
-                                                            C.byref(norm), conf_thr, iou_thr, conformal_q, merge_iou, base + 32,
-                                                            base, _stream_ptr(stream)))
-            return out
-        host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
-        n = C.c_int()
-        self._check(self.L.unina_infer_tiled_bgra(self.h, frame.data_ptr(), width, height, pitch, arr, len(tiles), C.byref(norm),
-                                                  conf_thr, iou_thr, conformal_q, merge_iou, host.ctypes.data, C.byref(n),
-                                                  _stream_ptr(stream)))
-        return host[:n.value].copy()
+        return self._camera_call("unina_infer_tiled_bgra", (_ptr(frame), width, height, pitch, _tile_array(tiles), len(tiles)), norm,
+                                 (conf_thr, iou_thr, conformal_q, merge_iou), out, stream)
 
     def merge_tiles(self, slots, counts, tiles, merge_iou: float = 0.45, out=None, stream=None):
         """The merge alone (unina_merge_tiles_async): `slots` int32 CUDA tensor [T, 8 * MAX_DETECTIONS] (records), `counts`
