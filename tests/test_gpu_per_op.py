@@ -100,11 +100,16 @@ def test_per_op_table_int8_with_saturation(pkg, sd7, torch_cuda, tmp_path, size)
         e.close()
 
 
-@pytest.mark.parametrize("size", [(80, 112), (96, 160)], ids=IDS)
-@pytest.mark.parametrize("precision", ["fp16", "int8"])
+# (STRICT at 80x112 only: the smallest of these sizes, every level has a partial tile; the split-fp16 rows are the table's most irregular)
+TILE_CASES = [(p, s) for p in ("fp16", "int8") for s in ((80, 112), (96, 160))] + [("strict", (80, 112))]
+
+
+@pytest.mark.parametrize("precision,size", TILE_CASES, ids=[f"{p}-{IDS(s)}" for p, s in TILE_CASES])
 def test_every_tile_configuration_within_the_bound(pkg, sd7, torch_cuda, tmp_path, precision, size):
     """Each tile configuration forced on every op that accepts it, then the autotuner's choice: the outputs of those ops
-    against float64 (test_tile_configs_and_autotune_are_bit_identical compares them with the default configuration only)."""
+    against float64 (test_tile_configs_and_autotune_are_bit_identical compares them with the default configuration only).
+    STRICT engines: the heads under every forced configuration also stay within the 5e-5 of the default configuration's that
+    test_frame_as_launched_equals_per_op_table allows a strict frame (the configurations differ in fp32 summation order)."""
     g = pkg.graph.Graph(in_h=size[0], in_w=size[1])
     b, e, _ = _make(pkg, sd7, g, precision, tmp_path, _amax(pkg, sd7, size) if precision == "int8" else None)
     try:
@@ -113,13 +118,17 @@ def test_every_tile_configuration_within_the_bound(pkg, sd7, torch_cuda, tmp_pat
         xd = torch_cuda.from_numpy(x).cuda()
         infos = e.op_infos()
         names = e.conv_configs()
+        default = {k: v.copy() for k, v in e.forward(xd).items()} if precision == "strict" else None
         tried = 0
         for cfg in range(len(names)):
             applied = [i for i, o in enumerate(infos) if o["kind"] == 1 and e.set_op_config(i, cfg)]
             if not applied:
                 continue
             tried += 1
-            _hold(b, x, _teacher(b, e, xd), f"{precision} {IDS(size)} config {cfg} {names[cfg]} on {len(applied)} ops", ops=applied)
+            teacher = _teacher(b, e, xd)
+            _hold(b, x, teacher, f"{precision} {IDS(size)} config {cfg} {names[cfg]} on {len(applied)} ops", ops=applied)
+            for k in default or ():
+                np.testing.assert_allclose(teacher[k], default[k], atol=5e-5, rtol=0, err_msg=f"config {cfg} {k}")
             for i in applied:
                 e.set_op_config(i, -1)
         assert tried >= 6

@@ -54,6 +54,18 @@ def test_forced_configuration_names_exist(pkg):
     build.build_native()
     lib = engine.load_library()
     names = [lib.unina_conv_config_name(i).decode() for i in range(lib.unina_conv_config_count())]
+    # one name per enumerator of ConvConfig as kernels.h states it, and no two configurations share one: a name is built from its
+    # row's tile, so two equal names would be one tile in two slots. The rows here are the fp16 ones, so the slots that exist for
+    # split fp16 alone (kCfgWsS*) are empty, "n/a" -- those and no others.
+    import os, re
+    header = open(os.path.join(build.CSRC, "kernels.h")).read()
+    body = re.search(r"enum ConvConfig : int \{(.*?)\};", header, re.S).group(1)
+    enum = [t.split("=")[0].strip() for t in re.sub(r"//[^\n]*", "", body).split(",") if t.strip()]
+    assert enum[-1] == "kCfgCount" and len(set(enum)) == len(enum)
+    assert len(names) == len(enum) - 1
+    assert [e for e, n in zip(enum, names) if n == "n/a"] == [e for e in enum if e.startswith("kCfgWsS")] != []
+    kernels = [n for n in names if n != "n/a"]
+    assert len(set(kernels)) == len(kernels), sorted(n for n in set(kernels) if kernels.count(n) > 1)
     for key in ("fp16", "fp16-small"):
         for n in LH.DUAL[key][1]:
             assert names.count(n) == 1, n

@@ -58,19 +58,17 @@ __device__ __forceinline__ void stamp_entry(const ConvParams& p, long long t) {
   if (p.stamps && blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) p.stamps[7] = t;
 }
 
-__device__ __forceinline__ void stamp(const ConvParams& p, int k) {
-  if (p.stamps && blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) {
-    p.stamps[k] = __builtin_amdgcn_s_memtime();
-    if (k == 0 || k == 4) p.stamps[5 + (k >> 2)] = wall_clock64();  // 100 MHz reference: effective shader clock
-  }
+// Phase stamp k, written by thread 0 of the launch's mid workgroup -- or, from a body that runs as workgroup `bid` of `nwg` inside
+// a larger grid (dual launches), of the mid workgroup of ITS conv.
+__device__ __forceinline__ void stamp_now(const ConvParams& p, int k) {
+  p.stamps[k] = __builtin_amdgcn_s_memtime();
+  if (k == 0 || k == 4) p.stamps[5 + (k >> 2)] = wall_clock64();  // 100 MHz reference: effective shader clock
 }
-
-// Same for a body that runs as workgroup `bid` of `nwg` inside a larger grid (dual launches): the mid workgroup of ITS conv.
-__device__ __forceinline__ void stamp_b(const ConvParams& p, int k, int bid, int nwg) {
-  if (p.stamps && bid == (nwg >> 1) && threadIdx.x == 0) {
-    p.stamps[k] = __builtin_amdgcn_s_memtime();
-    if (k == 0 || k == 4) p.stamps[5 + (k >> 2)] = wall_clock64();
-  }
+__device__ __forceinline__ void stamp(const ConvParams& p, int k) {
+  if (p.stamps && blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) stamp_now(p, k);
+}
+__device__ __forceinline__ void stamp(const ConvParams& p, int k, int bid, int nwg) {
+  if (p.stamps && bid == (nwg >> 1) && threadIdx.x == 0) stamp_now(p, k);
 }
 
 // debug: every workgroup's start / end on the 100 MHz wall clock (dispatch ramp and tail of a launch)
@@ -83,10 +81,13 @@ __device__ __forceinline__ void stamp_wg(const ConvParams& p, int which) {
 //   fp32: chunk = 4 k  -> block = 16 k, four v_mfma_f32_16x16x4_f32 (exact fp32 products and accumulation);
 //         MFMA e takes element e of every lane's chunk, i.e. k = {4*lq + e}: A and B use the same k permutation.
 //   int8: chunk = 16 k -> block = 64 k, one v_mfma_i32_16x16x64_i8 (exact int32 accumulation)
+// kDType / kTag: the DType of T and its tag in the kernels' display names.
 typedef int intx4 __attribute__((ext_vector_type(4)));
 template <typename T> struct Elem;
 template <> struct Elem<half_t> {
   static constexpr int kChunk = 8, kBlockK = 32, kPlanes = 1;
+  static constexpr int kDType = kF16;
+  static constexpr const char* kTag = "f16";
   typedef half8 frag;
   typedef floatx4 acc_t;
   static __device__ __forceinline__ acc_t mma(const frag& a, const frag& b, acc_t c) {
@@ -99,6 +100,8 @@ template <> struct Elem<half_t> {
 // bytes behind the hi plane (the next 1-KiB block of a staged block pair). Three MFMAs per k block, small terms first.
 template <> struct Elem<s16_t> {
   static constexpr int kChunk = 8, kBlockK = 32, kPlanes = 2;
+  static constexpr int kDType = kS16;
+  static constexpr const char* kTag = "s16";
   typedef half8x2 frag;
   typedef floatx4 acc_t;
   static __device__ __forceinline__ acc_t mma(const frag& a, const frag& b, acc_t c) { return mfma_split(a, b, c); }
@@ -109,6 +112,8 @@ template <> struct Elem<s16_t> {
 };
 template <> struct Elem<float> {
   static constexpr int kChunk = 4, kBlockK = 16, kPlanes = 1;
+  static constexpr int kDType = kF32;
+  static constexpr const char* kTag = "f32";
   static __device__ __forceinline__ floatx4_t lds(const unsigned char* at, int) { return *reinterpret_cast<const floatx4_t*>(at); }
   typedef floatx4_t frag;
   typedef floatx4 acc_t;
@@ -121,6 +126,8 @@ template <> struct Elem<float> {
 };
 template <> struct Elem<signed char> {
   static constexpr int kChunk = 16, kBlockK = 64, kPlanes = 1;
+  static constexpr int kDType = kI8;
+  static constexpr const char* kTag = "i8";
   static __device__ __forceinline__ intx4 lds(const unsigned char* at, int) { return *reinterpret_cast<const intx4*>(at); }
   typedef intx4 frag;
   typedef intx4 acc_t;
@@ -132,6 +139,35 @@ template <> struct Elem<signed char> {
   }
 };
 
+// ---- tiles ---------------------------------------------------------------------------------------------------
+// Every kernel family describes a tile with ONE type (GldsTile, HaloTile, RegqTile, WsTile, each in front of its kernel): the
+// geometry the host plans and launches with, the constants that lay the tile's LDS out -- the kernel body reads them from the
+// type --, the dynamic LDS size as a function of those same constants, and the display name. The configuration table and the
+// pair kernels are built from these types, so a tile is written down once.
+constexpr size_t stage_bytes(int bm, int bn) { return (size_t)bm * (bn * 4 + 16); }  // epilogue staging tile (fp32 worst case)
+constexpr size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+constexpr size_t round_kib(size_t b) { return (b + 1023) & ~(size_t)1023; }           // an LDS-DMA instruction fills a whole KiB
+
+struct TileDefaults {     // what a family that does not say otherwise has (the fields of CfgInfo, launch side)
+  static constexpr int th = 0, tw = 0, cin = 0, nthreads = 256, stride = 1, chunks = 0;
+  static constexpr bool ws = false;
+};
+
+struct Str {              // a display name, put together at compile time
+  char s[96] = {};
+  int n = 0;
+  constexpr Str& operator<<(const char* t) {
+    while (*t) s[n++] = *t++;
+    return *this;
+  }
+  constexpr Str& operator<<(int v) {
+    char d[12] = {};
+    int k = 0;
+    do d[k++] = (char)('0' + v % 10); while (v /= 10);
+    while (k) s[n++] = d[--k];
+    return *this;
+  }
+};
 
 // ---- epilogue ------------------------------------------------------------------------------------------------
 // y = act( acc * mult[n] + bias[n] ) (+ residual, after the ReLU: model.py:72-73), all in fp32 registers:
@@ -338,16 +374,30 @@ extern __shared__ __align__(16) unsigned char conv_smem[];
 // conv_glds_body: workgroup `bid` of `nwg` (a plain launch passes blockIdx.x / gridDim.x; conv_dual runs two convs'
 // workgroups side by side in one grid).
 template <typename T, int BM, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
+struct GldsTile : TileDefaults {
+  typedef T elem;
+  static constexpr int bm = BM, bn = BN, bk = BK, stages = STAGES;
+  static constexpr int KSUB = BK / 32;
+  static constexpr int NP = Elem<T>::kPlanes;   // split fp16: every block comes as a (hi, lo) pair of adjacent 1-KiB blocks
+  static constexpr int ABLK = (BM / 16) * KSUB * NP, WBLK = (BN / 16) * KSUB * NP, NBLK = ABLK + WBLK;
+  static constexpr int LPT = (NBLK + 3) / 4;    // LDS-DMA instructions per wave per stage (same for every wave)
+  static constexpr int STAGE_BYTES = LPT * 4 * 1024;
+  // the ring of STAGES stages; the epilogue stages the output tile through the same bytes
+  static constexpr size_t lds_bytes(int = 0) { return max_sz((size_t)STAGES * STAGE_BYTES, stage_bytes(BM, BN)); }
+  static constexpr Str name() {
+    return Str() << "conv_glds<" << Elem<T>::kTag << "," << BM << "," << BN << "," << BK << "," << WAVES_M << "," << WAVES_N << "," << STAGES << ">";
+  }
+};
+
+template <typename T, int BM, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
 __device__ __forceinline__ void conv_glds_body(const ConvParams& p, int bid, int nwg) {
   static_assert(WAVES_M * WAVES_N == 4, "256-thread blocks");
   typedef Elem<T> E;
   typedef typename E::frag frag_t;
-  constexpr int WM_T = BM / (WAVES_M * 16), WN_T = BN / (WAVES_N * 16), KSUB = BK / 32;
+  typedef GldsTile<T, BM, BN, BK, WAVES_M, WAVES_N, STAGES> Tile;
+  constexpr int WM_T = BM / (WAVES_M * 16), WN_T = BN / (WAVES_N * 16), KSUB = Tile::KSUB;
   constexpr int KSTEP = KSUB * E::kBlockK;  // input channels per K-step
-  constexpr int NP = E::kPlanes;            // split fp16: every block comes as a (hi, lo) pair of adjacent 1-KiB blocks
-  constexpr int ABLK = (BM / 16) * KSUB * NP, WBLK = (BN / 16) * KSUB * NP, NBLK = ABLK + WBLK;
-  constexpr int LPT = (NBLK + 3) / 4;            // LDS-DMA instructions per wave per stage (same for every wave)
-  constexpr int STAGE_BYTES = LPT * 4 * 1024;
+  constexpr int NP = Tile::NP, ABLK = Tile::ABLK, NBLK = Tile::NBLK, LPT = Tile::LPT, STAGE_BYTES = Tile::STAGE_BYTES;
   static_assert(WM_T >= 1 && WN_T >= 1 && KSUB >= 1, "tile");
 
   const long long t_entry = p.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -529,6 +579,8 @@ template <typename T, int BM, int BN, int BK, int WAVES_M, int WAVES_N, int STAG
 __global__ __launch_bounds__(256) void conv_glds(const ConvParams p) {
   conv_glds_body<T, BM, BN, BK, WAVES_M, WAVES_N, STAGES>(p, (int)blockIdx.x, (int)gridDim.x);
 }
+template <typename T, int BM, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
+constexpr auto kernel_of(GldsTile<T, BM, BN, BK, WAVES_M, WAVES_N, STAGES>) { return conv_glds<T, BM, BN, BK, WAVES_M, WAVES_N, STAGES>; }
 
 
 // ================================================================================================ 3x3 halo kernel
@@ -543,17 +595,29 @@ __global__ __launch_bounds__(256) void conv_glds(const ConvParams p) {
 // spreads them over the 16 bank slots; the loading lane fetches the matching source chunk, so every pixel's row is
 // still one contiguous global segment.
 template <typename T, int TH, int TW, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
+struct HaloTile : TileDefaults {
+  typedef T elem;
+  static constexpr int bm = TH * TW, bn = BN, bk = BK, stages = STAGES, th = TH, tw = TW;
+  static constexpr int KSUB = BK / 32, WBLK = (BN / 16) * KSUB, LPT = (WBLK + 3) / 4;
+  static constexpr int STAGE_BYTES = LPT * 4 * 1024, RING_BYTES = STAGES * STAGE_BYTES;
+  static constexpr int NPIX = (TH + 2) * (TW + 2);
+  // the weight ring, behind it the patch of `cin` channels (its DMA fills whole KiB); the epilogue stages through the same bytes
+  static constexpr size_t lds_bytes(int cin) { return max_sz(RING_BYTES + round_kib((size_t)NPIX * cin * sizeof(T)), stage_bytes(bm, BN)); }
+  static constexpr Str name() {
+    return Str() << "conv3x3_halo<" << Elem<T>::kTag << "," << TH << "x" << TW << "," << BN << "," << BK << "," << WAVES_M << "," << WAVES_N << "," << STAGES << ">";
+  }
+};
+
+template <typename T, int TH, int TW, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
 __global__ __launch_bounds__(256) void conv3x3_halo(const ConvParams p) {
   static_assert(WAVES_M * WAVES_N == 4, "256-thread blocks");
   typedef Elem<T> E;
   typedef typename E::frag frag_t;
-  constexpr int BM = TH * TW, HW_ = TW + 2, NPIX = (TH + 2) * (TW + 2);
-  constexpr int WM_T = BM / (WAVES_M * 16), WN_T = BN / (WAVES_N * 16), KSUB = BK / 32;
+  typedef HaloTile<T, TH, TW, BN, BK, WAVES_M, WAVES_N, STAGES> Tile;
+  constexpr int BM = TH * TW, HW_ = TW + 2, NPIX = Tile::NPIX;
+  constexpr int WM_T = BM / (WAVES_M * 16), WN_T = BN / (WAVES_N * 16), KSUB = Tile::KSUB;
   constexpr int KSTEP = KSUB * E::kBlockK;
-  constexpr int WBLK = (BN / 16) * KSUB;
-  constexpr int LPT = (WBLK + 3) / 4;
-  constexpr int STAGE_BYTES = LPT * 4 * 1024;
-  constexpr int RING_BYTES = STAGES * STAGE_BYTES;
+  constexpr int WBLK = Tile::WBLK, LPT = Tile::LPT, STAGE_BYTES = Tile::STAGE_BYTES, RING_BYTES = Tile::RING_BYTES;
   static_assert(WM_T >= 1 && WN_T >= 1 && (TW == 8 || TW == 16), "tile");
 
   const long long t_entry = p.stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
@@ -727,6 +791,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo(const ConvParams p) {
     stamp(p, 4);
   }
 }
+template <typename T, int TH, int TW, int BN, int BK, int WAVES_M, int WAVES_N, int STAGES>
+constexpr auto kernel_of(HaloTile<T, TH, TW, BN, BK, WAVES_M, WAVES_N, STAGES>) { return conv3x3_halo<T, TH, TW, BN, BK, WAVES_M, WAVES_N, STAGES>; }
 
 // ============================================================================================ 3x3 register-queue kernel
 // 3x3 / stride 1 / pad 1 with the input patch resident in LDS (as conv3x3_halo) and the WEIGHTS STREAMED L2 -> REGISTERS:
@@ -746,19 +812,37 @@ constexpr bool kPatchViaRegs = UNINA_PATCH_VIA_REGS != 0;   // input patch: 16-b
 // STAMPS (debug instantiations only: a branch around the loads would change the schedule of the product kernels): phase
 // stamps of the conv's mid workgroup -- 0 start, 1 patch DMA + first weight blocks issued, 2 patch landed (barrier passed),
 // 3 K loop done, 4 stores issued.
+// RegqTile: NW waves, a weight queue D blocks deep, stride S (WN = 1: what every row of the table and every pair uses)
+template <typename T, int TH, int TW, int BN, int CIN, int NW, int D, int S = 1>
+struct RegqTile : TileDefaults {
+  typedef T elem;
+  static constexpr int bm = TH * TW, bn = BN, bk = 32, stages = 3, th = TH, tw = TW, cin = CIN, nthreads = NW * 64, stride = S;
+  static constexpr int nw = NW, depth = D;
+  static constexpr bool SPLIT = Elem<T>::kPlanes == 2;
+  // S = stride (1 or 2): the patch is the (S*TH + 2 or S*TH + 1) x (...) input footprint of the tile
+  static constexpr int R0W = S * (TW - 1) + 3, R0H = S * (TH - 1) + 3;
+  static constexpr int PATCH = (int)round_kib(R0H * R0W * CIN * sizeof(T)) + 1024;   // one image + the < 1 KiB overrun of its last DMA instruction
+  static constexpr int LDS_LO = SPLIT ? PATCH : 0;                                    // split fp16: the lo image lies behind the hi image
+  // split fp16: hi and lo images, accumulators are stored straight from registers; otherwise the patch or the epilogue staging tile
+  static constexpr size_t lds_bytes(int = 0) { return SPLIT ? 2 * (size_t)PATCH : max_sz(PATCH, stage_bytes((bm + 15) & ~15, BN)); }
+  static constexpr Str name() {
+    return Str() << "conv3x3_regq<" << Elem<T>::kTag << "," << TH << "x" << TW << "," << BN << "," << CIN << "," << NW << (S == 2 ? "w,s2>" : "w>");
+  }
+};
+
 template <int TH, int TW, int BN, int CIN, int NW, int D, int S = 1, int WN = 1, typename T = half_t, bool STAMPS = false>
 __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, int nwg) {
   typedef Elem<T> E;
   typedef typename E::frag frag;
-  constexpr bool SPLIT = E::kPlanes == 2;
+  typedef RegqTile<T, TH, TW, BN, CIN, NW, D, S> Tile;
+  constexpr bool SPLIT = Tile::SPLIT;
   typedef typename std::conditional<sizeof(T) == 1, EltI8, typename std::conditional<SPLIT, EltS, EltH>::type>::type PE;   // block_pipeline.h element traits of T
-  // S = stride (1 or 2): the patch is the (S*TH + 2 or S*TH + 1) x (...) input footprint of the tile
-  constexpr int BM = TH * TW, R0W = S * (TW - 1) + 3, R0H = S * (TH - 1) + 3, NT = NW * 64, CB = CIN / E::kBlockK, KB = 9 * CB;
+  constexpr int BM = TH * TW, R0W = Tile::R0W, R0H = Tile::R0H, NT = NW * 64, CB = CIN / E::kBlockK, KB = 9 * CB;
   static_assert(CIN % E::kBlockK == 0, "a weight block must not straddle a tap");
   constexpr int NS = BN / 16 / WN, WVM = NW / NS, MS = (BM + 15) / 16, WM_T = (MS + WVM - 1) / WVM;   // NS = waves along the channels
   static_assert((BN / 16) % WN == 0 && NW % NS == 0 && WM_T >= 1 && KB * WN >= D, "tile");
 
-  if constexpr (STAMPS) { stamp_b(p, 0, bid, nwg); stamp_wg(p, 0); }
+  if constexpr (STAMPS) { stamp(p, 0, bid, nwg); stamp_wg(p, 0); }
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wid / NS, wn = wid % NS;
@@ -786,8 +870,7 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
     constexpr int g = decltype(gc)::value;
     if constexpr (g < KB * WN) q[g % D] = PE::ldw(wptr[g % WN] + (g / WN) * PE::WBLK);
   };
-  // split fp16: the lo image of the patch lies LDS_LO bytes behind the hi image
-  constexpr int LDS_LO = SPLIT ? ((R0H * R0W * CIN * 2 + 1023) / 1024) * 1024 + 1024 : 0;
+  constexpr int LDS_LO = Tile::LDS_LO;   // split fp16: the lo image of the patch lies LDS_LO bytes behind the hi image
 
   constexpr Img X = make_img(0, CIN / E::kChunk);
   if constexpr (SPLIT) {   // both planes by LDS-DMA (twice the registers of a register-staged patch would not fit)
@@ -798,7 +881,7 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
     PatchRegs<R0H, R0W, CIN, NT, PE> pr;
     patch_issue<R0H, R0W, CIN, NT, PE>(pr, static_cast<const T*>(p.src) + sg.src_coff, p.src_ld, p.H, p.W, S * ty0 - 1, S * tx0 - 1, wid, lane);
     static_for<0, D>(fetch);
-    if constexpr (STAMPS) stamp_b(p, 1, bid, nwg);
+    if constexpr (STAMPS) stamp(p, 1, bid, nwg);
     patch_commit<R0H, R0W, CIN, NT, PE>(pr, conv_smem, wid, lane);
   } else {
     load_patch<R0H, R0W, CIN, NT, PE>(conv_smem, static_cast<const T*>(p.src) + sg.src_coff, p.src_ld, p.H, p.W, S * ty0 - 1,
@@ -807,10 +890,10 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
   }
   EpiConsts<WN> ec;
   load_epi_consts<WN>(sg, nb0 + wn * (WN * 16), lq, ec);
-  if constexpr (STAMPS && (SPLIT || !kPatchViaRegs)) stamp_b(p, 1, bid, nwg);
+  if constexpr (STAMPS && (SPLIT || !kPatchViaRegs)) stamp(p, 1, bid, nwg);
   if constexpr (SPLIT || !kPatchViaRegs) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed
   lds_barrier();
-  if constexpr (STAMPS) stamp_b(p, 2, bid, nwg);
+  if constexpr (STAMPS) stamp(p, 2, bid, nwg);
 
   int row0[WM_T];
 #pragma unroll
@@ -847,20 +930,22 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
       for (int i = 0; i < WM_T; ++i) acc[j][i] = E::mma(a[j], b[kb & 1][i], acc[j][i]);
   });
 
-  if constexpr (STAMPS) stamp_b(p, 3, bid, nwg);
+  if constexpr (STAMPS) stamp(p, 3, bid, nwg);
   auto pix_to_m = [&](int pl) {
     const int oy = ty0 + pl / TW, ox = tx0 + pl % TW;
     return (pl < BM && oy < p.Ho && ox < p.Wo) ? oy * p.Wo + ox : -1;
   };
   conv_epilogue<T, BM, BN, WM_T, WN, decltype(pix_to_m), (UNINA_REGQ_DIRECT_STORE != 0 && sizeof(T) == 2)>(p, sg, acc, ec, wm, wn, nb0, l15, lq, pix_to_m,
                                                                                                        conv_smem, NT);
-  if constexpr (STAMPS) { stamp_b(p, 4, bid, nwg); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wg(p, 1); }
+  if constexpr (STAMPS) { stamp(p, 4, bid, nwg); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wg(p, 1); }
 }
 
 template <int TH, int TW, int BN, int CIN, int NW, int D, int S = 1, int WN = 1, typename T = half_t>
 __global__ __launch_bounds__(NW * 64) void conv3x3_regq(const ConvParams p) {
   conv3x3_regq_body<TH, TW, BN, CIN, NW, D, S, WN, T>(p, (int)blockIdx.x, (int)gridDim.x);
 }
+template <typename T, int TH, int TW, int BN, int CIN, int NW, int D, int S>
+constexpr auto kernel_of(RegqTile<T, TH, TW, BN, CIN, NW, D, S>) { return conv3x3_regq<TH, TW, BN, CIN, NW, D, S, 1, T>; }
 
 // ============================================================================================ 3x3 weights-stationary kernel
 // 3x3 / stride 1 / pad 1, ReLU, NHWC destination; fp16, int8 (INT8 engines: int8 patch, 64-k weight blocks, exact int32
@@ -883,23 +968,40 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_regq(const ConvParams p) {
 // kernel is NOT bit-identical to them in fp16 / split fp16 (fp32 accumulation: the difference is the last bit of an fp16 output
 // now and then; the tests hold it to that against the register-queue pair, and to the fp32 oracle like everything else). int8
 // accumulates exactly: there the codes are the same as every other kernel's.
+template <typename T, int TH, int CIN, int NCHUNK, int NW>
+struct WsTile : TileDefaults {
+  typedef T elem;
+  static constexpr int TW = 16, BN = NW * 16;
+  static constexpr int bm = TH * TW, bn = BN, bk = 32, stages = 3, th = TH, tw = TW, cin = CIN, nthreads = NW * 64, chunks = NCHUNK;
+  static constexpr int nw = NW;
+  static constexpr bool ws = true;   // fp16 NHWC destination, ReLU, no residual / upsample / planar output
+  static constexpr int ESZ = sizeof(T) == 1 ? 1 : 2;
+  static constexpr int R0W = TW + 2, R0H = TH + 2, CC = CIN / NCHUNK;
+  static constexpr int PITCH = CC * ESZ + 32;
+  static constexpr int PLANE = R0H * R0W * PITCH;              // one plane of a patch chunk; the lo image lies right behind the hi image
+  static constexpr int BUF = Elem<T>::kPlanes * PLANE;         // one LDS buffer; chunks alternate between two
+  static constexpr size_t lds_bytes(int = 0) { return (size_t)(NCHUNK > 1 ? 2 : 1) * BUF; }
+  static constexpr Str name() {
+    return Str() << "conv3x3_ws<" << Elem<T>::kTag << "," << TH << "x16," << CIN << "/" << NCHUNK << "," << NW << "w>";
+  }
+};
+
 template <typename T, int TH, int CIN, int NCHUNK, int NW, bool STAMPS = false>
 __device__ __forceinline__ void conv3x3_wsc_body(const ConvParams& p, int bid, int nwg) {
   typedef Elem<T> E;
   typedef typename E::frag frag;
+  typedef WsTile<T, TH, CIN, NCHUNK, NW> Tile;
   constexpr bool SP = E::kPlanes == 2;
   constexpr bool I8 = sizeof(T) == 1;                       // INT8 engines: int8 patch, 64-k weight blocks, exact int32 accumulators
-  constexpr int ESZ = I8 ? 1 : 2, KBLK = E::kBlockK;
+  constexpr int ESZ = Tile::ESZ, KBLK = E::kBlockK;
   constexpr int WB = 1024 * E::kPlanes;                     // bytes of a weight block (split: the (hi | lo) pair)
-  if constexpr (STAMPS) { stamp_b(p, 0, bid, nwg); stamp_wg(p, 0); }
+  if constexpr (STAMPS) { stamp(p, 0, bid, nwg); stamp_wg(p, 0); }
   typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
   typedef float floatx2 __attribute__((ext_vector_type(2)));
-  constexpr int TW = 16, R0W = TW + 2, R0H = TH + 2, NT = NW * 64, BN = NW * 16;
-  constexpr int CB = CIN / KBLK, CC = CIN / NCHUNK, CBC = CC / KBLK, KBC = 9 * CBC;
+  constexpr int TW = Tile::TW, R0W = Tile::R0W, R0H = Tile::R0H, NT = NW * 64, BN = Tile::BN;
+  constexpr int CB = CIN / KBLK, CC = Tile::CC, CBC = CC / KBLK, KBC = 9 * CBC;
   constexpr int STEPS = R0H * 3 * CBC, PF = 4;
-  constexpr int PITCH = CC * ESZ + 32;
-  constexpr int PLANE = R0H * R0W * PITCH;                   // one plane of a patch chunk; the lo image lies right behind the hi image
-  constexpr int BUF = E::kPlanes * PLANE;                    // one LDS buffer; chunks alternate between two
+  constexpr int PITCH = Tile::PITCH, PLANE = Tile::PLANE, BUF = Tile::BUF;
   static_assert(CIN % (KBLK * NCHUNK) == 0 && KBC * 4 * E::kPlanes <= 160 && PLANE % 16 == 0, "chunking: two weight sets must fit the registers");
   static_assert((R0H * R0W + 2) * PITCH < 65536, "ds_read immediate offsets");
   const int lane = threadIdx.x & 63;
@@ -1025,10 +1127,10 @@ __device__ __forceinline__ void conv3x3_wsc_body(const ConvParams& p, int bid, i
   w_request(wA, I0{}, I0{}, std::integral_constant<int, 3 * CBC>{});
   static_for<0, PITER>([&](auto itc) { patch_request_one(I0{}, itc); });
   w_request(wA, I0{}, std::integral_constant<int, 3 * CBC>{}, std::integral_constant<int, KBC>{});
-  if constexpr (STAMPS) stamp_b(p, 1, bid, nwg);
+  if constexpr (STAMPS) stamp(p, 1, bid, nwg);
   patch_commit(0);
   lds_barrier();
-  if constexpr (STAMPS) stamp_b(p, 2, bid, nwg);
+  if constexpr (STAMPS) stamp(p, 2, bid, nwg);
 
   // the next chunk's requests, one per K-loop step from step 0 on: its patch slice first (committed at the end of this
   // chunk), then its weight blocks in the order of first use (all issued well before this chunk's last steps)
@@ -1088,74 +1190,65 @@ __device__ __forceinline__ void conv3x3_wsc_body(const ConvParams& p, int bid, i
       lds_barrier();
     }
   });
-  if constexpr (STAMPS) stamp_b(p, 3, bid, nwg);
+  if constexpr (STAMPS) stamp(p, 3, bid, nwg);
   store_row(std::integral_constant<int, TH - 1>{});
-  if constexpr (STAMPS) { stamp_b(p, 4, bid, nwg); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wg(p, 1); }
+  if constexpr (STAMPS) { stamp(p, 4, bid, nwg); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wg(p, 1); }
 }
 
 template <typename T, int TH, int CIN, int NCHUNK, int NW>
 __global__ __launch_bounds__(NW * 64) void conv3x3_wsc(const ConvParams p) {
   conv3x3_wsc_body<T, TH, CIN, NCHUNK, NW>(p, (int)blockIdx.x, (int)gridDim.x);
 }
-// fp16 engines: the P3 | P4 head pair (P4's workgroups take the first block ids). P3: 16 x 16 pixel tiles, two chunks of 64
-// channels; P4: 8 x 16 tiles, four chunks. One wave per SIMD. (Two waves per SIMD -- 512-thread workgroups whose wave halves
-// split the chunks by parity and meet in LDS -- were built and measured: the K loop reaches the MFMA pipe's rate, the launch
-// does not get shorter: 14.3 against 13.4 us fp16, 30.7 against 28.5 us split; profiles/r03/head_pair_experiments.txt.)
-__global__ __launch_bounds__(256) void conv_dual_head3x3_ws(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<half_t, 8, 256, 4, 4>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<half_t, 16, 128, 2, 4>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
-}
-// The same pair on LARGE frames (more workgroups than CUs even with the tiles above: 1280^2, or several such launches in flight):
-// half-height tiles and at most 256 registers, so that TWO workgroups share a CU -- a SIMD's two waves together run at ~19 cycles
-// per MFMA against 25 for a lone wave. At 640^2 (220 workgroups: one round either way) this form starts 440 workgroups that each
-// load the same weights for half the pixels: launch 14.2 against 13.2 us; at 1280^2 38.2 -> 32.3 us, 0.32 -> 0.37 of the peak.
-__global__ __launch_bounds__(256, 2) void conv_dual_head3x3_ws_small(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<half_t, 4, 256, 4, 4>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<half_t, 8, 128, 2, 4>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
-}
-__global__ __launch_bounds__(256) void conv_dual_head3x3_ws_stamped(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<half_t, 8, 256, 4, 4, true>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<half_t, 16, 128, 2, 4, true>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
-}
-__global__ __launch_bounds__(256) void conv_dual_head3x3_ws_s16_stamped(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<s16_t, 8, 256, 4, 4, true>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<s16_t, 16, 128, 4, 4, true>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
-}
-// STRICT engines: the P3 | P4 head pair on it (P4's workgroups take the first block ids)
-__global__ __launch_bounds__(256) void conv_dual_head3x3_ws_s16(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<s16_t, 8, 256, 4, 4>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<s16_t, 16, 128, 4, 4>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
-}
+template <typename T, int TH, int CIN, int NCHUNK, int NW>
+constexpr auto kernel_of(WsTile<T, TH, CIN, NCHUNK, NW>) { return conv3x3_wsc<T, TH, CIN, NCHUNK, NW>; }
 
-// INT8 engines: the same pair on int8 tensors (18 / 36 weight blocks of 64 k per wave: 72 / 144 registers)
-__global__ __launch_bounds__(256) void conv_dual_head3x3_ws_i8(const ConvParams pa, const ConvParams pb, int nb) {
-  if ((int)blockIdx.x < nb) conv3x3_wsc_body<signed char, 8, 256, 4, 4>(pb, (int)blockIdx.x, nb);
-  else conv3x3_wsc_body<signed char, 16, 128, 2, 4>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
+// ================================================================================================ dual launches
+// Two INDEPENDENT convs of the same kernel family in ONE grid. The P3 and P4 head layers (model.py:361-365) are such pairs:
+// each alone half-fills the chip (200 workgroups) and sits on the ~11-14 us cold-weights + patch-wait + launch plateau
+// (DESIGN.md 4.2); side by side they share one launch and fill the CUs the other leaves idle. Same bodies, so results are
+// bit-identical to the separate launches. A pair kernel is instantiated with the tile types of its two halves; its row of
+// kDual[] (launch side) is built from the same two types.
+//
+// The weights-stationary pair's tiles, one wave per SIMD. P3: 16 x 16 pixels, two chunks of 64 channels (split fp16: four of 32 --
+// with 16-row tiles the pair's 100 + 120 workgroups run in ONE round; with 8-row tiles its 320 needed two); P4: 8 x 16, four
+// chunks (split fp16: 4-row tiles -- 240 workgroups of the P3 conv's size -- ran 34 us per pair against 30.6). int8: 18 / 36
+// weight blocks of 64 k per wave, 72 / 144 registers. (Two waves per SIMD -- 512-thread workgroups whose wave halves split
+// the chunks by parity and meet in LDS -- were built and measured: the K loop reaches the MFMA pipe's rate, the launch does
+// not get shorter: 14.3 against 13.4 us fp16, 30.7 against 28.5 us split; profiles/r03/head_pair_experiments.txt.)
+template <typename T> using WsP3 = WsTile<T, 16, 128, (Elem<T>::kPlanes == 2 ? 4 : 2), 4>;
+template <typename T> using WsP4 = WsTile<T, 8, 256, 4, 4>;
+// fp16 on LARGE frames (more workgroups than CUs even with the tiles above: 1280^2, or several such launches in flight):
+// half-height tiles and at most 256 registers (230), so that TWO workgroups share a CU -- a SIMD's two waves together run at
+// ~19 cycles per MFMA against 25 for a lone wave. At 640^2 (220 workgroups: one round either way) this form starts 440
+// workgroups that each load the same weights for half the pixels: launch 14.2 against 13.2 us; at 1280^2 38.2 -> 32.3 us,
+// 0.32 -> 0.37 of the peak.
+typedef WsTile<half_t, 8, 128, 2, 4> WsP3Half;
+typedef WsTile<half_t, 4, 256, 4, 4> WsP4Half;
+
+// Conv B's workgroups take the first `nb` block ids. STAMPS: the debug twin; MIN_WAVES: the second argument of
+// __launch_bounds__ (0: none).
+template <class A, class B, bool STAMPS = false, int MIN_WAVES = 0>
+__global__ __launch_bounds__(A::nthreads, MIN_WAVES) void conv_dual_ws(const ConvParams pa, const ConvParams pb, int nb) {
+  if ((int)blockIdx.x < nb) conv3x3_wsc_body<typename B::elem, B::th, B::cin, B::chunks, B::nw, STAMPS>(pb, (int)blockIdx.x, nb);
+  else conv3x3_wsc_body<typename A::elem, A::th, A::cin, A::chunks, A::nw, STAMPS>(pa, (int)blockIdx.x - nb, (int)gridDim.x - nb);
 }
 
 #ifndef UNINA_CONV_PROBE   // (ISA probe builds stop here: tools/isa_probe.sh compiles only the kernels above)
-// ================================================================================================ dual launches
-// Two INDEPENDENT convs of the same kernel family in ONE grid: workgroups [0, na) run conv A, the rest conv B. The P3
-// and P4 head layers (model.py:361-365) are such pairs: each alone half-fills the chip (200 workgroups) and sits on the
-// ~11-14 us cold-weights + patch-wait + launch plateau; side by side they share one launch and fill
-// the CUs the other leaves idle. Same bodies, so results are bit-identical to the separate launches.
-// (launch bound 4 waves per SIMD = two 512-thread workgroups per CU: both convs' workgroups must be co-resident for the
-// side-by-side launch to overlap them -- with the 207 VGPRs of the stand-alone 8x16 body only one fits and the two halves
-// simply run one after the other; hence the shallower queue, D = 8)
-__global__ __launch_bounds__(512, 4) void conv_dual_head3x3(const ConvParams pa, const ConvParams pb, int na) {
-  if ((int)blockIdx.x < na) conv3x3_regq_body<8, 16, 64, 128, 8, 8, 1>(pa, (int)blockIdx.x, na);
-  else conv3x3_regq_body<8, 8, 64, 256, 8, 8, 1>(pb, (int)blockIdx.x - na, (int)gridDim.x - na);
+// The register-queue pair's tiles: P3 8 x 16 pixels, P4 8 x 8, queue depth D = 8 where the single configurations have 16 --
+// fp16 / int8 launch with a bound of 4 waves per SIMD = two 512-thread workgroups per CU: both convs' workgroups must be
+// co-resident for the side-by-side launch to overlap them, and with the 207 VGPRs of the stand-alone 8x16 body only one fits
+// and the two halves simply run one after the other. Split fp16 (hi / lo patch images): one workgroup per CU, no bound.
+template <typename T> using RegqP3 = RegqTile<T, 8, 16, 64, 128, 8, 8>;
+template <typename T> using RegqP4 = RegqTile<T, 8, 8, 64, 256, 8, 8>;
+
+// Conv A's workgroups take the first `na` block ids.
+template <class A, class B>
+__global__ __launch_bounds__(A::nthreads, A::SPLIT ? 0 : 4) void conv_dual_regq(const ConvParams pa, const ConvParams pb, int na) {
+  if ((int)blockIdx.x < na) conv3x3_regq_body<A::th, A::tw, A::bn, A::cin, A::nw, A::depth, A::stride, 1, typename A::elem>(pa, (int)blockIdx.x, na);
+  else conv3x3_regq_body<B::th, B::tw, B::bn, B::cin, B::nw, B::depth, B::stride, 1, typename B::elem>(pb, (int)blockIdx.x - na, (int)gridDim.x - na);
 }
-// INT8 engines: the same pair on int8 inputs (P3 | P4 head layers .0 and .1 are int8 convs there)
-__global__ __launch_bounds__(512, 4) void conv_dual_head3x3_i8(const ConvParams pa, const ConvParams pb, int na) {
-  if ((int)blockIdx.x < na) conv3x3_regq_body<8, 16, 64, 128, 8, 8, 1, 1, signed char>(pa, (int)blockIdx.x, na);
-  else conv3x3_regq_body<8, 8, 64, 256, 8, 8, 1, 1, signed char>(pb, (int)blockIdx.x - na, (int)gridDim.x - na);
-}
-// STRICT engines: the same pair on split-fp16 tensors (hi / lo patch images: one workgroup per CU)
-__global__ __launch_bounds__(512) void conv_dual_head3x3_s16(const ConvParams pa, const ConvParams pb, int na) {
-  if ((int)blockIdx.x < na) conv3x3_regq_body<8, 16, 64, 128, 8, 8, 1, 1, s16_t>(pa, (int)blockIdx.x, na);
-  else conv3x3_regq_body<8, 8, 64, 256, 8, 8, 1, 1, s16_t>(pb, (int)blockIdx.x - na, (int)gridDim.x - na);
-}
+
+typedef GldsTile<half_t, 128, 16, 64, 4, 1, 4> Head1x1;   // both halves of conv_dual_head1x1
 __global__ __launch_bounds__(256) void conv_dual_head1x1(const ConvParams pa, const ConvParams pb, int na) {
   if ((int)blockIdx.x < na) conv_glds_body<half_t, 128, 16, 64, 4, 1, 4>(pa, (int)blockIdx.x, na);
   else conv_glds_body<half_t, 128, 16, 64, 4, 1, 4>(pb, (int)blockIdx.x - na, (int)gridDim.x - na);
@@ -1164,234 +1257,129 @@ __global__ __launch_bounds__(256) void conv_dual_head1x1(const ConvParams pa, co
 // ---------------------------------------------------------------------------------------------- launch side
 namespace {
 
-struct CfgInfo {
-  int bm, bn, bk, stages;
-  const char* name;
-  void (*fn)(const ConvParams);
-  size_t smem;         // im2col kernel: total dynamic LDS; halo kernel: weight ring only (the patch is added per op)
-  int th, tw;          // halo / register-queue kernels: spatial tile (0 = im2col kernel)
+constexpr int kCUs = 256;   // of an MI355X (not queried: plans are the same on every device)
+
+struct CfgInfo {       // a tile's geometry as the host plans and launches with it (the tile types' members of the same names)
+  int bm = 0, bn = 0, bk = 0, stages = 0;
+  Str name = Str() << "n/a";
+  void (*fn)(const ConvParams) = nullptr;   // nullptr: no kernel for this (dtype, configuration)
+  size_t (*lds_bytes)(int cin) = nullptr;   // dynamic LDS of a launch (only the halo kernel's depends on the conv's Cin)
+  int th = 0, tw = 0;  // halo / register-queue kernels: spatial tile (0 = im2col kernel)
   int cin = 0;         // register-queue kernel: the input channel count it is instantiated for (0 = any)
-  int nthreads = 256;
-  int stride = 1;      // register-queue kernel: conv stride it is instantiated for
+  int nthreads = 0;
+  int stride = 0;      // register-queue kernel: conv stride it is instantiated for
   bool ws = false;     // weights-stationary 3x3 kernel: fp16 NHWC destination, ReLU, no residual / upsample / planar output
   int chunks = 0;      // chunked weights-stationary kernel (conv3x3_wsc_body): channel chunks; 0 = another kernel
 };
+// [dtype][config], filled from a list of rows that each name their slot: add<Tile>(configuration), the dtype is the tile's.
+struct ConvTable {
+  CfgInfo at[kNumDTypes][kCfgCount];
+  int clashes = 0;   // rows whose slot an earlier row had taken
+  template <class Tile>
+  constexpr void add(ConvConfig cfg) {
+    CfgInfo& c = at[Elem<typename Tile::elem>::kDType][cfg];
+    if (c.fn) ++clashes;
+    c = {Tile::bm, Tile::bn, Tile::bk, Tile::stages, Tile::name(), kernel_of(Tile{}), &Tile::lds_bytes,
+         Tile::th, Tile::tw, Tile::cin, Tile::nthreads, Tile::stride, Tile::ws, Tile::chunks};
+  }
+};
 
-constexpr size_t stage_bytes(int bm, int bn) { return (size_t)bm * (bn * 4 + 16); }  // epilogue staging tile (fp32 worst case)
-constexpr size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-template <int BM, int BN, int BK, int WM, int WN, int ST, int NP = 1>
-constexpr size_t smem_of() {
-  return max_sz((size_t)ST * (((BM / 16 + BN / 16) * (BK / 32) * NP + 3) / 4) * 4 * 1024, stage_bytes(BM, BN));
+// im2col kernels. BK is in fp16-equivalent k (KSUB = BK/32 fragment blocks): a K-step covers BK channels in fp16 and BK/2
+// channels in fp32. These eight every dtype has; ST = ring depth of the ones with K-step 64 and 64 pixels or more.
+template <typename T, int ST>
+constexpr void add_glds(ConvTable& t) {
+  t.add<GldsTile<T, 64, 64, 64, 2, 2, ST>>(kCfg64x64k64);
+  t.add<GldsTile<T, 64, 64, 32, 2, 2, 4>>(kCfg64x64k32);
+  t.add<GldsTile<T, 128, 64, 64, 2, 2, ST>>(kCfg128x64k64);
+  t.add<GldsTile<T, 128, 64, 32, 2, 2, 4>>(kCfg128x64k32);
+  t.add<GldsTile<T, 128, 32, 64, 4, 1, ST>>(kCfg128x32k64);
+  t.add<GldsTile<T, 128, 32, 32, 4, 1, 4>>(kCfg128x32k32);
+  t.add<GldsTile<T, 128, 16, 64, 4, 1, ST>>(kCfg128x16k64);
+  t.add<GldsTile<T, 32, 64, 64, 1, 4, 4>>(kCfg32x64k64);
+}
+// fp16, fp32 and int8: the same geometry in all three, and the halo kernels
+template <typename T>
+constexpr void add_glds_halo(ConvTable& t) {
+  add_glds<T, 4>(t);
+  t.add<GldsTile<T, 128, 128, 64, 2, 2, 4>>(kCfg128x128k64);
+  t.add<GldsTile<T, 32, 64, 64, 1, 4, 8>>(kCfg32x64k64s8);   // (deep pipeline for latency-bound small grids)
+  t.add<GldsTile<T, 64, 64, 64, 2, 2, 6>>(kCfg64x64k64s6);
+  t.add<HaloTile<T, 8, 8, 64, 64, 2, 2, 4>>(kCfgHalo8x8n64);
+  t.add<HaloTile<T, 8, 8, 32, 64, 4, 1, 4>>(kCfgHalo8x8n32);
+  t.add<HaloTile<T, 8, 16, 64, 64, 2, 2, 4>>(kCfgHalo8x16n64);
+  t.add<HaloTile<T, 8, 16, 32, 64, 4, 1, 4>>(kCfgHalo8x16n32);
+  t.add<HaloTile<T, 8, 8, 64, 32, 2, 2, 4>>(kCfgHalo8x8n64k32);
+  t.add<HaloTile<T, 8, 16, 32, 32, 4, 1, 4>>(kCfgHalo8x16n32k32);
+  t.add<GldsTile<T, 32, 64, 128, 1, 4, 4>>(kCfg32x64k128);
+  t.add<GldsTile<T, 64, 64, 128, 2, 2, 4>>(kCfg64x64k128);
 }
 
-#define CFG(T, TN, BM, BN, BK, WM, WN, ST)                                                         \
-  {BM, BN, BK, ST, "conv_glds<" TN "," #BM "," #BN "," #BK "," #WM "," #WN "," #ST ">",            \
-   conv_glds<T, BM, BN, BK, WM, WN, ST>, smem_of<BM, BN, BK, WM, WN, ST, Elem<T>::kPlanes>(), 0, 0}
-#define HALO(T, TN, TH, TW, BN, BK, WM, WN, ST)                                                     \
-  {(TH) * (TW), BN, BK, ST, "conv3x3_halo<" TN "," #TH "x" #TW "," #BN "," #BK "," #WM "," #WN "," #ST ">", \
-   conv3x3_halo<T, TH, TW, BN, BK, WM, WN, ST>, (size_t)ST * ((((BN) / 16) * ((BK) / 32) + 3) / 4) * 4 * 1024, TH, TW}
+constexpr ConvTable conv_table() {
+  ConvTable t;
+  add_glds_halo<half_t>(t);
+  add_glds_halo<float>(t);
+  add_glds_halo<signed char>(t);
+  // split fp16: a K-step stages (hi, lo) block pairs -- twice the LDS per stage, hence rings of 3 on the wide tiles; no
+  // 128x128 (a stage would be 64 KB), no deeper rings, no K-step 128, no halo kernels
+  add_glds<s16_t, 3>(t);
 
-#define REGQ(TH, TW, BN, CIN, NW, D)                                                                 \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<f16," #TH "x" #TW "," #BN "," #CIN "," #NW "w>",                \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D>, 0, TH, TW, CIN, (NW) * 64, 1}
-#define REGQ2(TH, TW, BN, CIN, NW, D)                                                                \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<f16," #TH "x" #TW "," #BN "," #CIN "," #NW "w,s2>",             \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D, 2>, 0, TH, TW, CIN, (NW) * 64, 2}
-#define REGQI(TH, TW, BN, CIN, NW, D)                                                                \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<i8," #TH "x" #TW "," #BN "," #CIN "," #NW "w>",                 \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D, 1, 1, signed char>, 0, TH, TW, CIN, (NW) * 64, 1}
-#define REGQI2(TH, TW, BN, CIN, NW, D)                                                               \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<i8," #TH "x" #TW "," #BN "," #CIN "," #NW "w,s2>",              \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D, 2, 1, signed char>, 0, TH, TW, CIN, (NW) * 64, 2}
-#define REGQS(TH, TW, BN, CIN, NW, D)                                                                \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<s16," #TH "x" #TW "," #BN "," #CIN "," #NW "w>",                \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D, 1, 1, s16_t>, 0, TH, TW, CIN, (NW) * 64, 1}
-#define REGQS2(TH, TW, BN, CIN, NW, D)                                                               \
-  {(TH) * (TW), BN, 32, 3, "conv3x3_regq<s16," #TH "x" #TW "," #BN "," #CIN "," #NW "w,s2>",             \
-   conv3x3_regq<TH, TW, BN, CIN, NW, D, 2, 1, s16_t>, 0, TH, TW, CIN, (NW) * 64, 2}
-#define WS(TH, CIN, NCH, NW)                                                                         \
-  {(TH) * 16, (NW) * 16, 32, 3, "conv3x3_ws<f16," #TH "x16," #CIN "/" #NCH "," #NW "w>",                 \
-   conv3x3_wsc<half_t, TH, CIN, NCH, NW>, 0, TH, 16, CIN, (NW) * 64, 1, true, NCH}
-#define WSI(TH, CIN, NCH, NW)                                                                        \
-  {(TH) * 16, (NW) * 16, 32, 3, "conv3x3_ws<i8," #TH "x16," #CIN "/" #NCH "," #NW "w>",                  \
-   conv3x3_wsc<signed char, TH, CIN, NCH, NW>, 0, TH, 16, CIN, (NW) * 64, 1, true, NCH}
-#define WSS(TH, CIN, NCH, NW)                                                                        \
-  {(TH) * 16, (NW) * 16, 32, 3, "conv3x3_ws<s16," #TH "x16," #CIN "/" #NCH "," #NW "w>",                 \
-   conv3x3_wsc<s16_t, TH, CIN, NCH, NW>, 0, TH, 16, CIN, (NW) * 64, 1, true, NCH}
-#define NOCFG {0, 0, 0, 0, "n/a", nullptr, 0, 0, 0, -1, 0, 0}
+  // register-queue 3x3 (fp16, int8, split fp16): <T, TH, TW, BN, Cin, waves, queue depth, stride>
+  t.add<RegqTile<half_t, 8, 16, 64, 128, 8, 16>>(kCfgRegq8x16n64c128);        // (P3 head layers at 640^2)
+  t.add<RegqTile<half_t, 8, 8, 64, 128, 8, 16>>(kCfgRegq8x8n64c128);
+  t.add<RegqTile<half_t, 8, 8, 64, 256, 8, 16>>(kCfgRegq8x8n64c256);          // (P4 head layers)
+  t.add<RegqTile<half_t, 8, 8, 32, 256, 8, 16>>(kCfgRegq8x8n32c256);
+  t.add<RegqTile<half_t, 8, 16, 64, 64, 8, 16>>(kCfgRegq8x16n64c64);          // (P2 head layers when not fused)
+  t.add<RegqTile<half_t, 8, 16, 32, 128, 8, 16>>(kCfgRegq8x16n32c128);
+  // stride 2 (stage convs, PAN down-sampling convs)
+  t.add<RegqTile<half_t, 8, 8, 64, 64, 8, 16, 2>>(kCfgRegqS2_8x8n64c64);      // (stage2_conv, down1)
+  t.add<RegqTile<half_t, 8, 16, 64, 64, 8, 16, 2>>(kCfgRegqS2_8x16n64c64);
+  t.add<RegqTile<half_t, 8, 8, 64, 128, 8, 16, 2>>(kCfgRegqS2_8x8n64c128);    // (stage3_conv, down2)
+  t.add<RegqTile<half_t, 4, 8, 64, 128, 8, 16, 2>>(kCfgRegqS2_4x8n64c128);
+  t.add<RegqTile<half_t, 8, 16, 64, 32, 8, 8, 2>>(kCfgRegqS2_8x16n64c32);     // (stage1_conv)
+  t.add<RegqTile<half_t, 8, 8, 32, 128, 8, 16, 2>>(kCfgRegqS2_8x8n32c128);
+  // int8: no Cin 64 stride 1 (the P2 head is an fp16 carve-out), no Cin 32 (less than one int8 block)
+  t.add<RegqTile<signed char, 8, 16, 64, 128, 8, 16>>(kCfgRegq8x16n64c128);   // (P3 head layers)
+  t.add<RegqTile<signed char, 8, 8, 64, 128, 8, 16>>(kCfgRegq8x8n64c128);
+  t.add<RegqTile<signed char, 8, 8, 64, 256, 8, 16>>(kCfgRegq8x8n64c256);     // (P4 head layers)
+  t.add<RegqTile<signed char, 8, 8, 32, 256, 8, 16>>(kCfgRegq8x8n32c256);
+  t.add<RegqTile<signed char, 8, 16, 32, 128, 8, 16>>(kCfgRegq8x16n32c128);
+  t.add<RegqTile<signed char, 8, 8, 64, 64, 8, 8, 2>>(kCfgRegqS2_8x8n64c64);  // (down1)
+  t.add<RegqTile<signed char, 8, 16, 64, 64, 8, 8, 2>>(kCfgRegqS2_8x16n64c64);
+  t.add<RegqTile<signed char, 8, 8, 64, 128, 8, 16, 2>>(kCfgRegqS2_8x8n64c128);   // (stage3_conv, down2)
+  t.add<RegqTile<signed char, 4, 8, 64, 128, 8, 16, 2>>(kCfgRegqS2_4x8n64c128);
+  t.add<RegqTile<signed char, 8, 8, 32, 128, 8, 16, 2>>(kCfgRegqS2_8x8n32c128);
+  // split fp16: hi / lo patch images in LDS, (hi | lo) weight block pairs through the queue (D pairs = 2 D KiB in flight)
+  t.add<RegqTile<s16_t, 8, 16, 64, 128, 8, 8>>(kCfgRegq8x16n64c128);          // (P3 head layers)
+  t.add<RegqTile<s16_t, 8, 8, 64, 128, 8, 8>>(kCfgRegq8x8n64c128);
+  t.add<RegqTile<s16_t, 8, 8, 64, 256, 8, 8>>(kCfgRegq8x8n64c256);            // (P4 head layers)
+  t.add<RegqTile<s16_t, 8, 16, 64, 64, 8, 8>>(kCfgRegq8x16n64c64);            // (P2 head layers)
+  t.add<RegqTile<s16_t, 8, 8, 64, 64, 8, 8, 2>>(kCfgRegqS2_8x8n64c64);        // (stage2_conv, down1)
+  t.add<RegqTile<s16_t, 8, 8, 64, 128, 8, 8, 2>>(kCfgRegqS2_8x8n64c128);      // (stage3_conv, down2)
+  t.add<RegqTile<s16_t, 4, 8, 64, 128, 8, 8, 2>>(kCfgRegqS2_4x8n64c128);
+  t.add<RegqTile<s16_t, 8, 16, 64, 32, 8, 8, 2>>(kCfgRegqS2_8x16n64c32);      // (stage1_conv)
 
-// [dtype][config]; BK is in fp16-equivalent k (KSUB = BK/32 fragment blocks): a K-step covers BK channels in fp16
-// and BK/2 channels in fp32.
-const CfgInfo kCfg[kNumDTypes][kCfgCount] = {
-    {
-        CFG(half_t, "f16", 64, 64, 64, 2, 2, 4),    // kCfg64x64k64
-        CFG(half_t, "f16", 64, 64, 32, 2, 2, 4),    // kCfg64x64k32
-        CFG(half_t, "f16", 128, 64, 64, 2, 2, 4),    // kCfg128x64k64
-        CFG(half_t, "f16", 128, 64, 32, 2, 2, 4),    // kCfg128x64k32
-        CFG(half_t, "f16", 128, 128, 64, 2, 2, 4),    // kCfg128x128k64
-        CFG(half_t, "f16", 128, 32, 64, 4, 1, 4),    // kCfg128x32k64
-        CFG(half_t, "f16", 128, 32, 32, 4, 1, 4),    // kCfg128x32k32
-        CFG(half_t, "f16", 128, 16, 64, 4, 1, 4),    // kCfg128x16k64
-        CFG(half_t, "f16", 32, 64, 64, 1, 4, 4),    // kCfg32x64k64
-        CFG(half_t, "f16", 32, 64, 64, 1, 4, 8),    // kCfg32x64k64s8  (deep pipeline for latency-bound small grids)
-        CFG(half_t, "f16", 64, 64, 64, 2, 2, 6),    // kCfg64x64k64s6
-        HALO(half_t, "f16", 8, 8, 64, 64, 2, 2, 4),   // kCfgHalo8x8n64
-        HALO(half_t, "f16", 8, 8, 32, 64, 4, 1, 4),   // kCfgHalo8x8n32
-        HALO(half_t, "f16", 8, 16, 64, 64, 2, 2, 4),   // kCfgHalo8x16n64
-        HALO(half_t, "f16", 8, 16, 32, 64, 4, 1, 4),   // kCfgHalo8x16n32
-        HALO(half_t, "f16", 8, 8, 64, 32, 2, 2, 4),   // kCfgHalo8x8n64k32
-        HALO(half_t, "f16", 8, 16, 32, 32, 4, 1, 4),   // kCfgHalo8x16n32k32
-        CFG(half_t, "f16", 32, 64, 128, 1, 4, 4),     // kCfg32x64k128
-        CFG(half_t, "f16", 64, 64, 128, 2, 2, 4),     // kCfg64x64k128
-        REGQ(8, 16, 64, 128, 8, 16),                  // kCfgRegq8x16n64c128   (P3 head layers at 640^2)
-        REGQ(8, 8, 64, 128, 8, 16),                   // kCfgRegq8x8n64c128
-        REGQ(8, 8, 64, 256, 8, 16),                   // kCfgRegq8x8n64c256    (P4 head layers)
-        REGQ(8, 8, 32, 256, 8, 16),                   // kCfgRegq8x8n32c256
-        REGQ(8, 16, 64, 64, 8, 16),                   // kCfgRegq8x16n64c64    (P2 head layers when not fused)
-        REGQ(8, 16, 32, 128, 8, 16),                  // kCfgRegq8x16n32c128
-        // stride 2 (stage convs, PAN down-sampling convs)
-        REGQ2(8, 8, 64, 64, 8, 16),                   // kCfgRegqS2_8x8n64c64     (stage2_conv, down1)
-        REGQ2(8, 16, 64, 64, 8, 16),                  // kCfgRegqS2_8x16n64c64
-        REGQ2(8, 8, 64, 128, 8, 16),                  // kCfgRegqS2_8x8n64c128    (stage3_conv, down2)
-        REGQ2(4, 8, 64, 128, 8, 16),                  // kCfgRegqS2_4x8n64c128
-        REGQ2(8, 16, 64, 32, 8, 8),                   // kCfgRegqS2_8x16n64c32    (stage1_conv)
-        REGQ2(8, 8, 32, 128, 8, 16),                  // kCfgRegqS2_8x8n32c128
-        WS(16, 128, 2, 4),                            // kCfgWs16x16n64c128    (P3 head layers, weights-stationary, two chunks of 64 channels)
-        WS(8, 256, 4, 4),                             // kCfgWs8x16n64c256     (P4 head layers, weights-stationary, four chunks)
-        NOCFG, NOCFG, NOCFG,                          // (split-fp16 weights-stationary kernels)
-        WS(8, 128, 2, 4),                             // kCfgWs8x16n64c128     (the pair on large frames: half-height tiles, 230 VGPRs, two workgroups per CU)
-        WS(4, 256, 4, 4),                             // kCfgWs4x16n64c256
-    },
-    {
-        CFG(float, "f32", 64, 64, 64, 2, 2, 4),    // kCfg64x64k64
-        CFG(float, "f32", 64, 64, 32, 2, 2, 4),    // kCfg64x64k32
-        CFG(float, "f32", 128, 64, 64, 2, 2, 4),    // kCfg128x64k64
-        CFG(float, "f32", 128, 64, 32, 2, 2, 4),    // kCfg128x64k32
-        CFG(float, "f32", 128, 128, 64, 2, 2, 4),    // kCfg128x128k64
-        CFG(float, "f32", 128, 32, 64, 4, 1, 4),    // kCfg128x32k64
-        CFG(float, "f32", 128, 32, 32, 4, 1, 4),    // kCfg128x32k32
-        CFG(float, "f32", 128, 16, 64, 4, 1, 4),    // kCfg128x16k64
-        CFG(float, "f32", 32, 64, 64, 1, 4, 4),    // kCfg32x64k64
-        CFG(float, "f32", 32, 64, 64, 1, 4, 8),    // kCfg32x64k64s8  (deep pipeline for latency-bound small grids)
-        CFG(float, "f32", 64, 64, 64, 2, 2, 6),    // kCfg64x64k64s6
-        HALO(float, "f32", 8, 8, 64, 64, 2, 2, 4),   // kCfgHalo8x8n64
-        HALO(float, "f32", 8, 8, 32, 64, 4, 1, 4),   // kCfgHalo8x8n32
-        HALO(float, "f32", 8, 16, 64, 64, 2, 2, 4),   // kCfgHalo8x16n64
-        HALO(float, "f32", 8, 16, 32, 64, 4, 1, 4),   // kCfgHalo8x16n32
-        HALO(float, "f32", 8, 8, 64, 32, 2, 2, 4),   // kCfgHalo8x8n64k32
-        HALO(float, "f32", 8, 16, 32, 32, 4, 1, 4),   // kCfgHalo8x16n32k32
-        CFG(float, "f32", 32, 64, 128, 1, 4, 4),     // kCfg32x64k128
-        CFG(float, "f32", 64, 64, 128, 2, 2, 4),     // kCfg64x64k128
-        NOCFG, NOCFG, NOCFG, NOCFG, NOCFG, NOCFG,     // register-queue / weights-stationary kernels: fp16 / int8 / split fp16 only
-        NOCFG, NOCFG, NOCFG, NOCFG, NOCFG, NOCFG,
-        NOCFG, NOCFG,
-        NOCFG, NOCFG, NOCFG,
-        NOCFG, NOCFG,                                 // (fp16 half-height weights-stationary tiles)
-    },
-    {
-        CFG(signed char, "i8", 64, 64, 64, 2, 2, 4),    // kCfg64x64k64
-        CFG(signed char, "i8", 64, 64, 32, 2, 2, 4),    // kCfg64x64k32
-        CFG(signed char, "i8", 128, 64, 64, 2, 2, 4),    // kCfg128x64k64
-        CFG(signed char, "i8", 128, 64, 32, 2, 2, 4),    // kCfg128x64k32
-        CFG(signed char, "i8", 128, 128, 64, 2, 2, 4),    // kCfg128x128k64
-        CFG(signed char, "i8", 128, 32, 64, 4, 1, 4),    // kCfg128x32k64
-        CFG(signed char, "i8", 128, 32, 32, 4, 1, 4),    // kCfg128x32k32
-        CFG(signed char, "i8", 128, 16, 64, 4, 1, 4),    // kCfg128x16k64
-        CFG(signed char, "i8", 32, 64, 64, 1, 4, 4),    // kCfg32x64k64
-        CFG(signed char, "i8", 32, 64, 64, 1, 4, 8),    // kCfg32x64k64s8  (deep pipeline for latency-bound small grids)
-        CFG(signed char, "i8", 64, 64, 64, 2, 2, 6),    // kCfg64x64k64s6
-        HALO(signed char, "i8", 8, 8, 64, 64, 2, 2, 4),   // kCfgHalo8x8n64
-        HALO(signed char, "i8", 8, 8, 32, 64, 4, 1, 4),   // kCfgHalo8x8n32
-        HALO(signed char, "i8", 8, 16, 64, 64, 2, 2, 4),   // kCfgHalo8x16n64
-        HALO(signed char, "i8", 8, 16, 32, 64, 4, 1, 4),   // kCfgHalo8x16n32
-        HALO(signed char, "i8", 8, 8, 64, 32, 2, 2, 4),   // kCfgHalo8x8n64k32
-        HALO(signed char, "i8", 8, 16, 32, 32, 4, 1, 4),   // kCfgHalo8x16n32k32
-        CFG(signed char, "i8", 32, 64, 128, 1, 4, 4),     // kCfg32x64k128
-        CFG(signed char, "i8", 64, 64, 128, 2, 2, 4),     // kCfg64x64k128
-        REGQI(8, 16, 64, 128, 8, 16),                 // kCfgRegq8x16n64c128   (P3 head layers)
-        REGQI(8, 8, 64, 128, 8, 16),                  // kCfgRegq8x8n64c128
-        REGQI(8, 8, 64, 256, 8, 16),                  // kCfgRegq8x8n64c256    (P4 head layers)
-        REGQI(8, 8, 32, 256, 8, 16),                  // kCfgRegq8x8n32c256
-        NOCFG,                                        // kCfgRegq8x16n64c64    (the P2 head is an fp16 carve-out)
-        REGQI(8, 16, 32, 128, 8, 16),                 // kCfgRegq8x16n32c128
-        REGQI2(8, 8, 64, 64, 8, 8),                   // kCfgRegqS2_8x8n64c64     (down1)
-        REGQI2(8, 16, 64, 64, 8, 8),                  // kCfgRegqS2_8x16n64c64
-        REGQI2(8, 8, 64, 128, 8, 16),                 // kCfgRegqS2_8x8n64c128    (stage3_conv, down2)
-        REGQI2(4, 8, 64, 128, 8, 16),                 // kCfgRegqS2_4x8n64c128
-        NOCFG,                                        // kCfgRegqS2_8x16n64c32    (Cin 32 < one int8 block)
-        REGQI2(8, 8, 32, 128, 8, 16),                 // kCfgRegqS2_8x8n32c128
-        WSI(16, 128, 2, 4),                           // kCfgWs16x16n64c128
-        WSI(8, 256, 4, 4),                            // kCfgWs8x16n64c256
-        NOCFG, NOCFG, NOCFG,
-        NOCFG, NOCFG,                                 // (fp16 half-height weights-stationary tiles)
-    },
-    {   // split fp16 (kS16): a K-step stages (hi, lo) block pairs -- twice the LDS per stage, hence shallower rings on the wide tiles
-        CFG(s16_t, "s16", 64, 64, 64, 2, 2, 3),     // kCfg64x64k64
-        CFG(s16_t, "s16", 64, 64, 32, 2, 2, 4),     // kCfg64x64k32
-        CFG(s16_t, "s16", 128, 64, 64, 2, 2, 3),    // kCfg128x64k64
-        CFG(s16_t, "s16", 128, 64, 32, 2, 2, 4),    // kCfg128x64k32
-        NOCFG,                                      // kCfg128x128k64 (a stage would be 64 KB)
-        CFG(s16_t, "s16", 128, 32, 64, 4, 1, 3),    // kCfg128x32k64
-        CFG(s16_t, "s16", 128, 32, 32, 4, 1, 4),    // kCfg128x32k32
-        CFG(s16_t, "s16", 128, 16, 64, 4, 1, 3),    // kCfg128x16k64
-        CFG(s16_t, "s16", 32, 64, 64, 1, 4, 4),     // kCfg32x64k64
-        NOCFG,                                      // kCfg32x64k64s8
-        NOCFG,                                      // kCfg64x64k64s6
-        NOCFG, NOCFG, NOCFG, NOCFG, NOCFG, NOCFG,   // halo kernels
-        NOCFG, NOCFG,                               // kCfg32x64k128, kCfg64x64k128
-        // register-queue 3x3: hi / lo patch images in LDS, (hi | lo) weight block pairs through the queue (D pairs = 2 D KiB in flight)
-        REGQS(8, 16, 64, 128, 8, 8),                // kCfgRegq8x16n64c128   (P3 head layers)
-        REGQS(8, 8, 64, 128, 8, 8),                 // kCfgRegq8x8n64c128
-        REGQS(8, 8, 64, 256, 8, 8),                 // kCfgRegq8x8n64c256    (P4 head layers)
-        NOCFG,                                      // kCfgRegq8x8n32c256
-        REGQS(8, 16, 64, 64, 8, 8),                 // kCfgRegq8x16n64c64    (P2 head layers)
-        NOCFG,                                      // kCfgRegq8x16n32c128
-        REGQS2(8, 8, 64, 64, 8, 8),                 // kCfgRegqS2_8x8n64c64     (stage2_conv, down1)
-        NOCFG,                                      // kCfgRegqS2_8x16n64c64
-        REGQS2(8, 8, 64, 128, 8, 8),                // kCfgRegqS2_8x8n64c128    (stage3_conv, down2)
-        REGQS2(4, 8, 64, 128, 8, 8),                // kCfgRegqS2_4x8n64c128
-        REGQS2(8, 16, 64, 32, 8, 8),                // kCfgRegqS2_8x16n64c32    (stage1_conv)
-        NOCFG,                                      // kCfgRegqS2_8x8n32c128
-        WSS(16, 128, 4, 4),                         // kCfgWs16x16n64c128    (P3 head layers in the pair: 16-row tiles, four chunks of 32 channels --
-                                                    //  100 + 120 workgroups run in ONE round; with 8-row tiles the pair's 320 needed two)
-        NOCFG,                                      // kCfgWs8x16n64c256     (fp16 / int8 only)
-        WSS(16, 64, 2, 4),                          // kCfgWsS8x16n64c64     (P2 head layers: 16-row tiles, two chunks of 32 channels -- 200 workgroups, ONE round; the 8-row
-                                                    //  single-chunk form ran 400 workgroups at one per CU in two rounds: 18 us per layer)
-        WSS(8, 128, 2, 4),                          // kCfgWsS8x16n64c128    (P3 head layers: two chunks of 64 channels)
-        WSS(8, 256, 4, 4),                          // kCfgWsS8x16n64c256    (P4 head layers: four chunks. 4-row tiles -- 240 workgroups of the P3 conv's size -- ran 34 us per pair against 30.6)
-        NOCFG, NOCFG,                               // (fp16 half-height weights-stationary tiles)
-    },
-};
-#undef CFG
-#undef HALO
-#undef REGQ
-#undef REGQ2
-#undef REGQI
-#undef REGQI2
-#undef NOCFG
-#undef WS
-#undef WSI
-#undef WSS
-#undef REGQS
-#undef REGQS2
+  // weights-stationary 3x3: <T, TH, Cin, chunks, waves>; the pairs' tiles (WsP3, WsP4, WsP3Half, WsP4Half) are named at the pair kernel
+  t.add<WsP3<half_t>>(kCfgWs16x16n64c128);        // (P3 head layers: two chunks of 64 channels)
+  t.add<WsP4<half_t>>(kCfgWs8x16n64c256);         // (P4 head layers: four chunks)
+  t.add<WsP3Half>(kCfgWs8x16n64c128);             // (the pair on large frames: half-height tiles, two workgroups per CU)
+  t.add<WsP4Half>(kCfgWs4x16n64c256);
+  t.add<WsP3<signed char>>(kCfgWs16x16n64c128);
+  t.add<WsP4<signed char>>(kCfgWs8x16n64c256);
+  t.add<WsP3<s16_t>>(kCfgWs16x16n64c128);         // (P3 head layers in the pair: four chunks of 32 channels)
+  t.add<WsTile<s16_t, 16, 64, 2, 4>>(kCfgWsS16x16n64c64);   // (P2 head layers: 16-row tiles, two chunks of 32 channels -- 200 workgroups, ONE round;
+                                                            //  the 8-row single-chunk form ran 400 workgroups at one per CU in two rounds: 18 us per layer)
+  t.add<WsTile<s16_t, 8, 128, 2, 4>>(kCfgWsS8x16n64c128);   // (P3 head layers: two chunks of 64 channels)
+  t.add<WsP4<s16_t>>(kCfgWsS8x16n64c256);         // (P4 head layers, alone and in the pair)
+  return t;
+}
+constexpr ConvTable kTable = conv_table();
+static_assert(kTable.clashes == 0, "two rows of conv_table() name the same (dtype, configuration)");
+constexpr const CfgInfo (&kCfg)[kNumDTypes][kCfgCount] = kTable.at;
 
 inline int block_k(int dtype) { return dtype == kF32 ? 16 : (dtype == kI8 ? 64 : 32); }   // (kS16: 32 per plane)
 inline int kstep_of(const ConvParams& p, const CfgInfo& c) { return (c.bk / 32) * block_k(p.dtype); }
 inline size_t esize(const ConvParams& p) { return p.dtype == kF32 ? 4 : (p.dtype == kI8 ? 1 : 2); }   // (kS16: per plane)
-inline size_t smem_for(const ConvParams& p, const CfgInfo& c) {
-  if (!c.th) return c.smem;
-  if (c.cin) {  // register-queue kernel: patch (+ < 1 KiB overrun of its last DMA instruction) or the epilogue staging tile
-    const size_t ph = c.stride * (c.th - 1) + 3, pw = c.stride * (c.tw - 1) + 3;
-    const size_t patch = ((ph * pw * c.cin * esize(p) + 1023) & ~(size_t)1023) + 1024;
-    if (c.ws && c.chunks)   // image(s) of a channel chunk, two buffers (conv3x3_wsc_body)
-      return (c.chunks > 1 ? 2 : 1) * (p.dtype == kS16 ? 2 : 1) * ph * pw * ((c.cin / c.chunks) * (p.dtype == kI8 ? 1 : 2) + 32);
-    if (p.dtype == kS16) return 2 * patch;                // hi and lo images; accumulators are stored straight from registers
-    return max_sz(patch, stage_bytes((c.bm + 15) & ~15, c.bn));
-  }
-  const size_t patch = (size_t)(c.th + 2) * (c.tw + 2) * p.Cin * esize(p);
-  return max_sz(c.smem + ((patch + 1023) & ~(size_t)1023), stage_bytes(c.bm, c.bn));
-}
+inline size_t smem_for(const ConvParams& p, const CfgInfo& c) { return c.lds_bytes(p.Cin); }
 int n_tiles(const ConvParams& p, int bn) {
   int t = 0;
   for (int s = 0; s < p.nseg; ++s) t += (((p.seg[s].n_count + 15) & ~15) + bn - 1) / bn;
@@ -1405,9 +1393,9 @@ dim3 conv_grid(const ConvParams& p, int cfg) {
   return dim3((p.M + c.bm - 1) / c.bm, n_tiles(p, c.bn), 1);
 }
 
-// ---- dual launches (conv_dual_head3x3 / conv_dual_head1x1) ----
+// ---- dual launches ----
 struct DualKind {
-  int cfg_a, cfg_b, threads;
+  int cfg_a, cfg_b, threads;   // the configurations that launch like the kernel's two tiles
   const char* name;
   void (*fn)(const ConvParams, const ConvParams, int);
   bool b_first;   // the weights-stationary pairs put conv B's workgroups first
@@ -1415,23 +1403,41 @@ struct DualKind {
 };
 enum { kDualRegq = 0, kDual1x1, kDualRegqI8, kDualWs, kDualWsI8, kDualRegqS16, kDualWsS16, kDualWsSmall, kDualWsStamped, kDualWsS16Stamped,
        kDualKinds };
-#define WS_PAIR "conv_dual_head3x3_ws<ws 16x16,64,128/2 | ws 8x16,64,256/4>"
-#define WS_S16_PAIR "conv_dual_head3x3_ws_s16<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>"
-const DualKind kDual[kDualKinds] = {
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3<regq 8x16,64,128 | regq 8x8,64,256>", conv_dual_head3x3, false, -1},
-    {kCfg128x16k64, kCfg128x16k64, 256, "conv_dual_head1x1<glds 128,16,64 x2>", conv_dual_head1x1, false, -1},
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_i8<regq i8,8x16,64,128 | regq i8,8x8,64,256>", conv_dual_head3x3_i8, false, -1},
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, WS_PAIR, conv_dual_head3x3_ws, true, kDualWsStamped},
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws_i8<ws i8,16x16,64,128/2 | ws i8,8x16,64,256/4>", conv_dual_head3x3_ws_i8, true, -1},
-    {kCfgRegq8x16n64c128, kCfgRegq8x8n64c256, 512, "conv_dual_head3x3_s16<regq s16,8x16,64,128 | regq s16,8x8,64,256>", conv_dual_head3x3_s16, false, -1},
-    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, WS_S16_PAIR, conv_dual_head3x3_ws_s16, true, kDualWsS16Stamped},
-    {kCfgWs8x16n64c128, kCfgWs4x16n64c256, 256, "conv_dual_head3x3_ws_small<ws 8x16,64,128/2 | ws 4x16,64,256/4, 2 per CU>", conv_dual_head3x3_ws_small, true, -1},
+
+// The configuration whose row launches like `Tile`: same grid, same threads, same LDS bytes, valid for the same convs (a pair's
+// tile may differ from the row's in what the host never sees, the register-queue pairs' queue depth). No such row: no pair.
+template <class T>
+constexpr int slot_like() {
+  for (int i = 0; i < kCfgCount; ++i) {
+    const CfgInfo& c = kCfg[Elem<typename T::elem>::kDType][i];
+    if (c.fn && c.bm == T::bm && c.bn == T::bn && c.bk == T::bk && c.th == T::th && c.tw == T::tw && c.cin == T::cin && c.nthreads == T::nthreads &&
+        c.stride == T::stride && c.ws == T::ws && c.chunks == T::chunks && c.lds_bytes(T::cin) == T::lds_bytes(T::cin))
+      return i;
+  }
+  return -1;
+}
+// The row of a pair kernel that is instantiated with the tiles A, B
+template <class A, class B>
+constexpr DualKind pair_of(const char* name, void (*fn)(const ConvParams, const ConvParams, int), bool b_first, int twin = -1) {
+  static_assert(slot_like<A>() >= 0 && slot_like<B>() >= 0 && A::nthreads == B::nthreads, "a pair's tiles are rows of the table");
+  return {slot_like<A>(), slot_like<B>(), A::nthreads, name, fn, b_first, twin};
+}
+template <typename T> constexpr DualKind regq_pair(const char* name) { return pair_of<RegqP3<T>, RegqP4<T>>(name, conv_dual_regq<RegqP3<T>, RegqP4<T>>, false); }
+template <class A, class B, bool STAMPS = false, int MIN_WAVES = 0>
+constexpr DualKind ws_pair(const char* name, int twin = -1) { return pair_of<A, B>(name, conv_dual_ws<A, B, STAMPS, MIN_WAVES>, true, twin); }
+constexpr DualKind kDual[kDualKinds] = {
+    regq_pair<half_t>("conv_dual_head3x3<regq 8x16,64,128 | regq 8x8,64,256>"),
+    pair_of<Head1x1, Head1x1>("conv_dual_head1x1<glds 128,16,64 x2>", conv_dual_head1x1, false),
+    regq_pair<signed char>("conv_dual_head3x3_i8<regq i8,8x16,64,128 | regq i8,8x8,64,256>"),
+    ws_pair<WsP3<half_t>, WsP4<half_t>>("conv_dual_head3x3_ws<ws 16x16,64,128/2 | ws 8x16,64,256/4>", kDualWsStamped),
+    ws_pair<WsP3<signed char>, WsP4<signed char>>("conv_dual_head3x3_ws_i8<ws i8,16x16,64,128/2 | ws i8,8x16,64,256/4>"),
+    regq_pair<s16_t>("conv_dual_head3x3_s16<regq s16,8x16,64,128 | regq s16,8x8,64,256>"),
+    ws_pair<WsP3<s16_t>, WsP4<s16_t>>("conv_dual_head3x3_ws_s16<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>", kDualWsS16Stamped),
+    ws_pair<WsP3Half, WsP4Half, false, 2>("conv_dual_head3x3_ws_small<ws 8x16,64,128/2 | ws 4x16,64,256/4, 2 per CU>"),
     // (the debug twins carry names of their own: an op info that showed one would say so)
-    {kCfgWs16x16n64c128, kCfgWs8x16n64c256, 256, "conv_dual_head3x3_ws_stamped<ws 16x16,64,128/2 | ws 8x16,64,256/4>", conv_dual_head3x3_ws_stamped, true, -1},
-    {kCfgWs16x16n64c128, kCfgWsS8x16n64c256, 256, "conv_dual_head3x3_ws_s16_stamped<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>", conv_dual_head3x3_ws_s16_stamped, true, -1},
+    ws_pair<WsP3<half_t>, WsP4<half_t>, true>("conv_dual_head3x3_ws_stamped<ws 16x16,64,128/2 | ws 8x16,64,256/4>"),
+    ws_pair<WsP3<s16_t>, WsP4<s16_t>, true>("conv_dual_head3x3_ws_s16_stamped<ws s16,16x16,64,128/4 | ws s16,8x16,64,256/4>"),
 };
-#undef WS_PAIR
-#undef WS_S16_PAIR
 
 }  // namespace
 
@@ -1474,12 +1480,12 @@ bool conv_config_valid(const ConvParams& p, int cfg) {
   return c.bn <= min_npad || (c.bn == 16);
 }
 
-// Heuristic: the widest tile that still yields >= ~1.5 workgroups per CU (256 CUs), K-step 64 when Cin allows.
+// Heuristic: the widest tile that still yields >= ~1.5 workgroups per CU, K-step 64 when Cin allows.
 int conv_plan(const ConvParams& p) {
   const int override_cfg = p.force_cfg;
   if (override_cfg >= 0 && conv_config_valid(p, override_cfg)) return override_cfg;
   if (p.dtype == kS16 && p.ksize == 3) {   // STRICT engines: 3x3 convs on the patch-resident kernels even without autotuning
-    for (int c : {(int)kCfgWsS8x16n64c64, (int)kCfgWsS8x16n64c128, (int)kCfgWsS8x16n64c256, (int)kCfgRegqS2_8x16n64c32, (int)kCfgRegqS2_8x8n64c64,
+    for (int c : {(int)kCfgWsS16x16n64c64, (int)kCfgWsS8x16n64c128, (int)kCfgWsS8x16n64c256, (int)kCfgRegqS2_8x16n64c32, (int)kCfgRegqS2_8x8n64c64,
                   (int)kCfgRegqS2_4x8n64c128, (int)kCfgRegq8x16n64c64, (int)kCfgRegq8x16n64c128, (int)kCfgRegq8x8n64c256})
       if (conv_config_valid(p, c)) return c;
   }
@@ -1494,7 +1500,7 @@ int conv_plan(const ConvParams& p) {
   else if (min_npad < 64) cfg = k64 ? kCfg128x32k64 : kCfg128x32k32;
   else {
     auto blocks = [&](int c) { return ((p.M + kCfg[0][c].bm - 1) / kCfg[0][c].bm) * n_tiles(p, kCfg[0][c].bn); };
-    const int want = 384;
+    const int want = kCUs * 3 / 2;
     if (k64 && min_npad >= 128 && blocks(kCfg128x128k64) >= want) cfg = kCfg128x128k64;
     else if (blocks(k64 ? kCfg128x64k64 : kCfg128x64k32) >= want) cfg = k64 ? kCfg128x64k64 : kCfg128x64k32;
     else if (!k64 || blocks(kCfg64x64k64) >= want || p.M % 64) cfg = k64 ? kCfg64x64k64 : kCfg64x64k32;
@@ -1535,7 +1541,7 @@ hipError_t conv_desc(ConvParams& p, int cfg, LaunchDesc* d) {
   if (cfg < 0 || cfg >= kCfgCount || !kCfg[p.dtype][cfg].fn) return hipErrorInvalidValue;
   const CfgInfo& c = kCfg[p.dtype][cfg];
   const int n = conv_prepare(p, cfg);
-  *d = {reinterpret_cast<const void*>(c.fn), dim3(n), dim3(c.nthreads), (unsigned)smem_for(p, c), c.name};
+  *d = {reinterpret_cast<const void*>(c.fn), dim3(n), dim3(c.nthreads), (unsigned)smem_for(p, c), c.name.s};
   return hipSuccess;
 }
 
@@ -1560,7 +1566,7 @@ int conv_dual_match(const ConvParams& a, const ConvParams& b) {
   if (ws && fits(kDualWs)) {
     // more workgroups than CUs with the full-height tiles: the half-height form, two workgroups per CU
     const dim3 ga = conv_grid(a, kDual[kDualWs].cfg_a), gb = conv_grid(b, kDual[kDualWs].cfg_b);
-    if (fits(kDualWsSmall) && ga.x * ga.y + gb.x * gb.y > 256) return kDualWsSmall;
+    if (fits(kDualWsSmall) && ga.x * ga.y + gb.x * gb.y > kCUs) return kDualWsSmall;
     return kDualWs;
   }
   if (fits(kDualRegq)) return kDualRegq;
@@ -1585,10 +1591,14 @@ hipError_t conv_dual_desc(int kind, ConvParams& a, ConvParams& b, LaunchDesc* d,
 }
 
 const char* conv_config_name(int cfg, int dtype) {
-  return (cfg >= 0 && cfg < kCfgCount && dtype >= 0 && dtype < kNumDTypes) ? kCfg[dtype][cfg].name : "?";
+  return (cfg >= 0 && cfg < kCfgCount && dtype >= 0 && dtype < kNumDTypes) ? kCfg[dtype][cfg].name.s : "?";
 }
 
 }  // namespace unina
 #else
+// ISA probe builds: the pairs tools/isa_probe.sh prints
+template __global__ void conv_dual_ws<WsP3<half_t>, WsP4<half_t>>(const ConvParams, const ConvParams, int);
+template __global__ void conv_dual_ws<WsP3<signed char>, WsP4<signed char>>(const ConvParams, const ConvParams, int);
+template __global__ void conv_dual_ws<WsP3<s16_t>, WsP4<s16_t>>(const ConvParams, const ConvParams, int);
 }  // namespace unina
 #endif

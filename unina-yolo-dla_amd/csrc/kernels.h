@@ -107,8 +107,9 @@ enum ConvConfig : int {
   kCfg32x64k128, kCfg64x64k128,
   kCfgRegq8x16n64c128, kCfgRegq8x8n64c128, kCfgRegq8x8n64c256, kCfgRegq8x8n32c256, kCfgRegq8x16n64c64, kCfgRegq8x16n32c128,
   kCfgRegqS2_8x8n64c64, kCfgRegqS2_8x16n64c64, kCfgRegqS2_8x8n64c128, kCfgRegqS2_4x8n64c128, kCfgRegqS2_8x16n64c32, kCfgRegqS2_8x8n32c128,
-  kCfgWs16x16n64c128, kCfgWs8x16n64c256,
-  kCfgWsS8x16n64c64, kCfgWsS8x16n64c128, kCfgWsS8x16n64c256,   // split fp16 (STRICT engines): weights-stationary, row-walking, channel-chunked
+  kCfgWs16x16n64c128, kCfgWs8x16n64c256,                       // weights-stationary, row-walking, channel-chunked (Ws16x16n64c128: fp16 / int8
+                                                               // in two chunks of 64 channels, split fp16 in four of 32)
+  kCfgWsS16x16n64c64, kCfgWsS8x16n64c128, kCfgWsS8x16n64c256,  // the same, split fp16 (STRICT engines) only
   kCfgWs8x16n64c128, kCfgWs4x16n64c256,                        // fp16: the half-height tiles of the head pair on large frames (two workgroups per CU)
   kCfgCount
 };
