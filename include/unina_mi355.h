@@ -543,6 +543,64 @@ typedef struct { float x, y, z, u, v; int n_valid, n_samples, valid; } unina_con
 int unina_locate_async(const GpuDetection *d_dets, const int *d_count, const unina_depth *depth, const unina_pinhole *cam,
                        const unina_locate_params *p, unina_cone3d *d_out, hipStream_t stream);
 
+/* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
+ * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the
+ * device: stable ids, smoothed positions, hit and miss counts. One launch per frame (csrc/track.hip: one workgroup of 1024
+ * threads) enqueued behind unina_locate_async on the same stream; nothing is synchronised and nothing crosses to the host until
+ * unina_track_read. tracking.update_numpy is the definition, decision for decision and bit for bit. Everything is fp32, each
+ * operation rounded once in the order written, never contracted.
+ *   count     n = *d_count clamped to 0..MAX_DETECTIONS, on the device
+ *   point     record j < n: px = ((r00 * x + r01 * y) + r02 * z) + t0, py and pz from rows 1 and 2 of the pose ([R|t], row-major
+ *             3 x 4, camera frame -> tracking frame). USABLE iff cones[j].valid != 0 and px, py, pz are all finite; the record's
+ *             own `valid` is ignored, as in unina_locate_async
+ *   gate      (slot s with id != 0, usable j) is a CANDIDATE iff (class_aware == 0 or track.class_id == dets[j].class_id) and
+ *             d2 <= gate * gate, with dx = px - track.x (dy, dz likewise) and d2 = (dx * dx + dy * dy) + dz * dz. A NaN d2 fails;
+ *             d2 is never negative, so its bits order as an unsigned integer
+ *   match     greedy over all candidates in ascending (d2 bits, s, j); a pair is taken iff its slot and its record are both free
+ *   matched   x = x + alpha * dx with the dx of the gate (y, z likewise); confidence and class_id are the record's;
+ *             hits = min(hits + 1, 1 000 000 000); missed = 0
+ *   unmatched live slot: missed += 1 (it stays at INT_MAX); missed > max_missed: the slot becomes all-zero bytes (a death)
+ *   births    usable unmatched records with confidence >= birth_confidence (a NaN confidence fails), in ascending j, go to the
+ *             free slots in ascending s, the slots freed by this update's deaths included: (px, py, pz, confidence, id = next_id++,
+ *             class_id, hits = 1, missed = 0). A birth is DROPPED when no slot is left or next_id has reached INT_MAX
+ *   assign    assign[j] = id of the track record j matched or founded, else 0; all MAX_DETECTIONS words are written by every update
+ *   header    frame += 1; n_matched, n_born, n_died, n_dropped are of this update; n_live and n_confirmed (hits >= confirm_hits)
+ *             are of the table after it
+ * Integer counters and a fixed order of every fp32 operation: two runs give identical bytes. */
+#define UNINA_TRACK_MAX 1024
+typedef struct { float x, y, z, confidence; int id, class_id, hits, missed; } unina_track;   /* 32 bytes; id 0 = free slot = all-zero bytes */
+typedef struct { int frame, n_live, n_confirmed, next_id, n_matched, n_born, n_died, n_dropped; } unina_track_header;   /* 32 bytes */
+typedef struct {
+  float pose[12];                        /* row-major 3 x 4 [R|t]: camera frame -> tracking frame (odometry, or the identity) */
+  float gate, alpha, birth_confidence;   /* metres; smoothing step in (0, 1]; lowest confidence that may found a track       */
+  int class_aware, confirm_hits, max_missed;
+} unina_track_params;
+typedef struct unina_tracker unina_tracker_t;
+
+/* Host only: no HIP call. The device memory (the header and UNINA_TRACK_MAX slots) is allocated -- and reset -- by the first
+ * reset / update / read, on that call's stream, which then fails with UNINA_ERR_HIP where there is no device.
+ * UNINA_ERR_ARG: NULL out, negative device_id. */
+int unina_track_create(int device_id, unina_tracker_t **out);
+/* Waits for the device, frees. NULL is a no-op. */
+void unina_track_destroy(unina_tracker_t *t);
+/* Empty table, frame = 0, next_id = 1; enqueued on `stream`. */
+int unina_track_reset_async(unina_tracker_t *t, hipStream_t stream);
+/* One frame, enqueued on `stream`; nothing is synchronised.
+ *   d_dets / d_count : device, MAX_DETECTIONS records (16-byte aligned) / one int, as the _async calls write them
+ *   d_cones          : device, MAX_DETECTIONS unina_cone3d (16-byte aligned), as unina_locate_async writes them
+ *   d_assign         : device, MAX_DETECTIONS ints, or NULL (stored 16 bytes at a time where it is 16-byte aligned)
+ * UNINA_ERR_ARG, before any HIP call: a NULL t, d_dets, d_count, d_cones or p; d_dets or d_cones not 16-byte aligned, d_count or
+ * d_assign not 4-byte aligned; a non-finite pose element; gate not finite and positive, or gate * gate not finite (with a finite
+ * gate * gate no update stores a NaN coordinate, whose sign would be the processor's); alpha outside (0, 1]; a NaN
+ * birth_confidence; confirm_hits < 1; max_missed < 0. */
+int unina_track_update_async(unina_tracker_t *t, const GpuDetection *d_dets, const int *d_count, const unina_cone3d *d_cones,
+                             const unina_track_params *p, int *d_assign, hipStream_t stream);
+/* Device addresses of the table and the header, for a consumer that stays on the GPU (read them behind the update on its
+ * stream). Either out pointer may be NULL. UNINA_ERR_STATE before the first reset / update / read. */
+int unina_track_buffers(unina_tracker_t *t, const unina_track **d_tracks, const unina_track_header **d_header);
+/* Synchronises `stream`, then copies out the header and min(cap, UNINA_TRACK_MAX) slots (tracks may be NULL when cap is 0). */
+int unina_track_read(unina_tracker_t *t, unina_track_header *hdr, unina_track *tracks, size_t cap, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

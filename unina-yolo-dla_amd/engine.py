@@ -107,6 +107,12 @@ class LocateParams(C.Structure):
                 ("max_side", C.c_int), ("min_valid", C.c_int)]
 
 
+class TrackParams(C.Structure):
+    """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
+    _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
+                ("class_aware", C.c_int), ("confirm_hits", C.c_int), ("max_missed", C.c_int)]
+
+
 def _tile_array(tiles):
     return (Tile * len(tiles))(*[Tile(*map(int, t)) for t in tiles])
 
@@ -135,6 +141,8 @@ ABI_SYMBOLS = [
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
     "unina_locate_async",
+    "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
+    "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -244,6 +252,14 @@ def load_library() -> C.CDLL:
     L.unina_eval_read.argtypes = [vp, C.POINTER(EvalResult), vp, C.c_size_t, vp, C.c_size_t, vp]
     # 3-D localisation (csrc/locate.hip)
     L.unina_locate_async.argtypes = [vp, vp, C.POINTER(Depth), C.POINTER(Pinhole), C.POINTER(LocateParams), vp, vp]
+    # tracking (csrc/track.hip)
+    L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
+    L.unina_track_destroy.argtypes = [vp]
+    L.unina_track_destroy.restype = None
+    L.unina_track_reset_async.argtypes = [vp, vp]
+    L.unina_track_update_async.argtypes = [vp, vp, vp, vp, C.POINTER(TrackParams), vp, vp]
+    L.unina_track_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.unina_track_read.argtypes = [vp, vp, vp, C.c_size_t, vp]
     # multi-GPU: RCCL gather of detection slots behind the C ABI (csrc/comm.hip)
     L.unina_comm_unique_id.argtypes = [vp]
     L.unina_comm_init.argtypes = [C.POINTER(vp), vp, ci, ci, ci]
