@@ -666,7 +666,8 @@ int unina_debug_read_buffer(unina_engine_t *e, const char *name, float *host_out
  * when the environment has UNINA_POST_STAMPS=1. out16 (16 values): [7] launch 1 starts (workgroup 0), [0] its decode is
  * done, [1] last arriver found, [2] candidates gathered (launch 1 ends), [3] launch 2 starts, [4] its last arriver
  * found (all pair tiles done), [8] ranks / masks loaded, [9] per-class row lists built, [5] greedy scan done, [6] output
- * written. (The older launch forms use [0..6] as decode, hand-off, gather, sort, masks, scan, output.) */
+ * written, [10..13] scan wave v = 0..3: its number of rows in bits 0..19, the low clock bits at its end from bit 20 up.
+ * (The one-launch form uses [0..6] as decode, hand-off, gather, sort, masks, scan, output.) Slots 14 and 15 are unused. */
 int unina_debug_post_stamps(unina_engine_t *e, long long *out16);
 
 /* Debug: one launch of conv op `op_index` with in-kernel s_memtime stamps of a mid-grid workgroup:

@@ -50,8 +50,11 @@ def cut_model(conf):
     klo = bits(F(T) / F(pc.BINS))
     khi = 0x3F800001 if T == pc.BINS - 1 else bits(F(T + 1) / F(pc.BINS))
     levels = 0
+    out.update(klo0=klo, khi0=khi, wdt0=None)          # bin T's key range, and the width of its first split if there is one
     while cnt > pc.MEM_CAP and khi - klo > 1:
         wdt = (khi - klo + pc.BINS - 1) // pc.BINS
+        if levels == 0:
+            out["wdt0"] = wdt
         m = keys[(keys >= klo) & (keys < khi)]
         b, want, cnt = take_from_top(np.bincount((m - klo) // wdt, minlength=pc.BINS), want)
         nlo = klo + b * wdt

@@ -81,6 +81,7 @@ struct DeviceResult {  // what the fused post-process writes; one D2H brings cou
   GpuDetection det[MAX_DETECTIONS];
   long long pad_stamps[16]; // debug phase stamps of the post-process kernel (UNINA_POST_STAMPS=1) / of a conv or a dual conv launch
 };
+static_assert(kPostStampCount <= (int)(sizeof(DeviceResult::pad_stamps) / sizeof(long long)), "every PostStamp slot fits pad_stamps");
 
 }  // namespace
 
@@ -123,7 +124,7 @@ struct unina_engine {
   hipGraph_t fgraph = nullptr;
   hipGraphExec_t fexec = nullptr;
   hipGraphNode_t stem_node = nullptr, post_node = nullptr, post_node2 = nullptr;
-  bool post_split = true;            // post-process mode 2: two launches, compact candidate list, sort-free NMS (UNINA_POST_SPLIT=0: mode 0, one launch)
+  bool post_split = true;            // post-process kPostSplit: two launches, compact candidate list, sort-free NMS (UNINA_POST_SPLIT=0: kPostOneLaunch)
   bool fold_heads = true;            // full-frame graph: the heads' output convs run inside the decode launch (UNINA_POST_FOLD=0: off)
   int fold_op[3] = {-1, -1, -1};     // per head: the output-conv op the decode launch absorbs (-1: the head is read from its planes)
   int stem_op = -1;
@@ -803,7 +804,7 @@ void launch_info(unina_engine* e, size_t i, LaunchForm f) {
 bool launches_in_frame(const unina_engine* e, size_t j, const PostParams& pp) {
   auto folded = [&](int k) {
     for (int h = 0; h < 3; ++h)
-      if (pp.mode == 2 && e->fold_op[h] == k && pp.h1[h] != nullptr) return true;
+      if (pp.mode == kPostSplit && e->fold_op[h] == k && pp.h1[h] != nullptr) return true;
     return false;
   };
   const LaunchForm f = launch_form(e, j);
@@ -1317,9 +1318,9 @@ int fill_post_params(unina_engine* e, PostParams* pp, const FrameCall& call, flo
   pp->cand = e->d_cand;
   pp->block_count = e->d_block_count;
   pp->ticket = e->d_ticket;
-  pp->mode = e->post_split ? 2 : 0;
-  if (pp->mode) post_bind_workspace(pp, e->d_post_ws);
-  if (pp->mode == 2) {
+  pp->mode = e->post_split ? kPostSplit : kPostOneLaunch;
+  if (pp->mode == kPostSplit) {
+    post_bind_workspace(pp, e->d_post_ws, e->d_cand);
     for (int h = 0; h < 3 && fold; ++h) {
       if (e->fold_op[h] < 0) continue;
       const ConvParams& c = e->ops[e->fold_op[h]].cp;
@@ -1334,7 +1335,7 @@ int fill_post_params(unina_engine* e, PostParams* pp, const FrameCall& call, flo
       }
     }
     if (!post_plan_blocks(pp)) {     // does not fit the block table: everything in one launch
-      pp->mode = 0;
+      pp->mode = kPostOneLaunch;
       pp->ws_box = nullptr;
       for (int h = 0; h < 3; ++h) pp->h1[h] = nullptr;
     }
@@ -1522,7 +1523,7 @@ int load_device(unina_engine* e, const std::vector<char>& blob) {
   }
   e->post_blocks = post_num_blocks(gw, gh);
   if (e->post_blocks > kPostBlock) return fail(nullptr, UNINA_ERR_UNSUPPORTED, "input too large for the post-process workspace");
-  {  // candidate segments: post_blocks x 1024 records (modes 0 / 1) or up to 1024 workgroups x 256 (mode 2)
+  {  // candidate segments: post_blocks x 1024 records (one-launch form) or up to 1024 workgroups x 256 (split form)
     const size_t recs = (size_t)e->post_blocks * kPostBlock > (size_t)1024 * kPost2Block ? (size_t)e->post_blocks * kPostBlock : (size_t)1024 * kPost2Block;
     LOADCHK(hipMalloc(&e->d_cand, sizeof(GpuDetection) * recs));
     LOADCHK(hipMalloc(&e->d_block_count, sizeof(int) * (size_t)(e->post_blocks > 1024 ? e->post_blocks : 1024)));
@@ -2129,9 +2130,8 @@ static int enqueue_merge(unina_engine* e, TileGatherParams* g, const GpuDetectio
                          GpuDetection* d_out, int* d_out_count, unsigned int* done, unsigned int done_value, hipStream_t stream) {
   PostParams pp;
   memset(&pp, 0, sizeof pp);
-  post_bind_workspace(&pp, e->d_post_ws);
-  pp.mode = 2;
-  pp.cand = e->d_cand;
+  post_bind_workspace(&pp, e->d_post_ws, e->d_cand);
+  pp.mode = kPostSplit;
   pp.iou_thr = merge_iou;
   pp.eoff[2] = g->n_tiles * MAX_DETECTIONS;   // (the NMS launch sizes its enumeration-index split by eoff[2] + gw[2] * gh[2])
   pp.out = d_out;
@@ -2141,10 +2141,7 @@ static int enqueue_merge(unina_engine* e, TileGatherParams* g, const GpuDetectio
   pp.done_value = done_value;
   g->slots = d_slots;
   g->counts = d_counts;
-  g->cand = pp.cand;
-  g->ws_ke = pp.ws_ke;
-  g->ws_hist = pp.ws_hist;
-  g->ws_total = pp.ws_total;
+  g->list = pp.list;
   HIPCHK(e, merge_tiles_launch(*g, pp, stream));
   return UNINA_OK;
 }
@@ -2230,11 +2227,11 @@ int unina_infer_tiled_frame(unina_engine_t* e, const unina_frame* frame, const u
   return infer_tiled(e, "unina_infer_tiled_frame", frame, tiles, n_tiles, norm, conf, iou, q, merge_iou, false, out, out_count, stream);
 }
 
-int unina_debug_post_stamps(unina_engine_t* e, long long* out8) {
-  if (!e || !out8) return UNINA_ERR_ARG;
+int unina_debug_post_stamps(unina_engine_t* e, long long* out16) {
+  if (!e || !out16) return UNINA_ERR_ARG;
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipDeviceSynchronize());
-  HIPCHK(e, hipMemcpy(out8, e->d_result->pad_stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(out16, e->d_result->pad_stamps, sizeof(long long) * 16, hipMemcpyDeviceToHost));
   return UNINA_OK;
 }
 
@@ -2510,7 +2507,7 @@ int unina_debug_folded_heads(unina_engine_t* e) {
   fill_post_params(e, &pp, FrameCall{}, 0.5f, 0.45f, 0.1f, e->d_result->det, &e->d_result->count, &e->d_result->candidates, e->full_graph && e->use_graph);
   int mask = 0;
   for (int h = 0; h < 3; ++h)
-    if (pp.mode == 2 && pp.h1[h] != nullptr) mask |= 1 << h;
+    if (pp.mode == kPostSplit && pp.h1[h] != nullptr) mask |= 1 << h;
   return mask;
 }
 

@@ -294,6 +294,31 @@ hipError_t quant_desc(const QuantParams& p, LaunchDesc* d);
 // ------------------------------------------------------------------------------------------------
 // Fused post-process (one launch): decode three heads -> candidates -> top-1024 -> stable sort -> greedy NMS
 // ------------------------------------------------------------------------------------------------
+// The compact candidate list that post_decode_kernel (a run per workgroup) or tile_gather_kernel (a run per tile) appends to
+// and post_nms_kernel reads. A run is reserved with one atomic on *total; a record's `_pad` carries its enumeration index.
+struct CandList {
+  GpuDetection* cand;        // the records
+  uint2* ke;                 // [list] (confidence bit pattern, enumeration index), dense: what the > MAX_DETECTIONS selection sweeps
+  int* hist;                 // [4096] histogram of the candidates' confidences, bin = floor(conf * 4096) (zero at rest)
+  int* total;                // candidates in the list (zero at rest: post_nms_kernel's last arriver resets it)
+};
+enum PostMode { kPostOneLaunch = 0, kPostSplit = 1 };
+// Debug stamp slots (PostParams::stamps, wall_clock64; documented once in include/unina_mi355.h, unina_debug_post_stamps).
+// Slots 1..4 mean one thing in the one-launch form and another in the split form: both names are given, in that order.
+enum PostStamp {
+  kStampDecoded = 0,                             // decode done (workgroup 0)
+  kStampHandoff = 1, kStampListRead = 1,         // last arriver found | launch 2 has read the list length
+  kStampGathered = 2,                            // candidates gathered | tile 0's rows and columns fetched
+  kStampSorted = 3, kStampNmsStart = 3,          // sorted | launch 2 starts
+  kStampMasks = 4, kStampTilesDone = 4,          // suppression masks built | launch 2's last arriver found
+  kStampScanned = 5,                             // greedy scan done
+  kStampOutput = 6,                              // output written
+  kStampDecodeStart = 7,                         // split form: launch 1 starts (workgroup 0)
+  kStampLoaded = 8,                              // split form: ranks and masks loaded by the last arriver
+  kStampLists = 9,                               // split form: per-class row lists built
+  kStampScanWave0 = 10,                          // split form, [10..13]: rows of scan wave v | low clock bits at its end << 20
+  kPostStampCount = 14
+};
 struct PostParams {
   const float* cls[3];
   const float* reg[3];
@@ -301,29 +326,26 @@ struct PostParams {
   int num_classes;
   float conf_thr, iou_thr, conformal_q;
   // workspace (engine-owned)
-  GpuDetection* cand;        // mode 0: [nblocks][kPostBlock] per-block candidate segments; mode 2: the compact candidate list
-  int* block_count;          // mode 0: [nblocks]
+  GpuDetection* cand;        // one-launch form: [nblocks][kPostBlock] per-block candidate segments
+  int* block_count;          // one-launch form: [nblocks]
   unsigned int* ticket;      // arrival counter (zero at rest)
   // outputs
   GpuDetection* out;         // [MAX_DETECTIONS]
   int* out_count;            // kept
   int* out_candidates;       // optional (may be nullptr): number of cells that passed the threshold
-  long long* stamps;         // optional debug: 8 wall_clock64 stamps of the last block's phases (nullptr = off)
+  long long* stamps;         // optional debug: wall_clock64 stamps of the phases, slots PostStamp (nullptr = off)
   unsigned int* done_flag;   // optional (pinned host memory): receives done_value, system-scope release, after every output store
   unsigned int done_value;
-  // two-launch form (the engine's, mode 2; postprocess.hip): launch 1 = decode on many 256-thread workgroups, survivors appended to
-  // ONE compact candidate list (`cand`; a run per workgroup reserved with one atomic on ws_total; a record's `_pad` carries its
-  // enumeration index P2 -> P3 -> P4, row-major), confidences counted into ws_hist; launch 2 = one workgroup per 64x64 tile of
+  // two-launch form (the engine's, kPostSplit; postprocess.hip): launch 1 = decode on many 256-thread workgroups, survivors appended to
+  // ONE compact candidate list (`list`; enumeration index P2 -> P3 -> P4, row-major); launch 2 = one workgroup per 64x64 tile of
   // the candidate pairs computes the directional suppression bits (both directions) AND every candidate's rank (number of
   // candidates with a larger (confidence, ~enumeration index) key: a stable sort order without sorting), its last arriver runs
-  // the greedy scan in rank order (one wave per class residue) and writes the compacted output. Same results as mode 0.
-  int mode;                  // 0: everything in one launch (one workgroup gathers, sorts, scans); 2: the two-launch form
+  // the greedy scan in rank order (one wave per class residue) and writes the compacted output. Same results as kPostOneLaunch.
+  PostMode mode;             // kPostOneLaunch: one workgroup gathers, sorts, scans; kPostSplit: the two-launch form
+  CandList list;
   float4* ws_box;            // [MAX_DETECTIONS] boxes of the (selected) candidates, by list position
   float2* ws_cc;             // [MAX_DETECTIONS] (confidence, class | enumeration index << 14)
   unsigned int* ticket2;     // arrival counter of launch 2 (zero at rest)
-  int* ws_total;             // candidates in the list (zero at rest: launch 2's last arriver resets it)
-  int* ws_hist;              // [4096] histogram of the candidates' confidences, bin = floor(conf * 4096) (zero at rest)
-  uint2* ws_ke;              // [list] (confidence bit pattern, enumeration index), dense: what the > MAX_DETECTIONS selection sweeps
   int eoff[3];               // enumeration index of each head's first cell (post_plan_blocks)
   int* ws_rank;              // [MAX_DETECTIONS] rank of each candidate (zero at rest)
   unsigned long long* ws_full;    // [MAX_DETECTIONS][16] suppression bits, row = suppressor, bit = suppressed (list positions)
@@ -337,7 +359,7 @@ struct PostParams {
   int h1_coff[3][2];         // channel offset of the cls / reg branch's input
   const unsigned char* w2[3][2];  // 1-KiB fragment blocks [1][C/32] (16 rows, LANE order: ConvSeg::w_lane) of the cls / reg output conv
   const float* b2[3][2];     // [16] biases
-  int bstart[4];             // launch 1 of mode 2: first workgroup of each head, total (post_plan_blocks)
+  int bstart[4];             // launch 1 of the split form: first workgroup of each head, total (post_plan_blocks)
   int cpb[3];                // cells per workgroup of each head: 256 (planes, or 4 pixel subtiles per wave) or 64 (1 per wave)
   // box map (unina_infer_letterbox_*, map_boxes = 1): applied to the KEPT records where they are written, both corners, fp32, each
   // step rounded: X = (x - map_left) * map_sx, Y = (y - map_top) * map_sy. map_boxes == 0: no arithmetic touches a record.
@@ -345,11 +367,11 @@ struct PostParams {
   float map_left, map_top, map_sx, map_sy;
 };
 size_t post_workspace_bytes();
-void post_bind_workspace(PostParams* p, void* ws);   // ws: post_workspace_bytes() of device memory, zeroed once
-bool post_plan_blocks(PostParams* p);                // mode 2: fills bstart / cpb from gw, gh, h1; false if the grid would exceed 1024 workgroups
+void post_bind_workspace(PostParams* p, void* ws, GpuDetection* cand);   // ws: post_workspace_bytes() of device memory, zeroed once; cand: the list's records
+bool post_plan_blocks(PostParams* p);                // split form: fills bstart / cpb from gw, gh, h1; false if the grid would exceed 1024 workgroups
 constexpr int kPostBlock = 1024;
 constexpr int kMaxNumClasses = 16383;                // class ids the two-launch form's 14-bit class field holds (unina_load_engine checks)
-constexpr int kPost2Block = 256;                     // threads per workgroup of the mode-2 kernels (= candidate segment size)
+constexpr int kPost2Block = 256;                     // threads per workgroup of the split form's decode and gather kernels (= candidate segment size)
 int post_num_blocks(const int gw[3], const int gh[3]);
 hipError_t post_init();   // the post-process table, the step-wise API's kernels included
 hipError_t postprocess_launch(const PostParams& p, hipStream_t stream);
@@ -357,17 +379,14 @@ int postprocess_desc(const PostParams& p, LaunchDesc out[2]);   // number of lau
 
 // Sliced inference (unina_merge_tiles_async): the detection slots of up to kMaxTiles tiles of one camera frame -> ONE candidate
 // list in frame pixels (tile_gather_kernel, one workgroup per tile), in exactly the form launch 1 of the two-launch post-process
-// leaves behind (cand with the enumeration index in _pad, ws_ke, ws_hist, ws_total); the frame's own launch 2 (post_nms_kernel)
+// leaves behind (a CandList); the frame's own launch 2 (post_nms_kernel)
 // then merges it. Enumeration index of record i of tile t: t * MAX_DETECTIONS + i (tile-major).
 constexpr int kMaxTiles64 = 64;                       // == UNINA_MAX_TILES; kMaxTiles64 * MAX_DETECTIONS candidates fit the compact list
 struct TileMap { float sx, sy, ox, oy; };             // frame = tile * (sx, sy) + (ox, oy): fp32, multiply and add rounded separately
 struct TileGatherParams {
   const GpuDetection* slots;   // [n_tiles][MAX_DETECTIONS]
   const int* counts;           // [n_tiles] (clamped to 0..MAX_DETECTIONS on the device)
-  GpuDetection* cand;          // the handle's workspace, as PostParams
-  uint2* ws_ke;
-  int* ws_hist;
-  int* ws_total;
+  CandList list;               // the handle's workspace, as PostParams::list
   int n_tiles;
   TileMap map[kMaxTiles64];
 };

@@ -25,9 +25,17 @@
 // the segments in enumeration order, rank-sorts them in LDS (64-bit keys), builds the upper-triangular
 // suppression bitmap with broadcast LDS reads (16 waves x 64x64-bit tiles), scans it greedily, and compacts
 // with wave ballots.
+// (3) the engine's form of (1) as two launches, post_decode_kernel -> post_nms_kernel (below, "the frame's form"), and
+//     tile_gather_kernel, which feeds the same post_nms_kernel for sliced inference.
+// The three forms return the same bytes. Their shared pieces exist once: the workgroup primitives in wave_block.h (block_rank,
+// wave_incl_scan, lane_word), the integer and bit-pattern arithmetic in post_math.h (tile_of, tri_off, conf_bin, pack_ce,
+// bin_key_range, split_width: host-testable), the pair test iou_exceeds, the dummy record put_dummy, and the candidate list's
+// list_reserve / list_put.
 // Built with -ffp-contract=off: the box arithmetic must round exactly like the reference's scalar code.
 #include "kernels.h"
 #include "mfma_common.h"
+#include "post_math.h"
+#include "wave_block.h"
 
 #pragma clang fp contract(off)
 
@@ -59,23 +67,9 @@ constexpr size_t kPostSmemBytes = sizeof(Smem);
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// exclusive prefix of a 0/1 flag over the block, in thread order; returns this thread's offset, total in *total
-__device__ __forceinline__ int block_rank(bool flag, Smem& s, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int rank = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();  // protect wave_cnt from the previous use
-  if (lane == 0) s.wave_cnt[wid] = __popcll(b);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = s.wave_cnt[w];
-    if (w < wid) off += c;
-    tot += c;
-  }
-  *total = tot;
-  return off + rank;
+// debug stamp `slot` (PostStamp) by thread 0 -- of workgroup 0 only, or of whichever workgroup runs the phase
+__device__ __forceinline__ void stamp(long long* stamps, int slot, bool wg0_only = false) {
+  if (stamps && threadIdx.x == 0 && (!wg0_only || blockIdx.x == 0)) stamps[slot] = wall_clock64();
 }
 
 // one cell of one head -> (pass, record). cls_at(c) / reg_at(k) deliver the cell's raw head values (from the fp32 planes,
@@ -191,12 +185,7 @@ __device__ __forceinline__ int scan_block_counts(const int* block_count, int nbl
     for (int base = 0; base < nblocks; base += 64) {
       const int i = base + tid;
       const int v = i < nblocks ? __hip_atomic_load(block_count + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-      int incl = v;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (tid >= off) incl += t;
-      }
+      const int incl = wave_incl_scan(v, tid);
       if (i < nblocks) s.scan[i] = carry + incl - v;
       carry += __shfl(incl, 63);
     }
@@ -221,19 +210,19 @@ __device__ __forceinline__ void put(Smem& s, int pos, const GpuDetection* c) {
   s.cc[pos] = make_float2(c->confidence, __int_as_float(c->class_id));
 }
 
-__device__ __forceinline__ GpuDetection get(const Smem& s, int pos, int valid) {
+__device__ __forceinline__ GpuDetection make_det(const float4& b, float confidence, int class_id, int valid) {
   GpuDetection d;
-  const float4 b = s.box[pos];
-  const float2 c = s.cc[pos];
   d.x1 = b.x; d.y1 = b.y; d.x2 = b.z; d.y2 = b.w;
-  d.confidence = c.x;
-  d.class_id = __float_as_int(c.y);
+  d.confidence = confidence;
+  d.class_id = class_id;
   d.valid = valid;
   d._pad = 0;
   return d;
 }
 
-__device__ __forceinline__ int tri_off(int c, int nw) { return 64 * (c * nw - (c * (c - 1)) / 2); }
+__device__ __forceinline__ GpuDetection get(const Smem& s, int pos, int valid) {
+  return make_det(s.box[pos], s.cc[pos].x, __float_as_int(s.cc[pos].y), valid);
+}
 
 // Sequential greedy pass over the suppression bitmap by ONE wave: walks the 64-row chunks in order and visits only
 // rows that suppress something; a row that was itself suppressed suppresses nothing. lane w (< kWords) owns word w.
@@ -241,16 +230,10 @@ __device__ __forceinline__ int tri_off(int c, int nw) { return 64 * (c * nw - (c
 // with LDS atomics measured slower: 9.0 vs 4.4 us at n = 489.)
 __device__ __forceinline__ void greedy_scan(const unsigned long long* mask, const unsigned long long* rownz,
                                             unsigned long long* removed, int nw, int lane) {
-  unsigned long long removed_reg = 0ull;
-  // word c of the removed set lives in lane c: a wave-uniform v_readlane (c is a scalar loop counter), not a bpermute
-  auto word_of = [&](int c) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)removed_reg, c);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(removed_reg >> 32), c);
-    return ((unsigned long long)hi << 32) | lo;
-  };
+  unsigned long long removed_reg = 0ull;   // word c of the removed set lives in lane c
   for (int c = 0; c < nw; ++c) {
     unsigned long long todo = rownz[c];
-    unsigned long long cur = word_of(c);
+    unsigned long long cur = lane_word(removed_reg, c);
     const int base = tri_off(c, nw), stride = nw - c;
     const bool mine = lane >= c && lane < nw;
     const unsigned long long* row0 = mask + base + (mine ? lane - c : 0);
@@ -264,7 +247,7 @@ __device__ __forceinline__ void greedy_scan(const unsigned long long* mask, cons
       next_words = row0[rn * stride];
       if (!((cur >> r) & 1ull)) {   // (a row that was itself suppressed suppresses nothing)
         if (mine) removed_reg |= words;
-        cur = word_of(c);
+        cur = lane_word(removed_reg, c);
       }
       r = rn;
     }
@@ -328,6 +311,12 @@ __device__ __forceinline__ void sort_stages(unsigned long long& key, int N, int 
   }
 }
 
+// a record that can never be suppressed and suppresses nothing: class -1, empty box, confidence 0
+__device__ __forceinline__ void put_dummy(float4* box, float2* cc, int k) {
+  box[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  cc[k] = make_float2(0.f, __int_as_float(-1));
+}
+
 // Records 0..n) sit in s.box / s.cc in enumeration order; on return they are in SORTED order (confidence descending,
 // ties by enumeration order), padded to a multiple of 64 with never-suppressed dummies. The 64-bit keys
 // (confidence bits << 32 | ~enumeration position: all distinct, so the order is total and deterministic) are sorted
@@ -367,24 +356,26 @@ __device__ void rank_sort_records(Smem& s, int n) {
   }
   // pad the sorted arrays up to the next multiple of 64 with records that can never be suppressed (class -1)
   const int n64 = (n + 63) & ~63;
-  if (tid >= n && tid < n64) {
-    s.box[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-    s.cc[tid] = make_float2(0.f, __int_as_float(-1));
-  }
+  if (tid >= n && tid < n64) put_dummy(s.box, s.cc, tid);
   if (tid < kWords) s.rownz[tid] = 0ull;
   __syncthreads();
 }
 
-// One pair test of the greedy NMS, shared by the one-block and the tiled form (identical arithmetic and order).
-__device__ __forceinline__ bool suppresses(const float4& a, const float2& ac, float area_a, const float4& bb, const float2& bc,
-                                           bool ordered, float iou_thr) {
+// THE pair test of the greedy NMS, for every form: IoU(a, bb) > thr, symmetric bit for bit. area_a = (a.z - a.x) * (a.w - a.y)
+// is the caller's (one per row). The division only runs for boxes that intersect.
+__device__ __forceinline__ bool iou_exceeds(const float4& a, float area_a, const float4& bb, float thr) {
   const float ix1 = fmaxf(a.x, bb.x), iy1 = fmaxf(a.y, bb.y);
   const float ix2 = fminf(a.z, bb.z), iy2 = fminf(a.w, bb.w);
-  const bool cand = ordered && __float_as_int(bc.y) == __float_as_int(ac.y) && ac.x > bc.x && !(ix1 >= ix2 || iy1 >= iy2);
-  if (!cand) return false;
+  if (ix1 >= ix2 || iy1 >= iy2) return false;
   const float inter = (ix2 - ix1) * (iy2 - iy1);
   const float area_b = (bb.z - bb.x) * (bb.w - bb.y);
-  return inter / (area_a + area_b - inter + 1e-6f) > iou_thr;
+  return inter / (area_a + area_b - inter + 1e-6f) > thr;
+}
+
+// row a (sorted in front of bb: `ordered`) suppresses bb: same class, strictly higher confidence, IoU above the threshold
+__device__ __forceinline__ bool suppresses(const float4& a, const float2& ac, float area_a, const float4& bb, const float2& bc,
+                                           bool ordered, float iou_thr) {
+  return ordered && __float_as_int(bc.y) == __float_as_int(ac.y) && ac.x > bc.x && iou_exceeds(a, area_a, bb, iou_thr);
 }
 
 // One-block form: sort, then s.removed = greedy-NMS suppression bits by sorted index.
@@ -393,20 +384,15 @@ __device__ __forceinline__ bool suppresses(const float4& a, const float2& ac, fl
 //          that really overlap
 //   scan : wave 0 walks the chunks in order and visits only rows that suppress something
 __device__ void sort_and_nms(Smem& s, int n, float iou_thr, long long* stamps = nullptr) {
-#define STAMP(k) do { if (stamps && threadIdx.x == 0) stamps[k] = wall_clock64(); } while (0)
   rank_sort_records(s, n);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
-  STAMP(3);
+  stamp(stamps, kStampSorted);
   const int nw = (n + 63) >> 6;
   const int ntiles = nw * (nw + 1) / 2;
   for (int t = wid; t < ntiles; t += kWaves) {
-    int c = 0, rem = t;  // tile t -> (chunk row c, word w >= c)
-    while (rem >= nw - c) {
-      rem -= nw - c;
-      ++c;
-    }
-    const int w = c + rem;
+    const TileCW tile = tile_of(t, nw);
+    const int c = tile.c, w = tile.w;
     const int i = c * 64 + lane;
     const bool row_ok = i < n;
     const float4 a = s.box[row_ok ? i : 0];
@@ -432,12 +418,11 @@ __device__ void sort_and_nms(Smem& s, int n, float iou_thr, long long* stamps = 
     if (lane == 0 && nz) atomicOr(&s.rownz[c], nz);
   }
   __syncthreads();
-  STAMP(4);
+  stamp(stamps, kStampMasks);
 
   if (tid < 64) greedy_scan(s.mask, s.rownz, s.removed, nw, lane);
   __syncthreads();
-  STAMP(5);
-#undef STAMP
+  stamp(stamps, kStampScanned);
 }
 
 }  // namespace
@@ -486,13 +471,13 @@ __global__ __launch_bounds__(kPostBlock) void postprocess_kernel(const PostParam
                          idx, &d);
     }
     int total;
-    const int pos = block_rank(pass, s, &total);
+    const int pos = block_rank<kWaves>(pass, s.wave_cnt, &total);
     if (pass) p.cand[(size_t)blockIdx.x * kT + pos] = d;
     if (tid == 0) p.block_count[blockIdx.x] = total;
   }
-  if (p.stamps && tid == 0 && blockIdx.x == 0) p.stamps[0] = wall_clock64();
+  stamp(p.stamps, kStampDecoded, true);
   if (!arrive_and_check_last(p.ticket, &s.is_last)) return;
-  if (p.stamps && tid == 0) p.stamps[1] = wall_clock64();
+  stamp(p.stamps, kStampHandoff);
 
   // ---- phase 2 (one block): gather in enumeration order ----
   const int nblocks = gridDim.x;  // <= kT (checked on the host)
@@ -538,9 +523,9 @@ __global__ __launch_bounds__(kPostBlock) void postprocess_kernel(const PostParam
       const unsigned int key = c ? __float_as_uint(c->confidence) : 0u;
       const bool eq = c && key == T;
       int tot_eq, tot_sel;
-      const int rank_eq = block_rank(eq, s, &tot_eq);
+      const int rank_eq = block_rank<kWaves>(eq, s.wave_cnt, &tot_eq);
       const bool sel = c && (key > T || (eq && base_eq + rank_eq < want));
-      const int pos = base_sel + block_rank(sel, s, &tot_sel);
+      const int pos = base_sel + block_rank<kWaves>(sel, s.wave_cnt, &tot_sel);
       if (sel) put(s, pos, c);
       base_sel += tot_sel;
       base_eq += tot_eq;
@@ -548,13 +533,13 @@ __global__ __launch_bounds__(kPostBlock) void postprocess_kernel(const PostParam
   }
   __syncthreads();
 
-  if (p.stamps && tid == 0) p.stamps[2] = wall_clock64();
+  stamp(p.stamps, kStampGathered);
   sort_and_nms(s, n, p.iou_thr, p.stamps);
 
   // ---- compaction + output ----
   const bool kept = tid < n && !((s.removed[tid >> 6] >> (tid & 63)) & 1ull);
   int nkept;
-  const int opos = block_rank(kept, s, &nkept);
+  const int opos = block_rank<kWaves>(kept, s.wave_cnt, &nkept);
   if (kept) {
     GpuDetection d = get(s, tid, 1);
     map_box(p, d);
@@ -564,13 +549,12 @@ __global__ __launch_bounds__(kPostBlock) void postprocess_kernel(const PostParam
     *p.out_count = nkept;
     if (p.out_candidates) *p.out_candidates = total;
     __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    if (p.stamps) p.stamps[6] = wall_clock64();
   }
+  stamp(p.stamps, kStampOutput);
   signal_done(p, tid);
 }
 
 constexpr int kMaxTiles = kWords * (kWords + 1) / 2;
-
 
 // ================================================================================================ the frame's form: sort-free, folded
 // Launch 1 (post_decode_kernel, 256-thread workgroups, a few hundred of them): every workgroup owns a run of consecutive
@@ -581,9 +565,11 @@ constexpr int kMaxTiles = kWords * (kWords + 1) / 2;
 // bit; they go through LDS to the thread that decodes the cell. Survivors are appended to ONE compact candidate list (a run per
 // workgroup, reserved with one atomic; each record carries its enumeration index), their confidences counted into a 4096-bin
 // histogram -- and that is all: no ticket, no gather, no sort.
-// Launch 2 (post_nms_kernel, 512 threads): one workgroup per 64x64 tile of candidate pairs (I <= J). Each reads the list
+// Launch 2 (post_nms_kernel, 512 threads): one workgroup per 64x64 tile of candidate pairs (I <= J). Its body is a sequence of
+// phases, one function each: fetch_tile, pair_tile, the hand-off (arrive_and_check_last_sc1), and in the last arriver
+// load_ranks_and_masks, class_split_scan, emit_and_reset. Each workgroup reads the list
 // length and fetches its 64 rows and 64 columns straight from the list (when more than 1024 cells passed: the 1024 best by
-// histogram-guided selection, see the overflow branch), and besides the overlap test compares
+// histogram-guided selection, select_top), and besides the overlap test compares
 // the (confidence, ~enumeration index) keys of every pair, so a tile contributes (a) the DIRECTIONAL suppression bits of both
 // orientations -- rows of tile (I,J) per lane, rows of tile (J,I) as wave ballots -- into a full n x n bit matrix
 // indexed by list position, and (b) to every candidate's RANK = number of candidates with a larger key,
@@ -601,88 +587,56 @@ constexpr int kW2 = kT2 / 64;
 
 struct SmemD {                     // launch 1
   float stage[32][kT2];            // fold: [output channel: 0..15 cls, 16..31 reg][cell of the workgroup]
-  int scan[1024 + 8];
   int wave_cnt[kW2];
-  int hist[256];
-  int is_last;
-  int misc[4];
+  int run0;                        // first list entry of the workgroup's run
 };
 
 constexpr int kTN = 512;             // threads per workgroup of launch 2
 constexpr int kWN = kTN / 64;        // 8 waves: a 64 x 64 pair tile = 64 rows (lanes) x 8 columns per wave
 constexpr int kColsPerWave = 64 / kWN;
+constexpr int kMemCap = 1024;        // members of the cut's last bin that are ranked exactly
+struct SelectScratch {             // launch 2, more than kMaxDet candidates: select_top's working set
+  int hist[kBins];
+  unsigned mkey[kMemCap];          // the last bin's members: key, enumeration index, list entry
+  int meidx[kMemCap];
+  int mpos[kMemCap];
+  int part[kTN];                   // pick_bin: partial sums of 8 bins each; then the list entries of this tile's 64 rows | 64 columns
+};
 struct SmemN {                     // launch 2
   float4 rbox[64], cbox[64];
   float2 rcc[64], ccc[64];
   unsigned char piece[64][kWN];
   unsigned char rcnt[64][kWN];
-  unsigned long long mask[kMaxDet * kWords];   // last workgroup: row i, word w at [i * nw + w]
+  union {
+    unsigned long long mask[kMaxDet * kWords];   // last workgroup: row i, word w at [i * nw + w]
+    SelectScratch sel;                           // (the suppression matrix's LDS is free until the scan)
+  };
   unsigned short perm[kMaxDet];
-  unsigned char cls4[kMaxDet];
   unsigned short list[4][kMaxDet];
   unsigned long long removed[4][kWords];
   unsigned long long rownz[kWords];
-  int scan[1024 + 8];                // exclusive prefix of launch 1's per-workgroup candidate counts
-  int hist[256];
   int misc[4];
   int wave_cnt[kWN];
+  int sel_cnt[kWN];                  // select_top: selected members of the last bin per wave range
   int is_last;
 };
-
-// block_rank for the kTN-thread workgroups of launch 2
-__device__ __forceinline__ int block_rank_n(bool flag, int* wave_cnt /*LDS, kWN*/, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int rank = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wave_cnt[wid] = __popcll(b);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWN; ++w) {
-    const int c = wave_cnt[w];
-    if (w < wid) off += c;
-    tot += c;
-  }
-  *total = tot;
-  return off + rank;
-}
-
-// block_rank for a 256-thread workgroup
-__device__ __forceinline__ int block_rank2(bool flag, int* wave_cnt /*LDS, kW2*/, int* total) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int rank = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wave_cnt[wid] = __popcll(b);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kW2; ++w) {
-    const int c = wave_cnt[w];
-    if (w < wid) off += c;
-    tot += c;
-  }
-  *total = tot;
-  return off + rank;
-}
-
-// confidence -> bin of launch 1's histogram (4096 linear bins; x 4096 is exact in binary floating point, so bin T is
-// exactly the confidences in [T / 4096, (T + 1) / 4096))
-constexpr int kBins = 4096;
-__device__ __forceinline__ int conf_bin(float c) {
-  const int b = (int)(c * (float)kBins);
-  return b > kBins - 1 ? kBins - 1 : b;
-}
-// (class id | enumeration index << kClassBits) travels in the second float of a candidate's (confidence, class) pair. The
-// enumeration index is below kListCap = 2^18 (post_plan_blocks), which leaves 14 bits for the class; the all-ones field
-// is the padding dummy's class -1, so num_classes <= kClassMask = kMaxNumClasses (checked by unina_load_engine)
-constexpr int kClassBits = 14;
-constexpr int kClassMask = (1 << kClassBits) - 1;
+static_assert(sizeof(SelectScratch) <= sizeof(unsigned long long) * kMaxDet * kWords, "select_top's scratch lives in the mask's LDS");
 static_assert(kClassMask == kMaxNumClasses, "the all-ones class field is the dummy's -1");
-__device__ __forceinline__ float pack_ce(int class_id, int eidx) { return __int_as_float((class_id & kClassMask) | (eidx << kClassBits)); }
-__device__ __forceinline__ int ce_class(float y) { return (int)((unsigned)__float_as_int(y) << (32 - kClassBits)) >> (32 - kClassBits); }
-__device__ __forceinline__ unsigned ce_eidx(float y) { return (unsigned)__float_as_int(y) >> kClassBits; }
+
+// ---- the compact candidate list (CandList): a workgroup reserves a run with ONE atomic, then puts its records
+__device__ __forceinline__ int list_reserve(const CandList& l, int count) {
+  return count ? __hip_atomic_fetch_add(l.total, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+}
+// entry `at`: the record (two 16-byte stores) with its enumeration index in _pad, its key, its confidence into the histogram.
+// A confidence lies in [0, 1]; anything else still lands in a bin.
+__device__ __forceinline__ void list_put(const CandList& l, int at, uint4 box, uint4 rest, unsigned eidx) {
+  uint4* dst = reinterpret_cast<uint4*>(l.cand + at);
+  dst[0] = box;
+  dst[1] = make_uint4(rest.x, rest.y, rest.z, eidx);
+  l.ke[at] = make_uint2(rest.x, eidx);
+  const int bin = conf_bin(__uint_as_float(rest.x));
+  atomicAdd(&l.hist[bin < 0 ? 0 : bin], 1);
+}
 
 }  // namespace
 
@@ -695,7 +649,7 @@ __global__ __launch_bounds__(kPost2Block) void post_decode_kernel(const PostPara
   const int cell0 = (b - p.bstart[h]) * cpb;
   const int gw = p.gw[h], ncell = gw * p.gh[h];
   const int idx = cell0 + tid;
-  if (p.stamps && tid == 0 && b == 0) p.stamps[7] = wall_clock64();
+  stamp(p.stamps, kStampDecodeStart, true);
   bool pass = false;
   GpuDetection d;
   if (p.h1[h] == nullptr) {
@@ -766,362 +720,355 @@ __global__ __launch_bounds__(kPost2Block) void post_decode_kernel(const PostPara
       pass = decode_core([&](int c) { return s.stage[c][tid]; }, [&](int k) { return s.stage[16 + k][tid]; }, gw, p.stride[h],
                          p.num_classes, p.conf_thr, p.conformal_q, idx, &d);
   }
-  {
-    // survivors go to ONE compact candidate list: the workgroup reserves a run of it with a single atomic (the runs land in
-    // arrival order -- the order is immaterial, every later decision is keyed by (confidence, enumeration index), which each
-    // record carries). No per-workgroup count table, no scan, no search in launch 2. Next to the records: the confidence bit
-    // pattern and the enumeration index as dense arrays, and a 4096-bin histogram of the confidences -- what launch 2 needs to
-    // find the kMaxDet best of MORE than kMaxDet candidates in one or two coalesced sweeps.
-    int total;
-    const int pos = block_rank2(pass, s.wave_cnt, &total);
-    if (tid == 0) s.misc[0] = total ? __hip_atomic_fetch_add(p.ws_total, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    __syncthreads();
-    if (pass) {
-      const int at = s.misc[0] + pos;
-      d._pad = p.eoff[h] + idx;                       // enumeration index (P2 -> P3 -> P4, row-major): the tie-break of equal confidences
-      p.cand[at] = d;
-      p.ws_ke[at] = make_uint2(__float_as_uint(d.confidence), (unsigned)d._pad);
-      atomicAdd(&p.ws_hist[conf_bin(d.confidence)], 1);
-    }
-  }
-  if (p.stamps && tid == 0 && b == 0) p.stamps[0] = wall_clock64();
+  // survivors go to ONE compact candidate list: the workgroup reserves a run of it with a single atomic (the runs land in
+  // arrival order -- the order is immaterial, every later decision is keyed by (confidence, enumeration index), which each
+  // record carries). No per-workgroup count table, no scan, no search in launch 2. Next to the records: the confidence bit
+  // pattern and the enumeration index as dense arrays, and a 4096-bin histogram of the confidences -- what launch 2 needs to
+  // find the kMaxDet best of MORE than kMaxDet candidates in one or two coalesced sweeps.
+  int total;
+  const int pos = block_rank<kW2>(pass, s.wave_cnt, &total);
+  if (tid == 0) s.run0 = list_reserve(p.list, total);
+  __syncthreads();
+  if (pass)   // enumeration index (P2 -> P3 -> P4, row-major): the tie-break of equal confidences
+    list_put(p.list, s.run0 + pos, make_uint4(__float_as_uint(d.x1), __float_as_uint(d.y1), __float_as_uint(d.x2), __float_as_uint(d.y2)),
+             make_uint4(__float_as_uint(d.confidence), (unsigned)d.class_id, (unsigned)d.valid, 0u), (unsigned)(p.eoff[h] + idx));
+  stamp(p.stamps, kStampDecoded, true);
 }
 
-__global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
-  SmemN& s = *reinterpret_cast<SmemN*>(post_smem);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int t = blockIdx.x;
-  if (p.stamps && tid == 0 && t == 0) p.stamps[3] = wall_clock64();
-  // launch 1 left ONE compact candidate list and its length: no count table to scan, no search per row
-  const int total = __hip_atomic_load(p.ws_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (p.stamps && tid == 0 && t == 0) p.stamps[1] = wall_clock64();
-  const int n = total < kMaxDet ? total : kMaxDet;
-  const int nw = (n + 63) >> 6;
-  const int ntiles = nw * (nw + 1) / 2;
-  if (t >= (ntiles > 0 ? ntiles : 1)) return;   // (the grid is sized for 1024 candidates; with none, workgroup 0 writes the empty result)
-  if (ntiles > 0) {
-    int c = 0, rem = t;  // tile t -> (row chunk c, column chunk w >= c)
-    while (rem >= nw - c) {
-      rem -= nw - c;
-      ++c;
-    }
-    const int w = c + rem;
-    if (tid < 128) {   // rows 64c.. (tid < 64), columns 64w.. : dummies (class -1, empty box, the largest enumeration index) past the end
-      const int k = tid & 63;
-      if (tid < 64) {
-        s.rbox[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s.rcc[k] = make_float2(0.f, __int_as_float(-1));
-      } else {
-        s.cbox[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s.ccc[k] = make_float2(0.f, __int_as_float(-1));
-      }
-    }
-    auto fetch = [&](int e, int pos) {   // list entry e is candidate `pos` of the (selected) list: into this tile's rows / columns
-      const GpuDetection* cd = p.cand + e;
-      const float4 bx = make_float4(cd->x1, cd->y1, cd->x2, cd->y2);
-      const float2 cf = make_float2(cd->confidence, pack_ce(cd->class_id, cd->_pad));
-      if ((pos >> 6) == c) { s.rbox[pos & 63] = bx; s.rcc[pos & 63] = cf; }
-      if ((pos >> 6) == w) { s.cbox[pos & 63] = bx; s.ccc[pos & 63] = cf; }
-    };
-    if (total <= kMaxDet) {
-      if (tid < 128) {
-        const int e = (tid < 64 ? c : w) * 64 + (tid & 63);
-        if (e < n) fetch(e, e);
-      }
-    } else {
-      // ---- overflow: the kMaxDet largest keys (confidence, then the SMALLER enumeration index) of `total` candidates ----
-      // Every tile workgroup finds the same cut element (cutkey, cuteidx) -- selected <=> key > cutkey || (key == cutkey &&
-      // eidx <= cuteidx) -- and numbers the selected candidates in list order; it fetches those that fall into its rows / columns.
-      // Launch 1's histogram gives the confidence bin T that holds the cut; as long as that bin's members are too many to rank
-      // exactly (an untrained network puts half the frame into one bin) the bin is split again -- 4096 sub-ranges of the key,
-      // and once all keys are equal, of the enumeration index -- one coalesced sweep over the dense key array per level
-      // (typically none: ~10 members). Then: one sweep that collects the members and counts the candidates above the bin per
-      // wave range, the exact ranking of the <= 1024 members in LDS, one sweep that numbers and fetches. Was: five passes with a
-      // binary search per candidate (44 us at conf 0.3, 124 us at conf 0.05 on the synthetic weights).
-      constexpr int kMemCap = 1024;
-      int* hist = reinterpret_cast<int*>(s.mask);                       // (the suppression matrix's LDS is free until the scan)
-      unsigned* mkey = reinterpret_cast<unsigned*>(hist + kBins);
-      int* meidx = reinterpret_cast<int*>(mkey + kMemCap);
-      int* mpos = meidx + kMemCap;
-      int* part = mpos + kMemCap;                                       // [kTN] partial sums of 8 bins each
-      const int R = (((total + kWN - 1) / kWN) + 63) & ~63;             // list entries per wave range (a multiple of 64)
-      const int e_lo = wv * R, e_hi = (e_lo + R) < total ? (e_lo + R) : total;
-      // a wave sweeps its range 1024 keys at a time: 16 coalesced loads in flight per lane before the first is used (with 4 a
-      // sweep of 33 600 keys paid 17 dependent round trips through a loaded L2: ~20 us)
-      constexpr int U = 16;
-      auto for_chunks = [&](auto body) {   // body(e0, ke): ke[u] = (key, enumeration index) of list entry e0 + 64 u + lane, (0, 0) past the range
-        uint2 cur[U], nxt[U];
-        auto request = [&](uint2 (&d)[U], int e0) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) d[u] = e0 + 64 * u + lane < e_hi ? p.ws_ke[e0 + 64 * u + lane] : make_uint2(0u, 0u);
-        };
-        request(cur, e_lo);
-        for (int e0 = e_lo; e0 < e_hi; e0 += 64 * U) {
-          request(nxt, e0 + 64 * U);          // (the next chunk is on its way while this one is processed)
-          body(e0, cur);
-#pragma unroll
-          for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-      };
-      // the bin that holds the `want`-th element counted from the top (ascending == false) or from the bottom of hist[0..kBins):
-      // returns (bin, elements wanted from it, its count) through s.misc
-      auto pick_bin = [&](int want, bool ascending) {
-        int v8 = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v8 += hist[8 * tid + k];
-        part[tid] = v8;
-        __syncthreads();
-        if (wv == 0) {
-          int v = 0;
-#pragma unroll
-          for (int k = 0; k < 8; ++k) v += part[8 * lane + k];
-          int incl = v;
-#pragma unroll
-          for (int off = 1; off < 64; off <<= 1) {
-            const int u = __shfl_up(incl, off);
-            if (lane >= off) incl += u;
-          }
-          const int all = __shfl(incl, 63);
-          const int before = ascending ? incl - v : all - incl;          // elements in front of this lane's 64 bins, in walking order
-          // exactly one lane's 64 bins hold the element (all >= want); the bin inside them by a second wave-wide scan
-          const unsigned long long hit = __ballot(before < want && before + v >= want);
-          const int L = __ffsll((long long)hit) - 1;
-          const int before_l = __shfl(before, L);
-          const int bb = 64 * L + (ascending ? lane : 63 - lane);           // lane 0 = the first bin in walking order
-          const int hv = hist[bb];
-          int inc2 = hv;
-#pragma unroll
-          for (int off = 1; off < 64; off <<= 1) {
-            const int u = __shfl_up(inc2, off);
-            if (lane >= off) inc2 += u;
-          }
-          const int b2 = before_l + inc2 - hv;
-          if (b2 < want && b2 + hv >= want) {
-            s.misc[0] = bb;
-            s.misc[1] = want - b2;
-            s.misc[2] = hv;
-          }
-        }
-        __syncthreads();
-      };
-      for (int i = tid; i < kBins; i += kTN) hist[i] = p.ws_hist[i];
-      __syncthreads();
-      pick_bin(kMaxDet, false);
-      const int T = s.misc[0];
-      int want = s.misc[1], cnt = s.misc[2];
-      // the key range [klo, khi) of bin T (bit patterns of positive floats order like the values)
-      unsigned klo = __float_as_uint((float)T / (float)kBins);
-      unsigned khi = T == kBins - 1 ? 0x3F800001u : __float_as_uint((float)(T + 1) / (float)kBins);   // (a confidence is at most 1.0)
-      __syncthreads();
-      while (cnt > kMemCap && khi - klo > 1u) {                           // split the bin's key range 4096 ways
-        const unsigned wdt = (khi - klo + (unsigned)kBins - 1u) / (unsigned)kBins;
-        for (int i = tid; i < kBins; i += kTN) hist[i] = 0;
-        __syncthreads();
-        for_chunks([&](int e0, const uint2 (&ke)[U]) {
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-            if (e0 + 64 * u + lane < e_hi && ke[u].x >= klo && ke[u].x < khi) atomicAdd(&hist[(ke[u].x - klo) / wdt], 1);
-        });
-        __syncthreads();
-        pick_bin(want, false);
-        const unsigned nlo = klo + (unsigned)s.misc[0] * wdt;
-        khi = nlo + wdt < khi ? nlo + wdt : khi;
-        klo = nlo;
-        want = s.misc[1];
-        cnt = s.misc[2];
-        __syncthreads();
-      }
-      // all keys of the bin equal and still too many: split by enumeration index (the smaller index comes first)
-      int esh = 0, ebin = -1;
-      if (cnt > kMemCap) {
-        const int emax = p.eoff[2] + p.gw[2] * p.gh[2];
-        while ((emax >> esh) >= kBins) ++esh;
-        for (int i = tid; i < kBins; i += kTN) hist[i] = 0;
-        __syncthreads();
-        for_chunks([&](int e0, const uint2 (&ke)[U]) {
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-            if (e0 + 64 * u + lane < e_hi && ke[u].x == klo) atomicAdd(&hist[(int)ke[u].y >> esh], 1);
-        });
-        __syncthreads();
-        pick_bin(want, true);
-        ebin = s.misc[0];
-        want = s.misc[1];
-        cnt = s.misc[2];                                                  // <= 2^esh <= 64 members
-        __syncthreads();
-      }
-      // 2 = selected for certain, 1 = member of the last bin (ranked exactly below), 0 = out
-      auto classify = [&](unsigned key, int eidx) {
-        if (key >= khi) return 2;
-        if (key < klo) return 0;
-        if (ebin < 0) return 1;
-        const int eb = eidx >> esh;
-        return eb < ebin ? 2 : (eb == ebin ? 1 : 0);
-      };
-      if (tid == 0) s.misc[3] = 0;
-      if (tid < kWN) s.hist[tid] = 0;
-      __syncthreads();
-      // sweep: candidates selected for certain per wave range, members -> LDS
-      int sure = 0;
-      for_chunks([&](int e0, const uint2 (&ke)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int cl = e0 + 64 * u + lane < e_hi ? classify(ke[u].x, (int)ke[u].y) : 0;
-          sure += __popcll(__ballot(cl == 2));
-          if (cl == 1) {
-            const int slot = atomicAdd(&s.misc[3], 1);
-            if (slot < kMemCap) { mkey[slot] = ke[u].x; meidx[slot] = (int)ke[u].y; mpos[slot] = e0 + 64 * u + lane; }
-          }
-        }
-      });
-      if (lane == 0) s.wave_cnt[wv] = sure;
-      __syncthreads();
-      const int m = s.misc[3] < kMemCap ? s.misc[3] : kMemCap;           // (== cnt; the cap cannot bite: cnt <= kMemCap here)
-      // exact ranking of the members; the member of rank want - 1 is the cut, the members up to it are selected
-      for (int i = tid; i < m; i += kTN) {
-        const unsigned ki = mkey[i];
-        const int xi = meidx[i];
-        int r = 0;
-        for (int j = 0; j < m; ++j) r += (mkey[j] > ki || (mkey[j] == ki && meidx[j] < xi)) ? 1 : 0;
-        if (r == want - 1) { s.misc[0] = (int)ki; s.misc[1] = xi; }
-        if (r < want) atomicAdd(&s.hist[mpos[i] / R], 1);                 // selected members per wave range
-      }
-      __syncthreads();
-      const unsigned cutkey = (unsigned)s.misc[0];
-      const int cuteidx = s.misc[1];
-      int run = 0;
-      for (int v = 0; v < wv; ++v) run += s.wave_cnt[v] + s.hist[v];
-      // sweep: number the selected candidates in list order, fetch this tile's
-      for_chunks([&](int e0, const uint2 (&ke)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const bool sel = e0 + 64 * u + lane < e_hi && (ke[u].x > cutkey || (ke[u].x == cutkey && (int)ke[u].y <= cuteidx));
-          const unsigned long long bal = __ballot(sel);
-          const int pos = run + __popcll(bal & ((1ull << lane) - 1ull));
-          // (only the list entry is noted here: a record load inside this loop would be one serialised round trip per hit)
-          if (sel && (pos >> 6) == c) part[pos & 63] = e0 + 64 * u + lane;
-          if (sel && (pos >> 6) == w) part[64 + (pos & 63)] = e0 + 64 * u + lane;
-          run += __popcll(bal);
-        }
-      });
-      __syncthreads();
-      if (tid < 128) fetch(part[tid], (tid < 64 ? c : w) * 64 + (tid & 63));   // every slot is taken: 1024 candidates are selected
-    }
-    __syncthreads();
-    if (p.stamps && tid == 0 && t == 0) p.stamps[2] = wall_clock64();
-    if (c == w && tid < 64) {   // the diagonal tile publishes its chunk of the candidate list (output stage)
-      st_sc1(p.ws_box + c * 64 + tid, s.rbox[tid]);     // (everything the last arriver reads is stored sc1: arrive_and_check_last_sc1)
-      st_sc1(p.ws_cc + c * 64 + tid, s.rcc[tid]);
-    }
-    const int gi = c * 64 + lane;
-    const float4 a = s.rbox[lane];
-    const float2 ac = s.rcc[lane];
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    unsigned int rowbits = 0u;
-    int rowcnt = 0, colcnt = 0;
-    unsigned long long colword = 0ull;
-#pragma unroll
-    for (int u = 0; u < kColsPerWave; ++u) {
-      const int col = wv * kColsPerWave + u;
-      const int gj = w * 64 + col;
-      const float4 bb = s.cbox[col];
-      const float2 bc = s.ccc[col];
-      // key_j > key_i with key = (confidence, ~enumeration index): the stable descending order
-      const bool j_first = bc.x > ac.x || (bc.x == ac.x && ce_eidx(bc.y) < ce_eidx(ac.y));
-      const bool i_first = gi != gj && !j_first;
-      // the pair test of `suppresses` (same arithmetic; the IoU is symmetric bit for bit), once for both orientations
-      const float ix1 = fmaxf(a.x, bb.x), iy1 = fmaxf(a.y, bb.y);
-      const float ix2 = fminf(a.z, bb.z), iy2 = fminf(a.w, bb.w);
-      bool over = gi != gj && ((__float_as_int(bc.y) ^ __float_as_int(ac.y)) & kClassMask) == 0 && !(ix1 >= ix2 || iy1 >= iy2);
-      if (over) {
-        const float inter = (ix2 - ix1) * (iy2 - iy1);
-        const float area_b = (bb.z - bb.x) * (bb.w - bb.y);
-        over = inter / (area_a + area_b - inter + 1e-6f) > p.iou_thr;
-      }
-      if (over && ac.x > bc.x) rowbits |= 1u << u;                       // i suppresses j (strictly higher confidence)
-      rowcnt += j_first ? 1 : 0;
-      const unsigned long long cw = __ballot(over && bc.x > ac.x);      // j suppresses i: row j of tile (w, c), bit = lane
-      const int cc = __popcll(__ballot(i_first));
-      if (lane == u) {
-        colword = cw;
-        colcnt = cc;
-      }
-    }
-    s.piece[lane][wv] = (unsigned char)rowbits;
-    s.rcnt[lane][wv] = (unsigned char)rowcnt;
-    const unsigned long long colnz = __ballot(lane < kColsPerWave && colword != 0ull);
-    if (w != c) {   // (the diagonal tile visits every ordered pair itself)
-      if (lane < kColsPerWave) {
-        const int gj = w * 64 + wv * kColsPerWave + lane;
-        st_sc1(p.ws_full + (size_t)gj * kWords + c, colword);
-        atomicAdd(&p.ws_rank[gj], colcnt);
-      }
-      if (lane == 0 && colnz) atomicOr(&p.ws_rownz[w], colnz << (kColsPerWave * wv));
-    }
-    __syncthreads();
-    if (tid < 64) {
-      unsigned long long word = 0ull;
-      int cnt = 0;
-#pragma unroll
-      for (int v = 0; v < kWN; ++v) {
-        word |= (unsigned long long)s.piece[tid][v] << (kColsPerWave * v);
-        cnt += s.rcnt[tid][v];
-      }
-      st_sc1(p.ws_full + (size_t)gi * kWords + w, word);
-      atomicAdd(&p.ws_rank[gi], cnt);
-      const unsigned long long nz = __ballot(word != 0ull);
-      if (tid == 0 && nz) atomicOr(&p.ws_rownz[c], nz);
-    }
-    if (!arrive_and_check_last_sc1(p.ticket2, &s.is_last, ntiles)) return;
-  }
-  if (p.stamps && tid == 0) p.stamps[4] = wall_clock64();
+// ================================================================================================ launch 2, phase by phase
+namespace {
 
-  // ---- last arriver: ranks -> permutation, masks -> LDS, greedy scan per class residue, output ----
-  int rk[2];        // this thread's two candidates (enumeration positions tid, tid + kTN): rank, (confidence, class), box
-  float2 cc2[2];
-  float4 bx2[2];
-  {
-    // every load of this phase is requested before the first one is waited for (each is a trip to L2 / another XCD)
-    constexpr int B = 8;
-    const int total = n * nw;       // rows 0..n) x nw words
+// list entry e is candidate `pos` of the (selected) list: into this tile's rows / columns
+__device__ __forceinline__ void fetch_to_tile(SmemN& s, const GpuDetection* cand, int e, int pos, TileCW t) {
+  const GpuDetection* cd = cand + e;
+  const float4 bx = make_float4(cd->x1, cd->y1, cd->x2, cd->y2);
+  const float2 cf = make_float2(cd->confidence, pack_ce(cd->class_id, cd->_pad));
+  if ((pos >> 6) == t.c) { s.rbox[pos & 63] = bx; s.rcc[pos & 63] = cf; }
+  if ((pos >> 6) == t.w) { s.cbox[pos & 63] = bx; s.ccc[pos & 63] = cf; }
+}
+
+// One wave's range [e_lo, e_hi) of the dense key array, swept 1024 keys at a time: 16 coalesced loads in flight per lane before
+// the first is used (with 4 a sweep of 33 600 keys paid 17 dependent round trips through a loaded L2: ~20 us)
+constexpr int kSweepU = 16;
+struct KeySweep {
+  const uint2* ke;
+  int e_lo, e_hi, lane;
+  // body(e, ke, inside): list entry e = e0 + 64 u + lane of the chunk at e0, its (key, enumeration index) -- (0, 0) and
+  // inside == false past the range; every lane makes all 16 calls per chunk, so a body may ballot
+  template <typename F>
+  __device__ __forceinline__ void for_chunks(F body) const {
+    uint2 cur[kSweepU], nxt[kSweepU];
+    auto request = [&](uint2 (&d)[kSweepU], int e0) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int e = tid + q * kTN;
-      rk[q] = e < n ? __hip_atomic_load(p.ws_rank + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-      cc2[q] = e < n ? ld_sc1(p.ws_cc + e) : make_float2(0.f, 0.f);
-      bx2[q] = e < n ? ld_sc1(p.ws_box + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int u = 0; u < kSweepU; ++u) d[u] = e0 + 64 * u + lane < e_hi ? ke[e0 + 64 * u + lane] : make_uint2(0u, 0u);
+    };
+    // (an opaque copy of e_lo: every sweep starts at the same entry, and the compiler otherwise keeps the first chunk's 16
+    // bounds tests and addresses alive from one sweep to the next -- 99 VGPRs for the kernel instead of 82)
+    int first = e_lo;
+    asm volatile("" : "+v"(first));
+    request(cur, first);
+    for (int e0 = first; e0 < e_hi; e0 += 64 * kSweepU) {
+      request(nxt, e0 + 64 * kSweepU);          // (the next chunk is on its way while this one is processed)
+#pragma unroll
+      for (int u = 0; u < kSweepU; ++u) body(e0 + 64 * u + lane, cur[u], e0 + 64 * u + lane < e_hi);
+#pragma unroll
+      for (int u = 0; u < kSweepU; ++u) cur[u] = nxt[u];
     }
-    unsigned long long rz = tid < kWords ? __hip_atomic_load(p.ws_rownz + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    for (int k0 = tid; k0 < total; k0 += kTN * B) {
-      unsigned long long v[B];
+  }
+};
+
+// the bin that holds the `want`-th element counted from the top (ascending == false) or from the bottom of sel.hist[0..kBins):
+// returns (bin, elements wanted from it, its count) through s.misc
+__device__ __forceinline__ void pick_bin(SmemN& s, int want, bool ascending) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int* hist = s.sel.hist;
+  int v8 = 0;
 #pragma unroll
-      for (int q = 0; q < B; ++q) {
-        const int k = k0 + q * kTN;
-        const int row = k / nw, wd = k - row * nw;
-        v[q] = k < total ? ld_sc1(p.ws_full + (size_t)row * kWords + wd) : 0ull;
-      }
+  for (int k = 0; k < 8; ++k) v8 += hist[8 * tid + k];
+  s.sel.part[tid] = v8;
+  __syncthreads();
+  if (tid < 64) {
+    int v = 0;
 #pragma unroll
-      for (int q = 0; q < B; ++q) {
-        const int k = k0 + q * kTN;
-        if (k < total) s.mask[k] = v[q];
-      }
-    }
-    if (tid < kWords) s.rownz[tid] = rz;
-    __syncthreads();
-    // entry r of the rank-ordered list: candidate position | class residue << 10 | "its row marks something" << 12
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int e = tid + q * kTN;
-      if (e < n && (unsigned)rk[q] < (unsigned)n) {   // (ranks are a permutation of 0..n-1: keys are distinct)
-        const unsigned nz = (unsigned)((s.rownz[e >> 6] >> (e & 63)) & 1ull);
-        s.perm[rk[q]] = (unsigned short)(e | ((__float_as_int(cc2[q].y) & 3) << 10) | (nz << 12));
-      }
+    for (int k = 0; k < 8; ++k) v += s.sel.part[8 * lane + k];
+    const int incl = wave_incl_scan(v, lane);
+    const int all = __shfl(incl, 63);
+    const int before = ascending ? incl - v : all - incl;          // elements in front of this lane's 64 bins, in walking order
+    // exactly one lane's 64 bins hold the element (all >= want); the bin inside them by a second wave-wide scan
+    const unsigned long long hit = __ballot(before < want && before + v >= want);
+    const int L = __ffsll((long long)hit) - 1;
+    const int before_l = __shfl(before, L);
+    const int bb = 64 * L + (ascending ? lane : 63 - lane);           // lane 0 = the first bin in walking order
+    const int hv = hist[bb];
+    const int b2 = before_l + wave_incl_scan(hv, lane) - hv;
+    if (b2 < want && b2 + hv >= want) {
+      s.misc[0] = bb;
+      s.misc[1] = want - b2;
+      s.misc[2] = hv;
     }
   }
   __syncthreads();
-  if (p.stamps && tid == 0) p.stamps[8] = wall_clock64();
-  unsigned long long removed_reg = 0ull;                // wave v < 4, lane q < nw: word q of the wave's suppressed set
+}
+
+// One level of narrowing: histogram of bin_of(key, enumeration index) over the list (-1: not counted) in one sweep, then
+// pick_bin on it.
+template <typename B>
+__device__ __forceinline__ void split_level(SmemN& s, const KeySweep& sw, int want, bool ascending, B bin_of) {
+  for (int i = threadIdx.x; i < kBins; i += kTN) s.sel.hist[i] = 0;
+  __syncthreads();
+  sw.for_chunks([&](int, uint2 ke, bool inside) {
+    const int b = inside ? bin_of(ke) : -1;
+    if (b >= 0) atomicAdd(&s.sel.hist[b], 1);
+  });
+  __syncthreads();
+  pick_bin(s, want, ascending);
+}
+
+// The last bin of the cut: the candidates with klo <= key < khi (and, once all its keys are equal, enumeration index >> esh ==
+// ebin). `want` of its members are selected; everything above it is.
+struct CutBin {
+  unsigned klo, khi;
+  int esh, ebin, want;
+  // 2 = selected for certain, 1 = member of the last bin (ranked exactly by select_top), 0 = out
+  __device__ __forceinline__ int classify(unsigned key, int eidx) const {
+    if (key >= khi) return 2;
+    if (key < klo) return 0;
+    if (ebin < 0) return 1;
+    const int eb = eidx >> esh;
+    return eb < ebin ? 2 : (eb == ebin ? 1 : 0);
+  }
+};
+
+// Launch 1's histogram gives the confidence bin T that holds the cut; as long as that bin's members are too many to rank
+// exactly (an untrained network puts half the frame into one bin) the bin is split again -- 4096 sub-ranges of the key, and
+// once all keys are equal, of the enumeration index -- one coalesced sweep over the dense key array per level (typically none:
+// ~10 members). Leaves at most kMemCap members.
+__device__ __forceinline__ CutBin narrow_cut(SmemN& s, const PostParams& p, const KeySweep& sw) {
+  const int tid = threadIdx.x;
+  int* hist = s.sel.hist;
+  for (int i = tid; i < kBins; i += kTN) hist[i] = p.list.hist[i];
+  __syncthreads();
+  pick_bin(s, kMaxDet, false);
+  const KeyRange r0 = bin_key_range(s.misc[0]);
+  CutBin cut{r0.lo, r0.hi, 0, -1, s.misc[1]};
+  int cnt = s.misc[2];
+  __syncthreads();
+  while (cnt > kMemCap && cut.khi - cut.klo > 1u) {                     // split the bin's key range 4096 ways
+    const unsigned klo = cut.klo, khi = cut.khi, wdt = split_width(klo, khi);
+    split_level(s, sw, cut.want, false, [&](uint2 ke) { return ke.x >= klo && ke.x < khi ? (int)((ke.x - klo) / wdt) : -1; });
+    const unsigned nlo = klo + (unsigned)s.misc[0] * wdt;
+    cut.khi = nlo + wdt < khi ? nlo + wdt : khi;
+    cut.klo = nlo;
+    cut.want = s.misc[1];
+    cnt = s.misc[2];
+    __syncthreads();
+  }
+  // all keys of the bin equal and still too many: split by enumeration index (the smaller index comes first)
+  if (cnt > kMemCap) {
+    const unsigned klo = cut.klo;
+    const int emax = p.eoff[2] + p.gw[2] * p.gh[2];
+    int esh = 0;
+    while ((emax >> esh) >= kBins) ++esh;
+    split_level(s, sw, cut.want, true, [&](uint2 ke) { return ke.x == klo ? (int)ke.y >> esh : -1; });
+    cut.esh = esh;
+    cut.ebin = s.misc[0];
+    cut.want = s.misc[1];                                               // (its count: <= 2^esh <= 64 members)
+    __syncthreads();
+  }
+  return cut;
+}
+
+// ---- phase 1, more than kMaxDet candidates: the kMaxDet largest keys (confidence, then the SMALLER enumeration index) ----
+// Every tile workgroup finds the same cut element (cutkey, cuteidx) -- selected <=> key > cutkey || (key == cutkey && eidx <=
+// cuteidx) -- and numbers the selected candidates in list order; it fetches those that fall into its rows / columns.
+// narrow_cut leaves a last bin of at most kMemCap members. Then: one sweep that collects the members and counts the candidates
+// above the bin per wave range, the exact ranking of the members in LDS, one sweep that numbers and fetches. Was: five passes
+// with a binary search per candidate (44 us at conf 0.3, 124 us at conf 0.05 on the synthetic weights).
+__device__ __forceinline__ void select_top(SmemN& s, const PostParams& p, int total, TileCW t) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  SelectScratch& x = s.sel;
+  const int R = (((total + kWN - 1) / kWN) + 63) & ~63;             // list entries per wave range (a multiple of 64)
+  const KeySweep sw{p.list.ke, wv * R, (wv * R + R) < total ? (wv * R + R) : total, lane};
+  const CutBin cut = narrow_cut(s, p, sw);
+  if (tid == 0) s.misc[3] = 0;
+  if (tid < kWN) s.sel_cnt[tid] = 0;
+  __syncthreads();
+  // sweep: candidates selected for certain per wave range, members -> LDS
+  int sure = 0;
+  sw.for_chunks([&](int e, uint2 ke, bool inside) {
+    const int cl = inside ? cut.classify(ke.x, (int)ke.y) : 0;
+    sure += __popcll(__ballot(cl == 2));
+    if (cl == 1) {
+      const int slot = atomicAdd(&s.misc[3], 1);
+      if (slot < kMemCap) { x.mkey[slot] = ke.x; x.meidx[slot] = (int)ke.y; x.mpos[slot] = e; }
+    }
+  });
+  if (lane == 0) s.wave_cnt[wv] = sure;
+  __syncthreads();
+  const int m = s.misc[3] < kMemCap ? s.misc[3] : kMemCap;           // (the cap cannot bite: narrow_cut leaves <= kMemCap members)
+  // exact ranking of the members; the member of rank want - 1 is the cut, the members up to it are selected
+  for (int i = tid; i < m; i += kTN) {
+    const unsigned ki = x.mkey[i];
+    const int xi = x.meidx[i];
+    int r = 0;
+    for (int j = 0; j < m; ++j) r += (x.mkey[j] > ki || (x.mkey[j] == ki && x.meidx[j] < xi)) ? 1 : 0;
+    if (r == cut.want - 1) { s.misc[0] = (int)ki; s.misc[1] = xi; }
+    if (r < cut.want) atomicAdd(&s.sel_cnt[x.mpos[i] / R], 1);
+  }
+  __syncthreads();
+  const unsigned cutkey = (unsigned)s.misc[0];
+  const int cuteidx = s.misc[1];
+  int run = 0;
+  for (int v = 0; v < wv; ++v) run += s.wave_cnt[v] + s.sel_cnt[v];
+  // sweep: number the selected candidates in list order, note this tile's
+  sw.for_chunks([&](int e, uint2 ke, bool inside) {
+    const bool sel = inside && (ke.x > cutkey || (ke.x == cutkey && (int)ke.y <= cuteidx));
+    const unsigned long long bal = __ballot(sel);
+    const int pos = run + __popcll(bal & ((1ull << lane) - 1ull));
+    // (only the list entry is noted here: a record load inside this loop would be one serialised round trip per hit)
+    if (sel && (pos >> 6) == t.c) x.part[pos & 63] = e;
+    if (sel && (pos >> 6) == t.w) x.part[64 + (pos & 63)] = e;
+    run += __popcll(bal);
+  });
+  __syncthreads();
+  if (tid < 128) fetch_to_tile(s, p.list.cand, x.part[tid], (tid < 64 ? t.c : t.w) * 64 + (tid & 63), t);   // every slot is taken: kMaxDet candidates are selected
+}
+
+// ---- phase 1: this tile's 64 rows and 64 columns into LDS, dummies past the end of the list ----
+__device__ __forceinline__ void fetch_tile(SmemN& s, const PostParams& p, int total, int n, TileCW t) {
+  const int tid = threadIdx.x;
+  if (tid < 128) put_dummy(tid < 64 ? s.rbox : s.cbox, tid < 64 ? s.rcc : s.ccc, tid & 63);
+  if (total > kMaxDet) {
+    select_top(s, p, total, t);
+  } else if (tid < 128) {
+    const int e = (tid < 64 ? t.c : t.w) * 64 + (tid & 63);
+    if (e < n) fetch_to_tile(s, p.list.cand, e, e, t);
+  }
+  __syncthreads();
+}
+
+// ---- phase 2: the 64 x 64 pair tile (rows of chunk c = lanes, 8 columns of chunk w per wave) ----
+// Besides the overlap test it compares the (confidence, ~enumeration index) keys of every pair: the tile contributes the
+// DIRECTIONAL suppression bits of both orientations -- rows of tile (c, w) per lane, rows of tile (w, c) as wave ballots -- to
+// ws_full, and to every candidate's RANK (ws_rank). Everything the last arriver reads is stored sc1 (arrive_and_check_last_sc1).
+__device__ __forceinline__ void pair_tile(SmemN& s, const PostParams& p, TileCW t) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int c = t.c, w = t.w;
+  if (c == w && tid < 64) {   // the diagonal tile publishes its chunk of the candidate list (output stage)
+    st_sc1(p.ws_box + c * 64 + tid, s.rbox[tid]);
+    st_sc1(p.ws_cc + c * 64 + tid, s.rcc[tid]);
+  }
+  const int gi = c * 64 + lane;
+  const float4 a = s.rbox[lane];
+  const float2 ac = s.rcc[lane];
+  const float area_a = (a.z - a.x) * (a.w - a.y);
+  unsigned int rowbits = 0u;
+  int rowcnt = 0, colcnt = 0;
+  unsigned long long colword = 0ull;
+#pragma unroll
+  for (int u = 0; u < kColsPerWave; ++u) {
+    const int col = wv * kColsPerWave + u;
+    const int gj = w * 64 + col;
+    const float4 bb = s.cbox[col];
+    const float2 bc = s.ccc[col];
+    // key_j > key_i with key = (confidence, ~enumeration index): the stable descending order
+    const bool j_first = bc.x > ac.x || (bc.x == ac.x && ce_eidx(bc.y) < ce_eidx(ac.y));
+    const bool i_first = gi != gj && !j_first;
+    const bool over = gi != gj && ce_same_class(bc.y, ac.y) && iou_exceeds(a, area_a, bb, p.iou_thr);   // once for both orientations
+    if (over && ac.x > bc.x) rowbits |= 1u << u;                       // i suppresses j (strictly higher confidence)
+    rowcnt += j_first ? 1 : 0;
+    const unsigned long long cw = __ballot(over && bc.x > ac.x);      // j suppresses i: row j of tile (w, c), bit = lane
+    const int cc = __popcll(__ballot(i_first));
+    if (lane == u) {
+      colword = cw;
+      colcnt = cc;
+    }
+  }
+  s.piece[lane][wv] = (unsigned char)rowbits;
+  s.rcnt[lane][wv] = (unsigned char)rowcnt;
+  const unsigned long long colnz = __ballot(lane < kColsPerWave && colword != 0ull);
+  if (w != c) {   // (the diagonal tile visits every ordered pair itself)
+    if (lane < kColsPerWave) {
+      const int gj = w * 64 + wv * kColsPerWave + lane;
+      st_sc1(p.ws_full + (size_t)gj * kWords + c, colword);
+      atomicAdd(&p.ws_rank[gj], colcnt);
+    }
+    if (lane == 0 && colnz) atomicOr(&p.ws_rownz[w], colnz << (kColsPerWave * wv));
+  }
+  __syncthreads();
+  if (tid < 64) {
+    unsigned long long word = 0ull;
+    int cnt = 0;
+#pragma unroll
+    for (int v = 0; v < kWN; ++v) {
+      word |= (unsigned long long)s.piece[tid][v] << (kColsPerWave * v);
+      cnt += s.rcnt[tid][v];
+    }
+    st_sc1(p.ws_full + (size_t)gi * kWords + w, word);
+    atomicAdd(&p.ws_rank[gi], cnt);
+    const unsigned long long nz = __ballot(word != 0ull);
+    if (tid == 0 && nz) atomicOr(&p.ws_rownz[c], nz);
+  }
+}
+
+// this thread's two candidates (list positions tid, tid + kTN) in registers from the hand-off to the output
+struct OwnCands {
+  int rk[2];        // rank
+  float2 cc[2];     // (confidence, class | enumeration index)
+  float4 bx[2];
+};
+
+// ---- phase 4 (last arriver): ranks -> permutation s.perm, masks and rownz -> LDS ----
+// every load of this phase is requested before the first one is waited for (each is a trip to L2 / another XCD)
+__device__ __forceinline__ OwnCands load_ranks_and_masks(SmemN& s, const PostParams& p, int n, int nw) {
+  const int tid = threadIdx.x;
+  constexpr int B = 8;
+  const int words = n * nw;       // rows 0..n) x nw words
+  OwnCands o;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int e = tid + q * kTN;
+    o.rk[q] = e < n ? __hip_atomic_load(p.ws_rank + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    o.cc[q] = e < n ? ld_sc1(p.ws_cc + e) : make_float2(0.f, 0.f);
+    o.bx[q] = e < n ? ld_sc1(p.ws_box + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  unsigned long long rz = tid < kWords ? __hip_atomic_load(p.ws_rownz + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+  for (int k0 = tid; k0 < words; k0 += kTN * B) {
+    unsigned long long v[B];
+#pragma unroll
+    for (int q = 0; q < B; ++q) {
+      const int k = k0 + q * kTN;
+      const int row = k / nw, wd = k - row * nw;
+      v[q] = k < words ? ld_sc1(p.ws_full + (size_t)row * kWords + wd) : 0ull;
+    }
+#pragma unroll
+    for (int q = 0; q < B; ++q) {
+      const int k = k0 + q * kTN;
+      if (k < words) s.mask[k] = v[q];
+    }
+  }
+  if (tid < kWords) s.rownz[tid] = rz;
+  __syncthreads();
+  // entry r of the rank-ordered list: candidate position | class residue << 10 | "its row marks something" << 12
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int e = tid + q * kTN;
+    if (e < n && (unsigned)o.rk[q] < (unsigned)n) {   // (ranks are a permutation of 0..n-1: keys are distinct)
+      const unsigned nz = (unsigned)((s.rownz[e >> 6] >> (e & 63)) & 1ull);
+      s.perm[o.rk[q]] = (unsigned short)(e | ((__float_as_int(o.cc[q].y) & 3) << 10) | (nz << 12));
+    }
+  }
+  __syncthreads();
+  return o;
+}
+
+// ---- phase 5: the greedy scan, split by class residue; s.removed[0] = the suppressed set by list position ----
+// A row only ever marks candidates of strictly lower confidence (= processed later) and of its own class, so wave v < 4 walks
+// the candidates of class = v (mod 4) in rank order on its own, skipping rows that mark nothing.
+__device__ __forceinline__ void class_split_scan(SmemN& s, long long* stamps, int n, int nw) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (wv < 4) {
+    unsigned long long removed_reg = 0ull;                // lane q < nw: word q of the wave's suppressed set
     // this wave's rows, in rank order: class = wv (mod 4), mask not empty
     int m = 0;
     for (int r0 = 0; r0 < n; r0 += 64) {
@@ -1133,13 +1080,8 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
       m += __popcll(bal);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the list was written by this wave itself
-    if (p.stamps && tid == 0) p.stamps[9] = wall_clock64();
-    if (p.stamps && lane == 0) p.stamps[10 + wv] = m;
-    auto word_of = [&](int q) {
-      const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)removed_reg, q);
-      const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(removed_reg >> 32), q);
-      return ((unsigned long long)hi << 32) | lo;
-    };
+    stamp(stamps, kStampLists);
+    if (stamps && lane == 0) stamps[kStampScanWave0 + wv] = m;
     for (int k0 = 0; k0 < m; k0 += 64) {
       // 64 list entries in a register (lane L: entry k0 + L); per group of 16: the 16 mask rows are fetched together, then
       // the 16 decisions run from registers -- branch-free, so that no LDS latency sits in the dependent chain (with a
@@ -1156,21 +1098,25 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
           const int i = __builtin_amdgcn_readlane(mine, (kb + q) & 63);
-          const unsigned long long cur = word_of(i >> 6);
+          const unsigned long long cur = lane_word(removed_reg, i >> 6);
           const bool act = kb + q < cnt && !((cur >> (i & 63)) & 1ull);     // (a suppressed row suppresses nothing)
           removed_reg |= act ? pre[q] : 0ull;
         }
       }
     }
     if (lane < kWords) s.removed[wv][lane] = removed_reg;
-    if (p.stamps && lane == 0) p.stamps[10 + wv] |= (long long)(wall_clock64() & 0xFFFFFFFFll) << 20;
+    if (stamps && lane == 0) stamps[kStampScanWave0 + wv] |= (long long)(wall_clock64() & 0xFFFFFFFFll) << 20;
   }
   __syncthreads();
   if (tid < kWords) s.removed[0][tid] |= s.removed[1][tid] | s.removed[2][tid] | s.removed[3][tid];
   __syncthreads();
-  if (p.stamps && tid == 0) p.stamps[5] = wall_clock64();
-  // output position of a kept candidate = number of kept candidates of lower rank: prefix over the rank order, then every
-  // thread scatters ITS OWN records (enumeration order, already in registers) -- no second trip to memory
+}
+
+// ---- phase 6: unmarked candidates in rank order -> p.out; the workspace back to zero for the next frame ----
+// output position of a kept candidate = number of kept candidates of lower rank: prefix over the rank order, then every
+// thread scatters ITS OWN records (already in registers) -- no second trip to memory
+__device__ __forceinline__ void emit_and_reset(SmemN& s, const PostParams& p, int n, int nw, int total, const OwnCands& o) {
+  const int tid = threadIdx.x;
   int base = 0;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -1181,80 +1127,88 @@ __global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
       const int i = s.perm[r] & 1023;
       kept = !((s.removed[0][i >> 6] >> (i & 63)) & 1ull);
     }
-    const unsigned long long bal = __ballot(kept);
-    __syncthreads();
-    if (lane == 0) s.wave_cnt[wv] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int v = 0; v < kWN; ++v) {
-      const int cwv = s.wave_cnt[v];
-      if (v < wv) off += cwv;
-      tot += cwv;
-    }
-    if (r < n) s.list[0][r] = (unsigned short)(base + off + __popcll(bal & ((1ull << lane) - 1ull)));   // (the lists are done with)
+    int tot;
+    const int at = base + block_rank<kWN>(kept, s.wave_cnt, &tot);
+    if (r < n) s.list[0][r] = (unsigned short)at;   // (the lists are done with)
     base += tot;
   }
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int e = tid + q * kTN;
-    if (e < n && (unsigned)rk[q] < (unsigned)n && !((s.removed[0][e >> 6] >> (e & 63)) & 1ull)) {
-      GpuDetection d;
-      d.x1 = bx2[q].x; d.y1 = bx2[q].y; d.x2 = bx2[q].z; d.y2 = bx2[q].w;
-      d.confidence = cc2[q].x;
-      d.class_id = ce_class(cc2[q].y);
-      d.valid = 1;
-      d._pad = 0;
+    if (e < n && (unsigned)o.rk[q] < (unsigned)n && !((s.removed[0][e >> 6] >> (e & 63)) & 1ull)) {
+      GpuDetection d = make_det(o.bx[q], o.cc[q].x, ce_class(o.cc[q].y), 1);
       map_box(p, d);
-      p.out[s.list[0][rk[q]]] = d;
+      p.out[s.list[0][o.rk[q]]] = d;
     }
   }
   // the rank / row accumulators, the list length and the confidence histogram go back to zero for the next frame (they are
   // zero at rest, like the ticket)
   for (int e = tid; e < nw * 64; e += kTN) p.ws_rank[e] = 0;
   if (tid < kWords) p.ws_rownz[tid] = 0ull;
-  for (int i = tid; i < kBins; i += kTN) p.ws_hist[i] = 0;
+  for (int i = tid; i < kBins; i += kTN) p.list.hist[i] = 0;
   if (tid == 0) {
     *p.out_count = base;
     if (p.out_candidates) *p.out_candidates = total;
-    __hip_atomic_store(p.ws_total, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p.list.total, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(p.ticket2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    if (p.stamps) p.stamps[6] = wall_clock64();
   }
-  signal_done(p, tid);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kTN) void post_nms_kernel(const PostParams p) {
+  SmemN& s = *reinterpret_cast<SmemN*>(post_smem);
+  stamp(p.stamps, kStampNmsStart, true);
+  // launch 1 left ONE compact candidate list and its length: no count table to scan, no search per row
+  const int total = __hip_atomic_load(p.list.total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  stamp(p.stamps, kStampListRead, true);
+  const int n = total < kMaxDet ? total : kMaxDet;
+  const int nw = (n + 63) >> 6;
+  const int ntiles = nw * (nw + 1) / 2;
+  const int t = blockIdx.x;
+  if (t >= (ntiles > 0 ? ntiles : 1)) return;   // (the grid is sized for 1024 candidates; with none, workgroup 0 writes the empty result)
+  if (ntiles > 0) {
+    const TileCW tile = tile_of(t, nw);
+    fetch_tile(s, p, total, n, tile);
+    stamp(p.stamps, kStampGathered, true);
+    pair_tile(s, p, tile);
+    if (!arrive_and_check_last_sc1(p.ticket2, &s.is_last, ntiles)) return;   // one ticket per TILE, not per grid slot
+  }
+  stamp(p.stamps, kStampTilesDone);
+  const OwnCands own = load_ranks_and_masks(s, p, n, nw);
+  stamp(p.stamps, kStampLoaded);
+  class_split_scan(s, p.stamps, n, nw);
+  stamp(p.stamps, kStampScanned);
+  emit_and_reset(s, p, n, nw, total, own);
+  stamp(p.stamps, kStampOutput);
+  signal_done(p, threadIdx.x);
 }
 
 // ---- sliced inference: the detection slots of T tiles of one camera frame -> the compact candidate list, in frame pixels ----
 // One workgroup per tile. Record i of tile t is mapped to the frame (multiply, then add: two roundings per coordinate, the scale
 // is 1.0f for a network-sized tile and the map is then the reference's plain offset add, auto_labeler.py:158-165), takes the
 // enumeration index t * MAX_DETECTIONS + i and goes where post_decode_kernel's tail would have put it: a run of the list
-// reserved with one atomic per workgroup, its key in ws_ke, its confidence in the histogram. post_nms_kernel does the rest.
-// The slot is compact (records 0..count), so a record's place in the run is its index: no ranking. ws_total / ws_hist are zero
+// reserved with one atomic per workgroup, its key in list.ke, its confidence in the histogram. post_nms_kernel does the rest.
+// The slot is compact (records 0..count), so a record's place in the run is its index: no ranking. list.total / list.hist are zero
 // at rest (the previous post_nms_kernel on this stream reset them with plain stores; this launch is a later kernel).
 __global__ __launch_bounds__(kPost2Block) void tile_gather_kernel(const TileGatherParams g) {
   int& s_base = *reinterpret_cast<int*>(post_smem);   // (dynamic LDS like every kernel of the table: 16 bytes)
   const int t = blockIdx.x, tid = threadIdx.x;
   int cnt = g.counts[t];
   cnt = cnt < 0 ? 0 : (cnt > kMaxDet ? kMaxDet : cnt);      // (a count is never trusted with the workspace's bounds)
-  if (tid == 0) s_base = cnt ? __hip_atomic_fetch_add(g.ws_total, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+  if (tid == 0) s_base = list_reserve(g.list, cnt);
   __syncthreads();
   const int base = s_base;
   const TileMap m = g.map[t];
   // a record is 32 bytes: two 16-byte loads / stores per lane, consecutive lanes on consecutive records
   const uint4* src = reinterpret_cast<const uint4*>(g.slots + (size_t)t * kMaxDet);
-  uint4* dst = reinterpret_cast<uint4*>(g.cand + base);
   for (int i = tid; i < cnt; i += kPost2Block) {
     const uint4 bx = src[2 * i], rest = src[2 * i + 1];      // (x1, y1, x2, y2), (confidence, class, valid, _pad)
     const float x1 = __uint_as_float(bx.x) * m.sx + m.ox, y1 = __uint_as_float(bx.y) * m.sy + m.oy;
     const float x2 = __uint_as_float(bx.z) * m.sx + m.ox, y2 = __uint_as_float(bx.w) * m.sy + m.oy;
-    const unsigned eidx = (unsigned)(t * kMaxDet + i);
-    dst[2 * i] = make_uint4(__float_as_uint(x1), __float_as_uint(y1), __float_as_uint(x2), __float_as_uint(y2));
-    dst[2 * i + 1] = make_uint4(rest.x, rest.y, rest.z, eidx);
-    g.ws_ke[base + i] = make_uint2(rest.x, eidx);
-    int bin = conf_bin(__uint_as_float(rest.x));              // a confidence lies in [0, 1]; anything else still lands in a bin
-    bin = bin < 0 ? 0 : bin;
-    atomicAdd(&g.ws_hist[bin], 1);
+    list_put(g.list, base + i, make_uint4(__float_as_uint(x1), __float_as_uint(y1), __float_as_uint(x2), __float_as_uint(y2)), rest,
+             (unsigned)(t * kMaxDet + i));
   }
 }
 
@@ -1270,21 +1224,22 @@ size_t post_workspace_bytes() {
          sizeof(int) * kMaxDet + sizeof(unsigned long long) * ((size_t)kMaxDet * kWords + kWords);
 }
 
-void post_bind_workspace(PostParams* p, void* ws) {
+void post_bind_workspace(PostParams* p, void* ws, GpuDetection* cand) {
   char* c = static_cast<char*>(ws);
+  p->list.cand = cand;
   p->ws_box = reinterpret_cast<float4*>(c); c += sizeof(float4) * kMaxDet;
   p->ws_cc = reinterpret_cast<float2*>(c); c += sizeof(float2) * kMaxDet;
-  p->ws_total = reinterpret_cast<int*>(c);
+  p->list.total = reinterpret_cast<int*>(c);
   p->ticket2 = reinterpret_cast<unsigned int*>(c + 64);
   c += 256;
-  p->ws_hist = reinterpret_cast<int*>(c); c += sizeof(int) * kBins;
-  p->ws_ke = reinterpret_cast<uint2*>(c); c += sizeof(uint2) * kListCap;
+  p->list.hist = reinterpret_cast<int*>(c); c += sizeof(int) * kBins;
+  p->list.ke = reinterpret_cast<uint2*>(c); c += sizeof(uint2) * kListCap;
   p->ws_full = reinterpret_cast<unsigned long long*>(c); c += sizeof(unsigned long long) * (size_t)kMaxDet * kWords;
   p->ws_rownz = reinterpret_cast<unsigned long long*>(c); c += sizeof(unsigned long long) * kWords;
   p->ws_rank = reinterpret_cast<int*>(c);
 }
 
-// mode 2: workgroups per head. A head read from planes: 256 cells per workgroup. A folded head: 64 cells (one 16-pixel
+// split form: workgroups per head. A head read from planes: 256 cells per workgroup. A folded head: 64 cells (one 16-pixel
 // subtile per wave: its hidden tensor -- 64 px x 2C x 2 bytes per workgroup -- is then spread over many CUs), or 256 when
 // the grid would not fit the 1024-entry block table.
 bool post_plan_blocks(PostParams* p) {
@@ -1338,7 +1293,7 @@ __global__ __launch_bounds__(kPostBlock) void decode_head_append_kernel(const fl
   GpuDetection d;
   if (idx < gw * gh) pass = decode_cell(cls, reg, gw, gh, stride, num_classes, conf_thr, q, idx, &d);
   int total;
-  const int pos = block_rank(pass, s, &total);
+  const int pos = block_rank<kWaves>(pass, s.wave_cnt, &total);
   if (pass) cand[(size_t)blockIdx.x * kT + pos] = d;
   if (tid == 0) block_count[blockIdx.x] = total;
   if (!arrive_and_check_last(ticket, &s.is_last)) return;
@@ -1369,7 +1324,7 @@ __global__ __launch_bounds__(kPostBlock) void compact_valid_kernel(const GpuDete
   const int tid = threadIdx.x;
   const bool v = tid < n && dets[tid].valid != 0;  // IsValidDetection (gpu_postprocess.cu:247-251)
   int tot;
-  const int pos = block_rank(v, s, &tot);
+  const int pos = block_rank<kWaves>(v, s.wave_cnt, &tot);
   if (v) out[pos] = dets[tid];
   if (tid == 0) *num_selected = tot;
 }
@@ -1391,47 +1346,45 @@ const struct { const char* name; const void* fn; } kPostKernelTable[] = {
 // called by unina_load_engine after hipSetDevice (one handle per GPU) and by init_postprocess_resources
 hipError_t post_init() { return set_lds_limits(kPostKernelTable); }
 
+static LaunchDesc post_row(int k, dim3 grid, dim3 block, size_t shmem) {
+  return LaunchDesc{kPostKernelTable[k].fn, grid, block, (unsigned)shmem, kPostKernelTable[k].name};
+}
+// n is only known on the device: the grid is sized for MAX_DETECTIONS candidates, tiles past the triangle return at once
+static LaunchDesc post_nms_row() { return post_row(kPostNms, dim3(kMaxTiles), dim3(kTN), sizeof(SmemN)); }
+
 int postprocess_desc(const PostParams& p, LaunchDesc out[2]) {
-  auto row = [&](int k, dim3 grid, dim3 block, size_t shmem) {
-    return LaunchDesc{kPostKernelTable[k].fn, grid, block, (unsigned)shmem, kPostKernelTable[k].name};
-  };
-  if (p.mode == 2) {
+  if (p.mode == kPostSplit) {
     if (p.bstart[3] < 1 || p.bstart[3] > 1024 || !p.ws_full) return -1;
-    out[0] = row(kPostDecode, dim3(p.bstart[3]), dim3(kT2), sizeof(SmemD));
-    out[1] = row(kPostNms, dim3(kMaxTiles), dim3(kTN), sizeof(SmemN));   // n is only known on the device: tiles past the triangle just draw their ticket
+    out[0] = post_row(kPostDecode, dim3(p.bstart[3]), dim3(kT2), sizeof(SmemD));
+    out[1] = post_nms_row();
     return 2;
   }
   const int nb = post_num_blocks(p.gw, p.gh);
   if (nb < 1 || nb > kPostBlock) return -1;
-  out[0] = row(kPostOne, dim3(nb), dim3(kPostBlock), kPostSmemBytes);
+  out[0] = post_row(kPostOne, dim3(nb), dim3(kPostBlock), kPostSmemBytes);
   return 1;
+}
+
+template <typename P>
+static hipError_t launch_row(const LaunchDesc& d, P params, hipStream_t stream) {
+  void* args[] = {&params};
+  return launch_desc(d, args, stream);
 }
 
 hipError_t postprocess_launch(const PostParams& p, hipStream_t stream) {
   LaunchDesc d[2];
   const int n = postprocess_desc(p, d);
   if (n < 1) return hipErrorInvalidValue;
-  PostParams copy = p;
-  void* args[] = {&copy};
-  for (int k = 0; k < n; ++k) {
-    hipError_t e = launch_desc(d[k], args, stream);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < n && e == hipSuccess; ++k) e = launch_row(d[k], p, stream);
+  return e;
 }
 
 hipError_t merge_tiles_launch(const TileGatherParams& g, const PostParams& nms, hipStream_t stream) {
   static_assert((size_t)kMaxTiles64 * kMaxDet <= kListCap, "every record of every tile must fit the compact list");
   if (g.n_tiles < 1 || g.n_tiles > kMaxTiles64 || !nms.ws_full || !nms.out || !nms.out_count) return hipErrorInvalidValue;
-  TileGatherParams gcopy = g;
-  void* gargs[] = {&gcopy};
-  hipError_t e = launch_desc(LaunchDesc{kPostKernelTable[kTileGather].fn, dim3(g.n_tiles), dim3(kT2), 16, kPostKernelTable[kTileGather].name},
-                             gargs, stream);
-  if (e != hipSuccess) return e;
-  PostParams ncopy = nms;
-  void* nargs[] = {&ncopy};
-  return launch_desc(LaunchDesc{kPostKernelTable[kPostNms].fn, dim3(kMaxTiles), dim3(kTN), (unsigned)sizeof(SmemN), kPostKernelTable[kPostNms].name},
-                     nargs, stream);
+  const hipError_t e = launch_row(post_row(kTileGather, dim3(g.n_tiles), dim3(kT2), 16), g, stream);
+  return e != hipSuccess ? e : launch_row(post_nms_row(), nms, stream);
 }
 
 }  // namespace unina

@@ -37,6 +37,7 @@
 
 #include "../../include/unina_mi355.h"
 #include "track_math.h"
+#include "wave_block.h"
 
 struct unina_tracker {
   int device = 0;
@@ -71,24 +72,6 @@ union HeaderWords {
   uint4 q[2];
 };
 
-// rank of this thread among the threads of the workgroup whose flag is set, and their number (two barriers)
-__device__ __forceinline__ int block_rank(bool flag, int* s_wave, int* total) {
-  const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
-  const unsigned long long m = __ballot(flag);
-  if (lane == 0) s_wave[wave] = __popcll(m);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int v = 0; v < kTrkWaves; ++v) {
-    const int c = s_wave[v];
-    before += v < wave ? c : 0;
-    all += c;
-  }
-  __syncthreads();   // s_wave is free again
-  *total = all;
-  return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 __device__ __forceinline__ void block_add(bool flag, int* counter) {
   const unsigned long long m = __ballot(flag);
   if (((int)threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(counter, __popcll(m));
@@ -118,7 +101,7 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   __shared__ __align__(16) unsigned long long s_best[2][kTrkBlock];     // live list entry k: min (d2 bits << 32 | record) of the round
   __shared__ int s_rcls[kTrkBlock];                                     // record j: class_id
   __shared__ int s_match[kTrkBlock];                                    // live list entry k: the record it matched, or -1
-  __shared__ int s_wave[kTrkWaves];
+  __shared__ int s_wave[kTrkWaves];                                     // block_rank's, and only its
   __shared__ int s_cnt[4];                                              // matched, died, live, confirmed
   int* const s_birth = reinterpret_cast<int*>(&s_best[0][0]);           // after the rounds: k-th birth candidate's record
   int* const s_assign = reinterpret_cast<int*>(&s_best[1][0]);          // after the rounds: the assign words
@@ -158,7 +141,7 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   s_match[tid] = -1;
   if (tid < 4) s_cnt[tid] = 0;
   int n_list;
-  const int k_own = block_rank(live, s_wave, &n_list);   // the own slot's place in the live list
+  const int k_own = block_rank<kTrkWaves>(live, s_wave, &n_list);   // the own slot's place in the live list
   if (live) s_slot[k_own] = make_float4(tw.t.x, tw.t.y, tw.t.z, __int_as_float(tw.t.class_id));
 
   // ---- rounds of mutual nearest neighbours
@@ -233,8 +216,8 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   // ---- births: the k-th candidate record founds a track in the k-th free slot
   const bool wants = usable && !matched_rec && conf >= a.birth_confidence;   // a NaN confidence fails
   int n_wants, n_free;
-  const int kb = block_rank(wants, s_wave, &n_wants);
-  const int kf = block_rank(!live, s_wave, &n_free);
+  const int kb = block_rank<kTrkWaves>(wants, s_wave, &n_wants);
+  const int kf = block_rank<kTrkWaves>(!live, s_wave, &n_free);
   const int n_born = track_births_taken(n_wants, n_free, hw.h.next_id);
   if (wants && kb < n_born) {
     s_birth[kb] = tid;
