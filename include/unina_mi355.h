@@ -543,6 +543,65 @@ typedef struct { float x, y, z, u, v; int n_valid, n_samples, valid; } unina_con
 int unina_locate_async(const GpuDetection *d_dets, const int *d_count, const unina_depth *depth, const unina_pinhole *cam,
                        const unina_locate_params *p, unina_cone3d *d_out, hipStream_t stream);
 
+/* ------------------------------------------------------------------ 3-D localisation from a stereo pair (for a camera whose
+ * depth map is not on this GPU: two rectified luma planes are all it needs)
+ * Kept records + a rectified pair + the left camera's intrinsics + the baseline -> the same unina_cone3d records as
+ * unina_locate_async writes, so unina_track_update_async goes behind it unchanged. One launch (csrc/stereo.hip) enqueued behind
+ * whichever _async call produced the records; no engine handle, nothing is synchronised, neither plane crosses to the host. Only
+ * each record's window is matched, along its own rows of the right image: sum of absolute differences over the window's
+ * sampling grid, one cost per integer disparity. localize.locate_stereo_numpy is the definition, decision for decision and bit
+ * for bit. Every comparison of costs is on integers; the floats are fp32, each operation rounded once, never contracted; the
+ * divide is correctly rounded.
+ *   count    as unina_locate_async: *d_count clamped to 0..MAX_DETECTIONS on the device; the slots at and beyond it are all-zero
+ *            bytes in d_out and in d_match
+ *   window   and grid: exactly unina_locate_async's (above), on the LEFT plane, with max_side limited to 1..UNINA_STEREO_MAX_SIDE:
+ *            n_samples <= 4096, every cost <= 4096 * 255 = 1 044 480 < 2^20, and every integer converted to float below is under
+ *            2^24, so the conversion is exact. An empty window writes all-zero records (d_out and d_match)
+ *   range    once per call, on the host, in fp32: fxB = fx * baseline; d_lo = max(1, ceilf(fxB / max_depth)); d_hi_all =
+ *            min(floorf(fxB / min_depth), width - 1); both clipped in float before they become ints (d_lo also to `width`, which
+ *            changes no result). d_hi_all < d_lo is legal: no record can then be valid. Per record d_hi = min(d_hi_all, u0), so
+ *            every right column u - d >= 0; nd = max(0, d_hi - d_lo + 1) disparities are searched
+ *   cost     for d in d_lo..d_hi: cost(d) = sum over the grid's sampled (u, v) of |L[v, u] - R[v, u - d]|, a uint32
+ *   best     the minimum of (cost, d) in ascending order: the smaller disparity wins a tie. cost_second = the least cost over the
+ *            d with |d - d_best| > 1, 0xFFFFFFFF where there is none
+ *   accepted iff nd >= 1, and cost_best <= (uint64)max_mean_sad * n_samples, and (cost_second == 0xFFFFFFFF or
+ *            (uint64)cost_second * 100 > (uint64)cost_best * (100 + uniqueness)). The inequality is strict: an exact tie between
+ *            two separated disparities is ambiguous and fails, so a flat patch (all costs equal) fails whatever `uniqueness` is
+ *   subpixel only when d_lo < d_best < d_hi, with cm = cost(d_best - 1), cp = cost(d_best + 1): den = cm - 2 * cost_best + cp (an
+ *            integer, never negative); delta = den == 0 ? 0 : (float)(cm - cp) / (float)(2 * den); |delta| <= 0.5 always, because
+ *            |cm - cp| <= den. At either end of the range delta = 0: a parabola needs both neighbours, and half of one is a bias.
+ *            disparity = (float)d_best + delta
+ *   point    Z = fxB / disparity; x = ((uc - cx) * Z) / fx, y = ((vc - cy) * Z) / fy, z = Z; u = uc, v = vc: the expressions of
+ *            unina_locate_async. Z is NOT checked against [min_depth, max_depth] again: the sub-pixel step can carry it a hair
+ *            outside
+ *   record   n_samples = the grid's count; n_valid = nd, the disparities searched; valid = accepted. Not accepted: x = y = z = 0
+ *            (u, v, n_valid, n_samples stay). d_match[i] = {disparity, d_best, cost_best, cost_second} for every non-empty
+ *            window, accepted or not, with disparity = 0 where it is not; nd == 0 gives {0, 0, 0xFFFFFFFF, 0xFFFFFFFF}
+ * Integer costs and minima of packed integers (cost << 10 | d - d_lo): two runs give identical bytes.
+ * NOT covered: rectification (the planes must be row-aligned already), zero-mean or census costs (two cameras with different
+ * exposure or gain), a left-right consistency check (an occluded window can be accepted at a wrong disparity). */
+#define UNINA_STEREO_MAX_DISPARITIES 1024
+#define UNINA_STEREO_MAX_SIDE 64
+typedef struct { int width, height, pitch; const uint8_t *left, *right; } unina_stereo_pair;
+      /* rectified 8-bit luma planes of one size and pitch (bytes per row); an NV12 Y plane is one. Row v of left is row v of
+         right; a point at column u of left is at column u - d of right, d >= 0. No alignment is required of either pointer or
+         of the pitch. The planes may be the halves of one side-by-side buffer (right = left + width, shared pitch). */
+typedef struct { float sx, sy, shrink, min_depth, max_depth; int max_side, max_mean_sad, uniqueness; } unina_stereo_params;
+      /* sx, sy: record -> plane pixels; max_mean_sad: grey levels per sample, 0..255; uniqueness: per cent, 0..1000 */
+typedef struct { float disparity; int d_best; uint32_t cost_best, cost_second; } unina_stereo_match;   /* 16 bytes */
+/*   d_dets / d_count : device, MAX_DETECTIONS records (16-byte aligned) / one int, as the _async calls write them
+ *   pair->left/right : device; d_out : device, MAX_DETECTIONS unina_cone3d, 16-byte aligned
+ *   d_match          : device, MAX_DETECTIONS unina_stereo_match, 16-byte aligned, or NULL
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer other than d_match (left and right included); d_out, d_dets or d_match not
+ * 16-byte aligned, or d_count not 4-byte aligned; a width or height outside 1..16 777 216, or pitch < width; fx, fy, baseline, sx
+ * or sy not finite and positive; cx or cy not finite; fxB or fxB / min_depth not finite; shrink outside (0, 1]; max_side outside
+ * 1..UNINA_STEREO_MAX_SIDE; max_mean_sad outside 0..255; uniqueness outside 0..1000; not 0 < min_depth < max_depth < inf;
+ * d_hi_all - d_lo + 1 > UNINA_STEREO_MAX_DISPARITIES (raise min_depth). */
+int unina_locate_stereo_async(const GpuDetection *d_dets, const int *d_count, const unina_stereo_pair *pair,
+                              const unina_pinhole *cam /* left rectified image, plane pixels */, float baseline /* metres */,
+                              const unina_stereo_params *p, unina_cone3d *d_out,
+                              unina_stereo_match *d_match /* MAX_DETECTIONS, 16-byte aligned, or NULL */, hipStream_t stream);
+
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the
  * device: stable ids, smoothed positions, hit and miss counts. One launch per frame (csrc/track.hip: one workgroup of 1024

@@ -107,6 +107,22 @@ class LocateParams(C.Structure):
                 ("max_side", C.c_int), ("min_valid", C.c_int)]
 
 
+STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE = 1024, 64   # include/unina_mi355.h UNINA_STEREO_*
+STEREO_MATCH_DTYPE = np.dtype([("disparity", "<f4"), ("d_best", "<i4"), ("cost_best", "<u4"), ("cost_second", "<u4")])   # unina_stereo_match
+assert STEREO_MATCH_DTYPE.itemsize == 16
+
+
+class StereoPair(C.Structure):
+    """unina_stereo_pair: two rectified 8-bit luma planes of one size and pitch (bytes per row) on the device."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pitch", C.c_int), ("left", C.c_void_p), ("right", C.c_void_p)]
+
+
+class StereoParams(C.Structure):
+    """unina_stereo_params."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("shrink", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("max_side", C.c_int), ("max_mean_sad", C.c_int), ("uniqueness", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -140,7 +156,7 @@ ABI_SYMBOLS = [
     "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
-    "unina_locate_async",
+    "unina_locate_async", "unina_locate_stereo_async",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -252,6 +268,8 @@ def load_library() -> C.CDLL:
     L.unina_eval_read.argtypes = [vp, C.POINTER(EvalResult), vp, C.c_size_t, vp, C.c_size_t, vp]
     # 3-D localisation (csrc/locate.hip)
     L.unina_locate_async.argtypes = [vp, vp, C.POINTER(Depth), C.POINTER(Pinhole), C.POINTER(LocateParams), vp, vp]
+    # 3-D localisation from a stereo pair (csrc/stereo.hip)
+    L.unina_locate_stereo_async.argtypes = [vp, vp, C.POINTER(StereoPair), C.POINTER(Pinhole), cf, C.POINTER(StereoParams), vp, vp, vp]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]

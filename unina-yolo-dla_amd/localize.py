@@ -1,7 +1,10 @@
-"""Detections lifted to 3-D cone positions from a depth map (include/unina_mi355.h "3-D localisation").
+"""Detections lifted to 3-D cone positions from a depth map (include/unina_mi355.h "3-D localisation") or from a rectified
+stereo pair ("3-D localisation from a stereo pair").
 
 ``locate_numpy`` is the DEFINITION: fp32 scalars throughout, one rounding per operation, in the order the header states;
 csrc/locate.hip (through ``DeviceLocator``) returns its bytes. ``window_numpy`` is the twin of csrc/locate_window.h.
+``locate_stereo_numpy`` is the definition of the stereo route in the same sense: integer costs, fp32 scalars, the twin of
+csrc/stereo_match.h; csrc/stereo.hip (through ``DeviceStereoLocator``) returns its bytes.
 """
 from __future__ import annotations
 
@@ -9,8 +12,8 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, MAX_DETECTIONS, Depth, EngineError, ERRORS, LocateParams, Pinhole,
-                     _stream_ptr, _torch, load_library)
+from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, MAX_DETECTIONS, STEREO_MATCH_DTYPE, STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE,
+                     Depth, EngineError, ERRORS, LocateParams, Pinhole, StereoPair, StereoParams, _stream_ptr, _torch, load_library)
 
 F = np.float32
 
@@ -163,4 +166,183 @@ class DeviceLocator:
         return host.numpy().view(CONE3D_DTYPE).copy()
 
 
-__all__ = ["locate_numpy", "window_numpy", "DeviceLocator", "as_pinhole", "as_params"]
+# ---------------------------------------------------------------- from a stereo pair
+STEREO_NONE = 0xFFFFFFFF          # "no such cost" in unina_stereo_match
+
+
+def make_stereo_params(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.3, max_depth=40.0, max_side=64, max_mean_sad=20,
+                       uniqueness=10) -> StereoParams:
+    """unina_stereo_params. sx, sy: record -> plane pixels; max_mean_sad: grey levels per sample; uniqueness: per cent by which
+    the second-best cost (two or more disparities away) must exceed the best."""
+    return StereoParams(float(sx), float(sy), float(shrink), float(min_depth), float(max_depth), int(max_side), int(max_mean_sad),
+                        int(uniqueness))
+
+
+def as_stereo_params(params) -> StereoParams:
+    """A StereoParams, a dict of make_stereo_params' arguments, or a tuple in the struct's order."""
+    if isinstance(params, StereoParams):
+        return params
+    if isinstance(params, dict):
+        return make_stereo_params(**params)
+    return make_stereo_params(*params)
+
+
+def stereo_range_numpy(fx, baseline, min_depth, max_depth, width: int):
+    """csrc/stereo_match.h stereo_range: (fxB, d_lo, d_hi_all), fp32, both bounds clipped in float before they become ints.
+    ValueError where the entry point answers UNINA_ERR_ARG."""
+    with np.errstate(all="ignore"):
+        fxB = F(fx) * F(baseline)
+        nearest, farthest = fxB / F(min_depth), fxB / F(max_depth)
+        if not (np.isfinite(fxB) and np.isfinite(nearest)):
+            raise ValueError("fx * baseline or fx * baseline / min_depth is not finite")
+        lo, hi = np.ceil(farthest), np.floor(nearest)
+        w, last = F(width), F(width - 1)
+        lo = F(1) if lo < F(1) else lo
+        lo = w if lo > w else lo
+        hi = last if hi > last else hi
+        d_lo, d_hi_all = int(lo), int(hi)
+    if d_hi_all - d_lo + 1 > STEREO_MAX_DISPARITIES:
+        raise ValueError(f"{d_hi_all - d_lo + 1} disparities ({d_lo}..{d_hi_all}): more than {STEREO_MAX_DISPARITIES}; raise min_depth")
+    return fxB, d_lo, d_hi_all
+
+
+def stereo_costs_numpy(left: np.ndarray, right: np.ndarray, w: dict, d_lo: int, d_hi: int) -> np.ndarray:
+    """cost(d) for d = d_lo .. d_hi (uint32, index d - d_lo): the sum of |L[v, u] - R[v, u - d]| over the window's sampling grid."""
+    rows = slice(w["v0"], w["v1"] + 1, w["stride_y"])
+    tmpl = left[rows, w["u0"]:w["u1"] + 1:w["stride_x"]].astype(np.int32)
+    last = w["u0"] + (w["cols"] - 1) * w["stride_x"]                       # the last sampled column
+    strip = right[rows, w["u0"] - d_hi:last - d_lo + 1].astype(np.int32)   # offset o holds column u0 - d_hi + o
+    span = last - w["u0"] + 1
+    win = np.lib.stride_tricks.sliding_window_view(strip, span, axis=1)[:, :, ::w["stride_x"]]   # [rows, nd, cols], d = d_hi - o
+    assert win.shape == (w["rows"], d_hi - d_lo + 1, w["cols"])
+    cost = np.abs(win - tmpl[:, None, :]).sum(axis=(0, 2), dtype=np.int64)
+    return cost[::-1].astype(np.uint32)
+
+
+def stereo_select_numpy(cost: np.ndarray):
+    """(index of the best cost -- the smaller index wins a tie --, the best cost, the least cost at two or more indices from
+    it or STEREO_NONE)."""
+    k = int(np.argmin(cost))                                                # the first minimum
+    far = np.abs(np.arange(len(cost)) - k) > 1
+    return k, int(cost[k]), int(cost[far].min()) if far.any() else STEREO_NONE
+
+
+def stereo_accept_numpy(nd: int, cost_best: int, cost_second: int, n_samples: int, max_mean_sad: int, uniqueness: int) -> bool:
+    """python integers: nothing overflows."""
+    if nd < 1 or cost_best > max_mean_sad * n_samples:
+        return False
+    return cost_second == STEREO_NONE or cost_second * 100 > cost_best * (100 + uniqueness)
+
+
+def stereo_disparity_numpy(d_best: int, d_lo: int, d_hi: int, cm: int, c0: int, cp: int):
+    delta = F(0)
+    if d_lo < d_best < d_hi:
+        den = cm - 2 * c0 + cp
+        if den != 0:
+            delta = F(cm - cp) / F(2 * den)
+    return F(d_best) + delta
+
+
+def stereo_point_numpy(fxB, disparity, uc, vc, fx, fy, cx, cy):
+    """(x, y, z): the box centre back-projected at Z = fxB / disparity; all arguments np.float32."""
+    Z = fxB / disparity
+    return ((uc - cx) * Z) / fx, ((vc - cy) * Z) / fy, Z
+
+
+def locate_stereo_numpy(dets, count: int, left: np.ndarray, right: np.ndarray, cam, baseline, params):
+    """dets: DET_DTYPE records; count: as the device word; left, right: [H, W] uint8 rectified planes. Returns (cones, matches):
+    MAX_DETECTIONS CONE3D_DTYPE and MAX_DETECTIONS STEREO_MATCH_DTYPE records, zero behind the count."""
+    cam, p = as_pinhole(cam), as_stereo_params(params)
+    if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 2 or left.shape != right.shape:
+        raise ValueError("left and right must be 2-D uint8 arrays of one shape")
+    if not 1 <= p.max_side <= STEREO_MAX_SIDE:
+        raise ValueError(f"max_side outside 1..{STEREO_MAX_SIDE}")
+    height, width = left.shape
+    fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
+    fxB, d_lo, d_hi_all = stereo_range_numpy(cam.fx, baseline, p.min_depth, p.max_depth, width)
+    cones = np.zeros(MAX_DETECTIONS, dtype=CONE3D_DTYPE)
+    matches = np.zeros(MAX_DETECTIONS, dtype=STEREO_MATCH_DTYPE)
+    n = min(max(int(count), 0), MAX_DETECTIONS, len(dets))
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            d = dets[i]
+            w = window_numpy((d["x1"], d["y1"], d["x2"], d["y2"]), p.sx, p.sy, p.shrink, width, height, p.max_side)
+            if w is None:
+                continue                                                    # an empty window: all-zero records
+            d_hi = min(d_hi_all, w["u0"])
+            nd = max(0, d_hi - d_lo + 1)
+            r, m = cones[i], matches[i]
+            r["u"], r["v"], r["n_samples"], r["n_valid"] = w["uc"], w["vc"], w["n_samples"], nd
+            if nd == 0:
+                m["cost_best"] = m["cost_second"] = STEREO_NONE
+                continue
+            cost = stereo_costs_numpy(left, right, w, d_lo, d_hi)
+            k, best, second = stereo_select_numpy(cost)
+            m["d_best"], m["cost_best"], m["cost_second"] = d_lo + k, best, second
+            if not stereo_accept_numpy(nd, best, second, w["n_samples"], p.max_mean_sad, p.uniqueness):
+                continue
+            inner = 0 < k < nd - 1
+            disparity = stereo_disparity_numpy(d_lo + k, d_lo, d_hi, int(cost[k - 1]) if inner else 0, best,
+                                               int(cost[k + 1]) if inner else 0)
+            r["x"], r["y"], r["z"] = stereo_point_numpy(fxB, disparity, w["uc"], w["vc"], fx, fy, cx, cy)
+            r["valid"] = 1
+            m["disparity"] = disparity
+    return cones, matches
+
+
+class DeviceStereoLocator:
+    """unina_locate_stereo_async (csrc/stereo.hip): one launch per frame behind the call that produced the records. Holds the
+    two MAX_DETECTIONS-record output buffers on the device: `out` (unina_cone3d, what DeviceTracker.update_from_buffer takes)
+    and `match` (unina_stereo_match)."""
+
+    def __init__(self, device: int = 0):
+        torch = _torch()
+        self.L = load_library()
+        self.out = torch.zeros(MAX_DETECTIONS * CONE3D_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
+        self.match = torch.zeros(MAX_DETECTIONS * STEREO_MATCH_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
+        self._keep = None      # the planes of the launch in flight
+
+    @staticmethod
+    def describe(left, right) -> StereoPair:
+        """Two uint8 CUDA tensors or views [H, W] of one shape and row stride -> unina_stereo_pair; the row stride is the
+        pitch. The halves of a side-by-side buffer (buf[:, :W] and buf[:, W:]) are such a pair."""
+        torch = _torch()
+        for t in (left, right):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.stride(1) == 1
+        assert left.shape == right.shape and left.stride(0) == right.stride(0), "the planes share one size and one pitch"
+        return StereoPair(int(left.shape[1]), int(left.shape[0]), int(left.stride(0)), left.data_ptr(), right.data_ptr())
+
+    def update_async(self, d_dets, d_count, pair, cam, baseline, params, stream=None, match=True):
+        """Enqueues the launch; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and
+        the count; pair: a StereoPair or (left, right) tensors; match=False passes d_match = NULL. Returns the cone tensor."""
+        addr = lambda t: t if isinstance(t, int) else t.data_ptr()   # noqa: E731
+        self._keep = pair
+        desc = pair if isinstance(pair, StereoPair) else self.describe(*pair)
+        cam, p = as_pinhole(cam), as_stereo_params(params)
+        rc = self.L.unina_locate_stereo_async(addr(d_dets), addr(d_count), C.byref(desc), C.byref(cam), float(baseline), C.byref(p),
+                                              self.out.data_ptr(), self.match.data_ptr() if match else None, _stream_ptr(stream))
+        if rc:
+            raise EngineError(f"unina_locate_stereo_async failed [{ERRORS.get(rc, rc)}]")
+        return self.out
+
+    def update_from_buffer(self, det_buf, left, right, cam, baseline, params, stream=None, match=True):
+        """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
+        base = det_buf.data_ptr()
+        return self.update_async(base + 32, base, (left, right), cam, baseline, params, stream, match)
+
+    def read(self, stream=None):
+        """Synchronises `stream`; returns (cones, matches): all MAX_DETECTIONS records of each (zero behind the count)."""
+        torch = _torch()
+        s = torch.cuda.current_stream() if stream is None else stream
+        if not isinstance(s, int):
+            with torch.cuda.stream(s):
+                cones, matches = self.out.cpu(), self.match.cpu()
+        else:
+            torch.cuda.synchronize()
+            cones, matches = self.out.cpu(), self.match.cpu()
+        self._keep = None
+        return cones.numpy().view(CONE3D_DTYPE).copy(), matches.numpy().view(STEREO_MATCH_DTYPE).copy()
+
+
+__all__ = ["locate_numpy", "window_numpy", "DeviceLocator", "as_pinhole", "as_params", "locate_stereo_numpy", "make_stereo_params",
+           "as_stereo_params", "stereo_range_numpy", "DeviceStereoLocator"]
