@@ -1,12 +1,14 @@
 // locate_window_host.cpp -- stand-alone host driver of csrc/locate_window.h for tests/test_locate_cpu.py: the window, grid and
-// sample-key functions csrc/locate.hip calls, built by a host compiler (no HIP, no GPU) and run on cases from a file.
+// sample-key and point functions csrc/locate.hip calls, built by a host compiler (no HIP, no GPU) and run on cases from a file.
 //   locate_window_host IN OUT
 // IN : 3 int32 -- magic, mode, n -- then
 //      mode 0: n cases of 7 float32 (x1, y1, x2, y2, sx, sy, shrink) + 3 int32 (width, height, max_side)
 //      mode 1: 1 int32 (format) + 3 float32 (unit, min_depth, max_depth), then n uint32 raw samples
+//      mode 2: 4 float32 (fx, fy, cx, cy), then n triples of float32 (uc, vc, Z)
 // OUT: mode 0: per case 12 int32 -- empty, u0, u1, v0, v1, stride_x, stride_y, cols, rows, n_samples, bits of uc, bits of vc;
 //              every sampled index is also walked and checked against the map (exit 6 if one falls outside)
 //      mode 1: n uint32 keys
+//      mode 2: per triple 3 int32 -- the bits of x, y, z
 #include "../unina-yolo-dla_amd/csrc/locate_window.h"
 
 #include <cstdio>
@@ -56,6 +58,17 @@ int main(int argc, char** argv) {
     if (n && fread(raw.data(), sizeof(uint32_t), (size_t)n, f) != (size_t)n) return 4;
     out.reserve((size_t)n);
     for (uint32_t r : raw) out.push_back((int32_t)(fmt == 0 ? locate_key_f32(r, p[0], p[1], p[2]) : locate_key_u16(r, p[0], p[1], p[2])));
+  } else if (mode == 2) {
+    float cam[4];
+    if (fread(cam, sizeof cam, 1, f) != 1) return 4;
+    std::vector<float> in((size_t)n * 3);
+    if (n && fread(in.data(), 3 * sizeof(float), (size_t)n, f) != (size_t)n) return 4;
+    out.resize((size_t)n * 3);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      float xyz[3];
+      locate_point(in[3 * i], in[3 * i + 1], in[3 * i + 2], cam[0], cam[1], cam[2], cam[3], xyz);
+      memcpy(&out[3 * i], xyz, sizeof xyz);
+    }
   } else {
     return 4;
   }

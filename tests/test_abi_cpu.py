@@ -187,20 +187,12 @@ def test_header_is_plain_c_and_record_is_32_bytes(tmp_path):
     """include/unina_mi355.h must be consumable by a C compiler without the HIP headers (cgo / ctypes-gen / a C node):
     gcc -std=c99 -pedantic on the header itself, then a C translation unit that checks the record layout the reference
     fixes (gpu_postprocess.h:27-33) at compile time."""
-    import subprocess
-    hdr = os.path.join(ROOT, "include", "unina_mi355.h")
-    r = subprocess.run(["gcc", "-fsyntax-only", "-x", "c", "-std=c99", "-Wall", "-Wpedantic", "-Werror",
-                        "-DUNINA_NO_HIP_HEADERS", hdr], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "layout.c"
-    src.write_text('#define UNINA_NO_HIP_HEADERS\n#include "unina_mi355.h"\n#include <stddef.h>\n'
-                   'typedef char rec32[(sizeof(GpuDetection) == 32) ? 1 : -1];\n'
-                   'typedef char conf16[(offsetof(GpuDetection, confidence) == 16) ? 1 : -1];\n'
-                   'typedef char valid24[(offsetof(GpuDetection, valid) == 24) ? 1 : -1];\n'
-                   'int use(unina_engine_t *e) { int w, h, n; return unina_engine_input_dims(e, &w, &h, &n); }\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "layout.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    import hostprog
+    hostprog.assert_header_is_c99()
+    hostprog.compile_c99(tmp_path, 'typedef char rec32[(sizeof(GpuDetection) == 32) ? 1 : -1];\n'
+                                   'typedef char conf16[(offsetof(GpuDetection, confidence) == 16) ? 1 : -1];\n'
+                                   'typedef char valid24[(offsetof(GpuDetection, valid) == 24) ? 1 : -1];\n'
+                                   'int use(unina_engine_t *e) { int w, h, n; return unina_engine_input_dims(e, &w, &h, &n); }\n')
 
 
 def test_node_harness_builds_and_links_against_the_library(pkg):

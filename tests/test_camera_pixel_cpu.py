@@ -2,16 +2,13 @@
 and the pre-process kernels call -- compiled for the host (tests/camera_pixel_host.cpp: g++ -ffp-contract=off, no HIP) and compared
 BYTE for byte with the scalar oracle and the numpy twins. Every case also runs in a second build of the driver with
 -fsanitize=address,undefined as the stand-alone program it is. No GPU."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "camera_pixel_host.cpp")
+import hostprog
+
 TENSOR, BGRA_TAP, BGRA_RESIZE, NV12_TAP, NV12_RESIZE, BGRA_LETTERBOX, NV12_LETTERBOX = range(7)   # camera_source.h: CameraKind
 NORM = (0.485, 0.456, 0.406, 0.229, 0.224, 0.225)
 PAD = 114.0                                                                                        # (the letterbox cases: not 0)
@@ -19,39 +16,21 @@ PAD = 114.0                                                                     
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/camera_pixel_host.cpp"
     d = tmp_path_factory.mktemp("camera_pixel_host")
-    out = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT)
-        out.append(exe)
-    return out, d
+    return hostprog.build_pair(d, "camera_pixel_host.cpp"), d
 
 
 def run(drivers, kind, plane, uv, w, h, pitch, uv_pitch, dst_hw, origin=(0, 0), inner=(0, 0, 0, 0), mode=0, skew=(0, 0),
         wide=(1, 1), x_even=0):
     """Both builds of the driver on one case; returns (float32 [3, dh, dw], what the driver printed). The sanitised build must give
     the same bytes."""
-    exes, d = drivers
     dh, dw = dst_hw
     plane = np.ascontiguousarray(plane, dtype=np.uint8).tobytes()
     uv = b"" if uv is None else np.ascontiguousarray(uv, dtype=np.uint8).tobytes()
     head = struct.pack("<24i7f", 0x43414d31, mode, kind, w, h, pitch, uv_pitch, origin[0], origin[1], dw, dh, *inner, len(plane), len(uv),
                        skew[0], skew[1], wide[0], wide[1], x_even, 0, 0, PAD, *NORM)
-    src, dst = str(d / "case.in"), str(d / "case.out")
-    with open(src, "wb") as f:
-        f.write(head + plane + uv)
-    got = []
-    for exe in exes:
-        if os.path.exists(dst):
-            os.remove(dst)
-        r = subprocess.run([exe, src, dst], capture_output=True, text=True)
-        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
-        got.append((np.fromfile(dst, dtype=np.float32).reshape(3, dh, dw), r.stdout))
-    assert got[0][0].tobytes() == got[1][0].tobytes() and got[0][1] == got[1][1]
-    return got[0]
+    got, said = hostprog.run_pair(*drivers, head + plane + uv, dtype=np.float32, stdout=True)
+    return got.reshape(3, dh, dw), said
 
 
 def bgra_frame(seed, h, w, pitch):

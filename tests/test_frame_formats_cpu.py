@@ -11,8 +11,9 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "frame_formats_host.cpp")
+import hostprog
+
+ROOT = hostprog.ROOT
 BGRA, NV12, RGB, RGBA, YUYV, UYVY, RGGB, BGGR, GRBG, GBRG = range(10)      # include/unina_mi355.h: unina_pixel_format
 BAYER = (RGGB, BGGR, GRBG, GBRG)
 NORM = (0.485, 0.456, 0.406, 0.229, 0.224, 0.225)
@@ -21,41 +22,21 @@ PAD = 114.0
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/frame_formats_host.cpp"
     d = tmp_path_factory.mktemp("frame_formats_host")
-    out = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT, capture_output=True)
-        out.append(exe)
-    return out, d
+    return hostprog.build_pair(d, "frame_formats_host.cpp"), d
 
 
 def run(drivers, fmt, plane, fw, fh, pitch, dst_hw=None, region=None, inner=None, mode=0, skew=0, wide=1):
     """Both builds of the driver on one case; returns (float32 [3, dh, dw] or None, what the driver printed). The sanitised build
     must give the same bytes. region = (x, y, w, h), default the whole frame; inner = (left, top, new_w, new_h): letterboxed."""
-    exes, d = drivers
     x, y, w, h = region or (0, 0, fw, fh)
     dh, dw = dst_hw or (h, w)
     plane = b"" if plane is None else np.ascontiguousarray(plane, dtype=np.uint8).tobytes()
     boxed, inner = (0, (0, 0, 0, 0)) if inner is None else (1, inner)
     head = struct.pack("<24i7f", 0x43414d32, mode, fmt, fw, fh, pitch, x, y, w, h, dw, dh, boxed, *inner, len(plane), skew, wide, 0, 0, 0, 0,
                        PAD, *NORM)
-    src, dst = str(d / "case.in"), str(d / "case.out")
-    with open(src, "wb") as f:
-        f.write(head + plane)
-    got = []
-    for exe in exes:
-        if os.path.exists(dst):
-            os.remove(dst)
-        r = subprocess.run([exe, src, dst], capture_output=True, text=True)
-        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
-        got.append((None if mode == 2 else np.fromfile(dst, dtype=np.float32).reshape(3, dh, dw), r.stdout))
-    if mode != 2:
-        assert got[0][0].tobytes() == got[1][0].tobytes()
-    assert got[0][1] == got[1][1]
-    return got[0]
+    got, said = hostprog.run_pair(*drivers, head + plane, dtype=None if mode == 2 else np.float32, stdout=True)
+    return (None if mode == 2 else got.reshape(3, dh, dw)), said
 
 
 def pitched(rows: np.ndarray, pitch: int, seed: int = 99) -> np.ndarray:

@@ -7,10 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from records import MAXD, det_buffer
 
 pytestmark = pytest.mark.gpu
-
-MAXD = 1024
 
 
 @pytest.fixture(scope="module")
@@ -27,17 +26,6 @@ def gold():
     n = len(g["counts"])
     return {"n": n, "counts": g["counts"], "geom": g["geom"], "names": [str(s) for s in g["names"]],
             "dets": [g[f"dets/{i:02d}"] for i in range(n)], "labels": [g[f"labels/{i:02d}"] for i in range(n)]}
-
-
-def det_buffer(torch, dets):
-    """Records -> the int32 device tensor of Engine.infer_async (word 0 = count, records from word 8); the tail of the
-    buffer holds garbage a correct kernel never reads."""
-    from unina_yolo_dla_amd.engine import DET_DTYPE
-    host = np.full(8 + 8 * MAXD, 0x7fc00000, dtype=np.int32)          # NaN bit pattern everywhere
-    host[:8] = 0
-    host[0] = len(dets)
-    host[8:8 + 8 * len(dets)] = np.ascontiguousarray(dets, dtype=DET_DTYPE).view(np.int32)
-    return torch.from_numpy(host).cuda()
 
 
 def host_image(metrics, dets, labels, geom, imgsz=640):
@@ -86,7 +74,7 @@ def run_device(torch, engine, images, max_scores=1 << 16, max_rows=1 << 16, what
     try:
         ev.reset()
         for dets, labels, geom in images:
-            ev.update(det_buffer(torch, dets), labels, params(engine, geom), what)
+            ev.update(det_buffer(torch, dets, len(dets)), labels, params(engine, geom), what)
         return ev.read()
     finally:
         ev.close()
@@ -205,11 +193,11 @@ def test_updates_accumulate_reset_zeroes_and_runs_repeat(pkg, torch_cuda):
     try:
         ev.reset()
         for dets, labels, geom in images:
-            ev.update(det_buffer(torch_cuda, dets), labels, params(engine, geom), ALL)
+            ev.update(det_buffer(torch_cuda, dets, len(dets)), labels, params(engine, geom), ALL)
         ev.reset()
         res, scores, rows = ev.read()
         assert bytes(res)[:48 - 4] == bytes(44) and res.guard_intact == 1 and not any(res.label_counts) and len(scores) == 0 and len(rows) == 0
-        ev.update(det_buffer(torch_cuda, images[1][0]), images[1][1], params(engine, images[1][2]), ALL)   # and it counts from zero again
+        ev.update(det_buffer(torch_cuda, images[1][0], len(images[1][0])), images[1][1], params(engine, images[1][2]), ALL)   # and it counts from zero again
         res, scores, rows = ev.read()
         want = host_image(metrics, *images[1])
         assert (res.tp, res.fp, res.fn) == want[0] and scores.tobytes() == want[1].tobytes() and rows.tobytes() == want[2].tobytes()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import locate_cases as lc
+from records import assert_records_equal, det_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +25,6 @@ def env(pkg):
 @pytest.fixture(scope="module")
 def locator(env):
     return env[2].DeviceLocator()
-
-
-def det_buffer(torch, dets, count):
-    """Engine.infer_async's int32 buffer (word 0 = count, records from word 8); NaN bit patterns behind the records."""
-    from unina_yolo_dla_amd.engine import DET_DTYPE
-    host = np.full(8 + 8 * lc.MAXD, 0x7fc00000, dtype=np.int32)
-    host[:8] = 0
-    host[0] = count
-    host[8:8 + 8 * len(dets)] = np.ascontiguousarray(dets, dtype=DET_DTYPE).view(np.int32)
-    return torch.from_numpy(host).cuda()
 
 
 def pitched_plane(torch, depth, fmt):
@@ -60,9 +51,7 @@ def twin(env, c):
 
 def check(env, locator, c):
     got, want = run_device(env, locator, c), twin(env, c)
-    if got.tobytes() != want.tobytes():
-        bad = [i for i in range(lc.MAXD) if got[i].tobytes() != want[i].tobytes()]
-        raise AssertionError(f"{c['name']}: {len(bad)} records differ, first {bad[0]}: got {got[bad[0]]}, want {want[bad[0]]}")
+    assert_records_equal(got, want, c["name"])
     return got
 
 

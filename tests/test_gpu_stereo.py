@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import stereo_cases as sc
+from records import assert_records_equal, det_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +26,6 @@ def env(pkg):
 @pytest.fixture(scope="module")
 def locator(env):
     return env[2].DeviceStereoLocator()
-
-
-def det_buffer(torch, dets, count):
-    """Engine.infer_async's int32 buffer (word 0 = count, records from word 8); NaN bit patterns behind the records."""
-    from unina_yolo_dla_amd.engine import DET_DTYPE
-    host = np.full(8 + 8 * sc.MAXD, 0x7fc00000, dtype=np.int32)
-    host[:8] = 0
-    host[0] = count
-    host[8:8 + 8 * len(dets)] = np.ascontiguousarray(dets, dtype=DET_DTYPE).view(np.int32)
-    return torch.from_numpy(host).cuda()
 
 
 def pitched_plane(torch, img, offset, spare=6):
@@ -70,9 +61,7 @@ def twin(env, c):
 
 def assert_equal(got, want, name):
     for g, w, what in zip(got, want, ("cone", "match")):
-        if g.tobytes() != w.tobytes():
-            bad = [i for i in range(sc.MAXD) if g[i].tobytes() != w[i].tobytes()]
-            raise AssertionError(f"{name}: {len(bad)} {what} records differ, first {bad[0]}: got {g[bad[0]]}, want {w[bad[0]]}")
+        assert_records_equal(g, w, name, what)
 
 
 def check(env, locator, c, k=0):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import track_cases as tc
+from records import assert_records_equal, det_buffer, padded_words
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +29,7 @@ def tracker(env):
 
 def upload(torch, f):
     """(Engine.infer_async's int32 buffer, the cone records) of one frame on the device, garbage behind the records."""
-    m = len(f["dets"])
-    dets = np.full(8 + 8 * tc.MAXD, 0x7fc00000, dtype=np.int32)
-    dets[:8] = 0
-    dets[0] = f["count"]
-    dets[8:8 + 8 * m] = f["dets"].view(np.int32)
-    cones = np.full(8 * tc.MAXD, 0x7fc00000, dtype=np.int32)
-    cones[:8 * m] = f["cones"].view(np.int32)
-    return torch.from_numpy(dets).cuda(), torch.from_numpy(cones).cuda()
+    return det_buffer(torch, f["dets"], f["count"]), torch.from_numpy(padded_words(f["cones"], 8 * tc.MAXD)).cuda()
 
 
 def run_device(env, tracker, c, stream=None, frames=None):
@@ -63,9 +57,7 @@ def compare(name, got, want):
     for k, ((header, tracks, assign), (state, want_assign)) in enumerate(zip(got, want)):
         where = f"{name} frame {k}"
         assert header.tobytes() == state["header"].tobytes(), (where, header, state["header"])
-        if tracks.tobytes() != state["tracks"].tobytes():
-            bad = [i for i in range(tc.MAXD) if tracks[i].tobytes() != state["tracks"][i].tobytes()]
-            raise AssertionError(f"{where}: {len(bad)} slots differ, first {bad[0]}: got {tracks[bad[0]]}, want {state['tracks'][bad[0]]}")
+        assert_records_equal(tracks, state["tracks"], where, "slot")
         if assign.tobytes() != want_assign.tobytes():
             bad = np.nonzero(assign != want_assign)[0]
             raise AssertionError(f"{where}: {len(bad)} assign words differ, first {bad[0]}: got {assign[bad[0]]}, want {want_assign[bad[0]]}")

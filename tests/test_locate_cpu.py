@@ -3,18 +3,14 @@ csrc/locate_window.h compiled for the host (tests/locate_window_host.cpp, also u
 stand-alone program it is) against the numpy twin, the argument checks of the entry point, and the record layout in C."""
 import ctypes as C
 import math
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostprog
 import locate_cases as lc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "locate_window_host.cpp")
 F = np.float32
 
 
@@ -119,32 +115,14 @@ def test_twin_equals_brute_force_on_the_edge_cases(pkg, fmt):
 # ---------------------------------------------------------------- csrc/locate_window.h on the host
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/locate_window_host.cpp"
     d = tmp_path_factory.mktemp("locate_window_host")
-    out = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=undefined,address", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT)
-        out.append(exe)
-    return out, d
+    return hostprog.build_pair(d, "locate_window_host.cpp"), d
 
 
 def run_host(drivers, payload, n_words):
-    """Both builds on one input; the sanitised build must exit 0 and give the same bytes."""
-    exes, d = drivers
-    src, dst = str(d / "case.in"), str(d / "case.out")
-    with open(src, "wb") as f:
-        f.write(payload)
-    got = []
-    for exe in exes:
-        if os.path.exists(dst):
-            os.remove(dst)
-        r = subprocess.run([exe, src, dst], capture_output=True, text=True)
-        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
-        got.append(np.fromfile(dst, dtype=np.int32))
-    assert got[0].tobytes() == got[1].tobytes() and got[0].size == n_words
-    return got[0]
+    got = hostprog.run_pair(*drivers, payload)
+    assert got.size == n_words
+    return got
 
 
 def test_host_window_and_grid_equal_the_twin_over_a_sweep(pkg, drivers):
@@ -211,6 +189,29 @@ def test_host_sample_keys_equal_the_twins_validity(pkg, drivers, fmt):
     assert 0 < ok.sum() < len(raw)
 
 
+def test_host_point_equals_the_twin_over_a_sweep(pkg, drivers):
+    """locate_point, the back-projection csrc/locate.hip and csrc/stereo_match.h both call, bit for bit against
+    localize.point_numpy: centres on cx / cy, one ulp and a fraction of a pixel beside them and at the map's corners; Z at
+    min_depth and max_depth, their neighbours, and values whose product with the centre's offset overflows to +-inf."""
+    from unina_yolo_dla_amd import localize
+    cam = np.array([70.0, 71.5, 48.25, 30.5], dtype=np.float32)                              # fx, fy, cx, cy
+    cx, cy = cam[2], cam[3]
+    us = np.array([cx, np.nextafter(cx, F(0)), np.nextafter(cx, F(1e9)), cx - F(0.5), cx + F(0.125), 0.0, 96.5, -3.75, 1e6, -1e6], dtype=np.float32)
+    vs = np.array([cy, np.nextafter(cy, F(0)), np.nextafter(cy, F(1e9)), cy + F(0.5), 0.0, 60.5, 1e6], dtype=np.float32)
+    lo, hi = F(0.3), F(40.0)
+    zs = np.array([lo, np.nextafter(lo, F(1)), hi, np.nextafter(hi, F(0)), 1.0, 12.5, 1e-45, 1e-38, 3e32, 3.4e38], dtype=np.float32)
+    uc, vc, Z = (a.reshape(-1) for a in np.meshgrid(us, vs, zs, indexing="ij"))
+    payload = struct.pack("<3i", 0x4c4f4331, 2, len(Z)) + cam.tobytes() + np.stack([uc, vc, Z], axis=1).tobytes()
+    got = run_host(drivers, payload, 3 * len(Z)).view(np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        want = np.stack(localize.point_numpy(uc, vc, Z, *cam), axis=1)
+    assert want.dtype == np.float32 and len(Z) == 700 and not np.isnan(want).any()
+    assert got.tobytes() == want.tobytes()
+    assert np.isinf(want[:, 0]).sum() > 10 and np.isinf(want[:, 1]).sum() > 10                # overflowed products
+    assert (want[uc == cx, 0] == 0).all() and (want[vc == cy, 1] == 0).all() and (want[:, 2] == Z).all()
+    assert (want[:, 0] != 0).sum() > 500
+
+
 # ---------------------------------------------------------------- the entry point's argument checks
 def test_every_bad_argument_is_refused_before_any_hip_call(pkg):
     """UNINA_ERR_ARG (4) for each refusal the header lists, in a process that has no device: a HIP call in front of the
@@ -253,22 +254,14 @@ def test_cone_record_is_32_bytes_and_the_header_stays_plain_c(pkg, tmp_path):
     assert engine.CONE3D_DTYPE.itemsize == 32
     assert [engine.CONE3D_DTYPE.fields[n][1] for n in ("x", "y", "z", "u", "v", "n_valid", "n_samples", "valid")] == list(range(0, 32, 4))
     assert C.sizeof(engine.LocateParams) == 28 and C.sizeof(engine.Pinhole) == 16
-    hdr = os.path.join(ROOT, "include", "unina_mi355.h")
-    r = subprocess.run(["gcc", "-fsyntax-only", "-x", "c", "-std=c99", "-Wall", "-Wpedantic", "-Werror", "-DUNINA_NO_HIP_HEADERS", hdr],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "cone.c"
-    src.write_text('#define UNINA_NO_HIP_HEADERS\n#include "unina_mi355.h"\n#include <stddef.h>\n'
-                   'typedef char cone32[(sizeof(unina_cone3d) == 32) ? 1 : -1];\n'
-                   'typedef char u12[(offsetof(unina_cone3d, u) == 12) ? 1 : -1];\n'
-                   'typedef char valid28[(offsetof(unina_cone3d, valid) == 28) ? 1 : -1];\n'
-                   'typedef char par28[(sizeof(unina_locate_params) == 28) ? 1 : -1];\n'
-                   'typedef char plane16[(offsetof(unina_depth, plane) == 16) ? 1 : -1];\n'
-                   'int use(const GpuDetection *d, const int *n, unina_cone3d *o) {\n'
-                   '  unina_depth z = {UNINA_DEPTH_U16, 4, 4, 8, 0, 0.001f};\n'
-                   '  unina_pinhole c = {1.0f, 1.0f, 2.0f, 2.0f};\n'
-                   '  unina_locate_params p = {1.0f, 1.0f, 0.5f, 0.3f, 40.0f, 64, 1};\n'
-                   '  return unina_locate_async(d, n, &z, &c, &p, o, 0);\n}\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wpedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
-                        str(tmp_path / "cone.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    hostprog.assert_header_is_c99()
+    hostprog.compile_c99(tmp_path, 'typedef char cone32[(sizeof(unina_cone3d) == 32) ? 1 : -1];\n'
+                                   'typedef char u12[(offsetof(unina_cone3d, u) == 12) ? 1 : -1];\n'
+                                   'typedef char valid28[(offsetof(unina_cone3d, valid) == 28) ? 1 : -1];\n'
+                                   'typedef char par28[(sizeof(unina_locate_params) == 28) ? 1 : -1];\n'
+                                   'typedef char plane16[(offsetof(unina_depth, plane) == 16) ? 1 : -1];\n'
+                                   'int use(const GpuDetection *d, const int *n, unina_cone3d *o) {\n'
+                                   '  unina_depth z = {UNINA_DEPTH_U16, 4, 4, 8, 0, 0.001f};\n'
+                                   '  unina_pinhole c = {1.0f, 1.0f, 2.0f, 2.0f};\n'
+                                   '  unina_locate_params p = {1.0f, 1.0f, 0.5f, 0.3f, 40.0f, 64, 1};\n'
+                                   '  return unina_locate_async(d, n, &z, &c, &p, o, 0);\n}\n')

@@ -2,39 +2,29 @@
 (class | enumeration index) field and the key ranges of the top-MAX_DETECTIONS cut, compiled for the host
 (tests/post_math_host.cpp, also under -fsanitize=address,undefined as the stand-alone program it is) and held against
 definitions written out here and against cut_model of tests/test_post_cases_cpu.py."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import hostprog
 import post_cases as pc
 from test_post_cases_cpu import cut_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "post_math_host.cpp")
 F = np.float32
 CLASSES = (-1, 0, 1, 16382)
 INDICES = (0, 1, 2 ** 18 - 1)
 
 
 @pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    """The driver's output by line tag; both builds must exit 0 and print the same."""
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/post_math_host.cpp"
+def drivers(tmp_path_factory):
     d = tmp_path_factory.mktemp("post_math_host")
-    outs = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT)
-        r = subprocess.run([exe], capture_output=True, text=True)
-        assert r.returncode == 0, (name, r.returncode, r.stderr[-2000:])
-        outs.append(r.stdout)
-    assert outs[0] == outs[1]
+    return hostprog.build_pair(d, "post_math_host.cpp"), d
+
+
+@pytest.fixture(scope="module")
+def rows(drivers):
+    """The driver's output by line tag; both builds must exit 0 and print the same."""
     got = {}
-    for line in outs[0].splitlines():
+    for line in hostprog.run_pair(*drivers, None, stdout=True)[1].splitlines():
         tag, *v = line.split()
         got.setdefault(tag, []).append(tuple(int(x) for x in v))
     return got

@@ -4,17 +4,15 @@ construction, on rejections and on boundaries built so that equality occurs; csr
 twin; the argument checks of the entry point; the record layouts in C."""
 import ctypes as C
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostprog
 import stereo_cases as sc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "stereo_match_host.cpp")
 F = np.float32
 
 
@@ -149,32 +147,14 @@ def test_maximal_cost_and_the_last_index(pkg):
 # ---------------------------------------------------------------- csrc/stereo_match.h on the host
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/stereo_match_host.cpp"
     d = tmp_path_factory.mktemp("stereo_match_host")
-    out = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=undefined,address", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT)
-        out.append(exe)
-    return out, d
+    return hostprog.build_pair(d, "stereo_match_host.cpp"), d
 
 
 def run_host(drivers, payload, n_words):
-    """Both builds on one input; the sanitised build must exit 0 and give the same bytes."""
-    exes, d = drivers
-    src, dst = str(d / "case.in"), str(d / "case.out")
-    with open(src, "wb") as f:
-        f.write(payload)
-    got = []
-    for exe in exes:
-        if os.path.exists(dst):
-            os.remove(dst)
-        r = subprocess.run([exe, src, dst], capture_output=True, text=True)
-        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
-        got.append(np.fromfile(dst, dtype=np.int32))
-    assert got[0].tobytes() == got[1].tobytes() and got[0].size == n_words
-    return got[0]
+    got = hostprog.run_pair(*drivers, payload)
+    assert got.size == n_words
+    return got
 
 
 def test_host_range_equals_the_twin_over_a_sweep(pkg, drivers):
@@ -315,19 +295,14 @@ def test_records_are_plain_c_of_the_stated_sizes(pkg, tmp_path):
     assert [engine.STEREO_MATCH_DTYPE.fields[n][1] for n in ("disparity", "d_best", "cost_best", "cost_second")] == [0, 4, 8, 12]
     assert C.sizeof(engine.StereoParams) == 32 and C.sizeof(engine.StereoPair) == 32
     assert (engine.STEREO_MAX_DISPARITIES, engine.STEREO_MAX_SIDE) == (1024, 64)
-    src = tmp_path / "stereo.c"
-    src.write_text('#define UNINA_NO_HIP_HEADERS\n#include "unina_mi355.h"\n#include <stddef.h>\n'
-                   'typedef char match16[(sizeof(unina_stereo_match) == 16) ? 1 : -1];\n'
-                   'typedef char second12[(offsetof(unina_stereo_match, cost_second) == 12) ? 1 : -1];\n'
-                   'typedef char par32[(sizeof(unina_stereo_params) == 32) ? 1 : -1];\n'
-                   'typedef char left16[(offsetof(unina_stereo_pair, left) == 16) ? 1 : -1];\n'
-                   'typedef char lim[(UNINA_STEREO_MAX_DISPARITIES == 1024 && UNINA_STEREO_MAX_SIDE == 64) ? 1 : -1];\n'
-                   'int use(const GpuDetection *d, const int *n, const uint8_t *y, unina_cone3d *o, unina_stereo_match *m) {\n'
-                   '  unina_stereo_pair s = {640, 360, 1280, 0, 0};\n'
-                   '  unina_pinhole c = {700.0f, 700.0f, 320.0f, 180.0f};\n'
-                   '  unina_stereo_params p = {1.0f, 1.0f, 0.5f, 0.5f, 40.0f, 64, 20, 10};\n'
-                   '  s.left = y; s.right = y + 640;\n'
-                   '  return unina_locate_stereo_async(d, n, &s, &c, 0.12f, &p, o, m, 0);\n}\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wpedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
-                        str(tmp_path / "stereo.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    hostprog.compile_c99(tmp_path, 'typedef char match16[(sizeof(unina_stereo_match) == 16) ? 1 : -1];\n'
+                                   'typedef char second12[(offsetof(unina_stereo_match, cost_second) == 12) ? 1 : -1];\n'
+                                   'typedef char par32[(sizeof(unina_stereo_params) == 32) ? 1 : -1];\n'
+                                   'typedef char left16[(offsetof(unina_stereo_pair, left) == 16) ? 1 : -1];\n'
+                                   'typedef char lim[(UNINA_STEREO_MAX_DISPARITIES == 1024 && UNINA_STEREO_MAX_SIDE == 64) ? 1 : -1];\n'
+                                   'int use(const GpuDetection *d, const int *n, const uint8_t *y, unina_cone3d *o, unina_stereo_match *m) {\n'
+                                   '  unina_stereo_pair s = {640, 360, 1280, 0, 0};\n'
+                                   '  unina_pinhole c = {700.0f, 700.0f, 320.0f, 180.0f};\n'
+                                   '  unina_stereo_params p = {1.0f, 1.0f, 0.5f, 0.5f, 40.0f, 64, 20, 10};\n'
+                                   '  s.left = y; s.right = y + 640;\n'
+                                   '  return unina_locate_stereo_async(d, n, &s, &c, 0.12f, &p, o, m, 0);\n}\n')

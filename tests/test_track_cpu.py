@@ -4,18 +4,14 @@ against the rounds of mutual nearest neighbours csrc/track.hip computes, csrc/tr
 the argument checks of the entry point, the layouts in C, and what each constructed case of tests/track_cases.py contains."""
 import ctypes as C
 import math
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostprog
 import track_cases as tc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "track_math_host.cpp")
 F = np.float32
 INT_MAX = 2 ** 31 - 1
 
@@ -246,38 +242,22 @@ def test_next_id_stops_at_int_max(pkg):
 # ---------------------------------------------------------------- csrc/track_math.h on the host
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++")
-    assert cxx, "g++ is needed to build tests/track_math_host.cpp"
     d = tmp_path_factory.mktemp("track_math_host")
-    out = []
-    for name, extra in (("plain", []), ("san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
-        exe = str(d / name)
-        subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", *extra, SRC, "-o", exe], check=True, cwd=ROOT)
-        out.append(exe)
-    return out, d
+    return hostprog.build_pair(d, "track_math_host.cpp"), d
 
 
 def run_host(drivers, mode, words, float_cols):
     """Both builds on one input ([n, 16] uint32 words); the sanitised build must exit 0 and give the same words (a NaN in a
     float column is compared as a NaN: its sign differs between a folded constant and the FPU's result)."""
-    exes, d = drivers
-    src, dst = str(d / "case.in"), str(d / "case.out")
-    with open(src, "wb") as f:
-        f.write(struct.pack("<3i", 0x54524b31, mode, len(words)) + np.ascontiguousarray(words, dtype=np.uint32).tobytes())
-    got = []
-    for exe in exes:
-        if os.path.exists(dst):
-            os.remove(dst)
-        r = subprocess.run([exe, src, dst], capture_output=True, text=True)
-        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
-        g = np.fromfile(dst, dtype=np.uint32)
+    def canon(g):
         assert g.size == 4 * len(words)
         g = g.reshape(-1, 4)
         for col in float_cols:
             g[np.isnan(g[:, col].view(np.float32)), col] = 0x7fc00000
-        got.append(g)
-    assert got[0].tobytes() == got[1].tobytes()
-    return got[0]
+        return g
+
+    payload = struct.pack("<3i", 0x54524b31, mode, len(words)) + np.ascontiguousarray(words, dtype=np.uint32).tobytes()
+    return hostprog.run_pair(*drivers, payload, dtype=np.uint32, canon=canon)
 
 
 SPECIAL = np.array([0.0, -0.0, 1.0, -1.0, 0.25, 0.6, 1e-45, 1e-38, 3e38, -3e38, 3.4028235e38, np.inf, -np.inf, np.nan, 100.0, 0.1],
@@ -398,32 +378,24 @@ def test_layouts_and_the_header_stays_plain_c(pkg, tmp_path):
     assert set(n for n in engine.ABI_SYMBOLS if n.startswith("unina_track_")) == {
         "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
         "unina_track_read"}
-    hdr = os.path.join(ROOT, "include", "unina_mi355.h")
-    r = subprocess.run(["gcc", "-fsyntax-only", "-x", "c", "-std=c99", "-Wall", "-Wpedantic", "-Werror", "-DUNINA_NO_HIP_HEADERS", hdr],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    src = tmp_path / "track.c"
-    src.write_text('#define UNINA_NO_HIP_HEADERS\n#include "unina_mi355.h"\n#include <stddef.h>\n'
-                   'typedef char track32[(sizeof(unina_track) == 32) ? 1 : -1];\n'
-                   'typedef char id16[(offsetof(unina_track, id) == 16) ? 1 : -1];\n'
-                   'typedef char conf12[(offsetof(unina_track, confidence) == 12) ? 1 : -1];\n'
-                   'typedef char missed28[(offsetof(unina_track, missed) == 28) ? 1 : -1];\n'
-                   'typedef char head32[(sizeof(unina_track_header) == 32) ? 1 : -1];\n'
-                   'typedef char next12[(offsetof(unina_track_header, next_id) == 12) ? 1 : -1];\n'
-                   'typedef char dropped28[(offsetof(unina_track_header, n_dropped) == 28) ? 1 : -1];\n'
-                   'typedef char par72[(sizeof(unina_track_params) == 72) ? 1 : -1];\n'
-                   'typedef char gate48[(offsetof(unina_track_params, gate) == 48) ? 1 : -1];\n'
-                   'typedef char aware60[(offsetof(unina_track_params, class_aware) == 60) ? 1 : -1];\n'
-                   'typedef char max1024[(UNINA_TRACK_MAX == 1024) ? 1 : -1];\n'
-                   'int use(const GpuDetection *d, const int *n, const unina_cone3d *c, int *assign) {\n'
-                   '  unina_tracker_t *t = 0;\n'
-                   '  unina_track_params p = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, 0.5f, 0.5f, 0.3f, 1, 3, 5};\n'
-                   '  unina_track_header h;\n  unina_track tr[4];\n'
-                   '  const unina_track *dt;\n  const unina_track_header *dh;\n'
-                   '  if (unina_track_create(0, &t)) return 1;\n'
-                   '  if (unina_track_reset_async(t, 0) || unina_track_update_async(t, d, n, c, &p, assign, 0)) return 2;\n'
-                   '  if (unina_track_buffers(t, &dt, &dh) || unina_track_read(t, &h, tr, 4, 0)) return 3;\n'
-                   '  unina_track_destroy(t);\n  return h.n_live + tr[0].id;\n}\n')
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wpedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
-                        str(tmp_path / "track.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    hostprog.assert_header_is_c99()
+    hostprog.compile_c99(tmp_path, 'typedef char track32[(sizeof(unina_track) == 32) ? 1 : -1];\n'
+                                   'typedef char id16[(offsetof(unina_track, id) == 16) ? 1 : -1];\n'
+                                   'typedef char conf12[(offsetof(unina_track, confidence) == 12) ? 1 : -1];\n'
+                                   'typedef char missed28[(offsetof(unina_track, missed) == 28) ? 1 : -1];\n'
+                                   'typedef char head32[(sizeof(unina_track_header) == 32) ? 1 : -1];\n'
+                                   'typedef char next12[(offsetof(unina_track_header, next_id) == 12) ? 1 : -1];\n'
+                                   'typedef char dropped28[(offsetof(unina_track_header, n_dropped) == 28) ? 1 : -1];\n'
+                                   'typedef char par72[(sizeof(unina_track_params) == 72) ? 1 : -1];\n'
+                                   'typedef char gate48[(offsetof(unina_track_params, gate) == 48) ? 1 : -1];\n'
+                                   'typedef char aware60[(offsetof(unina_track_params, class_aware) == 60) ? 1 : -1];\n'
+                                   'typedef char max1024[(UNINA_TRACK_MAX == 1024) ? 1 : -1];\n'
+                                   'int use(const GpuDetection *d, const int *n, const unina_cone3d *c, int *assign) {\n'
+                                   '  unina_tracker_t *t = 0;\n'
+                                   '  unina_track_params p = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, 0.5f, 0.5f, 0.3f, 1, 3, 5};\n'
+                                   '  unina_track_header h;\n  unina_track tr[4];\n'
+                                   '  const unina_track *dt;\n  const unina_track_header *dh;\n'
+                                   '  if (unina_track_create(0, &t)) return 1;\n'
+                                   '  if (unina_track_reset_async(t, 0) || unina_track_update_async(t, d, n, c, &p, assign, 0)) return 2;\n'
+                                   '  if (unina_track_buffers(t, &dt, &dh) || unina_track_read(t, &h, tr, 4, 0)) return 3;\n'
+                                   '  unina_track_destroy(t);\n  return h.n_live + tr[0].id;\n}\n')

@@ -19,7 +19,7 @@
 
 #include <new>
 
-#include "../../include/unina_mi355.h"
+#include "record_io.h"
 
 namespace unina {
 namespace {
@@ -103,8 +103,7 @@ __global__ void __launch_bounds__(kEvalBlock) evalmatch_kernel(const float* __re
   __shared__ unsigned s_bits[kEvalWaves - 1][kWave];       // wave 1 + j: bit (k / 64) of lane (k % 64) = detection k matched at t_j
 
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int n = *d_count;
-  n = n < 0 ? 0 : (n > MAX_DETECTIONS ? MAX_DETECTIONS : n);
+  const int n = record_count(d_count);
   const unsigned long long row_base = ctr->n_rows, score_base = ctr->n_scores;   // read by everyone before anyone updates them
 
   for (int i = tid; i < n; i += kEvalBlock) s_raw[i] = dets[8 * i + 4];
@@ -367,7 +366,7 @@ extern "C" int unina_eval_update_async(unina_eval_t* ev, const GpuDetection* d_d
   hipLaunchKernelGGL(evalmatch_kernel, dim3(1), dim3(kEvalBlock), 0, stream, reinterpret_cast<const float*>(d_dets), d_count, d_labels,
                      n_labels, *p, what, ev->num_classes, ev->d_ctr, ev->d_scores, (unsigned long long)ev->max_scores, ev->d_rows,
                      (unsigned long long)ev->max_rows);
-  return hipGetLastError() == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+  return launch_status();
 }
 
 extern "C" int unina_eval_read(unina_eval_t* ev, unina_eval_result* res, double* scores, size_t score_cap, unina_eval_row* rows,

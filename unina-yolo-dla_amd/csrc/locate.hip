@@ -22,8 +22,7 @@
 // costs one small launch.
 #include <hip/hip_runtime.h>
 
-#include "../../include/unina_mi355.h"
-#include "locate_window.h"
+#include "locate_checks.h"
 
 namespace unina {
 namespace {
@@ -46,25 +45,6 @@ struct LocateArgs {
   int max_side, min_valid;
 };
 
-union ConeWords {
-  unina_cone3d c;
-  uint4 q[2];
-};
-
-// two 16-byte vector stores (d_out is 16-byte aligned)
-__device__ __forceinline__ void store_cone(unina_cone3d* __restrict__ out, int slot, const ConeWords& w) {
-  uint4* o = reinterpret_cast<uint4*>(out + slot);
-  o[0] = w.q[0];
-  o[1] = w.q[1];
-}
-
-__device__ __forceinline__ void store_zero(unina_cone3d* __restrict__ out, int slot) {
-  ConeWords w;
-  w.q[0] = make_uint4(0u, 0u, 0u, 0u);
-  w.q[1] = w.q[0];
-  store_cone(out, slot, w);
-}
-
 __device__ __forceinline__ LocateWindow slot_window(const GpuDetection* __restrict__ dets, int slot, const LocateArgs& a) {
   const float4 b = *reinterpret_cast<const float4*>(dets + slot);   // x1, y1, x2, y2
   return locate_window(b.x, b.y, b.z, b.w, a.sx, a.sy, a.shrink, a.width, a.height, a.max_side);
@@ -86,22 +66,23 @@ __device__ __forceinline__ uint32_t sample_key(const LocateArgs& a, const Locate
 // the record of a non-empty window: the point where enough samples are valid, zeros in x, y, z otherwise
 __device__ __forceinline__ void store_result(unina_cone3d* __restrict__ out, int slot, const LocateArgs& a, const LocateWindow& w,
                                              int n_valid, uint32_t median_key) {
-  ConeWords r;
-  r.c.x = r.c.y = r.c.z = 0.0f;
-  r.c.u = w.uc;
-  r.c.v = w.vc;
-  r.c.n_valid = n_valid;
-  r.c.n_samples = w.n_samples;
+  RecordWords<unina_cone3d> c;
+  c.r.x = c.r.y = c.r.z = 0.0f;
+  c.r.u = w.uc;
+  c.r.v = w.vc;
+  c.r.n_valid = n_valid;
+  c.r.n_samples = w.n_samples;
   const int need = a.min_valid > 1 ? a.min_valid : 1;
-  r.c.valid = n_valid >= need ? 1 : 0;
-  if (r.c.valid) {
+  c.r.valid = n_valid >= need ? 1 : 0;
+  if (c.r.valid) {
     const float raw = a.format == UNINA_DEPTH_F32 ? __uint_as_float(median_key) : (float)median_key;
-    const float Z = raw * a.unit;
-    r.c.x = ((w.uc - a.cx) * Z) / a.fx;
-    r.c.y = ((w.vc - a.cy) * Z) / a.fy;
-    r.c.z = Z;
+    float xyz[3];
+    locate_point(w.uc, w.vc, raw * a.unit, a.fx, a.fy, a.cx, a.cy, xyz);
+    c.r.x = xyz[0];
+    c.r.y = xyz[1];
+    c.r.z = xyz[2];
   }
-  store_cone(out, slot, r);
+  store_record(out + slot, c);
 }
 
 __global__ void __launch_bounds__(kLocBlock) locate_kernel(const GpuDetection* __restrict__ dets, const int* __restrict__ d_count,
@@ -112,8 +93,7 @@ __global__ void __launch_bounds__(kLocBlock) locate_kernel(const GpuDetection* _
   __shared__ int s_sel[3];   // bin, rank inside the bin, n_valid
 
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  int n = *d_count;
-  n = n < 0 ? 0 : (n > MAX_DETECTIONS ? MAX_DETECTIONS : n);
+  const int n = record_count(d_count);
   const int slot0 = (int)blockIdx.x * kLocWaves;
 
   // ---- phase 1: a wave per slot
@@ -121,11 +101,11 @@ __global__ void __launch_bounds__(kLocBlock) locate_kernel(const GpuDetection* _
     const int slot = slot0 + wave;
     int big = 0;
     if (slot >= n) {
-      if (lane == 0) store_zero(out, slot);
+      if (lane == 0) store_zero_record(out + slot);
     } else {
       const LocateWindow w = slot_window(dets, slot, a);
       if (w.empty) {
-        if (lane == 0) store_zero(out, slot);
+        if (lane == 0) store_zero_record(out + slot);
       } else if (w.n_samples > kWave) {
         big = 1;
       } else {
@@ -221,27 +201,20 @@ __global__ void __launch_bounds__(kLocBlock) locate_kernel(const GpuDetection* _
   }
 }
 
-bool finite_pos(float v) { return v > 0.0f && v - v == 0.0f; }
-
 }  // namespace
 }  // namespace unina
 
 extern "C" int unina_locate_async(const GpuDetection* d_dets, const int* d_count, const unina_depth* depth, const unina_pinhole* cam,
                                   const unina_locate_params* p, unina_cone3d* d_out, hipStream_t stream) {
   using namespace unina;
-  if (!d_dets || !d_count || !depth || !cam || !p || !d_out || !depth->plane) return UNINA_ERR_ARG;
+  if (!record_io_ok(d_dets, d_count, d_out) || !depth || !p || !depth->plane) return UNINA_ERR_ARG;
+  if (!plane_dims_ok(depth->width, depth->height) || !pinhole_ok(cam)) return UNINA_ERR_ARG;
+  if (!window_params_ok(p->sx, p->sy, p->shrink, p->min_depth, p->max_depth)) return UNINA_ERR_ARG;
   if (depth->format != UNINA_DEPTH_F32 && depth->format != UNINA_DEPTH_U16) return UNINA_ERR_ARG;
   const int elem = depth->format == UNINA_DEPTH_F32 ? 4 : 2;
-  if (depth->width < 1 || depth->height < 1 || depth->width > kLocateMaxDim || depth->height > kLocateMaxDim) return UNINA_ERR_ARG;
   if ((long long)depth->pitch < (long long)depth->width * elem || depth->pitch % elem != 0) return UNINA_ERR_ARG;
-  if (((uintptr_t)depth->plane & (uintptr_t)(elem - 1)) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_dets & 15) || ((uintptr_t)d_count & 3))
-    return UNINA_ERR_ARG;
-  if (!finite_pos(cam->fx) || !finite_pos(cam->fy) || !finite_pos(depth->unit) || !finite_pos(p->sx) || !finite_pos(p->sy))
-    return UNINA_ERR_ARG;
-  if (!locate_finite(cam->cx) || !locate_finite(cam->cy)) return UNINA_ERR_ARG;
-  if (!(p->shrink > 0.0f && p->shrink <= 1.0f)) return UNINA_ERR_ARG;
+  if (((uintptr_t)depth->plane & (uintptr_t)(elem - 1)) || !finite_pos(depth->unit)) return UNINA_ERR_ARG;
   if (p->max_side < 1 || p->max_side > 256 || p->min_valid < 0) return UNINA_ERR_ARG;
-  if (!(p->min_depth > 0.0f && p->min_depth < p->max_depth && locate_finite(p->max_depth))) return UNINA_ERR_ARG;
   LocateArgs a;
   a.plane = static_cast<const unsigned char*>(depth->plane);
   a.format = depth->format;
@@ -254,5 +227,5 @@ extern "C" int unina_locate_async(const GpuDetection* d_dets, const int* d_count
   a.max_side = p->max_side;
   a.min_valid = p->min_valid;
   hipLaunchKernelGGL(locate_kernel, dim3(MAX_DETECTIONS / kLocWaves), dim3(kLocBlock), 0, stream, d_dets, d_count, a, d_out);
-  return hipGetLastError() == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+  return launch_status();
 }

@@ -1,7 +1,8 @@
-// locate_window.h -- the window, the sampling grid and the sample key of unina_locate_async (include/unina_mi355.h "3-D
-// localisation"), as __host__ __device__ functions: csrc/locate.hip calls them on the device, tests/locate_window_host.cpp
-// sweeps them on the host, localize.locate_numpy is their numpy twin. fp32 throughout, one rounding per operation: every
-// translation unit that includes this header is compiled with -ffp-contract=off.
+// locate_window.h -- the window, the sampling grid, the sample key and the back-projected point of unina_locate_async
+// (include/unina_mi355.h "3-D localisation"), as __host__ __device__ functions (csrc/hd.h): csrc/locate.hip and csrc/stereo.hip
+// call them on the device, tests/locate_window_host.cpp sweeps them on the host, localize.window_numpy and localize.point_numpy
+// are their numpy twins. fp32 throughout, one rounding per operation: every translation unit that includes this header is
+// compiled with -ffp-contract=off.
 #ifndef UNINA_LOCATE_WINDOW_H
 #define UNINA_LOCATE_WINDOW_H
 
@@ -9,11 +10,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define UNINA_HD __host__ __device__ __forceinline__
-#else
-#define UNINA_HD inline
-#endif
+#include "hd.h"
 
 namespace unina {
 
@@ -29,13 +26,11 @@ struct LocateWindow {
   float uc, vc;     // centre of the box in depth-map pixels
 };
 
-UNINA_HD bool locate_finite(float v) { return v - v == 0.0f; }   // false for NaN and +-inf
-
 // one axis: the covered pixels floorf(c - h) .. floorf(c + h) against 0 .. n - 1, decided in float, converted after the clip
 UNINA_HD bool locate_axis(float c, float h, int n, int max_side, int* lo, int* hi, int* stride, int* count) {
   const float flo = floorf(c - h), fhi = floorf(c + h);
   const float last = (float)(n - 1);
-  if (!locate_finite(flo) || !locate_finite(fhi)) return false;
+  if (!finite(flo) || !finite(fhi)) return false;
   if (fhi < 0.0f || flo > last) return false;           // wholly off the map
   const int a = flo < 0.0f ? 0 : (int)flo;              // 0 <= flo <= last here
   const int b = fhi > last ? n - 1 : (int)fhi;
@@ -55,7 +50,7 @@ UNINA_HD LocateWindow locate_window(float x1, float y1, float x2, float y2, floa
   memset(&w, 0, sizeof(w));
   w.empty = 1;
   const float X1 = x1 * sx, X2 = x2 * sx, Y1 = y1 * sy, Y2 = y2 * sy;
-  if (!locate_finite(X1) || !locate_finite(X2) || !locate_finite(Y1) || !locate_finite(Y2)) return w;
+  if (!finite(X1) || !finite(X2) || !finite(Y1) || !finite(Y2)) return w;
   if (X2 < X1 || Y2 < Y1) return w;
   const float uc = 0.5f * (X1 + X2), vc = 0.5f * (Y1 + Y2);
   const float hs = 0.5f * shrink;
@@ -77,7 +72,7 @@ UNINA_HD LocateWindow locate_window(float x1, float y1, float x2, float y2, floa
 UNINA_HD uint32_t locate_key_f32(uint32_t bits, float unit, float min_depth, float max_depth) {
   float f;
   memcpy(&f, &bits, 4);
-  if (!locate_finite(f)) return 0u;
+  if (!finite(f)) return 0u;
   const float z = f * unit;
   return (z >= min_depth && z <= max_depth) ? bits : 0u;
 }
@@ -85,6 +80,13 @@ UNINA_HD uint32_t locate_key_u16(uint32_t raw, float unit, float min_depth, floa
   if (raw == 0u) return 0u;
   const float z = (float)raw * unit;
   return (z >= min_depth && z <= max_depth) ? raw : 0u;
+}
+
+// xyz[0..2] = the pixel (uc, vc) back-projected through the pinhole at depth Z
+UNINA_HD void locate_point(float uc, float vc, float Z, float fx, float fy, float cx, float cy, float* xyz) {
+  xyz[0] = ((uc - cx) * Z) / fx;
+  xyz[1] = ((vc - cy) * Z) / fy;
+  xyz[2] = Z;
 }
 
 }  // namespace unina

@@ -9,20 +9,16 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define UNINA_POST_HD __host__ __device__ __forceinline__
-#else
-#define UNINA_POST_HD inline
-#endif
+#include "hd.h"
 
 namespace unina {
 
-UNINA_POST_HD uint32_t post_bits(float v) { uint32_t b; memcpy(&b, &v, 4); return b; }
-UNINA_POST_HD float post_float(uint32_t b) { float v; memcpy(&v, &b, 4); return v; }
+UNINA_HD uint32_t post_bits(float v) { uint32_t b; memcpy(&b, &v, 4); return b; }
+UNINA_HD float post_float(uint32_t b) { float v; memcpy(&v, &b, 4); return v; }
 
 // ---- upper-triangular 64 x 64-bit tiles over nw chunks of 64 candidates: tile t <-> (row chunk c, column chunk w >= c), row-major
 struct TileCW { int c, w; };
-UNINA_POST_HD TileCW tile_of(int t, int nw) {
+UNINA_HD TileCW tile_of(int t, int nw) {
   int c = 0, rem = t;
   while (rem >= nw - c) {
     rem -= nw - c;
@@ -31,11 +27,11 @@ UNINA_POST_HD TileCW tile_of(int t, int nw) {
   return TileCW{c, c + rem};
 }
 // first 64-bit word of row chunk c's tiles (64 rows x (nw - c) words each) in the triangular mask
-UNINA_POST_HD int tri_off(int c, int nw) { return 64 * (c * nw - (c * (c - 1)) / 2); }
+UNINA_HD int tri_off(int c, int nw) { return 64 * (c * nw - (c * (c - 1)) / 2); }
 
 // ---- confidence -> bin of the decode launch's histogram: kBins linear bins, bin T = the confidences in [T / kBins, (T + 1) / kBins)
 constexpr int kBins = 4096;
-UNINA_POST_HD int conf_bin(float c) {
+UNINA_HD int conf_bin(float c) {
   const int b = (int)(c * (float)kBins);
   return b > kBins - 1 ? kBins - 1 : b;
 }
@@ -45,21 +41,21 @@ UNINA_POST_HD int conf_bin(float c) {
 // the padding dummy's class -1, so num_classes <= kClassMask (checked by unina_load_engine)
 constexpr int kClassBits = 14;
 constexpr int kClassMask = (1 << kClassBits) - 1;
-UNINA_POST_HD float pack_ce(int class_id, int eidx) { return post_float(((uint32_t)class_id & (uint32_t)kClassMask) | ((uint32_t)eidx << kClassBits)); }
-UNINA_POST_HD int ce_class(float y) {   // (not a sign extension: that would turn the ids from 8192 up into negative ones)
+UNINA_HD float pack_ce(int class_id, int eidx) { return post_float(((uint32_t)class_id & (uint32_t)kClassMask) | ((uint32_t)eidx << kClassBits)); }
+UNINA_HD int ce_class(float y) {   // (not a sign extension: that would turn the ids from 8192 up into negative ones)
   const int f = (int)(post_bits(y) & (uint32_t)kClassMask);
   return f == kClassMask ? -1 : f;
 }
-UNINA_POST_HD unsigned ce_eidx(float y) { return post_bits(y) >> kClassBits; }
-UNINA_POST_HD bool ce_same_class(float a, float b) { return ((post_bits(a) ^ post_bits(b)) & (uint32_t)kClassMask) == 0; }
+UNINA_HD unsigned ce_eidx(float y) { return post_bits(y) >> kClassBits; }
+UNINA_HD bool ce_same_class(float a, float b) { return ((post_bits(a) ^ post_bits(b)) & (uint32_t)kClassMask) == 0; }
 
 // ---- the cut: key = bit pattern of a confidence (positive floats: the patterns order like the values)
 struct KeyRange { uint32_t lo, hi; };   // [lo, hi)
-UNINA_POST_HD KeyRange bin_key_range(int T) {   // (a confidence is at most 1.0: the top bin ends just above its bit pattern)
+UNINA_HD KeyRange bin_key_range(int T) {   // (a confidence is at most 1.0: the top bin ends just above its bit pattern)
   return KeyRange{post_bits((float)T / (float)kBins), T == kBins - 1 ? 0x3F800001u : post_bits((float)(T + 1) / (float)kBins)};
 }
 // a key range too crowded to rank is split into kBins sub-ranges of this width (the last ones may be empty)
-UNINA_POST_HD uint32_t split_width(uint32_t klo, uint32_t khi) { return (khi - klo + (uint32_t)kBins - 1u) / (uint32_t)kBins; }
+UNINA_HD uint32_t split_width(uint32_t klo, uint32_t khi) { return (khi - klo + (uint32_t)kBins - 1u) / (uint32_t)kBins; }
 
 }  // namespace unina
 

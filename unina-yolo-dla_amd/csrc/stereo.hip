@@ -35,7 +35,7 @@
 
 #include <atomic>
 
-#include "../../include/unina_mi355.h"
+#include "locate_checks.h"
 #include "stereo_match.h"
 
 namespace unina {
@@ -65,29 +65,16 @@ struct StereoArgs {
   int max_side, max_mean_sad, uniqueness;
 };
 
-union ConeWords {
-  unina_cone3d c;
-  uint4 q[2];
-};
-union MatchWords {
-  unina_stereo_match m;
-  uint4 q;
-};
-
-// 16-byte vector stores (d_out and d_match are 16-byte aligned)
+// d_match may be NULL
 __device__ __forceinline__ void store_records(unina_cone3d* __restrict__ out, unina_stereo_match* __restrict__ match, int slot,
-                                              const ConeWords& c, const MatchWords& m) {
-  uint4* o = reinterpret_cast<uint4*>(out + slot);
-  o[0] = c.q[0];
-  o[1] = c.q[1];
-  if (match) *reinterpret_cast<uint4*>(match + slot) = m.q;
+                                              const RecordWords<unina_cone3d>& c, const RecordWords<unina_stereo_match>& m) {
+  store_record(out + slot, c);
+  if (match) store_record(match + slot, m);
 }
 
 __device__ __forceinline__ void store_zero(unina_cone3d* __restrict__ out, unina_stereo_match* __restrict__ match, int slot) {
-  ConeWords c;
-  MatchWords m;
-  c.q[0] = c.q[1] = m.q = make_uint4(0u, 0u, 0u, 0u);
-  store_records(out, match, slot, c, m);
+  store_zero_record(out + slot);
+  if (match) store_zero_record(match + slot);
 }
 
 // minimum over the workgroup; every thread calls it. The leading barrier also publishes what was written to LDS before the call.
@@ -202,8 +189,7 @@ __global__ void __launch_bounds__(kStBlock) stereo_kernel(const GpuDetection* __
 
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int slot = (int)blockIdx.x;   // < MAX_DETECTIONS: the grid's size
-  int n = *d_count;
-  n = n < 0 ? 0 : (n > MAX_DETECTIONS ? MAX_DETECTIONS : n);
+  const int n = record_count(d_count);
 
   // ---- everything up to the first barrier is the same in every thread: each return is the whole workgroup's
   if (slot >= n) {
@@ -216,20 +202,20 @@ __global__ void __launch_bounds__(kStBlock) stereo_kernel(const GpuDetection* __
     if (tid == 0) store_zero(out, match, slot);
     return;
   }
-  ConeWords rec;
-  MatchWords mw;
-  rec.c.x = rec.c.y = rec.c.z = 0.0f;
-  rec.c.u = w.uc;
-  rec.c.v = w.vc;
-  rec.c.n_samples = w.n_samples;
-  rec.c.valid = 0;
+  RecordWords<unina_cone3d> rec;
+  RecordWords<unina_stereo_match> mw;
+  rec.r.x = rec.r.y = rec.r.z = 0.0f;
+  rec.r.u = w.uc;
+  rec.r.v = w.vc;
+  rec.r.n_samples = w.n_samples;
+  rec.r.valid = 0;
   int d_hi;
   const int nd = stereo_nd(a.d_lo, a.d_hi_all, w.u0, &d_hi);   // <= kStereoMaxDisparities: the entry point refuses a longer range
-  rec.c.n_valid = nd;
+  rec.r.n_valid = nd;
   if (nd == 0) {
-    mw.m.disparity = 0.0f;
-    mw.m.d_best = 0;
-    mw.m.cost_best = mw.m.cost_second = kStereoNone;
+    mw.r.disparity = 0.0f;
+    mw.r.d_best = 0;
+    mw.r.cost_best = mw.r.cost_second = kStereoNone;
     if (tid == 0) store_records(out, match, slot, rec, mw);
     return;
   }
@@ -304,25 +290,23 @@ __global__ void __launch_bounds__(kStBlock) stereo_kernel(const GpuDetection* __
 
   const uint32_t cost_best = stereo_key_cost(best);
   const int d_best = a.d_lo + k_best;
-  mw.m.d_best = d_best;
-  mw.m.cost_best = cost_best;
-  mw.m.cost_second = second;
-  mw.m.disparity = 0.0f;
+  mw.r.d_best = d_best;
+  mw.r.cost_best = cost_best;
+  mw.r.cost_second = second;
+  mw.r.disparity = 0.0f;
   if (stereo_accept(nd, cost_best, second, w.n_samples, a.max_mean_sad, a.uniqueness)) {
     const bool inner = k_best > 0 && k_best < nd - 1;
     const float disparity = stereo_disparity(d_best, a.d_lo, d_hi, inner ? s_cost[k_best - 1] : 0u, cost_best, inner ? s_cost[k_best + 1] : 0u);
     float xyz[3];
     stereo_point(a.fxB, disparity, w.uc, w.vc, a.fx, a.fy, a.cx, a.cy, xyz);
-    rec.c.x = xyz[0];
-    rec.c.y = xyz[1];
-    rec.c.z = xyz[2];
-    rec.c.valid = 1;
-    mw.m.disparity = disparity;
+    rec.r.x = xyz[0];
+    rec.r.y = xyz[1];
+    rec.r.z = xyz[2];
+    rec.r.valid = 1;
+    mw.r.disparity = disparity;
   }
   store_records(out, match, slot, rec, mw);
 }
-
-bool finite_pos(float v) { return v > 0.0f && v - v == 0.0f; }
 
 // The kernel asks for more dynamic LDS than a launch gets by default: the limit is raised once per device (hipFuncSetAttribute
 // applies to the current one).
@@ -346,17 +330,12 @@ extern "C" int unina_locate_stereo_async(const GpuDetection* d_dets, const int* 
                                          const unina_pinhole* cam, float baseline, const unina_stereo_params* p, unina_cone3d* d_out,
                                          unina_stereo_match* d_match, hipStream_t stream) {
   using namespace unina;
-  if (!d_dets || !d_count || !pair || !cam || !p || !d_out || !pair->left || !pair->right) return UNINA_ERR_ARG;
-  if (((uintptr_t)d_out & 15) || ((uintptr_t)d_dets & 15) || ((uintptr_t)d_match & 15) || ((uintptr_t)d_count & 3)) return UNINA_ERR_ARG;
-  if (pair->width < 1 || pair->height < 1 || pair->width > kLocateMaxDim || pair->height > kLocateMaxDim) return UNINA_ERR_ARG;
-  if (pair->pitch < pair->width) return UNINA_ERR_ARG;
-  if (!finite_pos(cam->fx) || !finite_pos(cam->fy) || !finite_pos(baseline) || !finite_pos(p->sx) || !finite_pos(p->sy))
-    return UNINA_ERR_ARG;
-  if (!locate_finite(cam->cx) || !locate_finite(cam->cy)) return UNINA_ERR_ARG;
-  if (!(p->shrink > 0.0f && p->shrink <= 1.0f)) return UNINA_ERR_ARG;
+  if (!record_io_ok(d_dets, d_count, d_out) || !pair || !p || !pair->left || !pair->right) return UNINA_ERR_ARG;
+  if (!plane_dims_ok(pair->width, pair->height) || !pinhole_ok(cam)) return UNINA_ERR_ARG;
+  if (!window_params_ok(p->sx, p->sy, p->shrink, p->min_depth, p->max_depth)) return UNINA_ERR_ARG;
+  if (((uintptr_t)d_match & 15) || pair->pitch < pair->width || !finite_pos(baseline)) return UNINA_ERR_ARG;
   if (p->max_side < 1 || p->max_side > kStereoMaxSide) return UNINA_ERR_ARG;
   if (p->max_mean_sad < 0 || p->max_mean_sad > 255 || p->uniqueness < 0 || p->uniqueness > 1000) return UNINA_ERR_ARG;
-  if (!(p->min_depth > 0.0f && p->min_depth < p->max_depth && locate_finite(p->max_depth))) return UNINA_ERR_ARG;
   const StereoRange range = stereo_range(cam->fx, baseline, p->min_depth, p->max_depth, pair->width);
   if (range.status != 0) return UNINA_ERR_ARG;
   if (stereo_prepare() != hipSuccess) return UNINA_ERR_HIP;
@@ -375,5 +354,5 @@ extern "C" int unina_locate_stereo_async(const GpuDetection* d_dets, const int* 
   a.max_mean_sad = p->max_mean_sad;
   a.uniqueness = p->uniqueness;
   hipLaunchKernelGGL(stereo_kernel, dim3(MAX_DETECTIONS), dim3(kStBlock), kStereoLds, stream, d_dets, d_count, a, d_out, d_match);
-  return hipGetLastError() == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+  return launch_status();
 }

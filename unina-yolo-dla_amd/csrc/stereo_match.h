@@ -30,7 +30,7 @@ UNINA_HD StereoRange stereo_range(float fx, float baseline, float min_depth, flo
   r.d_lo = 1;
   r.d_hi_all = 0;
   const float nearest = r.fxB / min_depth, farthest = r.fxB / max_depth;
-  if (!locate_finite(r.fxB) || !locate_finite(nearest)) return r;
+  if (!finite(r.fxB) || !finite(nearest)) return r;
   float lo = ceilf(farthest), hi = floorf(nearest);
   const float w = (float)width, last = (float)(width - 1);
   lo = lo < 1.0f ? 1.0f : lo;
@@ -71,12 +71,9 @@ UNINA_HD float stereo_disparity(int d_best, int d_lo, int d_hi, uint32_t cm, uin
   return (float)d_best + delta;
 }
 
-// xyz[0..2] = the box centre back-projected at Z = fxB / disparity: unina_locate_async's expressions
+// xyz[0..2] = the box centre back-projected at Z = fxB / disparity
 UNINA_HD void stereo_point(float fxB, float disparity, float uc, float vc, float fx, float fy, float cx, float cy, float* xyz) {
-  const float Z = fxB / disparity;
-  xyz[0] = ((uc - cx) * Z) / fx;
-  xyz[1] = ((vc - cy) * Z) / fy;
-  xyz[2] = Z;
+  locate_point(uc, vc, fxB / disparity, fx, fy, cx, cy, xyz);
 }
 
 }  // namespace unina

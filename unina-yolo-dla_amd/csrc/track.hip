@@ -35,7 +35,7 @@
 
 #include <new>
 
-#include "../../include/unina_mi355.h"
+#include "record_io.h"
 #include "track_math.h"
 #include "wave_block.h"
 
@@ -62,34 +62,18 @@ struct TrackArgs {
   int class_aware, confirm_hits, max_missed;
 };
 
-union TrackWords {
-  unina_track t;
-  uint4 q[2];
-};
-
-union HeaderWords {
-  unina_track_header h;
-  uint4 q[2];
-};
-
 __device__ __forceinline__ void block_add(bool flag, int* counter) {
   const unsigned long long m = __ballot(flag);
   if (((int)threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(counter, __popcll(m));
 }
 
 __global__ void __launch_bounds__(kTrkBlock) track_reset_kernel(unina_track_header* __restrict__ hdr, unina_track* __restrict__ tracks) {
-  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-  uint4* o = reinterpret_cast<uint4*>(tracks + threadIdx.x);
-  o[0] = zero;
-  o[1] = zero;
+  store_zero_record(tracks + threadIdx.x);
   if (threadIdx.x == 0) {
-    HeaderWords w;
-    w.q[0] = zero;
-    w.q[1] = zero;
-    w.h.next_id = 1;
-    uint4* h = reinterpret_cast<uint4*>(hdr);
-    h[0] = w.q[0];
-    h[1] = w.q[1];
+    RecordWords<unina_track_header> w;
+    zero_record(w);
+    w.r.next_id = 1;
+    store_record(hdr, w);
   }
 }
 
@@ -107,17 +91,12 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   int* const s_assign = reinterpret_cast<int*>(&s_best[1][0]);          // after the rounds: the assign words
 
   const int tid = (int)threadIdx.x;
-  int n = *d_count;
-  n = n < 0 ? 0 : (n > MAX_DETECTIONS ? MAX_DETECTIONS : n);
-  HeaderWords hw;
-  hw.q[0] = reinterpret_cast<const uint4*>(hdr)[0];
-  hw.q[1] = reinterpret_cast<const uint4*>(hdr)[1];
+  const int n = record_count(d_count);
+  const RecordWords<unina_track_header> hw = load_record(hdr);
 
   // ---- setup: the own slot, the own record
-  TrackWords tw;
-  tw.q[0] = reinterpret_cast<const uint4*>(tracks + tid)[0];
-  tw.q[1] = reinterpret_cast<const uint4*>(tracks + tid)[1];
-  bool live = tw.t.id != 0;
+  RecordWords<unina_track> tw = load_record(tracks + tid);
+  bool live = tw.r.id != 0;
 
   float px = 0.0f, py = 0.0f, pz = 0.0f, conf = 0.0f;
   int rcls = 0;
@@ -142,7 +121,7 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   if (tid < 4) s_cnt[tid] = 0;
   int n_list;
   const int k_own = block_rank<kTrkWaves>(live, s_wave, &n_list);   // the own slot's place in the live list
-  if (live) s_slot[k_own] = make_float4(tw.t.x, tw.t.y, tw.t.z, __int_as_float(tw.t.class_id));
+  if (live) s_slot[k_own] = make_float4(tw.r.x, tw.r.y, tw.r.z, __int_as_float(tw.r.class_id));
 
   // ---- rounds of mutual nearest neighbours
   bool active = usable && n_list > 0;
@@ -192,19 +171,18 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   if (live) {
     if (mj >= 0) {
       const float4 r = s_rec[mj];
-      tw.t.x = track_step(tw.t.x, a.alpha, r.x);
-      tw.t.y = track_step(tw.t.y, a.alpha, r.y);
-      tw.t.z = track_step(tw.t.z, a.alpha, r.z);
-      tw.t.confidence = r.w;
-      tw.t.class_id = s_rcls[mj];
-      tw.t.hits = track_hit(tw.t.hits);
-      tw.t.missed = 0;
-      s_assign[mj] = tw.t.id;
+      tw.r.x = track_step(tw.r.x, a.alpha, r.x);
+      tw.r.y = track_step(tw.r.y, a.alpha, r.y);
+      tw.r.z = track_step(tw.r.z, a.alpha, r.z);
+      tw.r.confidence = r.w;
+      tw.r.class_id = s_rcls[mj];
+      tw.r.hits = track_hit(tw.r.hits);
+      tw.r.missed = 0;
+      s_assign[mj] = tw.r.id;
     } else {
-      tw.t.missed = track_miss(tw.t.missed);
-      if (tw.t.missed > a.max_missed) {
-        tw.q[0] = make_uint4(0u, 0u, 0u, 0u);
-        tw.q[1] = tw.q[0];
+      tw.r.missed = track_miss(tw.r.missed);
+      if (tw.r.missed > a.max_missed) {
+        zero_record(tw);
         died = true;
         live = false;
       }
@@ -218,29 +196,28 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
   int n_wants, n_free;
   const int kb = block_rank<kTrkWaves>(wants, s_wave, &n_wants);
   const int kf = block_rank<kTrkWaves>(!live, s_wave, &n_free);
-  const int n_born = track_births_taken(n_wants, n_free, hw.h.next_id);
+  const int n_born = track_births_taken(n_wants, n_free, hw.r.next_id);
   if (wants && kb < n_born) {
     s_birth[kb] = tid;
-    s_assign[tid] = hw.h.next_id + kb;
+    s_assign[tid] = hw.r.next_id + kb;
   }
   __syncthreads();
   if (!live && kf < n_born) {
     const int j = s_birth[kf];
     const float4 r = s_rec[j];
-    tw.t.x = r.x;
-    tw.t.y = r.y;
-    tw.t.z = r.z;
-    tw.t.confidence = r.w;
-    tw.t.id = hw.h.next_id + kf;
-    tw.t.class_id = s_rcls[j];
-    tw.t.hits = 1;
-    tw.t.missed = 0;
+    tw.r.x = r.x;
+    tw.r.y = r.y;
+    tw.r.z = r.z;
+    tw.r.confidence = r.w;
+    tw.r.id = hw.r.next_id + kf;
+    tw.r.class_id = s_rcls[j];
+    tw.r.hits = 1;
+    tw.r.missed = 0;
     live = true;
   }
-  reinterpret_cast<uint4*>(tracks + tid)[0] = tw.q[0];
-  reinterpret_cast<uint4*>(tracks + tid)[1] = tw.q[1];
+  store_record(tracks + tid, tw);
   block_add(live, &s_cnt[2]);
-  block_add(live && tw.t.hits >= a.confirm_hits, &s_cnt[3]);
+  block_add(live && tw.r.hits >= a.confirm_hits, &s_cnt[3]);
   __syncthreads();
 
   if (assign) {
@@ -251,17 +228,16 @@ __global__ void __launch_bounds__(kTrkBlock) track_update_kernel(const GpuDetect
     }
   }
   if (tid == 0) {
-    HeaderWords o;
-    o.h.frame = (int)((unsigned)hw.h.frame + 1u);
-    o.h.n_live = s_cnt[2];
-    o.h.n_confirmed = s_cnt[3];
-    o.h.next_id = hw.h.next_id + n_born;
-    o.h.n_matched = s_cnt[0];
-    o.h.n_born = n_born;
-    o.h.n_died = s_cnt[1];
-    o.h.n_dropped = n_wants - n_born;
-    reinterpret_cast<uint4*>(hdr)[0] = o.q[0];
-    reinterpret_cast<uint4*>(hdr)[1] = o.q[1];
+    RecordWords<unina_track_header> o;
+    o.r.frame = (int)((unsigned)hw.r.frame + 1u);
+    o.r.n_live = s_cnt[2];
+    o.r.n_confirmed = s_cnt[3];
+    o.r.next_id = hw.r.next_id + n_born;
+    o.r.n_matched = s_cnt[0];
+    o.r.n_born = n_born;
+    o.r.n_died = s_cnt[1];
+    o.r.n_dropped = n_wants - n_born;
+    store_record(hdr, o);
   }
 }
 
@@ -270,7 +246,7 @@ unina_track* slots_of(unina_tracker* t) { return reinterpret_cast<unina_track*>(
 
 int launch_reset(unina_tracker* t, hipStream_t stream) {
   hipLaunchKernelGGL(track_reset_kernel, dim3(1), dim3(kTrkBlock), 0, stream, header_of(t), slots_of(t));
-  return hipGetLastError() == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+  return launch_status();
 }
 
 // allocates the table on first use and resets it on `stream`; *fresh tells the caller that this call did
@@ -324,11 +300,10 @@ extern "C" int unina_track_reset_async(unina_tracker_t* t, hipStream_t stream) {
 extern "C" int unina_track_update_async(unina_tracker_t* t, const GpuDetection* d_dets, const int* d_count, const unina_cone3d* d_cones,
                                         const unina_track_params* p, int* d_assign, hipStream_t stream) {
   using namespace unina;
-  if (!t || !d_dets || !d_count || !d_cones || !p) return UNINA_ERR_ARG;
-  if (((uintptr_t)d_dets & 15) || ((uintptr_t)d_cones & 15) || ((uintptr_t)d_count & 3) || ((uintptr_t)d_assign & 3)) return UNINA_ERR_ARG;
+  if (!t || !p || !record_io_ok(d_dets, d_count, d_cones) || ((uintptr_t)d_assign & 3)) return UNINA_ERR_ARG;
   for (int i = 0; i < 12; ++i)
-    if (!track_finite(p->pose[i])) return UNINA_ERR_ARG;
-  if (!(p->gate > 0.0f && track_finite(p->gate * p->gate))) return UNINA_ERR_ARG;   // a finite gate2 keeps every stored coordinate free of NaN
+    if (!unina::finite(p->pose[i])) return UNINA_ERR_ARG;
+  if (!(p->gate > 0.0f && unina::finite(p->gate * p->gate))) return UNINA_ERR_ARG;   // a finite gate2 keeps every stored coordinate free of NaN
   if (!(p->alpha > 0.0f && p->alpha <= 1.0f)) return UNINA_ERR_ARG;
   if (p->birth_confidence != p->birth_confidence) return UNINA_ERR_ARG;
   if (p->confirm_hits < 1 || p->max_missed < 0) return UNINA_ERR_ARG;
@@ -344,7 +319,7 @@ extern "C" int unina_track_update_async(unina_tracker_t* t, const GpuDetection* 
   a.max_missed = p->max_missed;
   hipLaunchKernelGGL(track_update_kernel, dim3(1), dim3(kTrkBlock), 0, stream, d_dets, d_count, d_cones, a, header_of(t), slots_of(t),
                      d_assign);
-  return hipGetLastError() == hipSuccess ? UNINA_OK : UNINA_ERR_HIP;
+  return launch_status();
 }
 
 extern "C" int unina_track_buffers(unina_tracker_t* t, const unina_track** d_tracks, const unina_track_header** d_header) {

@@ -9,11 +9,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define UNINA_TRACK_HD __host__ __device__ __forceinline__
-#else
-#define UNINA_TRACK_HD inline
-#endif
+#include "hd.h"
 
 namespace unina {
 
@@ -25,46 +21,44 @@ struct TrackPoint {
   int usable;   // 1: the cone is valid and the point is finite
 };
 
-UNINA_TRACK_HD bool track_finite(float v) { return v - v == 0.0f; }   // false for NaN and +-inf
-
-UNINA_TRACK_HD uint32_t track_bits(float v) {
+UNINA_HD uint32_t track_bits(float v) {
   uint32_t b;
   memcpy(&b, &v, 4);
   return b;
 }
 
 // camera frame -> tracking frame through the row-major 3 x 4 pose [R|t]
-UNINA_TRACK_HD TrackPoint track_point(const float* pose, float x, float y, float z, int valid) {
+UNINA_HD TrackPoint track_point(const float* pose, float x, float y, float z, int valid) {
   TrackPoint p;
   p.x = ((pose[0] * x + pose[1] * y) + pose[2] * z) + pose[3];
   p.y = ((pose[4] * x + pose[5] * y) + pose[6] * z) + pose[7];
   p.z = ((pose[8] * x + pose[9] * y) + pose[10] * z) + pose[11];
-  p.usable = (valid != 0 && track_finite(p.x) && track_finite(p.y) && track_finite(p.z)) ? 1 : 0;
+  p.usable = (valid != 0 && finite(p.x) && finite(p.y) && finite(p.z)) ? 1 : 0;
   return p;
 }
 
 // squared distance of a point to a track; never negative, NaN where an operand is not finite
-UNINA_TRACK_HD float track_d2(float px, float py, float pz, float tx, float ty, float tz) {
+UNINA_HD float track_d2(float px, float py, float pz, float tx, float ty, float tz) {
   const float dx = px - tx, dy = py - ty, dz = pz - tz;
   return (dx * dx + dy * dy) + dz * dz;
 }
 
-UNINA_TRACK_HD bool track_gated(float d2, float gate2) { return d2 <= gate2; }   // a NaN d2 fails
+UNINA_HD bool track_gated(float d2, float gate2) { return d2 <= gate2; }   // a NaN d2 fails
 
 // (d2, index) as one unsigned key: ascending keys are ascending (d2, index)
-UNINA_TRACK_HD uint64_t track_key(float d2, uint32_t index) { return ((uint64_t)track_bits(d2) << 32) | index; }
+UNINA_HD uint64_t track_key(float d2, uint32_t index) { return ((uint64_t)track_bits(d2) << 32) | index; }
 
 // one coordinate of a matched slot: the dx of the gate, then the step
-UNINA_TRACK_HD float track_step(float t, float alpha, float p) {
+UNINA_HD float track_step(float t, float alpha, float p) {
   const float d = p - t;
   return t + alpha * d;
 }
 
-UNINA_TRACK_HD int track_hit(int hits) { return hits < kTrackMaxHits ? hits + 1 : kTrackMaxHits; }
-UNINA_TRACK_HD int track_miss(int missed) { return missed < INT_MAX ? missed + 1 : INT_MAX; }
+UNINA_HD int track_hit(int hits) { return hits < kTrackMaxHits ? hits + 1 : kTrackMaxHits; }
+UNINA_HD int track_miss(int missed) { return missed < INT_MAX ? missed + 1 : INT_MAX; }
 
 // how many of `births` birth candidates are taken: the first m, the rest are dropped
-UNINA_TRACK_HD int track_births_taken(int births, int free_slots, int next_id) {
+UNINA_HD int track_births_taken(int births, int free_slots, int next_id) {
   const int ids = INT_MAX - next_id;   // next_id >= 1
   int m = births < free_slots ? births : free_slots;
   return m < ids ? m : ids;

@@ -58,9 +58,8 @@ class Frame(C.Structure):
     @classmethod
     def from_tensors(cls, fmt: int, width: int, height: int, plane, pitch: int, uv=None, uv_pitch: int = 0) -> "Frame":
         """From uint8 CUDA tensors (or raw device addresses). The tensors must outlive the calls the frame is handed to."""
-        addr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
         f = cls(int(fmt), int(width), int(height))
-        f.plane[0], f.plane[1] = addr(plane), addr(uv)
+        f.plane[0], f.plane[1] = _addr(plane), _addr(uv)
         f.pitch[0], f.pitch[1] = int(pitch), int(uv_pitch)
         return f
 
@@ -328,6 +327,40 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _addr(t):
+    """_ptr for an argument that may also be a raw device address already."""
+    return t if isinstance(t, int) else _ptr(t)
+
+
+def _raise_on(rc: int, what: str) -> None:
+    if rc:
+        raise EngineError(f"{what} failed [{ERRORS.get(rc, rc)}]")
+
+
+def det_buffer_ptrs(det_buf):
+    """(records, count): the device addresses inside Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
+    base = det_buf.data_ptr()
+    return base + 32, base
+
+
+def read_records(stream, *pairs):
+    """Synchronises `stream`; each (uint8 CUDA tensor, dtype) pair comes back as a host array of records."""
+    torch = _torch()
+    s = torch.cuda.current_stream() if stream is None else stream
+    if not isinstance(s, int):
+        with torch.cuda.stream(s):
+            hosts = [t.cpu() for t, _ in pairs]
+    else:
+        torch.cuda.synchronize()
+        hosts = [t.cpu() for t, _ in pairs]
+    return tuple(h.numpy().view(dtype).copy() for h, (_, dtype) in zip(hosts, pairs))
+
+
+def clamp_count(count, *arrays) -> int:
+    """The device count word as the kernels read it, for the numpy twins: 0 .. MAX_DETECTIONS, and no more than the arrays hold."""
+    return min(max(int(count), 0), MAX_DETECTIONS, *(len(a) for a in arrays))
+
+
 class Engine:
     """One engine handle on one GPU. Use two handles to keep two frames in flight."""
 
@@ -445,8 +478,7 @@ class Engine:
         if norm is None:
             norm = self.L.create_norm_params_imagenet()
         if out is not None:
-            base = out.data_ptr()
-            self._check(getattr(self.L, symbol + "_async")(self.h, *lead, C.byref(norm), *tail, base + 32, base, _stream_ptr(stream)))
+            self._check(getattr(self.L, symbol + "_async")(self.h, *lead, C.byref(norm), *tail, *det_buffer_ptrs(out), _stream_ptr(stream)))
             return out
         host = np.zeros(MAX_DETECTIONS, dtype=DET_DTYPE)
         n = C.c_int()
@@ -541,9 +573,8 @@ class Engine:
             assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
         assert slots.numel() >= len(tiles) * 8 * MAX_DETECTIONS and counts.numel() >= len(tiles)
         out = self._det_buf if out is None else out
-        base = out.data_ptr()
         self._check(self.L.unina_merge_tiles_async(self.h, slots.data_ptr(), counts.data_ptr(), _tile_array(tiles), len(tiles),
-                                                   merge_iou, base + 32, base, _stream_ptr(stream)))
+                                                   merge_iou, *det_buffer_ptrs(out), _stream_ptr(stream)))
         return out
 
     def infer_async(self, images, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1,
@@ -553,15 +584,12 @@ class Engine:
         if images is not None:
             self.bind_images(images)
         out = self._det_buf if out is None else out
-        base = out.data_ptr()
-        self._check(self.L.unina_infer_async(self.h, None, conf_thr, iou_thr, conformal_q, base + 32, base,
-                                             _stream_ptr(stream)))
+        self._check(self.L.unina_infer_async(self.h, None, conf_thr, iou_thr, conformal_q, *det_buffer_ptrs(out), _stream_ptr(stream)))
         return out
 
     def postprocess(self, conf_thr: float = 0.5, iou_thr: float = 0.45, conformal_q: float = 0.1, stream=None):
         """Decode + NMS on whatever the six output tensors currently hold (synchronous)."""
-        base = self._det_buf.data_ptr()
-        self._check(self.L.unina_postprocess_async(self.h, conf_thr, iou_thr, conformal_q, base + 32, base,
+        self._check(self.L.unina_postprocess_async(self.h, conf_thr, iou_thr, conformal_q, *det_buffer_ptrs(self._det_buf),
                                                    _stream_ptr(stream)))
         return self.unpack(self._det_buf)
 
@@ -951,12 +979,8 @@ class DeviceEval:
             raise EngineError(f"unina_eval_create failed [{ERRORS.get(rc, rc)}] (num_classes={num_classes})")
         self._labels = []      # label tensors of the updates in flight (kept until the next read / reset)
 
-    def _check(self, rc: int, what: str):
-        if rc:
-            raise EngineError(f"{what} failed [{ERRORS.get(rc, rc)}]")
-
     def reset(self, stream=None) -> None:
-        self._check(self.L.unina_eval_reset_async(self.h, _stream_ptr(stream)), "unina_eval_reset_async")
+        _raise_on(self.L.unina_eval_reset_async(self.h, _stream_ptr(stream)), "unina_eval_reset_async")
 
     def update(self, det_buf, labels, params: EvalParams, what: int, stream=None) -> None:
         """One image, asynchronous. det_buf: int32 CUDA tensor as infer_async's (word 0 = count, records from word 8);
@@ -966,18 +990,17 @@ class DeviceEval:
             labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float64).reshape(-1, 5)).to(det_buf.device)
         assert labels.is_cuda and labels.dtype == torch.float64 and labels.is_contiguous()
         self._labels.append(labels)
-        base = det_buf.data_ptr()
         n = labels.shape[0]
-        self._check(self.L.unina_eval_update_async(self.h, base + 32, base, labels.data_ptr() if n else None, n, C.byref(params),
-                                                   what, _stream_ptr(stream)), f"unina_eval_update_async ({n} labels)")
+        _raise_on(self.L.unina_eval_update_async(self.h, *det_buffer_ptrs(det_buf), labels.data_ptr() if n else None, n, C.byref(params),
+                                                 what, _stream_ptr(stream)), f"unina_eval_update_async ({n} labels)")
 
     def read(self, stream=None):
         """Synchronises; returns (EvalResult, scores float64 [n], rows EVAL_ROW_DTYPE [m]) -- the lists as far as they fit."""
         res = EvalResult()
         scores = np.empty(self.max_scores, dtype=np.float64)
         rows = np.zeros(self.max_rows, dtype=EVAL_ROW_DTYPE)
-        self._check(self.L.unina_eval_read(self.h, C.byref(res), scores.ctypes.data, scores.size, rows.ctypes.data, rows.size,
-                                           _stream_ptr(stream)), "unina_eval_read")
+        _raise_on(self.L.unina_eval_read(self.h, C.byref(res), scores.ctypes.data, scores.size, rows.ctypes.data, rows.size,
+                                         _stream_ptr(stream)), "unina_eval_read")
         self._labels.clear()
         return res, scores[:min(res.n_scores, self.max_scores)].copy(), rows[:min(res.n_rows, self.max_rows)].copy()
 

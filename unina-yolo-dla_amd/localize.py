@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, MAX_DETECTIONS, STEREO_MATCH_DTYPE, STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE,
-                     Depth, EngineError, ERRORS, LocateParams, Pinhole, StereoPair, StereoParams, _stream_ptr, _torch, load_library)
+                     Depth, EngineError, LocateParams, Pinhole, StereoPair, StereoParams, _addr, _raise_on, _stream_ptr, _torch,
+                     clamp_count, det_buffer_ptrs, load_library, read_records)
 
 F = np.float32
 
@@ -69,6 +70,12 @@ def window_numpy(box, sx, sy, shrink, width: int, height: int, max_side: int):
                 "rows": ay[3], "n_samples": ax[3] * ay[3], "uc": uc, "vc": vc}
 
 
+def point_numpy(uc, vc, Z, fx, fy, cx, cy):
+    """csrc/locate_window.h locate_point: (x, y, z), the pixel (uc, vc) back-projected through the pinhole at depth Z; all
+    arguments np.float32 scalars or arrays."""
+    return ((uc - cx) * Z) / fx, ((vc - cy) * Z) / fy, Z
+
+
 def locate_numpy(dets, count: int, depth: np.ndarray, fmt: int, unit, cam, params) -> np.ndarray:
     """dets: DET_DTYPE records; count: as the device word (clamped to 0..MAX_DETECTIONS, and to len(dets)); depth: [H, W]
     float32 (DEPTH_F32) or uint16 (DEPTH_U16). Returns MAX_DETECTIONS CONE3D_DTYPE records, zero behind the count."""
@@ -80,7 +87,7 @@ def locate_numpy(dets, count: int, depth: np.ndarray, fmt: int, unit, cam, param
     unit, lo, hi = F(unit), F(p.min_depth), F(p.max_depth)
     fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
     out = np.zeros(MAX_DETECTIONS, dtype=CONE3D_DTYPE)
-    n = min(max(int(count), 0), MAX_DETECTIONS, len(dets))
+    n = clamp_count(count, dets)
     with np.errstate(all="ignore"):
         for i in range(n):
             d = dets[i]
@@ -97,9 +104,7 @@ def locate_numpy(dets, count: int, depth: np.ndarray, fmt: int, unit, cam, param
             r["u"], r["v"], r["n_samples"], r["n_valid"] = w["uc"], w["vc"], raw.size, valid_raw.size
             if valid_raw.size >= max(1, p.min_valid):
                 Z = F(np.sort(valid_raw)[(valid_raw.size - 1) // 2]) * unit    # the lower median, an actual sample
-                r["x"] = ((w["uc"] - cx) * Z) / fx
-                r["y"] = ((w["vc"] - cy) * Z) / fy
-                r["z"] = Z
+                r["x"], r["y"], r["z"] = point_numpy(w["uc"], w["vc"], Z, fx, fy, cx, cy)
                 r["valid"] = 1
     return out
 
@@ -137,33 +142,22 @@ class DeviceLocator:
     def update_async(self, d_dets, d_count, depth_tensor, unit, cam, params, fmt=None, width=None, stream=None):
         """Enqueues the launch; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and
         the count, as the _async calls write them. Returns the output tensor (bytes; read() gives the records)."""
-        addr = lambda t: t if isinstance(t, int) else t.data_ptr()   # noqa: E731
         depth = depth_tensor if isinstance(depth_tensor, Depth) else self.describe(depth_tensor, fmt, width, unit)
         cam, p = as_pinhole(cam), as_params(params)
         self._keep = depth_tensor
-        rc = self.L.unina_locate_async(addr(d_dets), addr(d_count), C.byref(depth), C.byref(cam), C.byref(p), self.out.data_ptr(),
-                                       _stream_ptr(stream))
-        if rc:
-            raise EngineError(f"unina_locate_async failed [{ERRORS.get(rc, rc)}]")
+        _raise_on(self.L.unina_locate_async(_addr(d_dets), _addr(d_count), C.byref(depth), C.byref(cam), C.byref(p), self.out.data_ptr(),
+                                            _stream_ptr(stream)), "unina_locate_async")
         return self.out
 
     def update_from_buffer(self, det_buf, depth_tensor, unit, cam, params, fmt=None, width=None, stream=None):
         """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
-        base = det_buf.data_ptr()
-        return self.update_async(base + 32, base, depth_tensor, unit, cam, params, fmt, width, stream)
+        return self.update_async(*det_buffer_ptrs(det_buf), depth_tensor, unit, cam, params, fmt, width, stream)
 
     def read(self, stream=None) -> np.ndarray:
         """Synchronises `stream`; returns all MAX_DETECTIONS CONE3D_DTYPE records (zero behind the count)."""
-        torch = _torch()
-        s = torch.cuda.current_stream() if stream is None else stream
-        if not isinstance(s, int):
-            with torch.cuda.stream(s):
-                host = self.out.cpu()
-        else:
-            torch.cuda.synchronize()
-            host = self.out.cpu()
+        cones, = read_records(stream, (self.out, CONE3D_DTYPE))
         self._keep = None
-        return host.numpy().view(CONE3D_DTYPE).copy()
+        return cones
 
 
 # ---------------------------------------------------------------- from a stereo pair
@@ -245,8 +239,7 @@ def stereo_disparity_numpy(d_best: int, d_lo: int, d_hi: int, cm: int, c0: int, 
 
 def stereo_point_numpy(fxB, disparity, uc, vc, fx, fy, cx, cy):
     """(x, y, z): the box centre back-projected at Z = fxB / disparity; all arguments np.float32."""
-    Z = fxB / disparity
-    return ((uc - cx) * Z) / fx, ((vc - cy) * Z) / fy, Z
+    return point_numpy(uc, vc, fxB / disparity, fx, fy, cx, cy)
 
 
 def locate_stereo_numpy(dets, count: int, left: np.ndarray, right: np.ndarray, cam, baseline, params):
@@ -262,7 +255,7 @@ def locate_stereo_numpy(dets, count: int, left: np.ndarray, right: np.ndarray, c
     fxB, d_lo, d_hi_all = stereo_range_numpy(cam.fx, baseline, p.min_depth, p.max_depth, width)
     cones = np.zeros(MAX_DETECTIONS, dtype=CONE3D_DTYPE)
     matches = np.zeros(MAX_DETECTIONS, dtype=STEREO_MATCH_DTYPE)
-    n = min(max(int(count), 0), MAX_DETECTIONS, len(dets))
+    n = clamp_count(count, dets)
     with np.errstate(all="ignore"):
         for i in range(n):
             d = dets[i]
@@ -315,34 +308,24 @@ class DeviceStereoLocator:
     def update_async(self, d_dets, d_count, pair, cam, baseline, params, stream=None, match=True):
         """Enqueues the launch; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and
         the count; pair: a StereoPair or (left, right) tensors; match=False passes d_match = NULL. Returns the cone tensor."""
-        addr = lambda t: t if isinstance(t, int) else t.data_ptr()   # noqa: E731
         self._keep = pair
         desc = pair if isinstance(pair, StereoPair) else self.describe(*pair)
         cam, p = as_pinhole(cam), as_stereo_params(params)
-        rc = self.L.unina_locate_stereo_async(addr(d_dets), addr(d_count), C.byref(desc), C.byref(cam), float(baseline), C.byref(p),
-                                              self.out.data_ptr(), self.match.data_ptr() if match else None, _stream_ptr(stream))
-        if rc:
-            raise EngineError(f"unina_locate_stereo_async failed [{ERRORS.get(rc, rc)}]")
+        _raise_on(self.L.unina_locate_stereo_async(_addr(d_dets), _addr(d_count), C.byref(desc), C.byref(cam), float(baseline), C.byref(p),
+                                                   self.out.data_ptr(), self.match.data_ptr() if match else None, _stream_ptr(stream)),
+                  "unina_locate_stereo_async")
         return self.out
 
     def update_from_buffer(self, det_buf, left, right, cam, baseline, params, stream=None, match=True):
         """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
-        base = det_buf.data_ptr()
-        return self.update_async(base + 32, base, (left, right), cam, baseline, params, stream, match)
+        return self.update_async(*det_buffer_ptrs(det_buf), (left, right), cam, baseline, params, stream, match)
 
     def read(self, stream=None):
         """Synchronises `stream`; returns (cones, matches): all MAX_DETECTIONS records of each (zero behind the count)."""
-        torch = _torch()
-        s = torch.cuda.current_stream() if stream is None else stream
-        if not isinstance(s, int):
-            with torch.cuda.stream(s):
-                cones, matches = self.out.cpu(), self.match.cpu()
-        else:
-            torch.cuda.synchronize()
-            cones, matches = self.out.cpu(), self.match.cpu()
+        records = read_records(stream, (self.out, CONE3D_DTYPE), (self.match, STEREO_MATCH_DTYPE))
         self._keep = None
-        return cones.numpy().view(CONE3D_DTYPE).copy(), matches.numpy().view(STEREO_MATCH_DTYPE).copy()
+        return records
 
 
-__all__ = ["locate_numpy", "window_numpy", "DeviceLocator", "as_pinhole", "as_params", "locate_stereo_numpy", "make_stereo_params",
+__all__ = ["locate_numpy", "window_numpy", "point_numpy", "DeviceLocator", "as_pinhole", "as_params", "locate_stereo_numpy", "make_stereo_params",
            "as_stereo_params", "stereo_range_numpy", "DeviceStereoLocator"]

@@ -10,7 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import (CONE3D_DTYPE, DET_DTYPE, MAX_DETECTIONS, EngineError, ERRORS, TrackParams, _stream_ptr, _torch, load_library)
+from .engine import (CONE3D_DTYPE, DET_DTYPE, MAX_DETECTIONS, TrackParams, _addr, _raise_on, _stream_ptr, _torch, clamp_count,
+                     det_buffer_ptrs, load_library)
 
 F = np.float32
 TRACK_MAX = 1024                      # UNINA_TRACK_MAX
@@ -73,7 +74,7 @@ def update_numpy(state: dict, dets, count: int, cones, params):
         raise ValueError("gate and gate * gate must be finite and positive")
     hdr, tr = state["header"].copy(), state["tracks"].copy()
     assign = np.zeros(MAX_DETECTIONS, dtype=np.int32)
-    n = min(max(int(count), 0), MAX_DETECTIONS, len(dets), len(cones))
+    n = clamp_count(count, dets, cones)
     dets, cones = np.asarray(dets)[:n], np.asarray(cones)[:n]
     with np.errstate(all="ignore"):
         x, y, z = cones["x"], cones["y"], cones["z"]
@@ -138,14 +139,8 @@ class DeviceTracker:
         torch = _torch()
         self.L = load_library()
         self.h = C.c_void_p()
-        rc = self.L.unina_track_create(device, C.byref(self.h))
-        if rc:
-            raise EngineError(f"unina_track_create failed [{ERRORS.get(rc, rc)}]")
+        _raise_on(self.L.unina_track_create(device, C.byref(self.h)), "unina_track_create")
         self.assign = torch.zeros(MAX_DETECTIONS, dtype=torch.int32, device=f"cuda:{device}")
-
-    def _check(self, rc, what):
-        if rc:
-            raise EngineError(f"{what} failed [{ERRORS.get(rc, rc)}]")
 
     def close(self):
         if self.h:
@@ -155,35 +150,33 @@ class DeviceTracker:
     __del__ = close
 
     def reset(self, stream=None):
-        self._check(self.L.unina_track_reset_async(self.h, _stream_ptr(stream)), "unina_track_reset_async")
+        _raise_on(self.L.unina_track_reset_async(self.h, _stream_ptr(stream)), "unina_track_reset_async")
 
     def update_async(self, d_dets, d_count, d_cones, params, stream=None, assign=None):
         """Enqueues the launch; nothing is synchronised. d_dets / d_count / d_cones: device addresses (or tensors) of the
         records, the count and the unina_cone3d points. assign: an int32 tensor of MAX_DETECTIONS words (or a device address)
         in place of the tracker's own, or False for none. Returns the assign tensor."""
-        addr = lambda t: t if isinstance(t, int) else t.data_ptr()   # noqa: E731
         p = as_params(params)
         out = self.assign if assign is None else assign
-        self._check(self.L.unina_track_update_async(self.h, addr(d_dets), addr(d_count), addr(d_cones), C.byref(p),
-                                                    None if out is False else addr(out), _stream_ptr(stream)), "unina_track_update_async")
+        _raise_on(self.L.unina_track_update_async(self.h, _addr(d_dets), _addr(d_count), _addr(d_cones), C.byref(p),
+                                                  None if out is False else _addr(out), _stream_ptr(stream)), "unina_track_update_async")
         return out
 
     def update_from_buffer(self, det_buf, locator_out, params, stream=None, assign=None):
         """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8) and DeviceLocator's output."""
-        base = det_buf.data_ptr()
-        return self.update_async(base + 32, base, locator_out, params, stream, assign)
+        return self.update_async(*det_buffer_ptrs(det_buf), locator_out, params, stream, assign)
 
     def buffers(self):
         """(device address of the slots, device address of the header) for a consumer that stays on the GPU."""
         tracks, header = C.c_void_p(), C.c_void_p()
-        self._check(self.L.unina_track_buffers(self.h, C.byref(tracks), C.byref(header)), "unina_track_buffers")
+        _raise_on(self.L.unina_track_buffers(self.h, C.byref(tracks), C.byref(header)), "unina_track_buffers")
         return tracks.value, header.value
 
     def read(self, stream=None):
         """Synchronises `stream`; returns (header, tracks): one TRACK_HEADER_DTYPE record and all TRACK_MAX TRACK_DTYPE slots."""
         header, tracks = np.zeros(1, dtype=TRACK_HEADER_DTYPE), np.zeros(TRACK_MAX, dtype=TRACK_DTYPE)
-        self._check(self.L.unina_track_read(self.h, header.ctypes.data, tracks.ctypes.data, TRACK_MAX, _stream_ptr(stream)),
-                    "unina_track_read")
+        _raise_on(self.L.unina_track_read(self.h, header.ctypes.data, tracks.ctypes.data, TRACK_MAX, _stream_ptr(stream)),
+                  "unina_track_read")
         return header, tracks
 
 
