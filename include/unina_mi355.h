@@ -602,6 +602,66 @@ int unina_locate_stereo_async(const GpuDetection *d_dets, const int *d_count, co
                               const unina_stereo_params *p, unina_cone3d *d_out,
                               unina_stereo_match *d_match /* MAX_DETECTIONS, 16-byte aligned, or NULL */, hipStream_t stream);
 
+/* ------------------------------------------------------------------ 3-D localisation from a LiDAR sweep (for a vehicle with one
+ * camera and a LiDAR: no depth map, no second image)
+ * Kept records + a point cloud on the device + the LiDAR -> camera extrinsic + the camera's intrinsics -> the same unina_cone3d
+ * records as unina_locate_async writes, so unina_track_update_async goes behind it unchanged. One call enqueues everything
+ * (csrc/lidar.hip: project and count, scan, scatter, select) on the caller's stream behind whichever _async call produced the
+ * records; nothing is synchronised, neither the records nor the cloud cross to the host. localize.locate_lidar_numpy is the
+ * definition, decision for decision and bit for bit (localize.project_lidar_numpy for the per-point half). Everything is fp32,
+ * each operation rounded once in the order written, never contracted; the divide is correctly rounded; every decision after the
+ * projection is on integers.
+ *   point    (x, y, z) = the first three float32 of each `stride`-byte point; the rest of a point is never read.
+ *            xc = ((r00 * x + r01 * y) + r02 * z) + t0, yc and zc from rows 1 and 2 of lidar_to_cam ([R|t], row-major 3 x 4,
+ *            LiDAR frame -> camera frame: the pose convention of unina_track_params);
+ *            u = (fx * xc) / zc + cx, v = (fy * yc) / zc + cy (image pixels; pixel i covers [i, i + 1))
+ *            PROJECTABLE iff xc, yc, zc are finite, zc > 0, 0 <= u < (float)width and 0 <= v < (float)height (a NaN fails).
+ *            pixel = ((int)u, (int)v); key = the bits of zc where min_depth <= zc <= max_depth, else 0. min_depth > 0, so a
+ *            non-zero key orders as an unsigned integer exactly as its depth does. A point that is not projectable contributes
+ *            nothing (its unina_lidar_pixel is all-zero)
+ *   count    as unina_locate_async: *d_count clamped to 0..MAX_DETECTIONS on the device; the slots at and beyond it are all-zero
+ *   window   exactly unina_locate_async's window on a width x height map, with max_side = UNINA_LIDAR_MAX_DIM: every covered
+ *            pixel u0..u1 x v0..v1 counts (stride 1). An empty window writes the all-zero record
+ *   members  the projectable points whose pixel lies in u0..u1 x v0..v1; a point may be a member of several records.
+ *            n_samples = the number of members, n_valid = the number of members with key != 0
+ *   depth    the LOWER MEDIAN of the valid keys (np.sort(keys)[(n_valid - 1) // 2]): an actual point's zc, found by counting, so
+ *            it does not depend on the order of the cloud
+ *   record   valid = n_valid >= max(1, min_valid); valid: x = ((uc - cx) * Z) / fx, y = ((vc - cy) * Z) / fy, z = Z (the
+ *            expressions of unina_locate_async), otherwise x = y = z = 0; u = uc, v = vc always
+ * Integer counters only (no float atomics): two runs, and any permutation of the cloud, give identical unina_cone3d bytes.
+ * NOT covered: ground removal, motion de-skew, time alignment of sweep and frame, lens distortion (the pinhole is the rectified
+ * image's), clustering -- the median of what falls in the shrunk box is the whole model. */
+#define UNINA_LIDAR_MAX_DIM    16384       /* width, height */
+#define UNINA_LIDAR_MAX_POINTS (1 << 22)
+typedef struct { int n_points, stride; const void *points; } unina_cloud;   /* device; xyz float32 first in each point */
+typedef struct { float sx, sy, shrink, min_depth, max_depth; int min_valid; } unina_lidar_params;   /* sx, sy: record -> image pixels */
+typedef struct { int u, v; uint32_t key; int projectable; } unina_lidar_pixel;   /* 16 bytes, point order; not projectable = all zero */
+typedef struct unina_lidar unina_lidar_t;
+
+/* Host only: no HIP call. The device workspace (bounded by max_points and by the 32 x 32-pixel cells of max_width x max_height,
+ * and by nothing else: no legal input can overflow a list) is allocated by the first unina_locate_lidar_async, on that call's
+ * stream, which then fails with UNINA_ERR_HIP where there is no device. One handle serves any sequence of clouds and image sizes
+ * within its limits; calls on one handle belong on one stream, or are ordered by the caller.
+ * UNINA_ERR_ARG: NULL out, negative device_id, max_points outside 1..UNINA_LIDAR_MAX_POINTS, max_width or max_height outside
+ * 1..UNINA_LIDAR_MAX_DIM. */
+int unina_lidar_create(int device_id, int max_points, int max_width, int max_height, unina_lidar_t **out);
+/* Waits for the device, frees. NULL is a no-op. */
+void unina_lidar_destroy(unina_lidar_t *l);
+/*   d_dets / d_count : device, MAX_DETECTIONS records (16-byte aligned) / one int, as the _async calls write them
+ *   cloud->points    : device, n_points * stride bytes, 4-byte aligned (read 16 bytes at a time where the base and the stride
+ *                      allow it); d_out : device, MAX_DETECTIONS unina_cone3d, 16-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer (points may be NULL only when n_points == 0); d_dets or d_out not 16-byte
+ * aligned, or d_count not 4-byte aligned; n_points outside 0..max_points; stride < 12 or not a multiple of 4, or points not
+ * 4-byte aligned; width or height outside 1..max_width / 1..max_height; a non-finite element of lidar_to_cam; fx, fy, sx or sy
+ * not finite and positive; cx or cy not finite; shrink outside (0, 1]; not 0 < min_depth < max_depth < inf; min_valid < 0.
+ * n_points == 0 is legal: every non-empty window gets n_samples = 0 and valid = 0, with u and v set. */
+int unina_locate_lidar_async(unina_lidar_t *l, const GpuDetection *d_dets, const int *d_count, const unina_cloud *cloud,
+                             const float lidar_to_cam[12], const unina_pinhole *cam, int width, int height,
+                             const unina_lidar_params *p, unina_cone3d *d_out, hipStream_t stream);
+/* Device address of the per-point result of the last call (n_points unina_lidar_pixel, in point order), for a consumer that
+ * stays on the GPU or a test; read it behind the call on its stream. UNINA_ERR_STATE before the first unina_locate_lidar_async. */
+int unina_lidar_buffers(unina_lidar_t *l, const unina_lidar_pixel **d_pixels);
+
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the
  * device: stable ids, smoothed positions, hit and miss counts. One launch per frame (csrc/track.hip: one workgroup of 1024

@@ -16,13 +16,14 @@
 //            histograms in LDS (four passes for f32, two for u16). Each wave adds into a histogram of its own (ds_add_u32
 //            without return; a flat region of the map sends every lane of a wave to one bin, and that serialisation is then
 //            not multiplied by four); wave 0 sums the four, scans the 256 bins with shuffles and publishes the bin that
-//            holds the rank. The first pass keeps the keys in LDS when the window has at most kCache samples; the later
-//            passes read them there, and re-read the map (L2) for larger windows.
+//            holds the rank (csrc/radix_select.h). The first pass keeps the keys in LDS when the window has at most kCache
+//            samples; the later passes read them there, and re-read the map (L2) for larger windows.
 // 256 workgroups of 256 threads: one per CU, 36 KB of LDS each, so occupancy is no concern; a frame with ~500 records
 // costs one small launch.
 #include <hip/hip_runtime.h>
 
 #include "locate_checks.h"
+#include "radix_select.h"
 
 namespace unina {
 namespace {
@@ -30,7 +31,7 @@ namespace {
 constexpr int kWave = 64;
 constexpr int kLocWaves = 4;
 constexpr int kLocBlock = kLocWaves * kWave;
-constexpr int kBins = 256;
+constexpr int kBins = kRadixBins;
 constexpr int kCache = 8192;   // keys of one window kept in LDS between the passes (32 KB)
 
 static_assert(MAX_DETECTIONS % kLocWaves == 0, "slots per workgroup");
@@ -152,42 +153,7 @@ __global__ void __launch_bounds__(kLocBlock) locate_kernel(const GpuDetection* _
         if (key != 0u && ((key ^ prefix) & himask) == 0u) atomicAdd(&s_hist[wave][(key >> shift) & (kBins - 1)], 1u);
       }
       __syncthreads();
-      if (wave == 0) {
-        // lane l owns bins 4 l .. 4 l + 3 of the summed histogram
-        uint32_t c[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          c[j] = 0u;
-#pragma unroll
-          for (int v = 0; v < kLocWaves; ++v) c[j] += s_hist[v][4 * lane + j];
-        }
-        const uint32_t mine = c[0] + c[1] + c[2] + c[3];
-        uint32_t incl = mine;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-          const uint32_t up = __shfl_up(incl, o, kWave);
-          if (lane >= o) incl += up;
-        }
-        const uint32_t total = __shfl(incl, kWave - 1, kWave);
-        uint32_t want = (uint32_t)k;
-        if (first) {
-          want = total ? (total - 1u) / 2u : 0u;
-          if (lane == 0) s_sel[2] = (int)total;
-        }
-        uint32_t excl = incl - mine;
-        if (total != 0u && excl <= want && want < incl) {   // exactly one lane
-          int bin = 4 * lane;
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            if (bin == 4 * lane + j && want >= excl + c[j]) {
-              excl += c[j];
-              ++bin;
-            }
-          }
-          s_sel[0] = bin;
-          s_sel[1] = (int)(want - excl);
-        }
-      }
+      if (wave == 0) radix_pick<kLocWaves>(s_hist, lane, first, k, s_sel);
       __syncthreads();
       if (first) n_valid = s_sel[2];
       const int need = a.min_valid > 1 ? a.min_valid : 1;

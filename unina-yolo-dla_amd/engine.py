@@ -122,6 +122,22 @@ class StereoParams(C.Structure):
                 ("max_side", C.c_int), ("max_mean_sad", C.c_int), ("uniqueness", C.c_int)]
 
 
+LIDAR_MAX_DIM, LIDAR_MAX_POINTS = 16384, 1 << 22   # include/unina_mi355.h UNINA_LIDAR_*
+LIDAR_PIXEL_DTYPE = np.dtype([("u", "<i4"), ("v", "<i4"), ("key", "<u4"), ("projectable", "<i4")])   # unina_lidar_pixel
+assert LIDAR_PIXEL_DTYPE.itemsize == 16
+
+
+class Cloud(C.Structure):
+    """unina_cloud: n_points points of `stride` bytes on the device, float32 x, y, z first in each."""
+    _fields_ = [("n_points", C.c_int), ("stride", C.c_int), ("points", C.c_void_p)]
+
+
+class LidarParams(C.Structure):
+    """unina_lidar_params."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float), ("shrink", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("min_valid", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -156,6 +172,7 @@ ABI_SYMBOLS = [
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
     "unina_locate_async", "unina_locate_stereo_async",
+    "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -269,6 +286,13 @@ def load_library() -> C.CDLL:
     L.unina_locate_async.argtypes = [vp, vp, C.POINTER(Depth), C.POINTER(Pinhole), C.POINTER(LocateParams), vp, vp]
     # 3-D localisation from a stereo pair (csrc/stereo.hip)
     L.unina_locate_stereo_async.argtypes = [vp, vp, C.POINTER(StereoPair), C.POINTER(Pinhole), cf, C.POINTER(StereoParams), vp, vp, vp]
+    # 3-D localisation from a LiDAR sweep (csrc/lidar.hip)
+    L.unina_lidar_create.argtypes = [ci, ci, ci, ci, C.POINTER(vp)]
+    L.unina_lidar_destroy.argtypes = [vp]
+    L.unina_lidar_destroy.restype = None
+    L.unina_locate_lidar_async.argtypes = [vp, vp, vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(Pinhole), ci, ci, C.POINTER(LidarParams),
+                                           vp, vp]
+    L.unina_lidar_buffers.argtypes = [vp, C.POINTER(vp)]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]

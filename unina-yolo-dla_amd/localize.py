@@ -1,10 +1,12 @@
 """Detections lifted to 3-D cone positions from a depth map (include/unina_mi355.h "3-D localisation") or from a rectified
-stereo pair ("3-D localisation from a stereo pair").
+stereo pair ("3-D localisation from a stereo pair"), or from a LiDAR sweep ("3-D localisation from a LiDAR sweep").
 
 ``locate_numpy`` is the DEFINITION: fp32 scalars throughout, one rounding per operation, in the order the header states;
 csrc/locate.hip (through ``DeviceLocator``) returns its bytes. ``window_numpy`` is the twin of csrc/locate_window.h.
 ``locate_stereo_numpy`` is the definition of the stereo route in the same sense: integer costs, fp32 scalars, the twin of
 csrc/stereo_match.h; csrc/stereo.hip (through ``DeviceStereoLocator``) returns its bytes.
+``locate_lidar_numpy`` is the definition of the LiDAR route, ``project_lidar_numpy`` (the twin of csrc/lidar_project.h) its
+per-point half; csrc/lidar.hip (through ``DeviceLidarLocator``) returns their bytes.
 """
 from __future__ import annotations
 
@@ -12,9 +14,10 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, MAX_DETECTIONS, STEREO_MATCH_DTYPE, STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE,
-                     Depth, EngineError, LocateParams, Pinhole, StereoPair, StereoParams, _addr, _raise_on, _stream_ptr, _torch,
-                     clamp_count, det_buffer_ptrs, load_library, read_records)
+from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, LIDAR_MAX_DIM, LIDAR_PIXEL_DTYPE, MAX_DETECTIONS,
+                     STEREO_MATCH_DTYPE, STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE, Cloud, Depth, EngineError, LidarParams, LocateParams,
+                     Pinhole, StereoPair, StereoParams, _addr, _raise_on, _stream_ptr, _torch, clamp_count, det_buffer_ptrs,
+                     load_library, read_records)
 
 F = np.float32
 
@@ -326,6 +329,168 @@ class DeviceStereoLocator:
         self._keep = None
         return records
 
+# ---------------------------------------------------------------- from a LiDAR sweep
+def make_lidar_params(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.3, max_depth=40.0, min_valid=1) -> LidarParams:
+    """unina_lidar_params. sx, sy: record -> image pixels."""
+    return LidarParams(float(sx), float(sy), float(shrink), float(min_depth), float(max_depth), int(min_valid))
+
+
+def as_lidar_params(params) -> LidarParams:
+    """A LidarParams, a dict of make_lidar_params' arguments, or a tuple in the struct's order."""
+    if isinstance(params, LidarParams):
+        return params
+    if isinstance(params, dict):
+        return make_lidar_params(**params)
+    return make_lidar_params(*params)
+
+
+def as_extrinsic(lidar_to_cam) -> np.ndarray:
+    """12 values or a [3, 4] array, row-major [R|t], LiDAR frame -> camera frame -> 12 np.float32 (rounded once, here)."""
+    m = np.asarray(lidar_to_cam, dtype=np.float64).reshape(-1).astype(np.float32)
+    if m.size != 12:
+        raise ValueError("an extrinsic is 12 values: the rows of [R|t]")
+    return m
+
+
+def project_lidar_numpy(points, lidar_to_cam, cam, width: int, height: int, min_depth, max_depth) -> np.ndarray:
+    """csrc/lidar_project.h lidar_project for every point. points: [n, >= 3] float32, x, y, z in the first three columns (the
+    others are not read). Returns n LIDAR_PIXEL_DTYPE records in point order, all-zero where a point is not projectable."""
+    cam, m = as_pinhole(cam), as_extrinsic(lidar_to_cam)
+    if not (1 <= width <= LIDAR_MAX_DIM and 1 <= height <= LIDAR_MAX_DIM):
+        raise ValueError(f"width and height must lie in 1..{LIDAR_MAX_DIM}")
+    pts = np.asarray(points)
+    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError("points must be a [n, >= 3] float32 array")
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
+    out = np.zeros(len(pts), dtype=LIDAR_PIXEL_DTYPE)
+    with np.errstate(all="ignore"):
+        xc = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
+        yc = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
+        zc = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+        u = (fx * xc) / zc + cx
+        v = (fy * yc) / zc + cy
+        ok = np.isfinite(xc) & np.isfinite(yc) & np.isfinite(zc) & (zc > F(0))
+        ok &= (u >= F(0)) & (u < F(width)) & (v >= F(0)) & (v < F(height))                # a NaN fails
+        in_range = ok & (zc >= F(min_depth)) & (zc <= F(max_depth))
+    out["u"] = np.where(ok, u, F(0)).astype(np.int32)                                   # truncation; -0.0 is pixel 0
+    out["v"] = np.where(ok, v, F(0)).astype(np.int32)
+    out["key"] = np.where(in_range, np.ascontiguousarray(zc, dtype=np.float32).view(np.uint32), np.uint32(0))
+    out["projectable"] = ok
+    return out
+
+
+def locate_lidar_numpy(dets, count: int, points, lidar_to_cam, cam, width: int, height: int, params, pixels=None) -> np.ndarray:
+    """dets: DET_DTYPE records; count: as the device word; points: [n, >= 3] float32 (n may be 0); lidar_to_cam: 12 values, row-major
+    [R|t]; width, height: the image's size. Returns MAX_DETECTIONS CONE3D_DTYPE records, zero behind the count. `pixels`: the
+    result of project_lidar_numpy on the same arguments, where the caller has it already."""
+    cam, p = as_pinhole(cam), as_lidar_params(params)
+    if pixels is None:
+        pixels = project_lidar_numpy(points, lidar_to_cam, cam, width, height, p.min_depth, p.max_depth)
+    fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
+    px = pixels[pixels["projectable"] != 0]
+    pu, pv, pk = px["u"], px["v"], px["key"]
+    out = np.zeros(MAX_DETECTIONS, dtype=CONE3D_DTYPE)
+    n = clamp_count(count, dets)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            d = dets[i]
+            w = window_numpy((d["x1"], d["y1"], d["x2"], d["y2"]), p.sx, p.sy, p.shrink, width, height, LIDAR_MAX_DIM)
+            if w is None:
+                continue                                                    # an empty window: the all-zero record
+            assert w["stride_x"] == w["stride_y"] == 1
+            member = (pu >= w["u0"]) & (pu <= w["u1"]) & (pv >= w["v0"]) & (pv <= w["v1"])
+            keys = pk[member]
+            valid_keys = keys[keys != 0]
+            r = out[i]
+            r["u"], r["v"], r["n_samples"], r["n_valid"] = w["uc"], w["vc"], keys.size, valid_keys.size
+            if valid_keys.size >= max(1, p.min_valid):
+                k = (valid_keys.size - 1) // 2
+                Z = np.sort(valid_keys)[k:k + 1].view(np.float32)[0]        # the lower median, an actual point's zc
+                r["x"], r["y"], r["z"] = point_numpy(w["uc"], w["vc"], Z, fx, fy, cx, cy)
+                r["valid"] = 1
+    return out
+
+
+def device_words(address: int, n_words: int, device: int = 0):
+    """An int32 CUDA tensor over n_words words at a device address: torch wraps the address, nothing is copied."""
+    class Words:
+        __cuda_array_interface__ = {"shape": (n_words,), "typestr": "<i4", "data": (address, False), "version": 2}
+    return _torch().as_tensor(Words(), device=f"cuda:{device}")
+
+
+class DeviceLidarLocator:
+    """unina_lidar_* (csrc/lidar.hip): one call per frame behind the call that produced the records. Holds the handle (its device
+    workspace is bounded by max_points and the image limits) and the MAX_DETECTIONS-record output buffer `out`, which is what
+    DeviceTracker.update_from_buffer takes."""
+
+    def __init__(self, max_points: int = 1 << 18, max_width: int = 4096, max_height: int = 4096, device: int = 0):
+        torch = _torch()
+        self.L = load_library()
+        self.device = device
+        self.h = C.c_void_p()
+        _raise_on(self.L.unina_lidar_create(device, int(max_points), int(max_width), int(max_height), C.byref(self.h)), "unina_lidar_create")
+        self.out = torch.zeros(MAX_DETECTIONS * CONE3D_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
+        self._keep = None      # the cloud of the call in flight
+        self._n_points = 0     # of the last call
+
+    def close(self):
+        if self.h:
+            self.L.unina_lidar_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    @staticmethod
+    def describe(points, n_points=None) -> Cloud:
+        """A CUDA tensor -> unina_cloud. [n, k] float32 with k >= 3 (x, y, z first; a row stride is carried as the point stride), or
+        [n, stride_bytes] uint8 as a driver hands a packed sweep over. n_points: fewer points than the tensor holds."""
+        torch = _torch()
+        assert points.is_cuda and points.dim() == 2 and (points.shape[1] == 1 or points.stride(1) == 1)
+        if points.dtype == torch.float32:
+            assert points.shape[1] >= 3
+            stride = int(points.stride(0)) * 4
+        elif points.dtype == torch.uint8:
+            stride = int(points.stride(0))
+        else:
+            raise EngineError(f"no point layout for a {points.dtype} tensor")
+        n = int(points.shape[0]) if n_points is None else int(n_points)
+        assert 0 <= n <= points.shape[0]
+        return Cloud(n, stride, points.data_ptr() if n else None)
+
+    def update_async(self, d_dets, d_count, points, lidar_to_cam, cam, width: int, height: int, params, stream=None):
+        """Enqueues the kernels; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and the
+        count; points: a Cloud or a tensor describe() takes. Returns the cone tensor (bytes; read() gives the records)."""
+        self._keep = points
+        cloud = points if isinstance(points, Cloud) else self.describe(points)
+        cam, p = as_pinhole(cam), as_lidar_params(params)
+        m = (C.c_float * 12)(*as_extrinsic(lidar_to_cam).tolist())
+        _raise_on(self.L.unina_locate_lidar_async(self.h, _addr(d_dets), _addr(d_count), C.byref(cloud), C.byref(m), C.byref(cam), int(width),
+                                                  int(height), C.byref(p), self.out.data_ptr(), _stream_ptr(stream)), "unina_locate_lidar_async")
+        self._n_points = cloud.n_points
+        return self.out
+
+    def update_from_buffer(self, det_buf, points, lidar_to_cam, cam, width: int, height: int, params, stream=None):
+        """The same behind Engine.infer_async's int32 buffer (word 0 = count, records from word 8)."""
+        return self.update_async(*det_buffer_ptrs(det_buf), points, lidar_to_cam, cam, width, height, params, stream)
+
+    def read(self, stream=None) -> np.ndarray:
+        """Synchronises `stream`; returns all MAX_DETECTIONS CONE3D_DTYPE records (zero behind the count)."""
+        cones, = read_records(stream, (self.out, CONE3D_DTYPE))
+        self._keep = None
+        return cones
+
+    def read_pixels(self, stream=None) -> np.ndarray:
+        """Synchronises `stream`; returns the LIDAR_PIXEL_DTYPE record of every point of the last call, in point order."""
+        if self._n_points == 0:
+            return np.zeros(0, dtype=LIDAR_PIXEL_DTYPE)
+        address = C.c_void_p()
+        _raise_on(self.L.unina_lidar_buffers(self.h, C.byref(address)), "unina_lidar_buffers")
+        words = device_words(address.value, 4 * self._n_points, self.device)
+        pixels, = read_records(stream, (words, LIDAR_PIXEL_DTYPE))
+        return pixels
+
 
 __all__ = ["locate_numpy", "window_numpy", "point_numpy", "DeviceLocator", "as_pinhole", "as_params", "locate_stereo_numpy", "make_stereo_params",
-           "as_stereo_params", "stereo_range_numpy", "DeviceStereoLocator"]
+           "as_stereo_params", "stereo_range_numpy", "DeviceStereoLocator", "locate_lidar_numpy", "project_lidar_numpy", "make_lidar_params",
+           "as_lidar_params", "as_extrinsic", "DeviceLidarLocator"]
