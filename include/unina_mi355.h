@@ -578,8 +578,9 @@ int unina_locate_async(const GpuDetection *d_dets, const int *d_count, const uni
  *            (u, v, n_valid, n_samples stay). d_match[i] = {disparity, d_best, cost_best, cost_second} for every non-empty
  *            window, accepted or not, with disparity = 0 where it is not; nd == 0 gives {0, 0, 0xFFFFFFFF, 0xFFFFFFFF}
  * Integer costs and minima of packed integers (cost << 10 | d - d_lo): two runs give identical bytes.
- * NOT covered: rectification (the planes must be row-aligned already), zero-mean or census costs (two cameras with different
- * exposure or gain), a left-right consistency check (an occluded window can be accepted at a wrong disparity). */
+ * The planes must be row-aligned: unina_rectify_async (below, "Rectification") makes them so from the raw images.
+ * NOT covered: zero-mean or census costs (two cameras with different exposure or gain), a left-right consistency check (an
+ * occluded window can be accepted at a wrong disparity). */
 #define UNINA_STEREO_MAX_DISPARITIES 1024
 #define UNINA_STEREO_MAX_SIDE 64
 typedef struct { int width, height, pitch; const uint8_t *left, *right; } unina_stereo_pair;
@@ -601,6 +602,55 @@ int unina_locate_stereo_async(const GpuDetection *d_dets, const int *d_count, co
                               const unina_pinhole *cam /* left rectified image, plane pixels */, float baseline /* metres */,
                               const unina_stereo_params *p, unina_cone3d *d_out,
                               unina_stereo_match *d_match /* MAX_DETECTIONS, 16-byte aligned, or NULL */, hipStream_t stream);
+
+/* ------------------------------------------------------------------ Rectification (a camera delivers raw, distorted images and
+ * a calibration; every locator above takes the rectified image's pinhole)
+ * 1 to UNINA_RECTIFY_MAX_IMAGES raw 8-bit images + one calibration each -> the undistorted, rotated images, in ONE launch
+ * (csrc/rectify.hip) on the caller's stream: the left and right luma planes of a stereo head and the colour frame the detector
+ * takes, say. No engine handle, nothing is synchronised, nothing is allocated, no image crosses to the host. The calibration is
+ * OpenCV's: camera matrix K and five distortion coefficients of the raw image, R1 / R2 and P1 / P2 of stereoRectify (or K, D, R, P
+ * of a ROS camera_info). Coordinates index PIXEL CENTRES, as initUndistortRectifyMap does, so such calibrations apply unchanged
+ * (the "pixel i covers [i, i + 1)" of the locators is a statement about binning, a different one). rectify.rectify_numpy is the
+ * definition, byte for byte (rectify.rectify_source_numpy for the coordinates). The coordinates are fp32, each operation rounded
+ * once in the order written, never contracted, the divides correctly rounded; everything behind the inside test is integer.
+ * For the integer output pixel (u, v) of job->dst:
+ *   ray      x = ((float)u - dst.cx) / dst.fx, y = ((float)v - dst.cy) / dst.fy
+ *            X = (r[0] * x + r[3] * y) + r[6], Y = (r[1] * x + r[4] * y) + r[7], W = (r[2] * x + r[5] * y) + r[8]   (R^T * (x, y, 1))
+ *            xn = X / W, yn = Y / W
+ *   lens     r2 = xn * xn + yn * yn; rad = ((k3 * r2 + k2) * r2 + k1) * r2 + 1.0f; xy2 = (2.0f * xn) * yn
+ *            xd = (xn * rad + p1 * xy2) + p2 * (r2 + 2.0f * (xn * xn)); yd = (yn * rad + p1 * (r2 + 2.0f * (yn * yn))) + p2 * xy2
+ *   source   us = src.fx * xd + src.cx, vs = src.fy * yd + src.cy (raw-image pixels); tx = us * 32.0f + 0.5f, ty = vs * 32.0f + 0.5f
+ *   inside   iff W > 0 and -32.0f <= tx < (float)(32 * src.width) and -32.0f <= ty < (float)(32 * src.height); a NaN fails. Sizes
+ *            are at most UNINA_RECTIFY_MAX_DIM, so the float bounds are exact. A pixel that is not inside is `border` in every
+ *            channel
+ *   taps     qx = (int)floorf(tx), x0 = qx >> 5 (arithmetic: -1 .. src.width - 1), ax = qx & 31; y0, ay likewise. The taps are
+ *            (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1); a tap outside the raw image has the value `border` and its
+ *            address is never formed, a tap of weight 0 included
+ *   blend    per channel, integers, 5 fractional bits as in OpenCV's fixed-point remap:
+ *            out = ((32 - ax) * (32 - ay) * t00 + ax * (32 - ay) * t10 + (32 - ax) * ay * t01 + ax * ay * t11 + 512) >> 10
+ * Source and destination sizes are independent: a crop or a scale goes through `dst` (the pinhole the locators then take).
+ * Images of different size and channel count may share a call. Every output byte is written by one thread from integers: two
+ * runs give identical bytes. Bytes of a destination row beyond width * channels are not written.
+ * NOT covered: rational, fisheye and thin-prism distortion models, precomputed maps, NV12 chroma and planar colour (an NV12 Y
+ * plane is a 1-channel image), bicubic sampling. */
+#define UNINA_RECTIFY_MAX_IMAGES 4
+#define UNINA_RECTIFY_MAX_DIM 16384
+typedef struct {
+  unina_pinhole src;          /* raw camera matrix K, raw-image pixels */
+  float k1, k2, p1, p2, k3;   /* OpenCV's 5-coefficient order */
+  float r[9];                 /* row-major 3x3, OpenCV's R1/R2: p_rect = R * p_raw */
+  unina_pinhole dst;          /* P[:, :3] of the rectified image; the pinhole the locators take */
+} unina_rectify_cam;
+typedef struct { int width, height, pitch, channels; const uint8_t *data; } unina_image;
+      /* device; interleaved 8-bit, channels 1, 3 or 4; pitch: bytes per row. No alignment is required of data or pitch (a
+         1-channel row is stored, and a 4-channel pixel loaded and stored, a dword at a time where the address allows) */
+typedef struct { unina_rectify_cam cam; unina_image src; unina_image dst; int border; } unina_rectify_job;
+      /* dst.data is written (the const is the shared type's) */
+/* UNINA_ERR_ARG, before any HIP call: jobs NULL or a NULL data pointer; n_jobs outside 1..UNINA_RECTIFY_MAX_IMAGES; a width or
+ * height outside 1..UNINA_RECTIFY_MAX_DIM; channels not 1, 3 or 4, or different between src and dst; pitch < width * channels;
+ * border outside 0..255; a non-finite field of cam; fx or fy of either pinhole not positive; dst.data == src.data. Images that
+ * overlap otherwise are the caller's to avoid. */
+int unina_rectify_async(const unina_rectify_job *jobs, int n_jobs, hipStream_t stream);
 
 /* ------------------------------------------------------------------ 3-D localisation from a LiDAR sweep (for a vehicle with one
  * camera and a LiDAR: no depth map, no second image)

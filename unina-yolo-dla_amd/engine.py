@@ -122,6 +122,25 @@ class StereoParams(C.Structure):
                 ("max_side", C.c_int), ("max_mean_sad", C.c_int), ("uniqueness", C.c_int)]
 
 
+RECTIFY_MAX_IMAGES, RECTIFY_MAX_DIM = 4, 16384   # include/unina_mi355.h UNINA_RECTIFY_*
+
+
+class RectifyCam(C.Structure):
+    """unina_rectify_cam: raw camera matrix, OpenCV's five distortion coefficients, row-major R (p_rect = R * p_raw), rectified pinhole."""
+    _fields_ = [("src", Pinhole), ("k1", C.c_float), ("k2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float),
+                ("r", C.c_float * 9), ("dst", Pinhole)]
+
+
+class Image(C.Structure):
+    """unina_image: an interleaved 8-bit image of 1, 3 or 4 channels on the device; pitch in bytes."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pitch", C.c_int), ("channels", C.c_int), ("data", C.c_void_p)]
+
+
+class RectifyJob(C.Structure):
+    """unina_rectify_job."""
+    _fields_ = [("cam", RectifyCam), ("src", Image), ("dst", Image), ("border", C.c_int)]
+
+
 LIDAR_MAX_DIM, LIDAR_MAX_POINTS = 16384, 1 << 22   # include/unina_mi355.h UNINA_LIDAR_*
 LIDAR_PIXEL_DTYPE = np.dtype([("u", "<i4"), ("v", "<i4"), ("key", "<u4"), ("projectable", "<i4")])   # unina_lidar_pixel
 assert LIDAR_PIXEL_DTYPE.itemsize == 16
@@ -171,7 +190,7 @@ ABI_SYMBOLS = [
     "unina_kmeans_workspace_bytes", "unina_kmeans", "unina_nearest_rows",
     "unina_abs_histogram_f16", "unina_calib_buffer_count", "unina_calib_buffer_name", "unina_calib_buffers_async", "unina_calib_async",
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
-    "unina_locate_async", "unina_locate_stereo_async",
+    "unina_locate_async", "unina_locate_stereo_async", "unina_rectify_async",
     "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
@@ -286,6 +305,8 @@ def load_library() -> C.CDLL:
     L.unina_locate_async.argtypes = [vp, vp, C.POINTER(Depth), C.POINTER(Pinhole), C.POINTER(LocateParams), vp, vp]
     # 3-D localisation from a stereo pair (csrc/stereo.hip)
     L.unina_locate_stereo_async.argtypes = [vp, vp, C.POINTER(StereoPair), C.POINTER(Pinhole), cf, C.POINTER(StereoParams), vp, vp, vp]
+    # rectification of raw camera images (csrc/rectify.hip)
+    L.unina_rectify_async.argtypes = [C.POINTER(RectifyJob), ci, vp]
     # 3-D localisation from a LiDAR sweep (csrc/lidar.hip)
     L.unina_lidar_create.argtypes = [ci, ci, ci, ci, C.POINTER(vp)]
     L.unina_lidar_destroy.argtypes = [vp]
