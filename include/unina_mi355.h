@@ -858,6 +858,19 @@ int unina_debug_block_stamps(unina_engine_t *e, int op_index, long long *out16, 
 /* Debug, read-only: which heads' output convs the decode launch of unina_infer computes itself (folded), as the frame stands
  * now: bit h (0 = P2, 1 = P3, 2 = P4) set = that head is not read from its planes. Negative error code for a null handle. */
 int unina_debug_folded_heads(unina_engine_t *e);
+/* Debug: the number of streams the library itself holds in this process, all handles together. The runtime maps streams onto
+ * GPU_MAX_HW_QUEUES hardware queues per priority (default 4) as they are created, and two streams on one queue run one after
+ * the other, so an idle stream of the library's could cost the caller the overlap of two frames in flight. The library makes
+ * a stream only for the duration of a graph capture (the first call of a plan): the count is 0 whenever no call is running.
+ * (create_preprocess_stream hands its stream to the caller and is not counted.) */
+int unina_debug_owned_streams(void);
+/* Debug: do streams `a` and `b` of device `device` run on the chip at the same time, or one after the other (one hardware
+ * queue)? `reps` (1..64) times: one single-wave kernel on each stream that holds its compute unit for 300 us of the 100 MHz
+ * wall clock and waits for nothing else, then both streams are synchronised. stamps (host, reps x 4): start and end of the
+ * kernel on `a`, start and end of the one on `b`; *overlapped = the repetitions whose two intervals intersect. a == b is the
+ * negative control: 0. Work already queued on the streams runs first. tools/stream_queues.py prints the matrix for the two
+ * frame streams and the null stream. */
+int unina_debug_streams_overlap(int device, hipStream_t a, hipStream_t b, int reps, long long *stamps, int *overlapped);
 
 /* Library/build identification: "unina_mi355 <version> gfx950". */
 const char *unina_version(void);

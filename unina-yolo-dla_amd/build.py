@@ -37,6 +37,7 @@ UNITS = {
     "rectify.hip": ["-ffp-contract=off"],       # raw images -> rectified images: the source coordinates round as rectify.rectify_source_numpy's fp32 arrays do
     "track.hip": ["-ffp-contract=off"],         # located cones -> persistent tracks: gate, keys and slot update round as tracking.update_numpy's fp32 scalars do
     "engine.hip": [],
+    "stream_probe.hip": [],                     # unina_debug_streams_overlap: do two streams run at the same time?
     "comm.hip": [],                             # host code only: RCCL all-gather of detection slots, librccl loaded on first use
 }
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result"]

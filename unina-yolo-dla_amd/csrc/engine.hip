@@ -111,7 +111,6 @@ struct unina_engine {
   // graph
   bool use_graph = true;
   bool plan_dirty = true;
-  hipStream_t capture_stream = nullptr;
   double t_submit_us = 0, t_wait_us = 0, t_copy_us = 0;   // UNINA_TIMING=1: host-side split of unina_infer (printed at unload)
   long t_calls = 0;
   hipGraph_t graph = nullptr;
@@ -178,6 +177,47 @@ size_t dtype_size(int dt) { return dt == kF32 ? 4 : (dt == kI8 ? 1 : 2); }      
 double dtype_bytes(int dt) { return dt == kS16 ? 4.0 : (double)dtype_size(dt); }   // bytes per value (traffic accounting)
 
 int engine_dtype(const unina_engine* e);
+
+// The library keeps NO stream of its own. The runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues per priority
+// (default 4) when they are created: a fresh queue while there is one, after that the least-referenced existing one -- and
+// two streams on one queue run one after the other. A stream that only ever records a graph still holds its queue, so one
+// per handle (as it was until round 5) pushed the caller's second frame stream onto a shared queue (profiles/r05). A
+// capture therefore makes its stream, records, and destroys it again, on every path out: once per plan, never per frame.
+// Per capture, not per process: the capture mode is thread-local and two threads may capture at once.
+std::atomic<int> g_owned_streams{0};   // streams of the library alive in this process (unina_debug_owned_streams): 0 at rest
+
+struct CaptureStream {
+  hipStream_t s = nullptr;
+  bool open = false;
+  hipError_t begin() {
+    hipError_t err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (err != hipSuccess) {
+      s = nullptr;
+      return err;
+    }
+    ++g_owned_streams;
+    err = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    open = err == hipSuccess;
+    return err;
+  }
+  hipError_t end(hipGraph_t* graph) {
+    open = false;
+    return hipStreamEndCapture(s, graph);
+  }
+  ~CaptureStream() {
+    if (open) {   // a return between begin and end: close the capture, drop what it recorded
+      hipGraph_t g = nullptr;
+      if (hipStreamEndCapture(s, &g) == hipSuccess && g) (void)hipGraphDestroy(g);
+    }
+    if (s) {
+      (void)hipStreamDestroy(s);
+      --g_owned_streams;
+    }
+  }
+  CaptureStream() = default;
+  CaptureStream(const CaptureStream&) = delete;
+  CaptureStream& operator=(const CaptureStream&) = delete;
+};
 
 void drop_graph(unina_engine* e) {
   if (e->exec) (void)hipGraphExecDestroy(e->exec);
@@ -846,19 +886,20 @@ int launch_all(unina_engine* e, hipStream_t s, int which = 0 /*0 all, 1 eager on
   return UNINA_OK;
 }
 
-// Captures the graph part of the forward as a plain chain on the capture stream. (Independent branches as parallel graph
+// Captures the graph part of the forward as a plain chain on a stream that lives for the capture. (Independent branches as parallel graph
 // paths -- heads | PAN path on side streams with event edges -- were implemented and measured in round 1: 1 821 / 2 503
 // frames/s with 2 / 3 paths against 5 837 as a chain; removed.)
 int capture(unina_engine* e) {
   drop_graph(e);
-  HIPCHK(e, hipStreamBeginCapture(e->capture_stream, hipStreamCaptureModeThreadLocal));
+  CaptureStream cs;
+  HIPCHK(e, cs.begin());
   int rc = UNINA_OK;
   for (size_t j = 0; j < e->ops.size() && rc == UNINA_OK; ++j) {
     if (is_eager(e, j)) continue;
-    const hipError_t err = launch_op(e, j, e->capture_stream);
+    const hipError_t err = launch_op(e, j, cs.s);
     if (err != hipSuccess) rc = fail(e, UNINA_ERR_HIP, "op %zu (%s): %s", j, e->ops[j].d.name, hipGetErrorString(err));
   }
-  const hipError_t end = hipStreamEndCapture(e->capture_stream, &e->graph);
+  const hipError_t end = cs.end(&e->graph);
   if (rc != UNINA_OK) return rc;
   if (end != hipSuccess) return fail(e, UNINA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(end));
   HIPCHK(e, hipGraphInstantiate(&e->exec, e->graph, nullptr, nullptr, 0));
@@ -1173,8 +1214,9 @@ int capture_full(unina_engine* e, const FrameCall& call, const PostParams& pp) {
   e->fgraph = nullptr;
   e->stem_node = e->post_node = e->post_node2 = nullptr;
   e->stem_op = -1;
-  hipStream_t st = e->capture_stream;
-  HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  CaptureStream cs;
+  HIPCHK(e, cs.begin());
+  hipStream_t st = cs.s;
   hipError_t err = hipSuccess;
   int rc = UNINA_OK;
   for (size_t j = 0; j < e->ops.size() && err == hipSuccess; ++j) {
@@ -1198,7 +1240,7 @@ int capture_full(unina_engine* e, const FrameCall& call, const PostParams& pp) {
     err = launch_desc(pd[k], args, st);
     if (err == hipSuccess) err = last_captured_node(st, k == 0 ? &e->post_node : &e->post_node2);
   }
-  hipError_t end = hipStreamEndCapture(st, &e->fgraph);
+  hipError_t end = cs.end(&e->fgraph);
   if (rc != UNINA_OK) return rc;
   if (err != hipSuccess) return fail(e, UNINA_ERR_HIP, "full-frame graph capture: %s", hipGetErrorString(err));
   if (end != hipSuccess) return fail(e, UNINA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(end));
@@ -1540,7 +1582,6 @@ int load_device(unina_engine* e, const std::vector<char>& blob) {
     e->h_result_dev = nullptr;
     (void)hipGetLastError();
   }
-  LOADCHK(hipStreamCreateWithFlags(&e->capture_stream, hipStreamNonBlocking));
   LOADCHK(hipDeviceSynchronize());
 #undef LOADCHK
   return UNINA_OK;
@@ -1584,7 +1625,6 @@ void unina_unload_engine(unina_engine_t* e) {
   if (e->t_calls) fprintf(stderr, "unina_infer host split over %ld calls: submit (params + hipGraphLaunch) %.2f us, wait for the completion word %.2f us, record copy %.2f us\n", e->t_calls, e->t_submit_us / e->t_calls, e->t_wait_us / e->t_calls, e->t_copy_us / e->t_calls);
   (void)hipSetDevice(e->device);
   drop_graph(e);
-  if (e->capture_stream) (void)hipStreamDestroy(e->capture_stream);
   void* dev[] = {e->d_blob, e->d_arena, e->d_zeros, e->d_cand, e->d_block_count, e->d_ticket, e->d_post_ws, e->d_result, e->d_mine_ws, e->d_tile_slots, e->d_calib_tab};
   for (void* p : dev)
     if (p) (void)hipFree(p);
@@ -2499,6 +2539,8 @@ int unina_profile_post(unina_engine_t* e, int iters, float conf, float iou, floa
     if (x) (void)hipEventDestroy(x);
   return rc;
 }
+
+int unina_debug_owned_streams(void) { return g_owned_streams.load(); }
 
 int unina_debug_folded_heads(unina_engine_t* e) {
   if (!e) return -UNINA_ERR_ARG;

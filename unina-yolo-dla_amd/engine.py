@@ -179,6 +179,7 @@ ABI_SYMBOLS = [
     "unina_tensor_address", "unina_enqueue", "unina_infer", "unina_infer_bgra", "unina_infer_nv12", "unina_infer_async", "unina_postprocess_async",
     "unina_last_error", "unina_op_count", "unina_get_op_info", "unina_profile_ops", "unina_profile_post", "unina_debug_read_buffer",
     "unina_version", "unina_conv_config_count", "unina_conv_config_name", "unina_set_op_config", "unina_autotune", "unina_debug_post_stamps", "unina_debug_conv_stamps", "unina_debug_dual_stamps", "unina_debug_dual_timeline", "unina_debug_block_stamps", "unina_debug_folded_heads", "unina_serial_latency",
+    "unina_debug_owned_streams", "unina_debug_streams_overlap",
     "unina_set_fusion", "unina_fusion_groups", "unina_debug_fusable_groups",
     "unina_slice_tiles", "unina_infer_tiled_bgra", "unina_infer_tiled_bgra_async", "unina_merge_tiles_async",
     "unina_infer_tiled_nv12", "unina_infer_tiled_nv12_async", "unina_preprocess_nv12_resize",
@@ -246,6 +247,8 @@ def load_library() -> C.CDLL:
     L.unina_debug_dual_timeline.argtypes = [vp, ci, C.POINTER(C.c_longlong), ci, vp]
     L.unina_debug_block_stamps.argtypes = [vp, ci, C.POINTER(C.c_longlong), vp]
     L.unina_debug_folded_heads.argtypes = [vp]
+    L.unina_debug_owned_streams.argtypes = []
+    L.unina_debug_streams_overlap.argtypes = [ci, vp, vp, ci, C.POINTER(C.c_longlong), C.POINTER(ci)]
     L.unina_serial_latency.argtypes = [vp, C.POINTER(vp), ci, ci, cf, cf, cf, C.POINTER(C.c_double), vp]
     # sliced inference (csrc/postprocess.hip: tile_gather_kernel)
     L.unina_slice_tiles.argtypes = [ci, ci, ci, ci, cf, cf, C.POINTER(Tile), ci]
@@ -404,6 +407,23 @@ def read_records(stream, *pairs):
 def clamp_count(count, *arrays) -> int:
     """The device count word as the kernels read it, for the numpy twins: 0 .. MAX_DETECTIONS, and no more than the arrays hold."""
     return min(max(int(count), 0), MAX_DETECTIONS, *(len(a) for a in arrays))
+
+
+def owned_streams() -> int:
+    """Streams the library itself holds in this process (unina_debug_owned_streams): 0 whenever no call is running."""
+    return load_library().unina_debug_owned_streams()
+
+
+def streams_overlap(a, b, reps: int = 3, device: int = 0):
+    """Do streams `a` and `b` (torch streams, raw handles, or None / 0 for the null stream) run on the chip at the same time
+    (unina_debug_streams_overlap)? Returns (repetitions that overlapped, stamps [reps, 4] int64: start / end on `a`, start /
+    end on `b`, 100 MHz ticks). Two streams that share a hardware queue give 0, as does a == b."""
+    _torch()
+    raw = [0 if s is None else (s if isinstance(s, int) else s.cuda_stream) for s in (a, b)]
+    stamps = (C.c_longlong * (4 * reps))()
+    n = C.c_int()
+    _raise_on(load_library().unina_debug_streams_overlap(device, raw[0], raw[1], reps, stamps, C.byref(n)), "unina_debug_streams_overlap")
+    return n.value, np.array(stamps[:], dtype=np.int64).reshape(reps, 4)
 
 
 class Engine:
