@@ -20,10 +20,13 @@
 
 #include "calib.h"
 #include "engine_format.h"
+#include "engine_validate.h"
 #include "kernels.h"
 #include "mining.h"
 
 using namespace unina;
+
+static_assert(kMaxClasses == (uint32_t)kMaxNumClasses, "the validator's class-count limit is the post-process's class field");
 
 hipError_t unina::kernels_init() {
   for (hipError_t (*init)() : {conv_init, c3k2_init, head_init, pair_init, block_dual_init, stem_pool_init, post_init, calib_init}) {
@@ -346,7 +349,8 @@ void find_fold_ops(unina_engine* e) {
   }
 }
 
-// Kernel parameters and info of op `i` as a launch of its own.
+// Kernel parameters and info of op `i` as a launch of its own. Kinds, types, slices, offsets and channel multiples are what
+// validate_engine (engine_validate.h) accepted at load; what is left here depends on the device and the handle.
 int plan_op(unina_engine* e, size_t i) {
   const char* blob = static_cast<const char*>(e->d_blob);
   PlannedOp& op = e->ops[i];
@@ -360,8 +364,6 @@ int plan_op(unina_engine* e, size_t i) {
     ConvParams& p = op.cp;
     memset(&p, 0, sizeof p);
     const int dt = act_dtype_of(src.d.dtype);
-    if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: source is not an activation buffer", i);
-    const size_t esz = dtype_size(dt);
     p.dtype = dt;
     p.src = src.ptr;
     p.src_lo = lo_plane(src.d);
@@ -373,13 +375,11 @@ int plan_op(unina_engine* e, size_t i) {
     if (d.res_buf >= 0) {
       const Buffer& rb = e->bufs[d.res_buf];
       const int rdt = act_dtype_of(rb.d.dtype);
-      if (rdt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: residual is not an activation buffer", i);
       p.res = static_cast<const char*>(rb.ptr) + (size_t)d.res_coff * dtype_size(rdt);
       p.res_ld = (int)rb.d.c;
       p.res_dtype = rdt;
       p.res_lo = lo_plane(rb.d);
       p.res_scale = rb.d.scale;
-      if ((rdt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv with a residual of another type", i);
     }
     p.nseg = (int)d.nseg;
     p.zeros = e->d_zeros;
@@ -394,12 +394,10 @@ int plan_op(unina_engine* e, size_t i) {
       cs.w_lane = op.w_lane_off[s] ? blob + op.w_lane_off[s] : nullptr;
       cs.bias = reinterpret_cast<const float*>(blob + sd.b_off);
       cs.mult = sd.m_off ? reinterpret_cast<const float*>(blob + sd.m_off) : nullptr;
-      if (dt == kI8 && !cs.mult) return fail(e, UNINA_ERR_FORMAT, "op %zu: int8 conv without multipliers", i);
       cs.src_coff = (int)sd.src_coff;
       cs.n_count = (int)sd.n_count;
       cs.up2 = (sd.flags & kSegUp2) ? 1 : 0;
       if (sd.flags & kSegPlanarF32) {
-        if (db.d.dtype != kBufF32Planar) return fail(e, UNINA_ERR_FORMAT, "op %zu: planar slice into non-planar buffer", i);
         cs.dst_planar = static_cast<float*>(db.ptr);
         cs.dst = nullptr;
         cs.dst_ld = 0;
@@ -407,22 +405,16 @@ int plan_op(unina_engine* e, size_t i) {
         out_bytes += 4.0 * sd.n_count * p.M;
       } else {
         const int odt = act_dtype_of(db.d.dtype);
-        const uint32_t al = odt == kI8 ? 16 : 8;   // a 16-byte store chunk must not straddle the slice
-        if (odt < 0 || sd.n_count % al || sd.dst_coff % al || db.d.c % al)
-          return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: NHWC slice needs channel counts/offsets that are multiples of %u", i, al);
         cs.dst = static_cast<char*>(db.ptr) + (size_t)sd.dst_coff * dtype_size(odt);
         cs.dst_planar = nullptr;
         cs.dst_ld = (int)db.d.c;
         cs.out_dtype = odt;
         cs.dst_lo = lo_plane(db.d);
-        if ((odt == kS16) != (dt == kS16)) return fail(e, UNINA_ERR_FORMAT, "op %zu: split-fp16 conv into a buffer of another type", i);
         cs.out_inv_scale = odt == kI8 ? 1.0f / db.d.scale : 1.0f;
         out_bytes += dtype_bytes(odt) * sd.n_count * p.M * (cs.up2 ? 4 : 1);
       }
       ntot += (int)sd.n_count;
     }
-    const int kb = dt == kF32 ? 16 : (dt == kI8 ? 64 : 32);
-    if (p.Cin % kb || (p.src_ld * esz) % 16) return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu (%s): Cin %% %d != 0", i, d.name, kb);
     if (p.force_cfg >= 0 && !conv_config_valid(p, p.force_cfg)) p.force_cfg = -1;
     op.cfg = conv_plan(p);
     const int K = p.ksize * p.ksize * p.Cin;
@@ -437,7 +429,6 @@ int plan_op(unina_engine* e, size_t i) {
     const Buffer& db = e->bufs[sd.dst_buf];
     StemParams& p = op.sp;
     const int odt = act_dtype_of(db.d.dtype);
-    if (odt != kF16 && odt != kF32 && odt != kS16) return fail(e, UNINA_ERR_UNSUPPORTED, "stem output must be fp16, fp32 or split fp16");
     p.dtype = odt;
     p.dst_lo = lo_plane(db.d);
     p.src = static_cast<const float*>(src.ptr);
@@ -453,24 +444,19 @@ int plan_op(unina_engine* e, size_t i) {
   } else if (d.kind == kOpSppfPool) {
     PoolParams& p = op.pp;
     const int dt = act_dtype_of(src.d.dtype);
-    if (dt < 0) return fail(e, UNINA_ERR_FORMAT, "op %zu: pool on a non-activation buffer", i);
     p.dtype = dt;
     p.buf = src.ptr;
     p.lo = lo_plane(src.d);
     p.H = (int)d.in_h; p.W = (int)d.in_w; p.C = (int)d.cin; p.ld = (int)src.d.c; p.coff = (int)d.seg[0].src_coff;
     info.bytes = dtype_bytes(dt) * p.H * p.W * p.C * 4;
-  } else if (d.kind == kOpQuant) {
+  } else {   // kOpQuant
     const Buffer& db = e->bufs[d.seg[0].dst_buf];
-    if (src.d.dtype != kBufF16Nhwc || db.d.dtype != kBufI8Nhwc || src.d.c != db.d.c || src.d.h != db.d.h || src.d.w != db.d.w)
-      return fail(e, UNINA_ERR_FORMAT, "op %zu: QUANT needs an fp16 source and an int8 twin of the same shape", i);
     QuantParams& p = op.qp;
     p.src = static_cast<const half_t*>(src.ptr);
     p.dst = static_cast<signed char*>(db.ptr);
     p.n = (size_t)src.d.h * src.d.w * src.d.c;
     p.inv_scale = 1.0f / db.d.scale;
     info.bytes = 3.0 * p.n;
-  } else {
-    return fail(e, UNINA_ERR_UNSUPPORTED, "op %zu: kind %u not executable", i, d.kind);
   }
   return UNINA_OK;
 }
@@ -1415,11 +1401,8 @@ int enqueue_frame(unina_engine* e, const FrameCall& call, float conf, float iou,
   return UNINA_OK;
 }
 
-// Bytes of a conv slice's weight blocks in the blob (fp32 and split-fp16 engines: 4 per weight, int8: 1, fp16: 2).
-uint64_t weight_bytes(const unina_engine* e, const OpDesc& d, const SegDesc& sd) {
-  const uint32_t sdt = e->bufs[d.src_buf].d.dtype;
-  return (uint64_t)sd.n_pad * d.ksize * d.ksize * d.cin * ((sdt == kBufF32Nhwc || sdt == kBufS16Nhwc) ? 4 : (sdt == kBufI8Nhwc ? 1 : 2));
-}
+// Bytes of a conv slice's weight blocks in the blob (engine_validate.h: validate_engine has held them inside the blob).
+uint64_t weight_bytes(const unina_engine* e, const OpDesc& d, const SegDesc& sd) { return conv_weight_bytes(d, sd, e->bufs[d.src_buf].d.dtype); }
 
 // Host side of loading an engine file: reads and validates it, appends the lane-order weight twins, the stem transpose and
 // the fused groups' streams to `blob` and sets e->fuse. No device is touched (unina_debug_fusable_groups runs exactly this).
@@ -1432,65 +1415,40 @@ int load_host(const char* path, unina_engine* e, std::vector<char>* blob_out) {
     if (f) fclose(f);
     return code;
   };
+  auto refused = [&](const Verdict& v) { return bail(v.code, v.msg); };
   std::vector<char>& blob = *blob_out;
-  if (fread(&e->h, sizeof e->h, 1, f) != 1) return bail(UNINA_ERR_FORMAT, "truncated header");
-  if (memcmp(e->h.magic, kMagic, 8)) return bail(UNINA_ERR_FORMAT, "bad magic (not a UNINAENG file)");
-  if (e->h.version != kVersion) return bail(UNINA_ERR_FORMAT, "unsupported engine file version");
-  if (e->h.precision != kFp16 && e->h.precision != kFp32 && e->h.precision != kInt8 && e->h.precision != kSplit16)
-    return bail(UNINA_ERR_UNSUPPORTED, "unknown engine precision");
-  if (e->h.n_heads != 3 || e->h.n_buffers == 0 || e->h.n_buffers > 4096 || e->h.n_ops == 0 || e->h.n_ops > 4096)
-    return bail(UNINA_ERR_FORMAT, "implausible table sizes");
-  e->bufs.resize(e->h.n_buffers);
-  for (auto& b : e->bufs)
-    if (fread(&b.d, sizeof b.d, 1, f) != 1) return bail(UNINA_ERR_FORMAT, "truncated buffer table");
-  e->ops.resize(e->h.n_ops);
-  for (auto& o : e->ops)
-    if (fread(&o.d, sizeof o.d, 1, f) != 1) return bail(UNINA_ERR_FORMAT, "truncated op table");
-  blob.resize(e->h.blob_bytes);
-  if (e->h.blob_bytes && fread(blob.data(), 1, blob.size(), f) != blob.size()) return bail(UNINA_ERR_FORMAT, "truncated weight blob");
+  // Every check that depends on the file alone is validate_engine's (engine_validate.h). Above that call nothing is allocated
+  // from a field of the file but the two tables, which read_engine_tables sizes after it has capped their lengths, and
+  // nothing is indexed or dereferenced through one.
+  EngineTables t;
+  Verdict v = read_engine_tables([&](void* dst, size_t bytes) { return bytes == 0 || fread(dst, bytes, 1, f) == 1; }, &t);
+  if (!v.ok()) return refused(v);
+  const long tables_end = ftell(f);
+  if (tables_end < 0 || fseek(f, 0, SEEK_END)) return bail(UNINA_ERR_IO, "cannot seek in the engine file");
+  const long file_end = ftell(f);
+  if (file_end < tables_end || fseek(f, tables_end, SEEK_SET)) return bail(UNINA_ERR_IO, "cannot seek in the engine file");
+  v = validate_engine(t.h, t.bufs.data(), t.ops.data(), (uint64_t)(file_end - tables_end));
+  if (!v.ok()) return refused(v);
+  e->h = t.h;
+  e->bufs.resize(t.bufs.size());
+  for (size_t i = 0; i < t.bufs.size(); ++i) e->bufs[i].d = t.bufs[i];
+  e->ops.resize(t.ops.size());
+  for (size_t i = 0; i < t.ops.size(); ++i) {
+    e->ops[i].d = t.ops[i];
+    e->ops[i].d.name[sizeof e->ops[i].d.name - 1] = 0;
+  }
+  blob.resize(e->h.blob_bytes);   // (no more than the file holds: validate_engine)
+  if (e->h.blob_bytes && fread(blob.data(), 1, blob.size(), f) != blob.size()) return bail(UNINA_ERR_IO, "cannot read the weight blob");
   fclose(f);
   f = nullptr;
 
-  // table validation (indices, offsets) before anything touches the GPU
-  for (auto& o : e->ops) {
-    o.d.name[sizeof o.d.name - 1] = 0;
-    if (o.d.src_buf >= e->h.n_buffers || o.d.nseg < 1 || o.d.nseg > 2 || (o.d.res_buf >= (int)e->h.n_buffers))
-      return bail(UNINA_ERR_FORMAT, "op table: bad buffer index");
-    for (uint32_t s = 0; s < o.d.nseg; ++s) {
-      const SegDesc& sd = o.d.seg[s];
-      if (sd.dst_buf >= e->h.n_buffers) return bail(UNINA_ERR_FORMAT, "op table: bad destination buffer");
-      if (o.d.kind == kOpConv) {
-        const uint64_t wbytes = weight_bytes(e, o.d, sd);
-        if (sd.m_off && (sd.m_off + (uint64_t)sd.n_pad * 4 > e->h.blob_bytes || sd.m_off % 16)) return bail(UNINA_ERR_FORMAT, "op table: multiplier offset outside blob");
-        if (sd.w_off + wbytes > e->h.blob_bytes || sd.b_off + (uint64_t)sd.n_pad * 4 > e->h.blob_bytes || sd.w_off % 16 || sd.b_off % 16)
-          return bail(UNINA_ERR_FORMAT, "op table: weight offset outside blob");
-        const BufferDesc& sb = e->bufs[o.d.src_buf].d;
-        const BufferDesc& db = e->bufs[sd.dst_buf].d;
-        if (sd.src_coff + o.d.cin > sb.c || sb.h != o.d.in_h || sb.w != o.d.in_w) return bail(UNINA_ERR_FORMAT, "op table: source slice outside buffer");
-        const uint32_t mul = (sd.flags & kSegUp2) ? 2 : 1;
-        if (sd.dst_coff + sd.n_count > db.c || db.h != o.d.out_h * mul || db.w != o.d.out_w * mul) return bail(UNINA_ERR_FORMAT, "op table: destination slice outside buffer");
-      }
-    }
-  }
   for (size_t i = 0; i < e->bufs.size(); ++i) {
-    e->bufs[i].d.name[sizeof e->bufs[i].d.name - 1] = 0;
     e->bufs[i].bytes = buffer_bytes(e->bufs[i].d);
     if (e->bufs[i].d.flags & kBufInput) e->images_buf = (int)i;
   }
-  static const char* kOut[6] = {"p2_cls", "p2_reg", "p3_cls", "p3_reg", "p4_cls", "p4_reg"};
-  for (int i = 0; i < 6; ++i) {
-    e->out_buf[i] = find_buffer(e, kOut[i]);
-    if (e->out_buf[i] < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks a head output buffer");
-  }
-  if (e->images_buf < 0) return bail(UNINA_ERR_FORMAT, "engine file lacks the images input buffer");
+  for (int i = 0; i < 6; ++i) e->out_buf[i] = find_buffer(e, kHeadOutputs[i]);
   for (size_t i = 0; i < e->ops.size(); ++i)   // graph (A)'s P4 before SPPF: what the mining path pools (unina_mine*)
     if (e->ops[i].d.kind == kOpConv && e->ops[i].d.nseg == 1 && !strcmp(e->ops[i].d.name, "backbone.stage3_c3k2.cv3")) e->embed_op = (int)i;
-  // the decode reads num_classes planes of every cls buffer; the two-launch NMS carries a class id in 14 bits
-  if (e->h.num_classes == 0 || e->h.num_classes > (uint32_t)kMaxNumClasses)
-    return bail(UNINA_ERR_UNSUPPORTED, "num_classes must be 1..16383");
-  for (int i = 0; i < 3; ++i)
-    if (e->bufs[e->out_buf[2 * i]].d.c != e->h.num_classes)
-      return bail(UNINA_ERR_FORMAT, "header num_classes differs from the channel count of a cls output buffer");
 
   // convs: a LANE-order twin of every slice's weight blocks (kernels.h weight_block_to_lane_order) for the kernels that take
   // weights straight into registers (conv3x3_regq / conv3x3_ws / the decode launch's output convs); the file's order stays
@@ -1515,7 +1473,6 @@ int load_host(const char* path, unina_engine* e, std::vector<char>* blob_out) {
     if (op.d.kind != kOpStem) continue;
     const SegDesc& sd = op.d.seg[0];
     const uint32_t co = sd.n_count;
-    if (sd.w_off + (uint64_t)co * 27 * 4 > blob.size()) return bail(UNINA_ERR_FORMAT, "stem weights out of range");
     std::vector<float> wt((size_t)27 * co);
     const float* w = reinterpret_cast<const float*>(blob.data() + sd.w_off);
     for (uint32_t c = 0; c < co; ++c)
