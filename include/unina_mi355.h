@@ -679,8 +679,9 @@ int unina_rectify_async(const unina_rectify_job *jobs, int n_jobs, hipStream_t s
  *   record   valid = n_valid >= max(1, min_valid); valid: x = ((uc - cx) * Z) / fx, y = ((vc - cy) * Z) / fy, z = Z (the
  *            expressions of unina_locate_async), otherwise x = y = z = 0; u = uc, v = vc always
  * Integer counters only (no float atomics): two runs, and any permutation of the cloud, give identical unina_cone3d bytes.
- * NOT covered: ground removal, motion de-skew, time alignment of sweep and frame, lens distortion (the pinhole is the rectified
- * image's), clustering -- the median of what falls in the shrunk box is the whole model. */
+ * NOT covered: ground removal (unina_ground_filter_async below goes in front of this call and strips the road; without it a
+ * ground point inside the window counts as any other), motion de-skew, time alignment of sweep and frame, lens distortion (the
+ * pinhole is the rectified image's), clustering -- the median of what falls in the shrunk box is the whole model. */
 #define UNINA_LIDAR_MAX_DIM    16384       /* width, height */
 #define UNINA_LIDAR_MAX_POINTS (1 << 22)
 typedef struct { int n_points, stride; const void *points; } unina_cloud;   /* device; xyz float32 first in each point */
@@ -711,6 +712,73 @@ int unina_locate_lidar_async(unina_lidar_t *l, const GpuDetection *d_dets, const
 /* Device address of the per-point result of the last call (n_points unina_lidar_pixel, in point order), for a consumer that
  * stays on the GPU or a test; read it behind the call on its stream. UNINA_ERR_STATE before the first unina_locate_lidar_async. */
 int unina_lidar_buffers(unina_lidar_t *l, const unina_lidar_pixel **d_pixels);
+
+/* ------------------------------------------------------------------ ground removal from a LiDAR sweep (in front of
+ * unina_locate_lidar_async: a road return inside a record's window would otherwise count as any other)
+ * A point cloud on the device + the LiDAR -> level extrinsic + a grid -> a filtered cloud of the same length on the device: the
+ * points that stand on the ground first, in cloud order, then entries of four NaN words, which unina_locate_lidar_async treats
+ * as not projectable. So the locator takes {n_points, 16, d_out} as its cloud unchanged, with the caller's lidar_to_cam, and the
+ * number of kept points never crosses to the host. One call enqueues everything (csrc/ground.hip: two memsets, then seed,
+ * envelope, classify, scan, scatter) on the caller's stream; nothing is synchronised. ground.ground_numpy is the definition,
+ * decision for decision and bit for bit. Everything is fp32, each operation rounded once in the order written, never
+ * contracted; the divides are correctly rounded; every decision after the transform compares integers, or fp32 values of which
+ * none is a NaN.
+ *   point     (x, y, z) = the first three float32 of each `stride`-byte point; the rest of a point is never read.
+ *             xl = ((r00 * x + r01 * y) + r02 * z) + t0, yl and zl from rows 1 and 2 of lidar_to_level ([R|t], row-major 3 x 4,
+ *             LiDAR frame -> a gravity-levelled frame with z up: the pose convention and the expression of lidar_to_cam)
+ *   grid      fx = (xl - x_min) / cell, fy = (yl - y_min) / cell. IN_GRID iff xl, yl, zl are finite, 0 <= fx < (float)nx and
+ *             0 <= fy < (float)ny (a NaN fails); the point's cell is (int)fy * nx + (int)fx
+ *   key       key(f) = bits(f) ^ (bits(f) >> 31 ? 0xffffffff : 0x80000000): keys order as unsigned integers exactly as finite
+ *             floats do, -0.0 below +0.0. 0xffffffff is no finite float's key and means EMPTY
+ *   seed      SEED iff IN_GRID and z_lo <= zl <= z_hi. cellmin[c] = the minimum key(zl) over the seeds of cell c, or EMPTY. The
+ *             band keeps multipath returns far below the road, and cells that see only a wall, from founding a ground height
+ *   envelope  g[c] = the minimum, over every non-EMPTY cell n of the grid at Chebyshev distance k = max(|di|, |dj|) <= reach of
+ *             c (c itself is k = 0), of key(cellmin_value[n] + (float)k * rise): one multiply and one add, each rounded once,
+ *             for every k (a -0.0 minimum therefore enters as +0.0); EMPTY where there is no such cell. rise, in metres per
+ *             ring of cells, is the steepest ground the envelope follows; rise = 0 is a plain minimum filter, reach = 0 the
+ *             cell's own minimum
+ *   label     0 OUTSIDE: not IN_GRID.  1 UNKNOWN: IN_GRID and g[cell] EMPTY.  With G = the value of g[cell]:
+ *             2 GROUND: zl <= G + band.  3 OBJECT: G + band < zl <= G + max_height.  4 ABOVE: otherwise. Each sum rounded once
+ *   kept      label == OBJECT, or label == UNKNOWN and keep_unknown != 0
+ *   output    entry r of d_out, for the r-th kept point in cloud order, is (x, y, z, h): the point's own three input words (the
+ *             LiDAR frame: the caller's lidar_to_cam still applies) and h = zl - G, or the word 0x7fc00000 for a kept UNKNOWN
+ *             point. Entries n_kept .. n_points - 1 are four words of 0x7fc00000 each
+ *   header    n_points, n_kept, n_label[5] (points per label), n_cells_seeded (cells whose cellmin is not EMPTY)
+ * Integer counters and integer minima only (no float atomics): two runs give identical bytes, and any permutation of the cloud
+ * gives every point the same label and the same cellmin, g and header.
+ * NOT covered: ground steeper than `rise` allows between neighbouring cells (a banked or sloped track beyond it is labelled
+ * OBJECT or ABOVE), plane or line fitting, clustering of what is kept, motion de-skew, an estimate of lidar_to_level (the
+ * caller's calibration or IMU supplies it). */
+#define UNINA_GROUND_MAX_SIDE  1024        /* nx, ny */
+#define UNINA_GROUND_MAX_REACH 4
+typedef struct { float x_min, y_min, cell; int nx, ny;
+                 float z_lo, z_hi, rise, band, max_height; int reach, keep_unknown; } unina_ground_params;   /* 48 bytes; metres, level frame */
+typedef struct { int n_points, n_kept, n_label[5], n_cells_seeded; } unina_ground_header;   /* 32 bytes */
+typedef struct unina_ground unina_ground_t;
+
+/* Host only: no HIP call, as unina_lidar_create. The device workspace (bounded by max_points and by the UNINA_GROUND_MAX_SIDE^2
+ * cells of the largest grid, and by nothing else: no legal input can overflow a list) is allocated by the first
+ * unina_ground_filter_async, on that call's stream, which then fails with UNINA_ERR_HIP where there is no device. One handle
+ * serves any sequence of clouds and grids within its limits; calls on one handle belong on one stream, or are ordered by the
+ * caller. UNINA_ERR_ARG: NULL out, negative device_id, max_points outside 1..UNINA_LIDAR_MAX_POINTS. */
+int unina_ground_create(int device_id, int max_points, unina_ground_t **out);
+/* Waits for the device, frees. NULL is a no-op. */
+void unina_ground_destroy(unina_ground_t *g);
+/*   cloud->points : device, n_points * stride bytes, 4-byte aligned (read 16 bytes at a time where the base and the stride allow)
+ *   d_out         : device, n_points * 16 bytes, 16-byte aligned; every entry is written exactly once
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer (points may be NULL only when n_points == 0); d_out not 16-byte aligned;
+ * n_points outside 0..max_points; stride < 12 or not a multiple of 4, or points not 4-byte aligned; a non-finite element of
+ * lidar_to_level; x_min, y_min, z_lo, z_hi, rise, band or max_height not finite; cell not finite and positive; nx or ny outside
+ * 1..UNINA_GROUND_MAX_SIDE; z_lo > z_hi; rise < 0, band < 0 or max_height < band; reach outside 0..UNINA_GROUND_MAX_REACH; the
+ * n_points * 16 bytes at d_out overlapping the n_points * stride bytes of the cloud.
+ * n_points == 0 is legal: the header is all-zero, cellmin and g are EMPTY and nothing is written to d_out. */
+int unina_ground_filter_async(unina_ground_t *g, const unina_cloud *cloud, const float lidar_to_level[12],
+                              const unina_ground_params *p, void *d_out, hipStream_t stream);
+/* Device addresses of what the last call left in the workspace, for a consumer that stays on the GPU or a test; read them behind
+ * the call on its stream: n_points label bytes in point order, the nx * ny words of cellmin and of g (row fy, column fx), and
+ * the header. A NULL argument is skipped. UNINA_ERR_STATE before the first unina_ground_filter_async. */
+int unina_ground_buffers(unina_ground_t *g, const uint8_t **d_labels, const uint32_t **d_cellmin, const uint32_t **d_ground,
+                         const unina_ground_header **d_header);
 
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the

@@ -34,15 +34,19 @@ struct LidarPixel {   // unina_lidar_pixel
 UNINA_HD int lidar_cells(int pixels) { return (pixels + (1 << kLidarCellShift) - 1) >> kLidarCellShift; }
 UNINA_HD int lidar_cell(int u, int v, int cells_x) { return (v >> kLidarCellShift) * cells_x + (u >> kLidarCellShift); }
 
+// one row (r0, r1, r2, t) of a row-major 3 x 4 [R|t] applied to a point of the LiDAR frame; csrc/ground_cell.h takes the sweep
+// into its level frame with the same expression
+UNINA_HD float lidar_transform_row(const float* row, float x, float y, float z) { return ((row[0] * x + row[1] * y) + row[2] * z) + row[3]; }
+
 // one point: all-zero where it is not projectable
 UNINA_HD LidarPixel lidar_project(const LidarCamera& c, float x, float y, float z) {
   LidarPixel p;
   p.u = p.v = 0;
   p.key = 0u;
   p.projectable = 0;
-  const float xc = ((c.m[0] * x + c.m[1] * y) + c.m[2] * z) + c.m[3];
-  const float yc = ((c.m[4] * x + c.m[5] * y) + c.m[6] * z) + c.m[7];
-  const float zc = ((c.m[8] * x + c.m[9] * y) + c.m[10] * z) + c.m[11];
+  const float xc = lidar_transform_row(c.m, x, y, z);
+  const float yc = lidar_transform_row(c.m + 4, x, y, z);
+  const float zc = lidar_transform_row(c.m + 8, x, y, z);
   if (!finite(xc) || !finite(yc) || !finite(zc) || !(zc > 0.0f)) return p;
   const float u = (c.fx * xc) / zc + c.cx;
   const float v = (c.fy * yc) / zc + c.cy;

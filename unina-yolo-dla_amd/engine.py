@@ -157,6 +157,18 @@ class LidarParams(C.Structure):
                 ("min_valid", C.c_int)]
 
 
+GROUND_MAX_SIDE, GROUND_MAX_REACH = 1024, 4   # include/unina_mi355.h UNINA_GROUND_*
+GROUND_HEADER_DTYPE = np.dtype([("n_points", "<i4"), ("n_kept", "<i4"), ("n_label", "<i4", (5,)), ("n_cells_seeded", "<i4")])   # unina_ground_header
+assert GROUND_HEADER_DTYPE.itemsize == 32
+
+
+class GroundParams(C.Structure):
+    """unina_ground_params: the grid (metres, level frame), the seed band, the envelope and the label thresholds."""
+    _fields_ = [("x_min", C.c_float), ("y_min", C.c_float), ("cell", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("z_lo", C.c_float),
+                ("z_hi", C.c_float), ("rise", C.c_float), ("band", C.c_float), ("max_height", C.c_float), ("reach", C.c_int),
+                ("keep_unknown", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -193,6 +205,7 @@ ABI_SYMBOLS = [
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
     "unina_locate_async", "unina_locate_stereo_async", "unina_rectify_async",
     "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
+    "unina_ground_create", "unina_ground_destroy", "unina_ground_filter_async", "unina_ground_buffers",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -317,6 +330,12 @@ def load_library() -> C.CDLL:
     L.unina_locate_lidar_async.argtypes = [vp, vp, vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(Pinhole), ci, ci, C.POINTER(LidarParams),
                                            vp, vp]
     L.unina_lidar_buffers.argtypes = [vp, C.POINTER(vp)]
+    # ground removal from a LiDAR sweep (csrc/ground.hip)
+    L.unina_ground_create.argtypes = [ci, ci, C.POINTER(vp)]
+    L.unina_ground_destroy.argtypes = [vp]
+    L.unina_ground_destroy.restype = None
+    L.unina_ground_filter_async.argtypes = [vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(GroundParams), vp, vp]
+    L.unina_ground_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]
