@@ -1,5 +1,5 @@
-"""What the GPU tests of the record stages (evalmatch, locate, stereo, track) share: the device buffers they upload, with
-garbage where a correct kernel never reads, and the report of a byte comparison of two record arrays."""
+"""What the GPU tests of the record stages (evalmatch, locate, stereo, track) and of the sweep stages (lidar, ground) share: the
+device buffers they upload, with garbage where a correct kernel never reads, and the report of a byte comparison of two arrays."""
 import numpy as np
 
 MAXD = 1024                       # MAX_DETECTIONS
@@ -22,8 +22,8 @@ def det_buffer(torch, dets, count):
 
 
 def assert_records_equal(got, want, name, what=""):
-    """Byte equality of two record arrays; the report names the first record that differs."""
+    """Byte equality of two record arrays, or of two plain arrays row by row; the report names the first record that differs."""
     if got.tobytes() != want.tobytes():
-        assert len(got) == len(want), (name, len(got), len(want))
+        assert got.shape == want.shape, (name, what, got.shape, want.shape)
         bad = [i for i in range(len(want)) if got[i].tobytes() != want[i].tobytes()]
         raise AssertionError(f"{name}: {len(bad)} {what + ' ' if what else ''}records differ, first {bad[0]}: got {got[bad[0]]}, want {want[bad[0]]}")

@@ -14,11 +14,11 @@ import numpy as np
 import pytest
 
 import ground_cases as gc
-from records import det_buffer
+from clouds import STRIDES, upload_cloud
+from records import assert_records_equal, det_buffer
 
 pytestmark = pytest.mark.gpu
 
-STRIDES = (16, 12, 32, 48)
 MAX_POINTS = 1 << 17
 NAMES = ("out", "labels", "cellmin", "ground", "header")
 
@@ -28,8 +28,8 @@ def env(pkg):
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    from unina_yolo_dla_amd import ground, localize
-    return torch, ground, localize
+    from unina_yolo_dla_amd import engine, ground, localize
+    return torch, ground, localize, engine
 
 
 @pytest.fixture(scope="module")
@@ -39,17 +39,6 @@ def filt(env):
     f.close()
 
 
-def upload_cloud(torch, pts, stride=16, offset=0):
-    """[n, 3] float32 -> a [n, stride] uint8 CUDA view that starts `offset` bytes into its allocation; every word that is not a
-    coordinate is a NaN bit pattern (the layout tests/test_gpu_lidar.py uploads)."""
-    n = len(pts)
-    host = np.full((offset + n * stride) // 4 + 4, 0x7fc00000, dtype=np.uint32)
-    rows = host[offset // 4:offset // 4 + n * stride // 4].reshape(n, stride // 4)
-    rows[:, :3] = np.ascontiguousarray(pts, dtype=np.float32).view(np.uint32)
-    dev = torch.from_numpy(host.view(np.uint8)).cuda()
-    return dev[offset:offset + n * stride].view(n, stride)
-
-
 def spoil(env, f, n_points, nx, ny):
     """0xFF over d_out and over what the call is to write of the workspace, once there is one."""
     f.out[:max(n_points, 1)].fill_(0xFF)
@@ -57,7 +46,7 @@ def spoil(env, f, n_points, nx, ny):
         labels, cellmin, ground, header = f.buffers()
         for address, n_bytes in ((labels, n_points), (cellmin, 4 * nx * ny), (ground, 4 * nx * ny), (header, 32)):
             if n_bytes:
-                env[1].device_bytes(address, n_bytes, f.device).fill_(0xFF)
+                env[3].device_view(address, n_bytes, device=f.device).fill_(0xFF)
 
 
 def run_device(env, f, c, stride=16, offset=0, cloud=None):
@@ -76,12 +65,7 @@ def twin(env, c):
 
 def assert_equal(got, want, name):
     for what in NAMES:
-        if got[what].tobytes() != want[what].tobytes():
-            a, b = got[what].reshape(-1).view(np.uint8), want[what].reshape(-1).view(np.uint8)
-            assert a.size == b.size, (name, what, a.size, b.size)
-            first = int(np.nonzero(a != b)[0][0]) // got[what].dtype.itemsize
-            raise AssertionError(f"{name}: {what} differs from the twin's, first at element {first}: got "
-                                 f"{got[what].reshape(-1)[first]!r}, want {want[what].reshape(-1)[first]!r}; header {got['header']}")
+        assert_records_equal(got[what], want[what], f"{name}: header {got['header']}", what)
 
 
 def check(env, f, c, stride=16, offset=0, want=None):
@@ -188,7 +172,7 @@ def test_in_front_of_the_locator_with_nothing_between_the_two_calls(env, filt):
     unina_cone3d bytes equal locate_lidar_numpy on the twin's `out`. On the cone scene the raw cloud's depth is a road return
     4.8 m behind the cone, the filtered cloud's a cone return, exactly as tests/test_ground_cpu.py established on the twins; then
     the same chain on a mounted LiDAR with 200 random records."""
-    torch, ground, localize = env
+    torch, ground, localize, _ = env
     import lidar_cases as lc
     locator = localize.DeviceLidarLocator(max_points=MAX_POINTS, max_width=2048, max_height=2048)
     try:

@@ -15,11 +15,11 @@ import numpy as np
 import pytest
 
 import lidar_cases as lc
+from clouds import STRIDES, upload_cloud
 from records import assert_records_equal, det_buffer
 
 pytestmark = pytest.mark.gpu
 
-STRIDES = (16, 12, 32, 48)
 LIMITS = dict(max_points=1 << 17, max_width=4096, max_height=2048)
 
 
@@ -39,22 +39,11 @@ def locator(env):
     loc.close()
 
 
-def upload_cloud(torch, pts, stride=16, offset=0):
-    """[n, 3] float32 -> a [n, stride] uint8 CUDA view that starts `offset` bytes into its allocation; every word that is not a
-    coordinate is a NaN bit pattern."""
-    n = len(pts)
-    host = np.full((offset + n * stride) // 4 + 4, 0x7fc00000, dtype=np.uint32)
-    rows = host[offset // 4:offset // 4 + n * stride // 4].reshape(n, stride // 4)
-    rows[:, :3] = np.ascontiguousarray(pts, dtype=np.float32).view(np.uint32)
-    dev = torch.from_numpy(host.view(np.uint8)).cuda()
-    return dev[offset:offset + n * stride].view(n, stride)
-
-
 def fill_pixels(env, loc, n_points):
     """0xFF over the first n_points unina_lidar_pixel of the workspace, once there is one."""
     address = C.c_void_p()
     if n_points and loc.L.unina_lidar_buffers(loc.h, C.byref(address)) == 0:
-        env[2].device_words(address.value, 4 * n_points).fill_(-1)
+        env[1].device_view(address.value, 4 * n_points, "<i4").fill_(-1)
 
 
 def run_device(env, loc, c, stride=16, offset=0, cloud=None, buf=None):

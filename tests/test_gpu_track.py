@@ -135,16 +135,12 @@ def test_assign_unaligned_and_absent(env, tracker):
 def test_ids_stop_at_int_max(env, tracker):
     """next_id two below INT_MAX, written into the device header through unina_track_buffers: of five births two are taken and
     three dropped, and the counter stays at INT_MAX afterwards."""
-    torch, _, tracking = env
+    torch, engine, tracking = env
     int_max = 2 ** 31 - 1
-
-    class Header:          # the device header as a tensor: torch wraps the address, nothing is copied
-        def __init__(self, address):
-            self.__cuda_array_interface__ = {"shape": (8,), "typestr": "<i4", "data": (address, False), "version": 2}
 
     tracker.reset()
     torch.cuda.synchronize()
-    torch.as_tensor(Header(tracker.buffers()[1]), device="cuda")[3] = int_max - 2
+    engine.device_view(tracker.buffers()[1], 8, "<i4")[3] = int_max - 2      # the device header as a tensor
     state = tracking.new_state()
     state["header"]["next_id"] = int_max - 2
     for f in (tc.frame(tc.grid(5)), tc.frame(tc.grid(8) + np.float32(0.01))):

@@ -8,8 +8,10 @@ import struct
 import numpy as np
 import pytest
 
+import clouds
 import ground_cases as gc
 import hostprog
+from clouds import ulp
 
 F = np.float32
 EMPTY = 0xffffffff
@@ -20,10 +22,6 @@ OUTSIDE, UNKNOWN, GROUND, OBJECT, ABOVE = range(5)
 def twin(c):
     from unina_yolo_dla_amd import ground
     return ground.ground_numpy(c["points"], c["m"], c["params"])
-
-
-def ulp(v, towards):
-    return np.nextafter(F(v), F(towards))
 
 
 def key(v):
@@ -287,29 +285,19 @@ def test_every_bad_argument_is_refused_before_any_hip_call(pkg):
     assert L.unina_ground_create(0, 1 << 22, C.byref(h)) == 0 and h.value                   # host only: no device is needed
     L.unina_ground_destroy(h)
     L.unina_ground_destroy(None)
-    assert L.unina_ground_create(0, 1000, C.byref(h)) == 0
+    assert L.unina_ground_create(0, clouds.MAX_POINTS, C.byref(h)) == 0
     four = [C.byref(C.c_void_p()) for _ in range(4)]
     assert L.unina_ground_buffers(h, *four) == 5 and L.unina_ground_buffers(None, *four) == 4   # UNINA_ERR_STATE: no call yet
-    POINTS, OUT = 0x30004, 0x50000
+    OUT = 0x50000
 
-    def call(handle=h, out=OUT, cloud=True, ext=True, par=True, m=gc.LIDAR_TO_LEVEL, **kw):
-        s = dict(n_points=500, stride=16, points=POINTS)
-        p = gc.params()
-        for k, v in kw.items():
-            next(t for t in (s, p) if k in t)[k] = v
-        ss, pp, mm = engine.Cloud(**s), engine.GroundParams(**p), (C.c_float * 12)(*m)
+    def invoke(f, mm, handle=h, out=OUT, cloud=True, ext=True, par=True):
+        ss, pp = engine.Cloud(**f["cloud"]), engine.GroundParams(**f["par"])
         return L.unina_ground_filter_async(handle, C.byref(ss) if cloud else None, C.byref(mm) if ext else None, C.byref(pp) if par else None,
                                            out, None)
 
-    def spoiled(i, v):
-        m = list(gc.LIDAR_TO_LEVEL)
-        m[i] = v
-        return m
-
+    call = clouds.caller(invoke, gc.LIDAR_TO_LEVEL, par=gc.params())
     bad = [dict(handle=None), dict(out=None), dict(cloud=False), dict(ext=False), dict(par=False), dict(points=None),
-           dict(out=OUT + 8), dict(out=OUT + 4), dict(n_points=-1), dict(n_points=1001),
-           dict(stride=8), dict(stride=0), dict(stride=-16), dict(stride=14), dict(stride=18), dict(points=POINTS + 2), dict(points=POINTS + 1),
-           *[dict(m=spoiled(i, v)) for i in range(12) for v in (nan, inf, -inf)],
+           dict(out=OUT + 8), dict(out=OUT + 4), *clouds.bad_cloud_args(gc.LIDAR_TO_LEVEL),
            *[{k: v} for k in ("x_min", "y_min", "z_lo", "z_hi", "rise", "band", "max_height") for v in (nan, inf, -inf)],
            *[dict(cell=v) for v in (0.0, -1.0, nan, inf)],
            *[{k: v} for k in ("nx", "ny") for v in (0, -1, 1025)],

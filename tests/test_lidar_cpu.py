@@ -8,9 +8,11 @@ import struct
 import numpy as np
 import pytest
 
+import clouds
 import hostprog
 import lidar_cases as lc
 import locate_cases
+from clouds import ulp
 
 F = np.float32
 
@@ -24,10 +26,6 @@ def pixels_of(c):
     from unina_yolo_dla_amd import localize
     p = c["params"]
     return localize.project_lidar_numpy(c["points"], c["m"], c["cam"], c["width"], c["height"], p["min_depth"], p["max_depth"])
-
-
-def ulp(v, towards):
-    return np.nextafter(F(v), F(towards))
 
 
 # ---------------------------------------------------------------- csrc/lidar_project.h on the host
@@ -258,31 +256,20 @@ def test_every_bad_argument_is_refused_before_any_hip_call(pkg):
     assert L.unina_lidar_create(0, 1 << 22, 16384, 16384, C.byref(h)) == 0 and h.value      # host only: no device is needed
     L.unina_lidar_destroy(h)
     L.unina_lidar_destroy(None)
-    assert L.unina_lidar_create(0, 1000, 1920, 1080, C.byref(h)) == 0
+    assert L.unina_lidar_create(0, clouds.MAX_POINTS, 1920, 1080, C.byref(h)) == 0
     assert L.unina_lidar_buffers(h, C.byref(C.c_void_p())) == 5 and L.unina_lidar_buffers(None, None) == 4   # UNINA_ERR_STATE: no call yet
-    DETS, COUNT, POINTS, OUT = 0x10000, 0x20000, 0x30004, 0x50000
+    DETS, COUNT, OUT = 0x10000, 0x20000, 0x50000
 
-    def call(handle=h, dets=DETS, count=COUNT, out=OUT, cloud=True, ext=True, cam=True, par=True, width=640, height=480, m=lc.MOUNTED, **kw):
-        s = dict(n_points=500, stride=16, points=POINTS)
-        c = dict(fx=500.0, fy=500.0, cx=320.0, cy=240.0)
-        p = dict(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.5, max_depth=40.0, min_valid=1)
-        for k, v in kw.items():
-            next(t for t in (s, c, p) if k in t)[k] = v
-        ss, cc, pp, mm = engine.Cloud(**s), engine.Pinhole(**c), engine.LidarParams(**p), (C.c_float * 12)(*m)
+    def invoke(f, mm, handle=h, dets=DETS, count=COUNT, out=OUT, cloud=True, ext=True, cam=True, par=True, width=640, height=480):
+        ss, cc, pp = engine.Cloud(**f["cloud"]), engine.Pinhole(**f["cam"]), engine.LidarParams(**f["par"])
         return L.unina_locate_lidar_async(handle, dets, count, C.byref(ss) if cloud else None, C.byref(mm) if ext else None,
                                           C.byref(cc) if cam else None, width, height, C.byref(pp) if par else None, out, None)
 
-    def spoiled(i, v):
-        m = list(lc.MOUNTED)
-        m[i] = v
-        return m
-
+    call = clouds.caller(invoke, lc.MOUNTED, cam=dict(fx=500.0, fy=500.0, cx=320.0, cy=240.0),
+                         par=dict(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.5, max_depth=40.0, min_valid=1))
     bad = [dict(handle=None), dict(dets=None), dict(count=None), dict(out=None), dict(cloud=False), dict(ext=False), dict(cam=False), dict(par=False),
-           dict(points=None), dict(out=OUT + 8), dict(dets=DETS + 4), dict(count=COUNT + 2),
-           dict(n_points=-1), dict(n_points=1001), dict(stride=8), dict(stride=0), dict(stride=-16), dict(stride=14), dict(stride=18),
-           dict(points=POINTS + 2), dict(points=POINTS + 1),
+           dict(points=None), dict(out=OUT + 8), dict(dets=DETS + 4), dict(count=COUNT + 2), *clouds.bad_cloud_args(lc.MOUNTED),
            dict(width=0), dict(width=-3), dict(width=1921), dict(height=0), dict(height=1081),
-           *[dict(m=spoiled(i, v)) for i in range(12) for v in (nan, inf, -inf)],
            *[{k: v} for k in ("fx", "fy", "sx", "sy") for v in (0.0, -1.0, nan, inf)],
            *[{k: v} for k in ("cx", "cy") for v in (nan, inf, -inf)],
            dict(shrink=0.0), dict(shrink=-0.5), dict(shrink=1.0001), dict(shrink=nan),

@@ -18,12 +18,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from benchlib import median_ms, wall_ms, window_ms  # noqa: E402
 
 
 def main():
@@ -47,14 +48,6 @@ def main():
                         (d["x2"] - d["x1"]) / size * (0.85 if i % 3 == 0 else 1.0), (d["y2"] - d["y1"]) / size]
                        for i, d in enumerate(top)], dtype=np.float64).reshape(-1, 5)
 
-    def median_ms(fn, reps):
-        times = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            out = fn()
-            times.append(time.perf_counter() - t0)
-        return out, float(np.median(times) * 1e3)
-
     def host_small():
         m = metrics.SmallObjectMetric(size_threshold=15, image_size=size)
         m.update([metrics.coco_to_metric_rows(metrics.detections_to_coco(dets, "x"), size, size)], [labels])
@@ -73,27 +66,15 @@ def main():
     assert (res.tp, res.fp, res.fn) == (so.true_positives, so.false_positives, so.false_negatives), "device counters differ from the host's"
     assert res.n_scores == cq["num_calibration_samples"] and metrics.conformal_from_scores(scores, 0.1) == cq, "device scores differ"
 
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(args.reps):
-        ev.update(buf, lab, params, what)
-    stop.record()
-    torch.cuda.synchronize()
-    kernel_ms = start.elapsed_time(stop) / args.reps
+    kernel_ms = window_ms(torch, lambda: ev.update(buf, lab, params, what), args.reps)
 
-    def frames(with_eval):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.reps):
-            b = eng.infer_async(None, conf, iou, 0.0)
-            if with_eval:
-                ev.update(b, lab, params, what)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / args.reps
-    frames(False)
-    frame_ms = min(frames(False) for _ in range(3))
-    both_ms = min(frames(True) for _ in range(3))
+    def frame(with_eval):
+        b = eng.infer_async(None, conf, iou, 0.0)
+        if with_eval:
+            ev.update(b, lab, params, what)
+    wall_ms(torch, lambda: frame(False), args.reps)
+    frame_ms = min(wall_ms(torch, lambda: frame(False), args.reps) for _ in range(3))
+    both_ms = min(wall_ms(torch, lambda: frame(True), args.reps) for _ in range(3))
     res, _, _ = ev.read()
     out = {"records": int(len(dets)), "labels": int(len(labels)), "reps": args.reps,
            "host_small_ms": host_small_ms, "host_conformal_ms": host_conf_ms, "host_ms": host_small_ms + host_conf_ms,

@@ -3,7 +3,7 @@
 cloud and against the HBM floor counted from the shapes; prints ONE JSON line per cloud size and writes them to
 profiles/r04/ground_latency.txt.
 
-The sweep is tools/bench_lidar.py's: 128 rings over 360 degrees in firing order, 16-byte points (x, y, z, intensity), a flat
+The sweep is tools/bench_lidar.py's (tools/benchlib.py): 128 rings over 360 degrees in firing order, 16-byte points (x, y, z, intensity), a flat
 ground 0.6 m below the LiDAR with 1 cm of noise or nothing (60 m); one point in 40 is lifted by 0.05 .. 0.5 m so that there is
 something to keep. The grid is 256 x 256 cells of 0.5 m around the LiDAR. Per size (30 000, 120 000 and 260 000 points):
   * host_numpy_ms: ground.ground_numpy on the host copy (vectorised numpy; the interpreter's cost, not a tuned implementation's),
@@ -23,15 +23,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from bench_lidar import CAM, GROUND, H, LIDAR_TO_CAM, W, cone_boxes, synthetic_sweep  # noqa: E402
+from benchlib import CAM, GROUND, H, LIDAR_TO_CAM, W, cone_boxes, det_words, median_ms, synthetic_sweep, windows_ms  # noqa: E402
 
 LIDAR_TO_LEVEL = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, -GROUND)     # the ground is z = 0
 GRID = dict(x_min=-64.0, y_min=-64.0, cell=0.5, nx=256, ny=256, z_lo=-0.3, z_hi=0.3, rise=0.05, band=0.05, max_height=0.6, reach=2,
@@ -58,22 +56,6 @@ def counted_bytes(n, stride, n_kept, nx, ny):
             "scatter": n + 4 * blocks + 16 * n_kept + 4 * n_kept + 16 * n}   # label, offset; a kept point's words and h; one entry each
 
 
-def windows_ms(torch, fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    out = []
-    for _ in range(3):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(reps):
-            fn()
-        stop.record()
-        torch.cuda.synchronize()
-        out.append(start.elapsed_time(stop) / reps)
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, nargs="+", default=[30000, 120000, 260000])
@@ -84,14 +66,11 @@ def main():
     ap.add_argument("--output", default=os.path.join(ROOT, "profiles", "r04", "ground_latency.txt"))
     args = ap.parse_args()
     import torch
-    from unina_yolo_dla_amd import engine, ground, localize
+    from unina_yolo_dla_amd import ground, localize
     if not torch.cuda.is_available():
         raise SystemExit("bench_ground.py measures on the GPU: no device is visible")
     dets = cone_boxes(args.records, 99)
-    words = np.zeros(8 + 8 * engine.MAX_DETECTIONS, dtype=np.int32)
-    words[0] = len(dets)
-    words[8:8 + 8 * len(dets)] = dets.view(np.int32).reshape(-1)
-    buf = torch.from_numpy(words).cuda()
+    buf = torch.from_numpy(det_words(dets)).cuda()
     lpar = localize.make_lidar_params(shrink=0.5, min_depth=0.5, max_depth=45.0, min_valid=2)
     lines = []
     for n in args.points:
@@ -100,12 +79,7 @@ def main():
         filt = ground.DeviceGroundFilter(max_points=n)
         loc = localize.DeviceLidarLocator(max_points=n, max_width=W, max_height=H)
 
-        times = []
-        for _ in range(args.host_reps):
-            t0 = time.perf_counter()
-            want = ground.ground_numpy(sweep, LIDAR_TO_LEVEL, GRID)
-            times.append(time.perf_counter() - t0)
-        numpy_ms = float(np.median(times) * 1e3)
+        want, numpy_ms = median_ms(lambda: ground.ground_numpy(sweep, LIDAR_TO_LEVEL, GRID), args.host_reps)
 
         def same_as_twin():
             header, out = filt.read()

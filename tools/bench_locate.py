@@ -17,12 +17,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from benchlib import median_ms, wall_ms, window_ms  # noqa: E402
 
 
 def synthetic_depth(seed, h, w, holes=0.3):
@@ -61,14 +62,6 @@ def main():
     got = loc.read()
     dets = engine.Engine.unpack(buf)
 
-    def median_ms(fn, reps):
-        times = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            out = fn()
-            times.append(time.perf_counter() - t0)
-        return out, float(np.median(times) * 1e3)
-
     def d2h():
         torch.cuda.synchronize()
         return d_depth.cpu().numpy()
@@ -76,27 +69,15 @@ def main():
     want, numpy_ms = median_ms(lambda: localize.locate_numpy(dets, len(dets), host_depth, engine.DEPTH_F32, 1.0, cam, par), args.host_reps)
     assert got.tobytes() == want.tobytes(), "device records differ from locate_numpy's"
 
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    start.record()
-    for _ in range(args.reps):
-        loc.update_from_buffer(buf, d_depth, 1.0, cam, par)
-    stop.record()
-    torch.cuda.synchronize()
-    kernel_ms = start.elapsed_time(stop) / args.reps
+    kernel_ms = window_ms(torch, lambda: loc.update_from_buffer(buf, d_depth, 1.0, cam, par), args.reps)
 
-    def frames(with_locate):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.reps):
-            b = eng.infer_async(None, conf, iou, 0.0)
-            if with_locate:
-                loc.update_from_buffer(b, d_depth, 1.0, cam, par)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / args.reps
-    frames(False)
-    frame_ms = min(frames(False) for _ in range(3))
-    both_ms = min(frames(True) for _ in range(3))
+    def frame(with_locate):
+        b = eng.infer_async(None, conf, iou, 0.0)
+        if with_locate:
+            loc.update_from_buffer(b, d_depth, 1.0, cam, par)
+    wall_ms(torch, lambda: frame(False), args.reps)
+    frame_ms = min(wall_ms(torch, lambda: frame(False), args.reps) for _ in range(3))
+    both_ms = min(wall_ms(torch, lambda: frame(True), args.reps) for _ in range(3))
     assert loc.read().tobytes() == want.tobytes(), "device records differ after the timed loops"
     n = len(dets)
     out = {"records": int(n), "located": int((got["valid"] == 1).sum()), "max_samples": int(got["n_samples"].max()),

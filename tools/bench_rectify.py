@@ -22,12 +22,13 @@ import json
 import math
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from benchlib import median_ms, window_ms  # noqa: E402
 
 W, H = 1920, 1080
 HBM_PEAK = 8.0e12          # bytes / s, HBM3E peak of the MI355X
@@ -64,14 +65,6 @@ def main():
     d_raws = [torch.from_numpy(r).cuda() for r in raws]
     rect = rectify.DeviceRectifier(specs)
 
-    def median_ms(fn, reps):
-        times = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            out = fn()
-            times.append(time.perf_counter() - t0)
-        return out, float(np.median(times) * 1e3)
-
     def d2h():
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in d_raws]
@@ -89,16 +82,8 @@ def main():
     for g, w in zip(got, want):
         assert g.shape == w.shape and g.tobytes() == w.tobytes(), "device image differs from rectify_numpy's"
 
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
     def timed(reps):
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(reps):
-            rect.update(d_raws)
-        stop.record()
-        torch.cuda.synchronize()
-        return start.elapsed_time(stop) / reps
+        return window_ms(torch, lambda: rect.update(d_raws), reps)
     timed(args.warmup)
     trial_ms = timed(50)
     reps = max(50, int(math.ceil(args.window * 1.2e3 / trial_ms)))

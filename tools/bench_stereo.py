@@ -19,12 +19,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from benchlib import median_ms, wall_ms, window_ms  # noqa: E402
 
 W, H = 1280, 720
 BANDS = (12, 24, 40, 64, 96, 140, 200, 300)
@@ -70,14 +71,6 @@ def main():
                                       uniqueness=10)
     loc = localize.DeviceStereoLocator()
 
-    def median_ms(fn, reps):
-        times = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            out = fn()
-            times.append(time.perf_counter() - t0)
-        return out, float(np.median(times) * 1e3)
-
     lines = []
     for records in args.records:
         conf = float(ranked[min(records, len(ranked)) - 1])            # the threshold that keeps about `records` of them
@@ -94,27 +87,15 @@ def main():
                                    args.host_reps)
         assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes(), "device records differ from locate_stereo_numpy's"
 
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        start.record()
-        for _ in range(args.reps):
-            loc.update_from_buffer(buf, d_left, d_right, cam, baseline, par)
-        stop.record()
-        torch.cuda.synchronize()
-        kernel_ms = start.elapsed_time(stop) / args.reps
+        kernel_ms = window_ms(torch, lambda: loc.update_from_buffer(buf, d_left, d_right, cam, baseline, par), args.reps)
 
-        def frames(with_stereo):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.reps):
-                b = eng.infer_async(None, conf, iou, 0.0)
-                if with_stereo:
-                    loc.update_from_buffer(b, d_left, d_right, cam, baseline, par)
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t0) * 1e3 / args.reps
-        frames(False)
-        frame_ms = min(frames(False) for _ in range(3))
-        both_ms = min(frames(True) for _ in range(3))
+        def frame(with_stereo):
+            b = eng.infer_async(None, conf, iou, 0.0)
+            if with_stereo:
+                loc.update_from_buffer(b, d_left, d_right, cam, baseline, par)
+        wall_ms(torch, lambda: frame(False), args.reps)
+        frame_ms = min(wall_ms(torch, lambda: frame(False), args.reps) for _ in range(3))
+        both_ms = min(wall_ms(torch, lambda: frame(True), args.reps) for _ in range(3))
         after = loc.read()
         assert after[0].tobytes() == want[0].tobytes() and after[1].tobytes() == want[1].tobytes(), "device records differ after the timed loops"
         n = len(dets)

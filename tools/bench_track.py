@@ -20,12 +20,13 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from benchlib import median_ms  # noqa: E402
 
 
 def records(points, conf=0.9):
@@ -90,20 +91,13 @@ def main():
         assert header.tobytes() == want["header"].tobytes() and tracks.tobytes() == want["tracks"].tobytes(), f"{name}: table differs"
         assert trk.assign.cpu().numpy().tobytes() == want_assign.tobytes(), f"{name}: assign differs"
 
-        def median_ms(fn):
-            t = []
-            for _ in range(args.host_reps):
-                t0 = time.perf_counter()
-                r = fn()
-                t.append(time.perf_counter() - t0)
-            return r, float(np.median(t) * 1e3)
-
         def d2h():
             torch.cuda.synchronize()
             return d_timed[0].cpu().numpy(), int(d_timed[1].cpu()[0]), d_timed[2].cpu().numpy()
-        (h_dets, h_count, h_cones), d2h_ms = median_ms(d2h)
+        (h_dets, h_count, h_cones), d2h_ms = median_ms(d2h, args.host_reps)
         from unina_yolo_dla_amd.engine import CONE3D_DTYPE, DET_DTYPE
-        _, numpy_ms = median_ms(lambda: tracking.update_numpy(state, h_dets.view(DET_DTYPE), h_count, h_cones.view(CONE3D_DTYPE), par))
+        _, numpy_ms = median_ms(lambda: tracking.update_numpy(state, h_dets.view(DET_DTYPE), h_count, h_cones.view(CONE3D_DTYPE), par),
+                                 args.host_reps)
         h = want["header"][0]
         out["scenes"][name] = {"live_before": int(state["header"]["n_live"][0]), "records": timed[2], "gate": gate,
                                "n_matched": int(h["n_matched"]), "n_born": int(h["n_born"]), "n_dropped": int(h["n_dropped"]),

@@ -14,12 +14,11 @@
 #include <atomic>
 
 #include "kernels.h"
+#include "wave_block.h"
 
 namespace unina {
 
 namespace {
-
-constexpr int kWave = 64;
 
 // One 15-bit pattern per lane; every lane of the wave calls this together (`ok`: the lane holds an element).
 __device__ __forceinline__ void calib_add(unsigned h, bool ok, unsigned* bins, unsigned& zeros) {

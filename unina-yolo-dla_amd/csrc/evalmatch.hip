@@ -20,11 +20,11 @@
 #include <new>
 
 #include "record_io.h"
+#include "wave_block.h"
 
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kEvalWaves = 11;                     // wave 0: small-object metric; waves 1..10: IoU thresholds 0.50 .. 0.95
 constexpr int kEvalBlock = kEvalWaves * kWave;
 constexpr int kSlots = UNINA_EVAL_MAX_LABELS / kWave;   // labels per lane

@@ -1,6 +1,6 @@
 // The ground stripped from a LiDAR sweep on the device, in front of unina_locate_lidar_async (include/unina_mi355.h "ground
 // removal from a LiDAR sweep"; ground.ground_numpy is the definition, bit for bit). The per-point and per-cell halves -- transform,
-// cell, key, envelope term, label -- are csrc/ground_cell.h.
+// cell, key, envelope term, label -- are csrc/ground_cell.h, the cloud's and the workspace's plumbing csrc/cloud_io.h.
 //
 // N points (30 000 .. 260 000 a sweep) against a grid of at most 1024 x 1024 cells. Five kernels, enqueued by the one call behind
 // a memset of the call's nx * ny cell keys to 0xff and of the header to 0, nothing synchronised; a stage boundary is a launch
@@ -40,20 +40,16 @@ struct unina_ground {
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kSeedBlock = 256;
 constexpr int kTileX = 32, kTileY = 8;        // envelope: cells a workgroup owns; a wave is two rows of the tile
 constexpr int kEnvBlock = kTileX * kTileY;
 constexpr int kHaloX = kTileX + 2 * kGroundMaxReach, kHaloY = kTileY + 2 * kGroundMaxReach;
 constexpr int kPtBlock = 1024;                // classify, scatter: the workgroup whose kept points are one word of the scan
 constexpr int kPtWaves = kPtBlock / kWave;
-constexpr int kScanBlock = 1024;
-constexpr int kScanWaves = kScanBlock / kWave;
-constexpr int kScanPer = 4;
-constexpr int kMaxBlocks = kLidarMaxPoints / kPtBlock;   // 4096: one pass of the scan
+constexpr int kMaxBlocks = kCloudMaxPoints / kPtBlock;   // 4096: one pass of the scan
 
 static_assert(kGroundMaxSide == UNINA_GROUND_MAX_SIDE && kGroundMaxReach == UNINA_GROUND_MAX_REACH, "header limits");
-static_assert(kLidarMaxPoints == UNINA_LIDAR_MAX_POINTS && kMaxBlocks == kScanBlock * kScanPer, "the scan is one pass");
+static_assert(kCloudMaxPoints == UNINA_LIDAR_MAX_POINTS && kMaxBlocks == kScanBlock * kScanPer, "the scan is one pass");
 static_assert(sizeof(unina_ground_header) == 32 && sizeof(unina_ground_params) == 48, "record layouts");
 static_assert(sizeof(GroundGrid) == 48 + sizeof(unina_ground_params), "GroundGrid is the extrinsic and the parameters");
 static_assert(kEnvBlock % kWave == 0 && kSeedBlock % kWave == 0, "whole waves");
@@ -70,42 +66,20 @@ struct Workspace {
   unina_ground_header* header;
 };
 
-size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// the arrays at `base` (what hipMalloc returned: 256-byte aligned); returns the bytes they take
+// the arrays at `base`; returns the bytes they take
 size_t workspace_layout(const unina_ground* g, uintptr_t base, Workspace* w) {
   const size_t np = (size_t)g->max_points;
   const size_t cells = (size_t)kGroundMaxSide * kGroundMaxSide;
   size_t at = 0;
-  w->cellz = reinterpret_cast<uint2*>(base + at);
-  at += round16(np * sizeof(uint2));
-  w->h = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(np * sizeof(uint32_t));
-  w->labels = reinterpret_cast<uint8_t*>(base + at);
-  at += round16(np);
-  w->cellmin = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(cells * sizeof(uint32_t));
-  w->ground = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(cells * sizeof(uint32_t));
-  w->kept = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(kMaxBlocks * sizeof(uint32_t));
-  w->offset = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(kMaxBlocks * sizeof(uint32_t));
-  w->header = reinterpret_cast<unina_ground_header*>(base + at);
-  at += round16(sizeof(unina_ground_header));
+  w->cellz = carve<uint2>(base, at, np);
+  w->h = carve<uint32_t>(base, at, np);
+  w->labels = carve<uint8_t>(base, at, np);
+  w->cellmin = carve<uint32_t>(base, at, cells);
+  w->ground = carve<uint32_t>(base, at, cells);
+  w->kept = carve<uint32_t>(base, at, kMaxBlocks);
+  w->offset = carve<uint32_t>(base, at, kMaxBlocks);
+  w->header = carve<unina_ground_header>(base, at, 1);
   return at;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void load_xyz(const unsigned char* __restrict__ points, int i, int stride, uint32_t* x, uint32_t* y, uint32_t* z) {
-  const unsigned char* src = points + (size_t)i * (size_t)stride;
-  if (VEC) {
-    const uint4 q = *reinterpret_cast<const uint4*>(src);
-    *x = q.x; *y = q.y; *z = q.z;
-  } else {
-    const uint32_t* f = reinterpret_cast<const uint32_t*>(src);
-    *x = f[0]; *y = f[1]; *z = f[2];
-  }
 }
 
 // ---------------------------------------------------------------- seed
@@ -119,28 +93,27 @@ __global__ void __launch_bounds__(kSeedBlock) ground_seed_kernel(const unsigned 
   if (i < n) {
     uint32_t x, y, z;
     load_xyz<VEC>(points, i, stride, &x, &y, &z);
-    const GroundPoint p = ground_point(grid, ground_float(x), ground_float(y), ground_float(z));
+    const GroundPoint p = ground_point(grid, bits_float(x), bits_float(y), bits_float(z));
     cellz[i] = make_uint2((uint32_t)p.cell, p.z_bits);
     if (p.seed) {
       cell = p.cell;   // < nx * ny: IN_GRID
-      key = ground_key(ground_float(p.z_bits));
+      key = ground_key(bits_float(p.z_bits));
     }
   }
   unsigned long long todo = __ballot(cell >= 0);
   while (todo) {   // wave-uniform
-    const int leader = __ffsll((long long)todo) - 1;
-    const int c = __shfl(cell, leader, kWave);
-    const unsigned long long same = __ballot(cell == c);
-    uint32_t m = cell == c ? key : kGroundEmpty;
-    if (same & (same - 1ull)) {   // wave-uniform: more than one lane in this cell
+    KeyGroup g;
+    wave_first_group(todo, cell, g);
+    uint32_t m = cell == g.key ? key : kGroundEmpty;
+    if (g.lanes & (g.lanes - 1ull)) {   // wave-uniform: more than one lane in this cell
 #pragma unroll
       for (int o = kWave / 2; o > 0; o >>= 1) {
         const uint32_t t = (uint32_t)__shfl_xor((int)m, o, kWave);
         m = t < m ? t : m;
       }
     }
-    if (lane == leader) atomicMin(&cellmin[c], m);
-    todo &= ~same;
+    if (lane == g.leader) atomicMin(&cellmin[g.key], m);
+    todo &= ~g.lanes;
   }
 }
 
@@ -193,7 +166,7 @@ __global__ void __launch_bounds__(kPtBlock) ground_classify_kernel(const uint2* 
     const int cell = (int)cz.x;
     const uint32_t g = cell >= 0 ? ground[cell] : kGroundEmpty;   // cell < nx * ny
     uint32_t h_bits;
-    label = ground_label(grid, cell, ground_float(cz.y), g, &h_bits);
+    label = ground_label(grid, cell, bits_float(cz.y), g, &h_bits);
     labels[i] = (uint8_t)label;
     h[i] = h_bits;
   }
@@ -261,17 +234,6 @@ __global__ void __launch_bounds__(kPtBlock) ground_scatter_kernel(const unsigned
   }
 }
 
-// allocates the workspace on first use
-int ground_ensure(unina_ground* g) {
-  if (hipSetDevice(g->device) != hipSuccess) return UNINA_ERR_HIP;
-  if (g->d_mem) return UNINA_OK;
-  Workspace w;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, workspace_layout(g, 0, &w)) != hipSuccess) return UNINA_ERR_HIP;
-  g->d_mem = static_cast<unsigned char*>(mem);
-  return UNINA_OK;
-}
-
 bool params_ok(const unina_ground_params* p) {
   if (!finite(p->x_min) || !finite(p->y_min) || !finite_pos(p->cell)) return false;
   if (p->nx < 1 || p->nx > kGroundMaxSide || p->ny < 1 || p->ny > kGroundMaxSide) return false;
@@ -287,7 +249,7 @@ extern "C" int unina_ground_create(int device_id, int max_points, unina_ground_t
   using namespace unina;
   if (!out) return UNINA_ERR_ARG;
   *out = nullptr;
-  if (device_id < 0 || max_points < 1 || max_points > kLidarMaxPoints) return UNINA_ERR_ARG;
+  if (!cloud_limits_ok(device_id, max_points)) return UNINA_ERR_ARG;
   unina_ground* g = new (std::nothrow) unina_ground();
   if (!g) return UNINA_ERR_IO;
   g->device = device_id;
@@ -298,30 +260,22 @@ extern "C" int unina_ground_create(int device_id, int max_points, unina_ground_t
 
 extern "C" void unina_ground_destroy(unina_ground_t* g) {
   if (!g) return;
-  if (g->d_mem) {
-    if (hipSetDevice(g->device) == hipSuccess) (void)hipDeviceSynchronize();
-    (void)hipFree(g->d_mem);
-  }
+  unina::workspace_release(g->device, g->d_mem);
   delete g;
 }
 
 extern "C" int unina_ground_filter_async(unina_ground_t* g, const unina_cloud* cloud, const float lidar_to_level[12],
                                          const unina_ground_params* p, void* d_out, hipStream_t stream) {
   using namespace unina;
-  if (!g || !cloud || !lidar_to_level || !p || !d_out || ((uintptr_t)d_out & 15)) return UNINA_ERR_ARG;
-  if (cloud->n_points < 0 || cloud->n_points > g->max_points || (cloud->n_points > 0 && !cloud->points)) return UNINA_ERR_ARG;
-  if (cloud->stride < 12 || cloud->stride % 4 != 0 || ((uintptr_t)cloud->points & 3)) return UNINA_ERR_ARG;
-  for (int i = 0; i < 12; ++i)
-    if (!unina::finite(lidar_to_level[i])) return UNINA_ERR_ARG;
-  if (!params_ok(p)) return UNINA_ERR_ARG;
+  if (!g || !p || !d_out || ((uintptr_t)d_out & 15)) return UNINA_ERR_ARG;
+  if (!cloud_ok(cloud, g->max_points) || !extrinsic_ok(lidar_to_level) || !params_ok(p)) return UNINA_ERR_ARG;
   const int n = cloud->n_points;
   {
     const uintptr_t in = (uintptr_t)cloud->points, out = (uintptr_t)d_out;
     if (n > 0 && in < out + (uintptr_t)n * 16u && out < in + (uintptr_t)n * (uintptr_t)cloud->stride) return UNINA_ERR_ARG;
   }
-  if (const int rc = ground_ensure(g)) return rc;
-
   Workspace ws;
+  if (const int rc = workspace_ensure(g->device, &g->d_mem, workspace_layout(g, 0, &ws))) return rc;   // allocated on first use
   workspace_layout(g, (uintptr_t)g->d_mem, &ws);
   GroundGrid grid;
   for (int i = 0; i < 12; ++i) grid.m[i] = lidar_to_level[i];
@@ -334,13 +288,10 @@ extern "C" int unina_ground_filter_async(unina_ground_t* g, const unina_cloud* c
   if (hipMemsetAsync(ws.cellmin, 0xff, cells * sizeof(uint32_t), stream) != hipSuccess) return UNINA_ERR_HIP;
   if (hipMemsetAsync(ws.header, 0, sizeof(unina_ground_header), stream) != hipSuccess) return UNINA_ERR_HIP;
   const unsigned char* points = static_cast<const unsigned char*>(cloud->points);
-  const bool vec = cloud->stride % 16 == 0 && ((uintptr_t)points & 15) == 0;
+  const bool vec = cloud_vec16(cloud);
   if (n > 0) {
     const dim3 blocks((unsigned)((n + kSeedBlock - 1) / kSeedBlock));
-    if (vec)
-      hipLaunchKernelGGL(ground_seed_kernel<true>, blocks, dim3(kSeedBlock), 0, stream, points, n, cloud->stride, grid, ws.cellz, ws.cellmin);
-    else
-      hipLaunchKernelGGL(ground_seed_kernel<false>, blocks, dim3(kSeedBlock), 0, stream, points, n, cloud->stride, grid, ws.cellz, ws.cellmin);
+    UNINA_LAUNCH_VEC(vec, ground_seed_kernel, blocks, dim3(kSeedBlock), stream, points, n, cloud->stride, grid, ws.cellz, ws.cellmin);
     if (launch_status() != UNINA_OK) return UNINA_ERR_HIP;
   }
   hipLaunchKernelGGL(ground_envelope_kernel, dim3((unsigned)((p->nx + kTileX - 1) / kTileX), (unsigned)((p->ny + kTileY - 1) / kTileY)),
@@ -354,12 +305,8 @@ extern "C" int unina_ground_filter_async(unina_ground_t* g, const unina_cloud* c
   hipLaunchKernelGGL(ground_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, ws.kept, ws.offset, n_blocks, n, ws.header);
   if (launch_status() != UNINA_OK) return UNINA_ERR_HIP;
   uint4* out = static_cast<uint4*>(d_out);
-  if (vec)
-    hipLaunchKernelGGL(ground_scatter_kernel<true>, dim3((unsigned)n_blocks), dim3(kPtBlock), 0, stream, points, n, cloud->stride,
-                       p->keep_unknown, ws.labels, ws.h, ws.offset, ws.header, out);
-  else
-    hipLaunchKernelGGL(ground_scatter_kernel<false>, dim3((unsigned)n_blocks), dim3(kPtBlock), 0, stream, points, n, cloud->stride,
-                       p->keep_unknown, ws.labels, ws.h, ws.offset, ws.header, out);
+  UNINA_LAUNCH_VEC(vec, ground_scatter_kernel, dim3((unsigned)n_blocks), dim3(kPtBlock), stream, points, n, cloud->stride, p->keep_unknown,
+                   ws.labels, ws.h, ws.offset, ws.header, out);
   return launch_status();
 }
 

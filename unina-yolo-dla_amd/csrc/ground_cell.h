@@ -1,5 +1,5 @@
 // ground_cell.h -- the per-point and per-cell halves of unina_ground_filter_async (include/unina_mi355.h "ground removal from a
-// LiDAR sweep"), as __host__ __device__ functions (csrc/hd.h): the LiDAR -> level transform (csrc/lidar_project.h's expression),
+// LiDAR sweep"), as __host__ __device__ functions (csrc/hd.h): the LiDAR -> level transform (csrc/cloud_io.h),
 // the grid cell of a point, the ordered key of a height, one term of the envelope and the label. csrc/ground.hip calls them on
 // the device, tests/ground_cell_host.cpp sweeps them on the host, ground.ground_numpy is their numpy twin. fp32 throughout, one
 // rounding per operation in the order written: every translation unit that includes this header is compiled with
@@ -8,11 +8,7 @@
 #ifndef UNINA_GROUND_CELL_H
 #define UNINA_GROUND_CELL_H
 
-#include <stdint.h>
-#include <string.h>
-
-#include "hd.h"
-#include "lidar_project.h"
+#include "cloud_io.h"
 
 namespace unina {
 
@@ -37,16 +33,9 @@ struct GroundPoint {
   int seed;
 };
 
-UNINA_HD uint32_t ground_bits(float f) {
-  uint32_t b;
-  memcpy(&b, &f, 4);
-  return b;
-}
-UNINA_HD float ground_float(uint32_t b) {
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
+// the casts of csrc/cloud_io.h under the names this header has always given them
+UNINA_HD uint32_t ground_bits(float f) { return float_bits(f); }
+UNINA_HD float ground_float(uint32_t b) { return bits_float(b); }
 
 // unsigned order of keys = order of finite floats, -0.0 below +0.0
 UNINA_HD uint32_t ground_key(float f) {
@@ -58,9 +47,9 @@ UNINA_HD float ground_unkey(uint32_t k) { return ground_float((k >> 31) ? (k ^ 0
 // one point: its cell, the bits of its height in the level frame, and whether it may found a ground height
 UNINA_HD GroundPoint ground_point(const GroundGrid& g, float x, float y, float z) {
   GroundPoint p;
-  const float xl = lidar_transform_row(g.m, x, y, z);
-  const float yl = lidar_transform_row(g.m + 4, x, y, z);
-  const float zl = lidar_transform_row(g.m + 8, x, y, z);
+  const float xl = cloud_transform_row(g.m, x, y, z);
+  const float yl = cloud_transform_row(g.m + 4, x, y, z);
+  const float zl = cloud_transform_row(g.m + 8, x, y, z);
   p.cell = -1;
   p.z_bits = ground_bits(zl);
   p.seed = 0;

@@ -17,11 +17,11 @@
 #include <climits>
 
 #include "kernels.h"
+#include "wave_block.h"
 
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
 

@@ -1,7 +1,7 @@
 // Detections lifted to 3-D cone positions from a LiDAR sweep on the device: one call per frame behind the call that produced the
 // records (include/unina_mi355.h "3-D localisation from a LiDAR sweep"; localize.locate_lidar_numpy is the definition, bit for
 // bit). The per-point half -- transform, projection, pixel, key -- is csrc/lidar_project.h; the window, the point and the checks
-// are the depth route's (csrc/locate_window.h, csrc/locate_checks.h).
+// are the depth route's (csrc/locate_window.h, csrc/locate_checks.h), the cloud's and the workspace's plumbing csrc/cloud_io.h.
 //
 // The work is N points (30 000 .. 260 000 a sweep) against at most 1024 windows, so the points are first sorted by image cell
 // (32 x 32 pixels) with a counting sort, and a record then reads only the cells its window touches. Four kernels, enqueued by the
@@ -43,16 +43,12 @@ struct unina_lidar {
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kPtBlock = 256;                 // project, scatter
-constexpr int kScanBlock = 1024;
-constexpr int kScanWaves = kScanBlock / kWave;
-constexpr int kScanPer = 4;                   // cells a thread scans in a pass
 constexpr int kSelWaves = 4;
 constexpr int kSelBlock = kSelWaves * kWave;
 constexpr int kCache = 8192;                  // valid keys of one record kept in LDS between the passes (32 KB)
 
-static_assert(kLidarMaxDim == UNINA_LIDAR_MAX_DIM && kLidarMaxPoints == UNINA_LIDAR_MAX_POINTS, "header limits");
+static_assert(kLidarMaxDim == UNINA_LIDAR_MAX_DIM && kCloudMaxPoints == UNINA_LIDAR_MAX_POINTS, "header limits");
 static_assert(kLidarMaxDim <= 1 << 16, "a sorted entry packs u and v into 16 bits each");
 static_assert(MAX_DETECTIONS % kSelWaves == 0, "slots per workgroup");
 static_assert(sizeof(unina_cone3d) == 32 && sizeof(GpuDetection) == 32, "record layouts");
@@ -69,23 +65,16 @@ struct Workspace {
   uint32_t* offset;   // cells + 1: exclusive prefix of count
 };
 
-size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// the arrays at `base` (what hipMalloc returned: 256-byte aligned); returns the bytes they take
+// the arrays at `base`; returns the bytes they take
 size_t workspace_layout(const unina_lidar* l, uintptr_t base, Workspace* w) {
   const size_t np = (size_t)l->max_points;
   const size_t cells = (size_t)lidar_cells(l->max_width) * (size_t)lidar_cells(l->max_height);
   size_t at = 0;
-  w->pixels = reinterpret_cast<uint4*>(base + at);
-  at += round16(np * sizeof(uint4));
-  w->sorted = reinterpret_cast<uint2*>(base + at);
-  at += round16(np * sizeof(uint2));
-  w->pos = reinterpret_cast<uint32_t*>(base + at);
-  at += round16(np * sizeof(uint32_t));
-  w->count = reinterpret_cast<uint32_t*>(base + at);
-  at += round16((cells + kScanPer) * sizeof(uint32_t));
-  w->offset = reinterpret_cast<uint32_t*>(base + at);
-  at += round16((cells + 1) * sizeof(uint32_t));
+  w->pixels = carve<uint4>(base, at, np);
+  w->sorted = carve<uint2>(base, at, np);
+  w->pos = carve<uint32_t>(base, at, np);
+  w->count = carve<uint32_t>(base, at, cells + kScanPer);
+  w->offset = carve<uint32_t>(base, at, cells + 1);
   return at;
 }
 
@@ -98,16 +87,9 @@ __global__ void __launch_bounds__(kPtBlock) lidar_project_kernel(const unsigned 
   const int lane = (int)threadIdx.x & (kWave - 1);
   int cell = -1;   // no lane leaves before the fold: every lane takes part in its shuffles
   if (i < n) {
-    const unsigned char* src = points + (size_t)i * (size_t)stride;
-    float x, y, z;
-    if (VEC) {
-      const float4 q = *reinterpret_cast<const float4*>(src);
-      x = q.x; y = q.y; z = q.z;
-    } else {
-      const float* f = reinterpret_cast<const float*>(src);
-      x = f[0]; y = f[1]; z = f[2];
-    }
-    const LidarPixel p = lidar_project(cam, x, y, z);
+    uint32_t x, y, z;
+    load_xyz<VEC>(points, i, stride, &x, &y, &z);
+    const LidarPixel p = lidar_project(cam, bits_float(x), bits_float(y), bits_float(z));
     pixels[i] = make_uint4((uint32_t)p.u, (uint32_t)p.v, p.key, (uint32_t)p.projectable);
     if (p.projectable) cell = lidar_cell(p.u, p.v, cells_x);   // < cells_x * cells_y: the pixel is inside the image
   }
@@ -115,14 +97,13 @@ __global__ void __launch_bounds__(kPtBlock) lidar_project_kernel(const unsigned 
   unsigned long long todo = __ballot(cell >= 0);
   uint32_t mine = 0u;
   while (todo) {   // wave-uniform
-    const int leader = __ffsll((long long)todo) - 1;
-    const int c = __shfl(cell, leader, kWave);
-    const unsigned long long same = __ballot(cell == c);
+    KeyGroup g;
+    wave_first_group(todo, cell, g);
     uint32_t base = 0u;
-    if (lane == leader) base = atomicAdd(&count[c], (uint32_t)__popcll(same));
-    base = (uint32_t)__shfl((int)base, leader, kWave);
-    if (cell == c) mine = base + (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-    todo &= ~same;
+    if (lane == g.leader) base = atomicAdd(&count[g.key], (uint32_t)__popcll(g.lanes));
+    base = (uint32_t)__shfl((int)base, g.leader, kWave);
+    if (cell == g.key) mine = base + (uint32_t)__popcll(g.lanes & ((1ull << lane) - 1ull));
+    todo &= ~g.lanes;
   }
   if (cell >= 0) pos[i] = mine;
 }
@@ -374,17 +355,6 @@ __global__ void __launch_bounds__(kSelBlock) lidar_select_kernel(const GpuDetect
   }
 }
 
-// allocates the workspace on first use
-int lidar_ensure(unina_lidar* l) {
-  if (hipSetDevice(l->device) != hipSuccess) return UNINA_ERR_HIP;
-  if (l->d_mem) return UNINA_OK;
-  Workspace w;
-  void* mem = nullptr;
-  if (hipMalloc(&mem, workspace_layout(l, 0, &w)) != hipSuccess) return UNINA_ERR_HIP;
-  l->d_mem = static_cast<unsigned char*>(mem);
-  return UNINA_OK;
-}
-
 }  // namespace
 }  // namespace unina
 
@@ -392,7 +362,7 @@ extern "C" int unina_lidar_create(int device_id, int max_points, int max_width, 
   using namespace unina;
   if (!out) return UNINA_ERR_ARG;
   *out = nullptr;
-  if (device_id < 0 || max_points < 1 || max_points > kLidarMaxPoints) return UNINA_ERR_ARG;
+  if (!cloud_limits_ok(device_id, max_points)) return UNINA_ERR_ARG;
   if (max_width < 1 || max_width > kLidarMaxDim || max_height < 1 || max_height > kLidarMaxDim) return UNINA_ERR_ARG;
   unina_lidar* l = new (std::nothrow) unina_lidar();
   if (!l) return UNINA_ERR_IO;
@@ -406,10 +376,7 @@ extern "C" int unina_lidar_create(int device_id, int max_points, int max_width, 
 
 extern "C" void unina_lidar_destroy(unina_lidar_t* l) {
   if (!l) return;
-  if (l->d_mem) {
-    if (hipSetDevice(l->device) == hipSuccess) (void)hipDeviceSynchronize();
-    (void)hipFree(l->d_mem);
-  }
+  unina::workspace_release(l->device, l->d_mem);
   delete l;
 }
 
@@ -417,16 +384,12 @@ extern "C" int unina_locate_lidar_async(unina_lidar_t* l, const GpuDetection* d_
                                         const float lidar_to_cam[12], const unina_pinhole* cam, int width, int height,
                                         const unina_lidar_params* p, unina_cone3d* d_out, hipStream_t stream) {
   using namespace unina;
-  if (!l || !cloud || !lidar_to_cam || !p || !record_io_ok(d_dets, d_count, d_out)) return UNINA_ERR_ARG;
-  if (cloud->n_points < 0 || cloud->n_points > l->max_points || (cloud->n_points > 0 && !cloud->points)) return UNINA_ERR_ARG;
-  if (cloud->stride < 12 || cloud->stride % 4 != 0 || ((uintptr_t)cloud->points & 3)) return UNINA_ERR_ARG;
+  if (!l || !p || !record_io_ok(d_dets, d_count, d_out)) return UNINA_ERR_ARG;
+  if (!cloud_ok(cloud, l->max_points) || !extrinsic_ok(lidar_to_cam)) return UNINA_ERR_ARG;
   if (width < 1 || width > l->max_width || height < 1 || height > l->max_height) return UNINA_ERR_ARG;
-  for (int i = 0; i < 12; ++i)
-    if (!unina::finite(lidar_to_cam[i])) return UNINA_ERR_ARG;
   if (!pinhole_ok(cam) || !window_params_ok(p->sx, p->sy, p->shrink, p->min_depth, p->max_depth) || p->min_valid < 0) return UNINA_ERR_ARG;
-  if (const int rc = lidar_ensure(l)) return rc;
-
   Workspace ws;
+  if (const int rc = workspace_ensure(l->device, &l->d_mem, workspace_layout(l, 0, &ws))) return rc;   // allocated on first use
   workspace_layout(l, (uintptr_t)l->d_mem, &ws);
   const int n = cloud->n_points;
   const int cells_x = lidar_cells(width), n_cells = cells_x * lidar_cells(height);
@@ -450,12 +413,8 @@ extern "C" int unina_locate_lidar_async(unina_lidar_t* l, const GpuDetection* d_
   const unsigned char* points = static_cast<const unsigned char*>(cloud->points);
   const dim3 per_point((unsigned)((n + kPtBlock - 1) / kPtBlock));
   if (n > 0) {
-    if (cloud->stride % 16 == 0 && ((uintptr_t)points & 15) == 0)
-      hipLaunchKernelGGL(lidar_project_kernel<true>, per_point, dim3(kPtBlock), 0, stream, points, n, cloud->stride, c, cells_x, ws.pixels,
-                         ws.pos, ws.count);
-    else
-      hipLaunchKernelGGL(lidar_project_kernel<false>, per_point, dim3(kPtBlock), 0, stream, points, n, cloud->stride, c, cells_x, ws.pixels,
-                         ws.pos, ws.count);
+    UNINA_LAUNCH_VEC(cloud_vec16(cloud), lidar_project_kernel, per_point, dim3(kPtBlock), stream, points, n, cloud->stride, c, cells_x,
+                     ws.pixels, ws.pos, ws.count);
     if (launch_status() != UNINA_OK) return UNINA_ERR_HIP;
   }
   hipLaunchKernelGGL(lidar_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, ws.count, ws.offset, n_cells);

@@ -1,20 +1,16 @@
 // lidar_project.h -- the per-point half of unina_locate_lidar_async (include/unina_mi355.h "3-D localisation from a LiDAR sweep"),
-// as __host__ __device__ functions (csrc/hd.h): the LiDAR -> camera transform, the pinhole projection, the pixel, the key and
+// as __host__ __device__ functions (csrc/hd.h): the LiDAR -> camera transform (csrc/cloud_io.h), the pinhole projection, the pixel, the key and
 // the image cell of one point. csrc/lidar.hip calls them on the device, tests/lidar_project_host.cpp sweeps them on the host,
 // localize.project_lidar_numpy is their numpy twin. fp32 throughout, one rounding per operation in the order written: every
 // translation unit that includes this header is compiled with -ffp-contract=off.
 #ifndef UNINA_LIDAR_PROJECT_H
 #define UNINA_LIDAR_PROJECT_H
 
-#include <stdint.h>
-#include <string.h>
-
-#include "hd.h"
+#include "cloud_io.h"
 
 namespace unina {
 
 constexpr int kLidarMaxDim = 16384;          // width / height limit: a pixel coordinate fits 14 bits, (float)width is exact
-constexpr int kLidarMaxPoints = 1 << 22;
 constexpr int kLidarCellShift = 5;           // image cells of 32 x 32 pixels
 constexpr int kLidarMaxCells = (kLidarMaxDim >> kLidarCellShift) * (kLidarMaxDim >> kLidarCellShift);
 
@@ -34,19 +30,15 @@ struct LidarPixel {   // unina_lidar_pixel
 UNINA_HD int lidar_cells(int pixels) { return (pixels + (1 << kLidarCellShift) - 1) >> kLidarCellShift; }
 UNINA_HD int lidar_cell(int u, int v, int cells_x) { return (v >> kLidarCellShift) * cells_x + (u >> kLidarCellShift); }
 
-// one row (r0, r1, r2, t) of a row-major 3 x 4 [R|t] applied to a point of the LiDAR frame; csrc/ground_cell.h takes the sweep
-// into its level frame with the same expression
-UNINA_HD float lidar_transform_row(const float* row, float x, float y, float z) { return ((row[0] * x + row[1] * y) + row[2] * z) + row[3]; }
-
 // one point: all-zero where it is not projectable
 UNINA_HD LidarPixel lidar_project(const LidarCamera& c, float x, float y, float z) {
   LidarPixel p;
   p.u = p.v = 0;
   p.key = 0u;
   p.projectable = 0;
-  const float xc = lidar_transform_row(c.m, x, y, z);
-  const float yc = lidar_transform_row(c.m + 4, x, y, z);
-  const float zc = lidar_transform_row(c.m + 8, x, y, z);
+  const float xc = cloud_transform_row(c.m, x, y, z);
+  const float yc = cloud_transform_row(c.m + 4, x, y, z);
+  const float zc = cloud_transform_row(c.m + 8, x, y, z);
   if (!finite(xc) || !finite(yc) || !finite(zc) || !(zc > 0.0f)) return p;
   const float u = (c.fx * xc) / zc + c.cx;
   const float v = (c.fy * yc) / zc + c.cy;

@@ -24,11 +24,11 @@
 
 #include "locate_checks.h"
 #include "radix_select.h"
+#include "wave_block.h"
 
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kLocWaves = 4;
 constexpr int kLocBlock = kLocWaves * kWave;
 constexpr int kBins = kRadixBins;

@@ -11,11 +11,11 @@
 #include "mining.h"
 
 #include "kernels.h"
+#include "wave_block.h"
 
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kWaves = kMineBlock / kWave;
 
 __device__ __forceinline__ float wave_max(float v) {

@@ -37,11 +37,11 @@
 
 #include "locate_checks.h"
 #include "stereo_match.h"
+#include "wave_block.h"
 
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kStWaves = 4;
 constexpr int kStBlock = kStWaves * kWave;
 constexpr int kOwned = kStereoMaxDisparities / kStBlock;   // disparities a lane can own

@@ -47,7 +47,6 @@ struct unina_tracker {
 namespace unina {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kTrkBlock = 1024;
 constexpr int kTrkWaves = kTrkBlock / kWave;
 

@@ -399,6 +399,21 @@ def _addr(t):
     return t if isinstance(t, int) else _ptr(t)
 
 
+def as_struct(cls, make, params):
+    """`params` as a `cls`: the struct itself, a dict of `make`'s arguments, or a tuple in the struct's order."""
+    if isinstance(params, cls):
+        return params
+    return make(**params) if isinstance(params, dict) else make(*params)
+
+
+def device_view(address: int, count: int, typestr: str = "|u1", device: int = 0):
+    """A CUDA tensor over `count` elements of `typestr` ("|u1" bytes, "<i4" words) at a device address: torch wraps the address,
+    nothing is copied."""
+    class View:
+        __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (address, False), "version": 2}
+    return _torch().as_tensor(View(), device=f"cuda:{device}")
+
+
 def _raise_on(rc: int, what: str) -> None:
     if rc:
         raise EngineError(f"{what} failed [{ERRORS.get(rc, rc)}]")

@@ -11,9 +11,9 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import (GROUND_HEADER_DTYPE, GROUND_MAX_REACH, GROUND_MAX_SIDE, Cloud, GroundParams, _raise_on, _stream_ptr,
-                     _torch, load_library, read_records)
-from .localize import DeviceLidarLocator, as_extrinsic
+from .engine import (GROUND_HEADER_DTYPE, GROUND_MAX_REACH, GROUND_MAX_SIDE, GroundParams, _raise_on, _stream_ptr, _torch, as_struct,
+                     device_view, read_records)
+from .localize import SweepStage, as_extrinsic, check_points, transform_numpy
 
 F = np.float32
 EMPTY = np.uint32(0xffffffff)          # no finite float's key: a cell without a seed, a cell without an envelope
@@ -32,11 +32,7 @@ def make_ground_params(x_min=0.0, y_min=-20.0, cell=0.5, nx=128, ny=80, z_lo=-0.
 
 def as_ground_params(params) -> GroundParams:
     """A GroundParams, a dict of make_ground_params' arguments, or a tuple in the struct's order."""
-    if isinstance(params, GroundParams):
-        return params
-    if isinstance(params, dict):
-        return make_ground_params(**params)
-    return make_ground_params(*params)
+    return as_struct(GroundParams, make_ground_params, params)
 
 
 def key_numpy(values) -> np.ndarray:
@@ -81,17 +77,12 @@ def ground_numpy(points, lidar_to_level, params) -> dict:
     header (one GROUND_HEADER_DTYPE record) and out (float32 [n, 4]: the kept points' x, y, z, h first, NaN words behind)."""
     p, m = as_ground_params(params), as_extrinsic(lidar_to_level)
     check_params(p)
-    pts = np.asarray(points)
-    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
-        raise ValueError("points must be a [n, >= 3] float32 array")
+    pts = check_points(points)
     if not np.isfinite(m).all():
         raise ValueError("lidar_to_level must be finite")
     n, nx, ny = len(pts), p.nx, p.ny
-    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
     with np.errstate(all="ignore"):
-        xl = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
-        yl = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
-        zl = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+        xl, yl, zl = transform_numpy(m, pts)
         fx = (xl - F(p.x_min)) / F(p.cell)
         fy = (yl - F(p.y_min)) / F(p.cell)
         in_grid = np.isfinite(xl) & np.isfinite(yl) & np.isfinite(zl) & (fx >= F(0)) & (fx < F(nx)) & (fy >= F(0)) & (fy < F(ny))   # a NaN fails
@@ -126,41 +117,25 @@ def ground_numpy(points, lidar_to_level, params) -> dict:
 
 
 def device_bytes(address: int, n_bytes: int, device: int = 0):
-    """A uint8 CUDA tensor over n_bytes bytes at a device address: torch wraps the address, nothing is copied."""
-    class Bytes:
-        __cuda_array_interface__ = {"shape": (n_bytes,), "typestr": "|u1", "data": (address, False), "version": 2}
-    return _torch().as_tensor(Bytes(), device=f"cuda:{device}")
+    """engine.device_view of bytes, under the name callers of this module know."""
+    return device_view(address, n_bytes, "|u1", device)
 
 
-class DeviceGroundFilter:
+class DeviceGroundFilter(SweepStage):
     """unina_ground_* (csrc/ground.hip): one call per sweep in front of DeviceLidarLocator.update_async. Holds the handle (its device
     workspace is bounded by max_points and the largest grid) and the max_points x 16-byte output buffer `out`."""
 
     def __init__(self, max_points: int = 1 << 18, device: int = 0):
         torch = _torch()
-        self.L = load_library()
-        self.device = device
-        self.h = C.c_void_p()
-        _raise_on(self.L.unina_ground_create(device, int(max_points), C.byref(self.h)), "unina_ground_create")
+        self._create(device, "unina_ground_create", "unina_ground_destroy", max_points)
         self.out = torch.zeros((int(max_points), 16), dtype=torch.uint8, device=f"cuda:{device}")
-        self._keep = None        # the cloud of the call in flight
-        self._n_points = 0       # of the last call
         self._grid = (0, 0)      # nx, ny of the last call
-
-    def close(self):
-        if self.h:
-            self.L.unina_ground_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
 
     def filter_async(self, points, lidar_to_level, params, stream=None):
         """Enqueues the kernels; nothing is synchronised. points: a Cloud or a tensor DeviceLidarLocator.describe() takes. Returns
         the filtered cloud, a [n_points, 16] uint8 view of `out`: what DeviceLidarLocator.update_async takes as its cloud."""
-        self._keep = points
-        cloud = points if isinstance(points, Cloud) else DeviceLidarLocator.describe(points)
+        cloud, m = self._marshal(points, lidar_to_level)
         p = as_ground_params(params)
-        m = (C.c_float * 12)(*as_extrinsic(lidar_to_level).tolist())
         _raise_on(self.L.unina_ground_filter_async(self.h, C.byref(cloud), C.byref(m), C.byref(p), self.out.data_ptr(), _stream_ptr(stream)),
                   "unina_ground_filter_async")
         self._n_points, self._grid = cloud.n_points, (p.nx, p.ny)
@@ -176,7 +151,7 @@ class DeviceGroundFilter:
         """Synchronises `stream`; returns (header, out): the GROUND_HEADER_DTYPE record and the float32 [n_points, 4] entries of
         the last call."""
         header_at = self.buffers()[3]
-        header, out = read_records(stream, (device_bytes(header_at, 32, self.device), GROUND_HEADER_DTYPE),
+        header, out = read_records(stream, (device_view(header_at, 32, device=self.device), GROUND_HEADER_DTYPE),
                                    (self.out[:self._n_points].reshape(-1), np.float32))
         self._keep = None
         return header, out.reshape(-1, 4)
@@ -185,17 +160,17 @@ class DeviceGroundFilter:
         """Synchronises `stream`; returns the label byte of every point of the last call, in point order."""
         if self._n_points == 0:
             return np.zeros(0, dtype=np.uint8)
-        labels, = read_records(stream, (device_bytes(self.buffers()[0], self._n_points, self.device), np.uint8))
+        labels, = read_records(stream, (device_view(self.buffers()[0], self._n_points, device=self.device), np.uint8))
         return labels
 
     def read_grids(self, stream=None):
         """Synchronises `stream`; returns (cellmin, ground): the uint32 [ny, nx] keys of the last call."""
         nx, ny = self._grid
         _, cellmin_at, ground_at, _ = self.buffers()
-        cellmin, ground = read_records(stream, (device_bytes(cellmin_at, 4 * nx * ny, self.device), np.uint32),
-                                       (device_bytes(ground_at, 4 * nx * ny, self.device), np.uint32))
+        cellmin, ground = read_records(stream, (device_view(cellmin_at, 4 * nx * ny, device=self.device), np.uint32),
+                                       (device_view(ground_at, 4 * nx * ny, device=self.device), np.uint32))
         return cellmin.reshape(ny, nx), ground.reshape(ny, nx)
 
 
 __all__ = ["ground_numpy", "envelope_numpy", "key_numpy", "unkey_numpy", "make_ground_params", "as_ground_params", "check_params",
-           "DeviceGroundFilter", "device_bytes", "EMPTY", "NAN_WORD", "OUTSIDE", "UNKNOWN", "GROUND", "OBJECT", "ABOVE"]
+           "DeviceGroundFilter", "device_bytes", "device_view", "EMPTY", "NAN_WORD", "OUTSIDE", "UNKNOWN", "GROUND", "OBJECT", "ABOVE"]

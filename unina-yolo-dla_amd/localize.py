@@ -16,8 +16,8 @@ import numpy as np
 
 from .engine import (CONE3D_DTYPE, DEPTH_F32, DEPTH_U16, LIDAR_MAX_DIM, LIDAR_PIXEL_DTYPE, MAX_DETECTIONS,
                      STEREO_MATCH_DTYPE, STEREO_MAX_DISPARITIES, STEREO_MAX_SIDE, Cloud, Depth, EngineError, LidarParams, LocateParams,
-                     Pinhole, StereoPair, StereoParams, _addr, _raise_on, _stream_ptr, _torch, clamp_count, det_buffer_ptrs,
-                     load_library, read_records)
+                     Pinhole, StereoPair, StereoParams, _addr, _raise_on, _stream_ptr, _torch, as_struct, clamp_count, det_buffer_ptrs,
+                     device_view, load_library, read_records)
 
 F = np.float32
 
@@ -29,11 +29,7 @@ def as_pinhole(cam) -> Pinhole:
 
 def as_params(params) -> LocateParams:
     """A LocateParams, a dict of its fields, or (sx, sy, shrink, min_depth, max_depth, max_side, min_valid)."""
-    if isinstance(params, LocateParams):
-        return params
-    if isinstance(params, dict):
-        return LocateParams(**params)
-    return LocateParams(*params)
+    return as_struct(LocateParams, LocateParams, params)
 
 
 def _axis(c, h, n: int, max_side: int):
@@ -177,11 +173,7 @@ def make_stereo_params(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.3, max_depth=40.0
 
 def as_stereo_params(params) -> StereoParams:
     """A StereoParams, a dict of make_stereo_params' arguments, or a tuple in the struct's order."""
-    if isinstance(params, StereoParams):
-        return params
-    if isinstance(params, dict):
-        return make_stereo_params(**params)
-    return make_stereo_params(*params)
+    return as_struct(StereoParams, make_stereo_params, params)
 
 
 def stereo_range_numpy(fx, baseline, min_depth, max_depth, width: int):
@@ -337,11 +329,7 @@ def make_lidar_params(sx=1.0, sy=1.0, shrink=0.5, min_depth=0.3, max_depth=40.0,
 
 def as_lidar_params(params) -> LidarParams:
     """A LidarParams, a dict of make_lidar_params' arguments, or a tuple in the struct's order."""
-    if isinstance(params, LidarParams):
-        return params
-    if isinstance(params, dict):
-        return make_lidar_params(**params)
-    return make_lidar_params(*params)
+    return as_struct(LidarParams, make_lidar_params, params)
 
 
 def as_extrinsic(lidar_to_cam) -> np.ndarray:
@@ -352,22 +340,34 @@ def as_extrinsic(lidar_to_cam) -> np.ndarray:
     return m
 
 
+def check_points(points) -> np.ndarray:
+    """What every twin of a sweep stage takes: a [n, >= 3] float32 array, x, y, z in the first three columns; ValueError otherwise."""
+    pts = np.asarray(points)
+    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError("points must be a [n, >= 3] float32 array")
+    return pts
+
+
+def transform_numpy(m, pts):
+    """csrc/cloud_io.h cloud_transform_row for every point and the three rows of the extrinsic m (12 np.float32): the three
+    transformed columns, each sum rounded in the order written. The caller holds np.errstate."""
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    return (((m[0] * x + m[1] * y) + m[2] * z) + m[3],
+            ((m[4] * x + m[5] * y) + m[6] * z) + m[7],
+            ((m[8] * x + m[9] * y) + m[10] * z) + m[11])
+
+
 def project_lidar_numpy(points, lidar_to_cam, cam, width: int, height: int, min_depth, max_depth) -> np.ndarray:
     """csrc/lidar_project.h lidar_project for every point. points: [n, >= 3] float32, x, y, z in the first three columns (the
     others are not read). Returns n LIDAR_PIXEL_DTYPE records in point order, all-zero where a point is not projectable."""
     cam, m = as_pinhole(cam), as_extrinsic(lidar_to_cam)
     if not (1 <= width <= LIDAR_MAX_DIM and 1 <= height <= LIDAR_MAX_DIM):
         raise ValueError(f"width and height must lie in 1..{LIDAR_MAX_DIM}")
-    pts = np.asarray(points)
-    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
-        raise ValueError("points must be a [n, >= 3] float32 array")
-    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    pts = check_points(points)
     fx, fy, cx, cy = F(cam.fx), F(cam.fy), F(cam.cx), F(cam.cy)
     out = np.zeros(len(pts), dtype=LIDAR_PIXEL_DTYPE)
     with np.errstate(all="ignore"):
-        xc = ((m[0] * x + m[1] * y) + m[2] * z) + m[3]
-        yc = ((m[4] * x + m[5] * y) + m[6] * z) + m[7]
-        zc = ((m[8] * x + m[9] * y) + m[10] * z) + m[11]
+        xc, yc, zc = transform_numpy(m, pts)
         u = (fx * xc) / zc + cx
         v = (fy * yc) / zc + cy
         ok = np.isfinite(xc) & np.isfinite(yc) & np.isfinite(zc) & (zc > F(0))
@@ -413,33 +413,46 @@ def locate_lidar_numpy(dets, count: int, points, lidar_to_cam, cam, width: int, 
 
 
 def device_words(address: int, n_words: int, device: int = 0):
-    """An int32 CUDA tensor over n_words words at a device address: torch wraps the address, nothing is copied."""
-    class Words:
-        __cuda_array_interface__ = {"shape": (n_words,), "typestr": "<i4", "data": (address, False), "version": 2}
-    return _torch().as_tensor(Words(), device=f"cuda:{device}")
+    """engine.device_view of int32 words, under the name callers of this module know."""
+    return device_view(address, n_words, "<i4", device)
 
 
-class DeviceLidarLocator:
+class SweepStage:
+    """What the handles of the stages that take a LiDAR sweep share (DeviceLidarLocator, ground.DeviceGroundFilter): the handle
+    of a named create / destroy pair of the ABI, the cloud of the call in flight, and a cloud and an extrinsic as the ABI takes them."""
+
+    def _create(self, device: int, create: str, destroy: str, *limits):
+        self.L = load_library()
+        self.device = device
+        self._destroy = destroy
+        self.h = C.c_void_p()
+        _raise_on(getattr(self.L, create)(device, *[int(v) for v in limits], C.byref(self.h)), create)
+        self._keep = None      # the cloud of the call in flight
+        self._n_points = 0     # of the last call
+
+    def close(self):
+        if self.h:
+            getattr(self.L, self._destroy)(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def _marshal(self, points, extrinsic):
+        """(unina_cloud, float[12]) of a Cloud or a tensor DeviceLidarLocator.describe() takes, and 12 values; keeps the cloud alive."""
+        self._keep = points
+        cloud = points if isinstance(points, Cloud) else DeviceLidarLocator.describe(points)
+        return cloud, (C.c_float * 12)(*as_extrinsic(extrinsic).tolist())
+
+
+class DeviceLidarLocator(SweepStage):
     """unina_lidar_* (csrc/lidar.hip): one call per frame behind the call that produced the records. Holds the handle (its device
     workspace is bounded by max_points and the image limits) and the MAX_DETECTIONS-record output buffer `out`, which is what
     DeviceTracker.update_from_buffer takes."""
 
     def __init__(self, max_points: int = 1 << 18, max_width: int = 4096, max_height: int = 4096, device: int = 0):
         torch = _torch()
-        self.L = load_library()
-        self.device = device
-        self.h = C.c_void_p()
-        _raise_on(self.L.unina_lidar_create(device, int(max_points), int(max_width), int(max_height), C.byref(self.h)), "unina_lidar_create")
+        self._create(device, "unina_lidar_create", "unina_lidar_destroy", max_points, max_width, max_height)
         self.out = torch.zeros(MAX_DETECTIONS * CONE3D_DTYPE.itemsize, dtype=torch.uint8, device=f"cuda:{device}")
-        self._keep = None      # the cloud of the call in flight
-        self._n_points = 0     # of the last call
-
-    def close(self):
-        if self.h:
-            self.L.unina_lidar_destroy(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
 
     @staticmethod
     def describe(points, n_points=None) -> Cloud:
@@ -461,10 +474,8 @@ class DeviceLidarLocator:
     def update_async(self, d_dets, d_count, points, lidar_to_cam, cam, width: int, height: int, params, stream=None):
         """Enqueues the kernels; nothing is synchronised. d_dets / d_count: device addresses (or tensors) of the records and the
         count; points: a Cloud or a tensor describe() takes. Returns the cone tensor (bytes; read() gives the records)."""
-        self._keep = points
-        cloud = points if isinstance(points, Cloud) else self.describe(points)
+        cloud, m = self._marshal(points, lidar_to_cam)
         cam, p = as_pinhole(cam), as_lidar_params(params)
-        m = (C.c_float * 12)(*as_extrinsic(lidar_to_cam).tolist())
         _raise_on(self.L.unina_locate_lidar_async(self.h, _addr(d_dets), _addr(d_count), C.byref(cloud), C.byref(m), C.byref(cam), int(width),
                                                   int(height), C.byref(p), self.out.data_ptr(), _stream_ptr(stream)), "unina_locate_lidar_async")
         self._n_points = cloud.n_points
@@ -486,11 +497,11 @@ class DeviceLidarLocator:
             return np.zeros(0, dtype=LIDAR_PIXEL_DTYPE)
         address = C.c_void_p()
         _raise_on(self.L.unina_lidar_buffers(self.h, C.byref(address)), "unina_lidar_buffers")
-        words = device_words(address.value, 4 * self._n_points, self.device)
+        words = device_view(address.value, 4 * self._n_points, "<i4", self.device)
         pixels, = read_records(stream, (words, LIDAR_PIXEL_DTYPE))
         return pixels
 
 
 __all__ = ["locate_numpy", "window_numpy", "point_numpy", "DeviceLocator", "as_pinhole", "as_params", "locate_stereo_numpy", "make_stereo_params",
            "as_stereo_params", "stereo_range_numpy", "DeviceStereoLocator", "locate_lidar_numpy", "project_lidar_numpy", "make_lidar_params",
-           "as_lidar_params", "as_extrinsic", "DeviceLidarLocator"]
+           "as_lidar_params", "as_extrinsic", "check_points", "transform_numpy", "SweepStage", "DeviceLidarLocator"]
