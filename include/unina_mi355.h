@@ -747,8 +747,8 @@ int unina_lidar_buffers(unina_lidar_t *l, const unina_lidar_pixel **d_pixels);
  * Integer counters and integer minima only (no float atomics): two runs give identical bytes, and any permutation of the cloud
  * gives every point the same label and the same cellmin, g and header.
  * NOT covered: ground steeper than `rise` allows between neighbouring cells (a banked or sloped track beyond it is labelled
- * OBJECT or ABOVE), plane or line fitting, clustering of what is kept, motion de-skew, an estimate of lidar_to_level (the
- * caller's calibration or IMU supplies it). */
+ * OBJECT or ABOVE), plane or line fitting, motion de-skew, an estimate of lidar_to_level (the caller's calibration or IMU
+ * supplies it). Clustering of what is kept is unina_cluster_async below, which takes {n_points, 16, d_out} as its cloud. */
 #define UNINA_GROUND_MAX_SIDE  1024        /* nx, ny */
 #define UNINA_GROUND_MAX_REACH 4
 typedef struct { float x_min, y_min, cell; int nx, ny;
@@ -779,6 +779,71 @@ int unina_ground_filter_async(unina_ground_t *g, const unina_cloud *cloud, const
  * the header. A NULL argument is skipped. UNINA_ERR_STATE before the first unina_ground_filter_async. */
 int unina_ground_buffers(unina_ground_t *g, const uint8_t **d_labels, const uint32_t **d_cellmin, const uint32_t **d_ground,
                          const unina_ground_header **d_header);
+
+/* ------------------------------------------------------------------ cone candidates from a ground-free LiDAR sweep (behind
+ * unina_ground_filter_async, in front of unina_track_update_async: a cone the camera detector missed still becomes an object)
+ * A point cloud on the device (normally {n_points, 16, d_out} of the ground filter, whose NaN entries fall out by themselves) +
+ * the LiDAR -> level extrinsic + a grid + a gate -> the connected components of the occupied grid cells, their statistics, and
+ * those that pass the gate as GpuDetection + unina_cone3d records with a count: exactly what unina_track_update_async takes. One
+ * call enqueues everything (csrc/cluster.hip: two memsets, then mark, label, merge, flatten, scan, rank, cells, sums, finish,
+ * scan, emit) on the caller's stream; nothing is synchronised, nothing crosses to the host. cluster.cluster_numpy is the
+ * definition, decision for decision and bit for bit. Everything is fp32, each operation rounded once in the order written, never
+ * contracted; the divides are correctly rounded; every decision compares integers, or fp32 values of which none is a NaN.
+ *   point      xl, yl, zl, fx, fy, IN_GRID and the cell exactly as unina_ground_filter_async computes them (one expression in
+ *              csrc/ground_cell.h serves both), with this call's x_min, y_min, cell, nx, ny
+ *   occupied   a cell that holds at least one IN_GRID point
+ *   component  occupied cells joined under 8-connectivity; root = the smallest cell index of the component
+ *   statistics per component over its points: n_points; n_cells; x_lo / x_hi, y_lo / y_hi, z_lo / z_hi = the values of the
+ *              minimum / maximum key (the ground stage's key) of xl, yl, zl; Sx = the sum of (int)(fx * 256.0f), Sy likewise, as
+ *              64-bit integers (the product is exact, below 2^18 and not negative: the conversion truncates)
+ *   position   x = x_min + ((float)(Sx / n_points) * 0.00390625f) * cell, y likewise (an integer division; the conversion and the
+ *              first product are exact), z = z_lo
+ *   gate       CONE iff min_points <= n_points <= max_points and x_hi - x_lo <= max_width and y_hi - y_lo <= max_width and
+ *              min_height <= z_hi - z_lo <= max_height, each difference rounded once
+ *   table      one unina_cluster per component in ascending root; cone = 1 for CONE, else 0
+ *   records    the CONE components in ascending root go to slots 0, 1, ..; at most MAX_DETECTIONS are written (n_written), the
+ *              others are counted in n_dropped. GpuDetection: (x1, y1, x2, y2) = (x_lo, y_lo, x_hi, y_hi), a bird's-eye box in
+ *              metres of the level frame; confidence and class_id are the parameters'; valid = 1, _pad = 0. unina_cone3d:
+ *              (x, y, z), u = v = 0, n_valid = n_samples = n_points, valid = 1. *d_count = n_written. Every slot at and beyond
+ *              n_written is all-zero bytes in both arrays: all MAX_DETECTIONS entries are defined after every call
+ *   per point  the position of the point's component in the table, -1 for a point that is not IN_GRID
+ *   header     n_points, n_in_grid, n_cells (occupied), n_components, n_cones, n_written, n_dropped, 0
+ * The coordinates are those of the LEVEL frame: the pose handed to unina_track_update_async behind this call is level frame ->
+ * tracking frame. Integer counters, minima, maxima and sums only (no float atomics): two runs give identical bytes, and any
+ * permutation of the cloud the same header, table, records and count, and every point its component.
+ * NOT covered: bridging of gaps wider than a cell (a cone whose returns leave an empty cell between them is two components),
+ * colour and class from the image, association of LiDAR cones with camera records, motion de-skew, 3-D (voxel) connectivity (a
+ * branch over a cone joins it). */
+typedef struct { float x_min, y_min, cell; int nx, ny; int min_points, max_points;
+                 float min_height, max_height, max_width, confidence; int class_id; } unina_cluster_params;   /* 48 bytes; nx, ny in 1..UNINA_GROUND_MAX_SIDE */
+typedef struct { float x, y, z_lo, z_hi, x_lo, x_hi, y_lo, y_hi; int n_points, n_cells, root, cone; } unina_cluster;   /* 48 bytes */
+typedef struct { int n_points, n_in_grid, n_cells, n_components, n_cones, n_written, n_dropped, reserved; } unina_cluster_header;   /* 32 bytes */
+typedef struct unina_clusterer unina_cluster_t;
+
+/* Host only: no HIP call, as unina_ground_create. The device workspace (8 bytes per cell of the UNINA_GROUND_MAX_SIDE^2 cells of
+ * the largest grid, about 100 bytes per point of max_points, and nothing else: there are never more components than IN_GRID
+ * points, so the table has max_points entries and no legal input can overflow a list) is allocated by the first
+ * unina_cluster_async, on that call's stream, which then fails with UNINA_ERR_HIP where there is no device. One handle serves any
+ * sequence of clouds and grids within its limits; calls on one handle belong on one stream, or are ordered by the caller.
+ * UNINA_ERR_ARG: NULL out, negative device_id, max_points outside 1..UNINA_LIDAR_MAX_POINTS. */
+int unina_cluster_create(int device_id, int max_points, unina_cluster_t **out);
+/* Waits for the device, frees. NULL is a no-op. */
+void unina_cluster_destroy(unina_cluster_t *c);
+/*   cloud->points   : device, n_points * stride bytes, 4-byte aligned (read 16 bytes at a time where the base and the stride allow)
+ *   d_dets, d_cones : device, MAX_DETECTIONS records each, 16-byte aligned; d_count : device, one int, 4-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer (points may be NULL only when n_points == 0); d_dets or d_cones not 16-byte
+ * aligned, d_count not 4-byte aligned; n_points outside 0..max_points; stride < 12 or not a multiple of 4, or points not 4-byte
+ * aligned; a non-finite element of lidar_to_level; x_min, y_min, min_height, max_height or max_width not finite; cell not finite
+ * and positive; nx or ny outside 1..UNINA_GROUND_MAX_SIDE; min_points < 1 or max_points < min_points; min_height < 0 or
+ * max_height < min_height; max_width < 0; a NaN confidence; d_dets, d_cones or d_count overlapping the n_points * stride bytes
+ * of the cloud. n_points == 0 is legal: the header, the records and the count are all-zero. */
+int unina_cluster_async(unina_cluster_t *c, const unina_cloud *cloud, const float lidar_to_level[12], const unina_cluster_params *p,
+                        GpuDetection *d_dets, int *d_count, unina_cone3d *d_cones, hipStream_t stream);
+/* Device addresses of what the last call left in the workspace, for a consumer that stays on the GPU or a test; read them behind
+ * the call on its stream: the n_components entries of the table, the n_points component indices in point order, and the header.
+ * A NULL argument is skipped. UNINA_ERR_STATE before the first unina_cluster_async. */
+int unina_cluster_buffers(unina_cluster_t *c, const unina_cluster **d_components, const int **d_point_component,
+                          const unina_cluster_header **d_header);
 
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the

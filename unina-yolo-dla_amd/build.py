@@ -35,6 +35,7 @@ UNITS = {
     "stereo.hip": ["-ffp-contract=off"],        # detections -> 3-D points from a stereo pair: range, sub-pixel step and point round as localize.locate_stereo_numpy's fp32 scalars do
     "lidar.hip": ["-ffp-contract=off"],         # detections -> 3-D points from a LiDAR sweep: transform, projection and point round as localize.locate_lidar_numpy's fp32 scalars do
     "ground.hip": ["-ffp-contract=off"],        # LiDAR sweep -> the sweep without its ground: transform, cell, envelope and label round as ground.ground_numpy's fp32 arrays do
+    "cluster.hip": ["-ffp-contract=off"],       # ground-free sweep -> cone candidates: transform, cell, position and gate round as cluster.cluster_numpy's fp32 arrays do
     "rectify.hip": ["-ffp-contract=off"],       # raw images -> rectified images: the source coordinates round as rectify.rectify_source_numpy's fp32 arrays do
     "track.hip": ["-ffp-contract=off"],         # located cones -> persistent tracks: gate, keys and slot update round as tracking.update_numpy's fp32 scalars do
     "engine.hip": [],

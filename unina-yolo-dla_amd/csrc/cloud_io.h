@@ -1,4 +1,4 @@
-// cloud_io.h -- what every stage that reads a unina_cloud does with it (csrc/lidar.hip, ground.hip), one copy each: the limit
+// cloud_io.h -- what every stage that reads a unina_cloud does with it (csrc/lidar.hip, ground.hip, cluster.hip), one copy each: the limit
 // of a sweep, one row of an extrinsic applied to a point, the float/bits casts, the checks of the cloud and the extrinsic; then,
 // for hipcc alone (the stand-alone programs under tests/ compile the first half without HIP): the loads of a point, the launch
 // of a kernel's 16-byte-load form, the workspace of a handle. Every unit that includes it is compiled with -ffp-contract=off.

@@ -1,6 +1,6 @@
 // ground_cell.h -- the per-point and per-cell halves of unina_ground_filter_async (include/unina_mi355.h "ground removal from a
 // LiDAR sweep"), as __host__ __device__ functions (csrc/hd.h): the LiDAR -> level transform (csrc/cloud_io.h),
-// the grid cell of a point, the ordered key of a height, one term of the envelope and the label. csrc/ground.hip calls them on
+// the grid cell of a point (also csrc/cluster_cell.h's), the ordered key of a height, one term of the envelope and the label. csrc/ground.hip calls them on
 // the device, tests/ground_cell_host.cpp sweeps them on the host, ground.ground_numpy is their numpy twin. fp32 throughout, one
 // rounding per operation in the order written: every translation unit that includes this header is compiled with
 // -ffp-contract=off. Every decision after the transform and the two divides is a comparison of integers or of fp32 values
@@ -44,21 +44,27 @@ UNINA_HD uint32_t ground_key(float f) {
 }
 UNINA_HD float ground_unkey(uint32_t k) { return ground_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
 
+// the grid cell of a point of the level frame, -1 where it is not IN_GRID; *fx, *fy: its position in cells (set whenever the
+// three coordinates are finite). The one copy of the expression: ground_point and cluster_point (csrc/cluster_cell.h) call it.
+UNINA_HD int grid_cell(float xl, float yl, float zl, float x_min, float y_min, float cell, int nx, int ny, float* fx, float* fy) {
+  *fx = *fy = 0.0f;
+  if (!finite(xl) || !finite(yl) || !finite(zl)) return -1;
+  *fx = (xl - x_min) / cell;
+  *fy = (yl - y_min) / cell;
+  if (!(*fx >= 0.0f && *fx < (float)nx && *fy >= 0.0f && *fy < (float)ny)) return -1;   // a NaN fails
+  return (int)*fy * nx + (int)*fx;   // 0 <= fx < nx <= 1024: the conversion truncates inside the grid; -0.0 is column 0
+}
+
 // one point: its cell, the bits of its height in the level frame, and whether it may found a ground height
 UNINA_HD GroundPoint ground_point(const GroundGrid& g, float x, float y, float z) {
   GroundPoint p;
   const float xl = cloud_transform_row(g.m, x, y, z);
   const float yl = cloud_transform_row(g.m + 4, x, y, z);
   const float zl = cloud_transform_row(g.m + 8, x, y, z);
-  p.cell = -1;
+  float fx, fy;
+  p.cell = grid_cell(xl, yl, zl, g.x_min, g.y_min, g.cell, g.nx, g.ny, &fx, &fy);
   p.z_bits = ground_bits(zl);
-  p.seed = 0;
-  if (!finite(xl) || !finite(yl) || !finite(zl)) return p;
-  const float fx = (xl - g.x_min) / g.cell;
-  const float fy = (yl - g.y_min) / g.cell;
-  if (!(fx >= 0.0f && fx < (float)g.nx && fy >= 0.0f && fy < (float)g.ny)) return p;   // a NaN fails
-  p.cell = (int)fy * g.nx + (int)fx;   // 0 <= fx < nx <= 1024: the conversion truncates inside the grid; -0.0 is column 0
-  p.seed = (zl >= g.z_lo && zl <= g.z_hi) ? 1 : 0;
+  p.seed = (p.cell >= 0 && zl >= g.z_lo && zl <= g.z_hi) ? 1 : 0;
   return p;
 }
 

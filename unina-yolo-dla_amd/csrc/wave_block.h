@@ -1,6 +1,6 @@
 // wave_block.h -- workgroup primitives on 64-lane waves, one copy each: the rank of a flag over the workgroup, the inclusive
 // scan of a wave, one 64-bit word of a set held a word per lane, the fold of a wave's lanes by key, and the shape of the
-// one-workgroup scan. csrc/postprocess.hip, csrc/track.hip, csrc/lidar.hip and csrc/ground.hip call them.
+// one-workgroup scan. csrc/postprocess.hip, csrc/track.hip, csrc/lidar.hip, csrc/ground.hip and csrc/cluster.hip call them.
 #ifndef UNINA_WAVE_BLOCK_H
 #define UNINA_WAVE_BLOCK_H
 
@@ -9,7 +9,7 @@
 namespace unina {
 
 constexpr int kWave = 64;
-// the one-workgroup exclusive scan of csrc/lidar.hip and csrc/ground.hip: the kernels keep a copy each of the pass itself (a
+// the one-workgroup exclusive scan of csrc/lidar.hip, csrc/ground.hip and csrc/cluster.hip: the kernels keep a copy each of the pass itself (a
 // shared function is simplified before it is inlined, and lidar_scan_kernel then needs 52 VGPRs for 40)
 constexpr int kScanBlock = 1024;
 constexpr int kScanWaves = kScanBlock / kWave;

@@ -169,6 +169,20 @@ class GroundParams(C.Structure):
                 ("keep_unknown", C.c_int)]
 
 
+CLUSTER_DTYPE = np.dtype([(n, "<f4") for n in ("x", "y", "z_lo", "z_hi", "x_lo", "x_hi", "y_lo", "y_hi")] +
+                         [(n, "<i4") for n in ("n_points", "n_cells", "root", "cone")])             # unina_cluster
+CLUSTER_HEADER_DTYPE = np.dtype([(n, "<i4") for n in ("n_points", "n_in_grid", "n_cells", "n_components", "n_cones", "n_written", "n_dropped",
+                                                      "reserved")])                                   # unina_cluster_header
+assert CLUSTER_DTYPE.itemsize == 48 and CLUSTER_HEADER_DTYPE.itemsize == 32
+
+
+class ClusterParams(C.Structure):
+    """unina_cluster_params: the grid (metres, level frame), the gate, and what the records of a CONE component carry."""
+    _fields_ = [("x_min", C.c_float), ("y_min", C.c_float), ("cell", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("min_points", C.c_int),
+                ("max_points", C.c_int), ("min_height", C.c_float), ("max_height", C.c_float), ("max_width", C.c_float),
+                ("confidence", C.c_float), ("class_id", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -206,6 +220,7 @@ ABI_SYMBOLS = [
     "unina_locate_async", "unina_locate_stereo_async", "unina_rectify_async",
     "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
     "unina_ground_create", "unina_ground_destroy", "unina_ground_filter_async", "unina_ground_buffers",
+    "unina_cluster_create", "unina_cluster_destroy", "unina_cluster_async", "unina_cluster_buffers",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -336,6 +351,12 @@ def load_library() -> C.CDLL:
     L.unina_ground_destroy.restype = None
     L.unina_ground_filter_async.argtypes = [vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(GroundParams), vp, vp]
     L.unina_ground_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    # cone candidates from a ground-free LiDAR sweep (csrc/cluster.hip)
+    L.unina_cluster_create.argtypes = [ci, ci, C.POINTER(vp)]
+    L.unina_cluster_destroy.argtypes = [vp]
+    L.unina_cluster_destroy.restype = None
+    L.unina_cluster_async.argtypes = [vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(ClusterParams), vp, vp, vp, vp]
+    L.unina_cluster_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]

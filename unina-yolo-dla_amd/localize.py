@@ -418,7 +418,7 @@ def device_words(address: int, n_words: int, device: int = 0):
 
 
 class SweepStage:
-    """What the handles of the stages that take a LiDAR sweep share (DeviceLidarLocator, ground.DeviceGroundFilter): the handle
+    """What the handles of the stages that take a LiDAR sweep share (DeviceLidarLocator, ground.DeviceGroundFilter, cluster.DeviceClusterer): the handle
     of a named create / destroy pair of the ABI, the cloud of the call in flight, and a cloud and an extrinsic as the ABI takes them."""
 
     def _create(self, device: int, create: str, destroy: str, *limits):
