@@ -24,6 +24,7 @@
 // Pipeline: STAGES LDS buffers, STAGES-1 K-steps in flight, one s_barrier per K-step, counted s_waitcnt vmcnt.
 #include "kernels.h"
 #include "block_pipeline.h"
+#include "regq_s2.h"
 
 #include <cstdlib>
 
@@ -809,9 +810,12 @@ constexpr auto kernel_of(HaloTile<T, TH, TW, BN, BK, WAVES_M, WAVES_N, STAGES>) 
 #define UNINA_PATCH_VIA_REGS 1
 #endif
 constexpr bool kPatchViaRegs = UNINA_PATCH_VIA_REGS != 0;   // input patch: 16-byte loads to registers + ds_write (1) or LDS-DMA (0)
-// STAMPS (debug instantiations only: a branch around the loads would change the schedule of the product kernels): phase
-// stamps of the conv's mid workgroup -- 0 start, 1 patch DMA + first weight blocks issued, 2 patch landed (barrier passed),
-// 3 K loop done, 4 stores issued.
+// STAMPS (debug twins only, the fp16 stride-2 rows have one: a branch around the loads would change the schedule of the product
+// kernels): phase stamps of the conv's mid workgroup -- 0 start, 1 patch + first weight blocks requested, 2 patch landed (barrier
+// passed), 7 first MFMA issued, 3 K loop done, 4 stores drained (tools/regq_phases.py).
+#ifndef UNINA_REGQ_S2_LAYOUT
+#define UNINA_REGQ_S2_LAYOUT 1     // stride-2 fp16 / int8 tiles: the conflict-free image of regq_s2.h (0: the stride-1 image, as before)
+#endif
 // RegqTile: NW waves, a weight queue D blocks deep, stride S (WN = 1: what every row of the table and every pair uses)
 template <typename T, int TH, int TW, int BN, int CIN, int NW, int D, int S = 1>
 struct RegqTile : TileDefaults {
@@ -821,7 +825,12 @@ struct RegqTile : TileDefaults {
   static constexpr bool SPLIT = Elem<T>::kPlanes == 2;
   // S = stride (1 or 2): the patch is the (S*TH + 2 or S*TH + 1) x (...) input footprint of the tile
   static constexpr int R0W = S * (TW - 1) + 3, R0H = S * (TH - 1) + 3;
-  static constexpr int PATCH = (int)round_kib(R0H * R0W * CIN * sizeof(T)) + 1024;   // one image + the < 1 KiB overrun of its last DMA instruction
+  // stride 2, patch through registers (not split fp16, whose two images by LDS-DMA keep the stride-1 layout: with the wider rows
+  // the 8x8 Cin-128 pair of images would not fit the CU): the image of regq_s2.h, S2P pixels a row, odd columns S2H behind the even
+  static constexpr bool S2L = S == 2 && !SPLIT && UNINA_REGQ_S2_LAYOUT != 0 && UNINA_PATCH_VIA_REGS != 0;
+  static constexpr int NCH = CIN / Elem<T>::kChunk, S2H = s2::half_w(R0W), S2P = S2L ? s2::pitch(TW, R0W) : R0W;
+  static_assert(!S2L || (s2::nch_ok(NCH) && (TW == 8 || TW == 16)), "regq_s2.h covers 8- and 16-wide tiles of 4, 8 or 16 chunks a pixel");
+  static constexpr int PATCH = (int)round_kib(R0H * S2P * CIN * sizeof(T)) + 1024;   // one image + the < 1 KiB overrun of its last DMA instruction
   static constexpr int LDS_LO = SPLIT ? PATCH : 0;                                    // split fp16: the lo image lies behind the hi image
   // split fp16: hi and lo images, accumulators are stored straight from registers; otherwise the patch or the epilogue staging tile
   static constexpr size_t lds_bytes(int = 0) { return SPLIT ? 2 * (size_t)PATCH : max_sz(PATCH, stage_bytes((bm + 15) & ~15, BN)); }
@@ -830,12 +839,46 @@ struct RegqTile : TileDefaults {
   }
 };
 
+// A stride-2 tile's patch through registers, as patch_issue / patch_commit do it for the stride-1 image: which (row, column,
+// chunk) a lane fetches, and where it goes, is regq_s2.h's.
+template <class Tile>
+struct PatchRegsS2 {
+  static constexpr int nreq = s2::requests(Tile::R0H, Tile::R0W, Tile::NCH), ITER = s2::loads(Tile::R0H, Tile::R0W, Tile::NCH, Tile::nthreads);
+  floatx4 v[ITER];
+};
+template <class Tile>
+__device__ __forceinline__ void patch_issue_s2(PatchRegsS2<Tile>& pr, const void* src_, int src_ld, int H, int W, int y0, int x0) {
+  const unsigned char* src = static_cast<const unsigned char*>(src_);
+#pragma unroll
+  for (int it = 0; it < PatchRegsS2<Tile>::ITER; ++it) {
+    const int s = it * Tile::nthreads + (int)threadIdx.x;
+    pr.v[it] = floatx4{0.f, 0.f, 0.f, 0.f};
+    if (s < PatchRegsS2<Tile>::nreq) {
+      const s2::Request r = s2::request(s, Tile::R0W, Tile::NCH);
+      const int iy = y0 + r.ry, ix = x0 + r.rx;
+      if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
+        pr.v[it] = *reinterpret_cast<const floatx4*>(src + ((size_t)(iy * W + ix) * src_ld) * sizeof(typename Tile::elem) + (r.chunk << 4));
+    }
+  }
+}
+template <class Tile>
+__device__ __forceinline__ void patch_commit_s2(const PatchRegsS2<Tile>& pr, unsigned char* lds_img) {
+#pragma unroll
+  for (int it = 0; it < PatchRegsS2<Tile>::ITER; ++it) {
+    const int s = it * Tile::nthreads + (int)threadIdx.x;
+    if (s < PatchRegsS2<Tile>::nreq) {
+      const s2::Request r = s2::request(s, Tile::R0W, Tile::NCH);
+      *reinterpret_cast<floatx4*>(lds_img + (s2::slot(s2::pixel(r.ry, r.rx, Tile::S2P, Tile::S2H), r.chunk, Tile::NCH) << 4)) = pr.v[it];
+    }
+  }
+}
+
 template <int TH, int TW, int BN, int CIN, int NW, int D, int S = 1, int WN = 1, typename T = half_t, bool STAMPS = false>
 __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, int nwg) {
   typedef Elem<T> E;
   typedef typename E::frag frag;
   typedef RegqTile<T, TH, TW, BN, CIN, NW, D, S> Tile;
-  constexpr bool SPLIT = Tile::SPLIT;
+  constexpr bool SPLIT = Tile::SPLIT, S2L = Tile::S2L;
   typedef typename std::conditional<sizeof(T) == 1, EltI8, typename std::conditional<SPLIT, EltS, EltH>::type>::type PE;   // block_pipeline.h element traits of T
   constexpr int BM = TH * TW, R0W = Tile::R0W, R0H = Tile::R0H, NT = NW * 64, CB = CIN / E::kBlockK, KB = 9 * CB;
   static_assert(CIN % E::kBlockK == 0, "a weight block must not straddle a tap");
@@ -873,7 +916,17 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
   constexpr int LDS_LO = Tile::LDS_LO;   // split fp16: the lo image of the patch lies LDS_LO bytes behind the hi image
 
   constexpr Img X = make_img(0, CIN / E::kChunk);
-  if constexpr (SPLIT) {   // both planes by LDS-DMA (twice the registers of a register-staged patch would not fit)
+  EpiConsts<WN> ec;
+  if constexpr (S2L) {
+    // request order: patch, constants, the first D weight blocks. Every load lands in a register, so the wait in front of the
+    // commit is the compiler's own counted vmcnt: the constants and the weight queue stay in flight across the barrier.
+    PatchRegsS2<Tile> pr;
+    patch_issue_s2<Tile>(pr, static_cast<const T*>(p.src) + sg.src_coff, p.src_ld, p.H, p.W, S * ty0 - 1, S * tx0 - 1);
+    load_epi_consts<WN>(sg, nb0 + wn * (WN * 16), lq, ec);
+    static_for<0, D>(fetch);
+    if constexpr (STAMPS) stamp(p, 1, bid, nwg);
+    patch_commit_s2<Tile>(pr, conv_smem);
+  } else if constexpr (SPLIT) {   // both planes by LDS-DMA (twice the registers of a register-staged patch would not fit)
     load_patch<R0H, R0W, CIN, NT, PE>(conv_smem, static_cast<const T*>(p.src) + sg.src_coff, p.src_ld, p.H, p.W, S * ty0 - 1,
                                       S * tx0 - 1, p.zeros, wid, lane, p.src_lo, LDS_LO);
     static_for<0, D>(fetch);
@@ -888,10 +941,9 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
                                       S * tx0 - 1, p.zeros, wid, lane);
     static_for<0, D>(fetch);
   }
-  EpiConsts<WN> ec;
-  load_epi_consts<WN>(sg, nb0 + wn * (WN * 16), lq, ec);
-  if constexpr (STAMPS && (SPLIT || !kPatchViaRegs)) stamp(p, 1, bid, nwg);
-  if constexpr (SPLIT || !kPatchViaRegs) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed
+  if constexpr (!S2L) load_epi_consts<WN>(sg, nb0 + wn * (WN * 16), lq, ec);
+  if constexpr (STAMPS && !S2L && (SPLIT || !kPatchViaRegs)) stamp(p, 1, bid, nwg);
+  if constexpr (!S2L && (SPLIT || !kPatchViaRegs)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the patch has landed
   lds_barrier();
   if constexpr (STAMPS) stamp(p, 2, bid, nwg);
 
@@ -900,11 +952,12 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
   for (int i = 0; i < WM_T; ++i) {
     int pp = (wm * WM_T + i) * 16 + l15;
     pp = pp < BM ? pp : BM - 1;                     // subtiles past the tile: any valid pixel (never stored)
-    row0[i] = S * ((pp / TW) * R0W + pp % TW);
+    row0[i] = S2L ? s2::pixel(2 * (pp / TW), 2 * (pp % TW), Tile::S2P, Tile::S2H) : S * ((pp / TW) * R0W + pp % TW);
   }
   auto baddr = [&](int i, auto kc) {
     constexpr int kb = decltype(kc)::value, tap = kb / CB, cb = kb - tap * CB, th3 = tap / 3;
-    return X.addr(row0[i] + th3 * R0W + (tap - th3 * 3), cb * 4 + lq);
+    if constexpr (S2L) return s2::slot(row0[i] + s2::pixel(th3, tap - th3 * 3, Tile::S2P, Tile::S2H), cb * 4 + lq, Tile::NCH) << 4;
+    else return X.addr(row0[i] + th3 * R0W + (tap - th3 * 3), cb * 4 + lq);
   };
   typename E::acc_t acc[WN][WM_T];
   frag b[2][WM_T];
@@ -928,6 +981,7 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
     for (int j = 0; j < WN; ++j)
 #pragma unroll
       for (int i = 0; i < WM_T; ++i) acc[j][i] = E::mma(a[j], b[kb & 1][i], acc[j][i]);
+    if constexpr (STAMPS && kb == 0) stamp(p, 7, bid, nwg);
   });
 
   if constexpr (STAMPS) stamp(p, 3, bid, nwg);
@@ -937,7 +991,7 @@ __device__ __forceinline__ void conv3x3_regq_body(const ConvParams& p, int bid, 
   };
   conv_epilogue<T, BM, BN, WM_T, WN, decltype(pix_to_m), (UNINA_REGQ_DIRECT_STORE != 0 && sizeof(T) == 2)>(p, sg, acc, ec, wm, wn, nb0, l15, lq, pix_to_m,
                                                                                                        conv_smem, NT);
-  if constexpr (STAMPS) { stamp(p, 4, bid, nwg); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wg(p, 1); }
+  if constexpr (STAMPS) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(p, 4, bid, nwg); stamp_wg(p, 1); }
 }
 
 template <int TH, int TW, int BN, int CIN, int NW, int D, int S = 1, int WN = 1, typename T = half_t>
@@ -946,6 +1000,17 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_regq(const ConvParams p) {
 }
 template <typename T, int TH, int TW, int BN, int CIN, int NW, int D, int S>
 constexpr auto kernel_of(RegqTile<T, TH, TW, BN, CIN, NW, D, S>) { return conv3x3_regq<TH, TW, BN, CIN, NW, D, S, 1, T>; }
+
+// Debug twin with phase stamps (ConvParams::stamps set: unina_debug_conv_stamps launches it in place of the row's kernel): the
+// fp16 stride-2 rows -- the stand-alone stage convs -- have one.
+template <int TH, int TW, int BN, int CIN, int NW, int D, int S, typename T>
+__global__ __launch_bounds__(NW * 64) void conv3x3_regq_stamped(const ConvParams p) {
+  conv3x3_regq_body<TH, TW, BN, CIN, NW, D, S, 1, T, true>(p, (int)blockIdx.x, (int)gridDim.x);
+}
+template <class Tile>
+constexpr auto stamped_kernel_of(Tile) { return static_cast<void (*)(const ConvParams)>(nullptr); }
+template <int TH, int TW, int BN, int CIN, int NW, int D>
+constexpr auto stamped_kernel_of(RegqTile<half_t, TH, TW, BN, CIN, NW, D, 2>) { return conv3x3_regq_stamped<TH, TW, BN, CIN, NW, D, 2, half_t>; }
 
 // ============================================================================================ 3x3 weights-stationary kernel
 // 3x3 / stride 1 / pad 1, ReLU, NHWC destination; fp16, int8 (INT8 engines: int8 patch, 64-k weight blocks, exact int32
@@ -1270,6 +1335,7 @@ struct CfgInfo {       // a tile's geometry as the host plans and launches with 
   int stride = 0;      // register-queue kernel: conv stride it is instantiated for
   bool ws = false;     // weights-stationary 3x3 kernel: fp16 NHWC destination, ReLU, no residual / upsample / planar output
   int chunks = 0;      // chunked weights-stationary kernel (conv3x3_wsc_body): channel chunks; 0 = another kernel
+  void (*fn_stamped)(const ConvParams) = nullptr;   // debug twin with phase stamps (same launch), where the row has one
 };
 // [dtype][config], filled from a list of rows that each name their slot: add<Tile>(configuration), the dtype is the tile's.
 struct ConvTable {
@@ -1280,7 +1346,7 @@ struct ConvTable {
     CfgInfo& c = at[Elem<typename Tile::elem>::kDType][cfg];
     if (c.fn) ++clashes;
     c = {Tile::bm, Tile::bn, Tile::bk, Tile::stages, Tile::name(), kernel_of(Tile{}), &Tile::lds_bytes,
-         Tile::th, Tile::tw, Tile::cin, Tile::nthreads, Tile::stride, Tile::ws, Tile::chunks};
+         Tile::th, Tile::tw, Tile::cin, Tile::nthreads, Tile::stride, Tile::ws, Tile::chunks, stamped_kernel_of(Tile{})};
   }
 };
 
@@ -1443,7 +1509,9 @@ constexpr DualKind kDual[kDualKinds] = {
 
 hipError_t conv_init() {
   for (const auto& row : kCfg) {
-    const hipError_t e = set_lds_limits(row);
+    hipError_t e = set_lds_limits(row);
+    for (const CfgInfo& c : row)
+      if (e == hipSuccess && c.fn_stamped) e = hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn_stamped), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
     if (e != hipSuccess) return e;
   }
   return set_lds_limits(kDual);
@@ -1541,7 +1609,7 @@ hipError_t conv_desc(ConvParams& p, int cfg, LaunchDesc* d) {
   if (cfg < 0 || cfg >= kCfgCount || !kCfg[p.dtype][cfg].fn) return hipErrorInvalidValue;
   const CfgInfo& c = kCfg[p.dtype][cfg];
   const int n = conv_prepare(p, cfg);
-  *d = {reinterpret_cast<const void*>(c.fn), dim3(n), dim3(c.nthreads), (unsigned)smem_for(p, c), c.name.s};
+  *d = {reinterpret_cast<const void*>(p.stamps && c.fn_stamped ? c.fn_stamped : c.fn), dim3(n), dim3(c.nthreads), (unsigned)smem_for(p, c), c.name.s};
   return hipSuccess;
 }
 
