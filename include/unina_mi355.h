@@ -339,6 +339,8 @@ int unina_infer_tiled_frame_async(unina_engine_t *e, const unina_frame *frame, c
  *   [0..2] per level P2,P3,P4: max over classes and cells of -(p*log(p+1e-10) + (1-p)*log(1-p+1e-10))   active_learning.py:292-294
  *   [3..5] per level: max over cells of 1 - |max_c p_c - 0.5| * 2                                        active_learning.py:298-301
  *   [6] = max of [0..2]: the image's score in mode "entropy"; [7] = max of [3..5]: mode "loc_var"        active_learning.py:303
+ * Every max is numpy's / torch's: it keeps a NaN. A level that holds a NaN logit reports NaN in both of its scores, and so do
+ * [6] and [7]; the other levels are untouched. +-inf and saturating logits give finite scores (p = 0 or 1: entropy and loc_var 0).
  * embedding: mean over H, W of the backbone's P4 map before SPPF (features[2], the output of backbone.stage3_c3k2;
  * adaptive_avg_pool2d, active_learning.py:57-60,90-91), fp32 accumulation in a fixed order: two runs give identical bits.
  * Graph (B) engines (qat.py models: no .backbone) score but do not embed: UNINA_ERR_UNSUPPORTED. */

@@ -18,9 +18,13 @@ namespace {
 
 constexpr int kWaves = kMineBlock / kWave;
 
+// The max of the scores is numpy's / torch's, which KEEPS a NaN operand; fmaxf drops it. For NaN-free operands this is fmaxf,
+// bit for bit, so a level that holds a NaN logit reports NaN and every other result is unchanged.
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+  for (int o = kWave / 2; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, kWave));
   return v;
 }
 
@@ -32,12 +36,13 @@ __device__ __forceinline__ float block_max(float v, float* sm) {
   __syncthreads();
   float r = sm[0];
 #pragma unroll
-  for (int w = 1; w < kWaves; ++w) r = fmaxf(r, sm[w]);
+  for (int w = 1; w < kWaves; ++w) r = max_nan(r, sm[w]);
   return r;
 }
 
 // One thread per cell of one level: binary entropy of every class (max) and 1 - |max_c p_c - 0.5| * 2, both as the reference
-// computes them (active_learning.py:287-301). Every value is >= 0, so 0 is the neutral element of the max (idle threads).
+// computes them (active_learning.py:287-301). Every value is >= 0 or NaN, so 0 is the neutral element of the max (idle threads);
+// a NaN logit makes the cell's entropy, its conf and with it its loc_var NaN, and max_nan carries that to the level's scores.
 __global__ void __launch_bounds__(kMineBlock) mine_score_kernel(MineParams p) {
   __shared__ float sm[kWaves];
   const int b = (int)blockIdx.x;
@@ -52,8 +57,8 @@ __global__ void __launch_bounds__(kMineBlock) mine_score_kernel(MineParams p) {
       const float v = x[(size_t)c * cells];
       const float pr = 1.0f / (1.0f + expf(-v));
       const float e = -(pr * logf(pr + 1e-10f) + (1.0f - pr) * logf(1.0f - pr + 1e-10f));
-      ent = fmaxf(ent, e);
-      conf = fmaxf(conf, pr);
+      ent = max_nan(ent, e);
+      conf = max_nan(conf, pr);
     }
     loc = 1.0f - fabsf(conf - 0.5f) * 2.0f;
   }
@@ -137,16 +142,16 @@ __global__ void __launch_bounds__(kMineBlock) mine_finish_kernel(MineParams p) {
     for (int level = 0; level < 3; ++level) {
       float ent = 0.f, loc = 0.f;
       for (int b = p.blk0[level] + tid; b < p.blk0[level + 1]; b += kMineBlock) {
-        ent = fmaxf(ent, p.score_partial[2 * b]);
-        loc = fmaxf(loc, p.score_partial[2 * b + 1]);
+        ent = max_nan(ent, p.score_partial[2 * b]);
+        loc = max_nan(loc, p.score_partial[2 * b + 1]);
       }
       out[level] = block_max(ent, sm);
       out[3 + level] = block_max(loc, sm);
     }
     if (tid == 0) {
       for (int i = 0; i < 6; ++i) p.scores[i] = out[i];
-      p.scores[6] = fmaxf(fmaxf(out[0], out[1]), out[2]);
-      p.scores[7] = fmaxf(fmaxf(out[3], out[4]), out[5]);
+      p.scores[6] = max_nan(max_nan(out[0], out[1]), out[2]);
+      p.scores[7] = max_nan(max_nan(out[3], out[4]), out[5]);
     }
     return;
   }
