@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from eval_cases import conformal_scores, host_image   # noqa: F401  (the host path of one image, shared with the edge tests)
 from records import MAXD, det_buffer
 
 pytestmark = pytest.mark.gpu
@@ -26,38 +27,6 @@ def gold():
     n = len(g["counts"])
     return {"n": n, "counts": g["counts"], "geom": g["geom"], "names": [str(s) for s in g["names"]],
             "dets": [g[f"dets/{i:02d}"] for i in range(n)], "labels": [g[f"labels/{i:02d}"] for i in range(n)]}
-
-
-def host_image(metrics, dets, labels, geom, imgsz=640):
-    """The host path of evaluate() for one image: (tp, fp, fn), conformal scores in order, AP rows."""
-    w, h, nw, nh = (int(v) for v in geom)
-    s = dets.copy()
-    s["x1"], s["x2"], s["y1"], s["y2"] = dets["x1"] * (w / nw), dets["x2"] * (w / nw), dets["y1"] * (h / nh), dets["y2"] * (h / nh)
-    m = metrics.SmallObjectMetric(size_threshold=15, image_size=imgsz)
-    m.update([metrics.coco_to_metric_rows(metrics.detections_to_coco(s, "x"), w, h)], [labels])
-    c = dets.copy()
-    c["x1"], c["x2"] = dets["x1"] * (imgsz / nw), dets["x2"] * (imgsz / nw)
-    c["y1"], c["y2"] = dets["y1"] * (imgsz / nh), dets["y2"] * (imgsz / nh)
-    rows = metrics.ap_rows_numpy(c, labels, imgsz)
-    scores = conformal_scores(metrics, c, labels, imgsz)
-    assert len(scores) == int((rows["tp_mask"] & 1).sum())
-    return (m.true_positives, m.false_positives, m.false_negatives), scores, rows
-
-
-def conformal_scores(metrics, dets, labels, imgsz):
-    """metrics.conformal_quantile's own score list for one image (it only returns statistics): np.quantile is intercepted
-    to see the array it is handed."""
-    seen = []
-    real = np.quantile
-    try:
-        np.quantile = lambda s, q: (seen.append(np.array(s, dtype=np.float64)), real(s, q))[1]
-        try:
-            metrics.conformal_quantile([dets], [labels], 0.1, imgsz)
-        except ValueError:                               # no matched prediction
-            return np.zeros(0)
-    finally:
-        np.quantile = real
-    return seen[0]
 
 
 def params(engine, geom, imgsz=640):
