@@ -397,7 +397,12 @@ int unina_kcenter(const float *d_embeddings, int n, int dim, int k, int first_in
  *                  then returns only when the loop has finished. With a workspace nothing is synchronised.
  * UNINA_ERR_ARG: null / misaligned pointer, dim % 4 != 0, k < 1, k > n, max_iter < 1 (unina_kmeans_workspace_bytes: 0).
  * An init row outside [0, n) is found ON THE DEVICE (the indices live there): the call returns UNINA_OK, *d_iters becomes -1
- * and centroids, labels and history are left untouched. */
+ * and centroids, labels and history are left untouched.
+ * NON-FINITE VALUES are not validated; they follow IEEE arithmetic and one rule. The arg-min is a running minimum that
+ * starts at (+inf, index 0) and that only a strictly smaller score replaces, so a NaN score never wins, and a row all of
+ * whose scores are NaN or +inf takes label 0. (A row with a NaN channel therefore joins cluster 0 in the first iteration and
+ * makes that centroid NaN; from the second iteration on no other row can choose it. The inertia of such a run is NaN.)
+ * mining.kmeans_numpy follows the same rule. */
 #define UNINA_KMEANS_CONVERGED (1 << 30)
 size_t unina_kmeans_workspace_bytes(int n, int dim, int k);
 int unina_kmeans(const float *d_embeddings, int n, int dim, int k, const int *d_init_rows, int max_iter, float *d_centroids,

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from kmeans_cases import one_step_case
 from test_kmeans_cpu import blob_case, blob_cases, overlapping, shared_nearest_case
 from test_mining_cpu import kcenter_data
 
@@ -48,41 +49,35 @@ def overlap():
     return emb, mining.kmeans_pp_init(emb, 20, 0)
 
 
-def raw_kmeans(torch, emb, k, max_iter, init_rows=None, centroids=None, workspace=True):
-    """unina_kmeans itself: (centroids, labels, history [max_iter], raw d_iters) as host arrays, nothing trimmed."""
+def raw_kmeans(torch, emb, k, max_iter, init_rows=None, centroids=None, workspace=True, history=True):
+    """unina_kmeans itself: (centroids, labels, history [max_iter], raw d_iters) as host arrays, nothing trimmed.
+    history=False passes d_inertia_history = NULL and returns None in its place."""
     from unina_yolo_dla_amd import engine
     L = engine.load_library()
-    x = emb if isinstance(emb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).cuda()
+    # (np.array: a copy, the constructed cases are read-only arrays)
+    x = emb if isinstance(emb, torch.Tensor) else torch.from_numpy(np.array(emb, dtype=np.float32, order="C")).cuda()
     n, d = x.shape
     init = None if init_rows is None else torch.from_numpy(np.asarray(init_rows, dtype=np.int32)).cuda()
     cen = torch.zeros((k, d), dtype=torch.float32, device="cuda") if centroids is None else \
-        torch.from_numpy(np.ascontiguousarray(centroids, dtype=np.float32)).cuda()
+        torch.from_numpy(np.array(centroids, dtype=np.float32, order="C")).cuda()
     labels = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-    hist = torch.full((max_iter,), 3.0, dtype=torch.float64, device="cuda")
+    hist = torch.full((max_iter,), 3.0, dtype=torch.float64, device="cuda") if history else None
     iters = torch.full((1,), -9, dtype=torch.int32, device="cuda")
     ws = torch.empty(L.unina_kmeans_workspace_bytes(n, d, k), dtype=torch.uint8, device="cuda") if workspace else None
     rc = L.unina_kmeans(x.data_ptr(), n, d, k, None if init is None else init.data_ptr(), max_iter, cen.data_ptr(), labels.data_ptr(),
-                        hist.data_ptr(), iters.data_ptr(), None if ws is None else ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                        None if hist is None else hist.data_ptr(), iters.data_ptr(), None if ws is None else ws.data_ptr(),
+                        torch.cuda.current_stream().cuda_stream)
     assert rc == 0, rc
     torch.cuda.synchronize()
-    return cen.cpu().numpy(), labels.cpu().numpy(), hist.cpu().numpy(), int(iters.cpu()[0])
+    return cen.cpu().numpy(), labels.cpu().numpy(), None if hist is None else hist.cpu().numpy(), int(iters.cpu()[0])
 
 
-def one_step_case(n, dim, k):
-    rng = np.random.RandomState(1000 * n + dim + k)
-    emb = np.maximum(rng.normal(0.16, 0.24, size=(n, dim)), 0).astype(np.float32)
-    emb[:, : dim // 2] -= np.float32(0.1)                                    # both signs
-    start = (emb[rng.permutation(n)[:k]] * np.float32(0.9) + np.float32(0.02)).astype(np.float32)
-    return emb, start
-
-
-@pytest.mark.parametrize("n,dim,k", SHAPES)
-def test_one_step_against_float64(pkg, torch_cuda, n, dim, k):
+def check_one_step(torch, emb, start, what=None):
     """max_iter = 1 from given centroids, every stage against float64 on the device's own inputs: labels (tol above),
     centroids (a sequential fp32 sum of `count` terms and one division: gamma(count + 1) * mean_members |x| per channel),
-    inertia (double on the device: 1e-6 relative)."""
-    emb, start = one_step_case(n, dim, k)
-    cen, labels, hist, iters = raw_kmeans(torch_cuda, emb, k, 1, centroids=start)
+    inertia (double on the device: 1e-6 relative). Prints the slack under each bound; returns the device's labels."""
+    (n, dim), k = emb.shape, len(start)
+    cen, labels, hist, iters = raw_kmeans(torch, emb, k, 1, centroids=start)
     assert iters == 1 and labels.min() >= 0 and labels.max() < k
     x, c = emb.astype(np.float64), start.astype(np.float64)
     d2 = np.stack([((x - cj) ** 2).sum(axis=1) for cj in c], axis=1)
@@ -91,7 +86,8 @@ def test_one_step_against_float64(pkg, torch_cuda, n, dim, k):
     best = d2.argmin(axis=1)
     allowed = tol[rows, labels] + tol[rows, best]
     excess = d2[rows, labels] - d2[rows, best]
-    print(f"({n},{dim},{k}) labels: {int((labels != best).sum())} differ from the float64 arg-min; "
+    what = f"({n},{dim},{k})" if what is None else f"{what} ({n},{dim},{k})"
+    print(f"{what} labels: {int((labels != best).sum())} differ from the float64 arg-min; "
           f"worst excess / allowed {float((excess / allowed).max()):.3g}")
     assert (excess <= allowed).all(), (n, dim, k, float((excess / allowed).max()))
     gap = d2 - d2[rows, best][:, None] - tol - tol[rows, best][:, None]      # > 0: centroid j cannot win row i
@@ -113,8 +109,14 @@ def test_one_step_against_float64(pkg, torch_cuda, n, dim, k):
         worst = max(worst, float((err / np.maximum(bound, 1e-300)).max()))
     want = float(((x - cen.astype(np.float64)[labels]) ** 2).sum())
     rel = abs(hist[0] - want) / max(want, 1e-300)
-    print(f"({n},{dim},{k}) centroids: worst error / bound {worst:.3g}; inertia: relative error {rel:.3g} (bound 1e-6)")
+    print(f"{what} centroids: worst error / bound {worst:.3g}; inertia: relative error {rel:.3g} (bound 1e-6)")
     assert rel <= 1e-6, (hist[0], want)
+    return labels
+
+
+@pytest.mark.parametrize("n,dim,k", SHAPES)
+def test_one_step_against_float64(pkg, torch_cuda, n, dim, k):
+    check_one_step(torch_cuda, *one_step_case(n, dim, k))
 
 
 def test_exact_ties_and_empty_clusters(pkg, torch_cuda):

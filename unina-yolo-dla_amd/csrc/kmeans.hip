@@ -7,7 +7,9 @@
 // scikit-learn's mini-batch trajectory and RNG stream cannot be reproduced, so the clustering arithmetic is this build's own
 // specification: per iteration  |c|^2 -> assign -> update -> inertia.
 //   assign : label[i] = argmin_j |c_j|^2 - 2 <x_i, c_j>, the LOWEST index winning exact ties; the dot products run on the
-//            f32-input MFMA (v_mfma_f32_32x32x2_f32: a d-ordered fmaf chain, one rounding per product).
+//            f32-input MFMA (v_mfma_f32_32x32x2_f32: a d-ordered fmaf chain, one rounding per product). Non-finite values are
+//            not validated: the running minimum starts at (+inf, 0) and only `s < best` replaces it, so a NaN score never
+//            wins and a row all of whose scores are NaN or +inf takes label 0 (include/unina_mi355.h).
 //   update : c_j = (sum of member rows in ascending row index, fp32) / count_j; a cluster without members keeps its centroid.
 //   inertia: sum_i sum_d (x_id - c_{label_i,d})^2 with the NEW centroids, differences and sums in double.
 // The rule of mining.hip holds: every reduction has a fixed order and there are no float atomics (the one atomic is an integer

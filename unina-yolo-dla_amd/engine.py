@@ -928,9 +928,25 @@ class Engine:
         return out.reshape(c.value, h.value, w.value)
 
 
+def _behind_current(torch, stream, device):
+    """For the selection wrappers, which create and initialise their tensors on the CURRENT stream and launch on `stream`:
+    the torch stream of `stream` (a torch stream or a raw handle), made to wait for everything enqueued on the current
+    stream of `device` so far, so the kernels run behind those fills, clones and uploads; None when the launch goes to the
+    current stream anyway. The caller synchronises the returned stream before it reads results back on the current one."""
+    if stream is None:
+        return None
+    current = torch.cuda.current_stream(device)
+    side = torch.cuda.ExternalStream(stream, device=device) if isinstance(stream, int) else stream
+    if side.cuda_stream == current.cuda_stream:
+        return None
+    side.wait_stream(current)
+    return side
+
+
 def kcenter(embeddings, k: int, first_index: int, stream=None) -> np.ndarray:
     """K-center greedy on the GPU (coreset_selection_kcenter's loop, active_learning.py:139-161): the `k` selected row
-    indices in selection order. `embeddings`: [N,D] fp32, a CUDA tensor (used in place) or an ndarray (uploaded)."""
+    indices in selection order. `embeddings`: [N,D] fp32, a CUDA tensor (used in place) or an ndarray (uploaded). `stream`:
+    the launches go there, behind whatever the current stream holds at the call; the call returns when they are done."""
     L = load_library()
     torch = _torch()
     if not isinstance(embeddings, torch.Tensor):
@@ -940,9 +956,12 @@ def kcenter(embeddings, k: int, first_index: int, stream=None) -> np.ndarray:
     with torch.cuda.device(embeddings.device):
         sel = torch.zeros(max(k, 1), dtype=torch.int32, device=embeddings.device)
         ws = torch.empty(n, dtype=torch.float32, device=embeddings.device)
+        side = _behind_current(torch, stream, embeddings.device)
         rc = L.unina_kcenter(embeddings.data_ptr(), n, d, k, first_index, sel.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
         if rc:
             raise EngineError(f"unina_kcenter failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, k={k}, first_index={first_index})")
+        if side is not None:
+            side.synchronize()   # (the copy below runs on the current stream, the selection on `stream`)
         return sel.cpu().numpy()[:k].astype(np.int64)
 
 
@@ -986,12 +1005,13 @@ def kmeans(embeddings, k: int, init_rows=None, centroids=None, max_iter: int = 1
         hist = torch.zeros(max(max_iter, 1), dtype=torch.float64, device=dev)
         iters = torch.zeros(1, dtype=torch.int32, device=dev)
         ws = torch.empty(max(int(L.unina_kmeans_workspace_bytes(n, d, k)), 16), dtype=torch.uint8, device=dev)
+        side = _behind_current(torch, stream, dev)
         rc = L.unina_kmeans(embeddings.data_ptr(), n, d, k, init.data_ptr() if init is not None else None, max_iter, cen.data_ptr(),
                             labels.data_ptr(), hist.data_ptr(), iters.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
         if rc:
             raise EngineError(f"unina_kmeans failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, k={k}, max_iter={max_iter})")
-        if stream is not None:
-            torch.cuda.synchronize(dev)   # (the copies below run on the current stream, the loop on `stream`)
+        if side is not None:
+            side.synchronize()   # (the copies below run on the current stream, the loop on `stream`)
         it = int(iters.cpu()[0])
         if it < 0:
             raise EngineError(f"unina_kmeans: an init row lies outside [0, {n})")
@@ -1014,11 +1034,12 @@ def nearest_rows(embeddings, centroids, stream=None) -> np.ndarray:
     with torch.cuda.device(embeddings.device):
         sel = torch.zeros(max(k, 1), dtype=torch.int32, device=embeddings.device)
         ws = torch.empty(n, dtype=torch.float32, device=embeddings.device)
+        side = _behind_current(torch, stream, embeddings.device)
         rc = L.unina_nearest_rows(embeddings.data_ptr(), n, d, centroids.data_ptr(), k, sel.data_ptr(), ws.data_ptr(), _stream_ptr(stream))
         if rc:
             raise EngineError(f"unina_nearest_rows failed [{ERRORS.get(rc, rc)}] (n={n}, dim={d}, centroids {tuple(centroids.shape)})")
-        if stream is not None:
-            torch.cuda.synchronize(embeddings.device)
+        if side is not None:
+            side.synchronize()
         return sel.cpu().numpy()[:k].astype(np.int64)
 
 

@@ -183,8 +183,9 @@ def kmeans_numpy(embeddings: np.ndarray, k: int, init_rows=None, max_iter: int =
     """float64 twin of the device loop (csrc/kmeans.hip), same rules, same outputs. Per iteration: label = argmin_j
     |c_j|^2 - 2 <x, c_j> (lowest index on ties); c_j = mean of its members, a cluster without members keeps its centroid;
     inertia = sum (x - c_label)^2 with the new centroids. An iteration whose assignment changes no label is completed and
-    is the last; labels are compared from the second iteration on. Returns (centroids, labels, inertia_history [iters],
-    iters, converged)."""
+    is the last; labels are compared from the second iteration on. Non-finite values are not validated and follow the
+    device's rule (include/unina_mi355.h): a NaN score never wins, and a row all of whose scores are NaN or +inf takes
+    label 0. Returns (centroids, labels, inertia_history [iters], iters, converged)."""
     x = np.asarray(embeddings, dtype=np.float64)
     n = x.shape[0]
     if (init_rows is None) == (centroids is None):
@@ -201,18 +202,23 @@ def kmeans_numpy(embeddings: np.ndarray, k: int, init_rows=None, max_iter: int =
     labels = np.full(n, -1, dtype=np.int64)
     history: List[float] = []
     converged = False
+    def nearest(block):
+        scores = cn - 2.0 * (block @ c.T)
+        return np.argmin(np.where(np.isnan(scores), np.inf, scores), axis=1)   # the device's strict <: a NaN never wins
+
     for _ in range(max_iter):
-        cn = (c * c).sum(axis=1)[None, :]
-        new = np.concatenate([np.argmin(cn - 2.0 * (x[r:r + 8192] @ c.T), axis=1) for r in range(0, n, 8192)])   # (row blocks: memory)
-        changed = int((new != labels).sum())
-        labels = new
-        order = np.argsort(labels, kind="stable")
-        counts = np.bincount(labels, minlength=k)
-        starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
-        live = counts > 0
-        sums = np.add.reduceat(x[order], starts[live], axis=0)
-        c[live] = sums / counts[live][:, None]
-        history.append(float(((x - c[labels]) ** 2).sum()))
+        with np.errstate(invalid="ignore", over="ignore"):                     # (non-finite data is not an error here)
+            cn = (c * c).sum(axis=1)[None, :]
+            new = np.concatenate([nearest(x[r:r + 8192]) for r in range(0, n, 8192)])   # (row blocks: memory)
+            changed = int((new != labels).sum())
+            labels = new
+            order = np.argsort(labels, kind="stable")
+            counts = np.bincount(labels, minlength=k)
+            starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+            live = counts > 0
+            sums = np.add.reduceat(x[order], starts[live], axis=0)
+            c[live] = sums / counts[live][:, None]
+            history.append(float(((x - c[labels]) ** 2).sum()))
         if changed == 0:
             converged = True
             break
