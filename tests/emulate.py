@@ -452,9 +452,11 @@ def check_per_op(records, named: dict, ops=None):
 
 # the sizes and topologies the per-op bound is held at (tests/test_gpu_per_op.py on the kernels, tests/test_per_op_bound_cpu.py
 # on this emulator): P2 / P3 / P4 maps of 4x4 / 2x2 / 1x1 (every map smaller than every tile), a one-row P4 map, odd maps whose
-# widths are no multiple of 4 or 8, and partial tiles in both directions on every level
+# widths are no multiple of 4 or 8, and partial tiles in both directions on every level. Graph (B)'s stride-32 map: 1x1, one
+# row of three, 3x5 (odd both ways, partial tiles on every level)
 PER_OP_SIZES = ((16, 16), (16, 48), (80, 112), (96, 160))
-PER_OP_TOPOLOGIES = (("B-32x32", dict(variant="B", in_h=32, in_w=32)), ("B-96x160", dict(variant="B", in_h=96, in_w=160)),
+PER_OP_TOPOLOGIES = (("B-32x32", dict(variant="B", in_h=32, in_w=32)), ("B-32x96", dict(variant="B", in_h=32, in_w=96)),
+                     ("B-96x160", dict(variant="B", in_h=96, in_w=160)),
                      ("lite_p2", dict(lite_p2=True, in_h=80, in_w=112)), ("base16", dict(base_channels=16, in_h=80, in_w=112)),
                      ("classes1", dict(num_classes=1, in_h=80, in_w=112)), ("classes7", dict(num_classes=7, in_h=80, in_w=112)),
                      ("classes20", dict(num_classes=20, in_h=80, in_w=112)))

@@ -95,11 +95,13 @@ def _geometries():
 
 # Fusable groups the PARENT of the validator's commit found in each file (unina_debug_fusable_groups of that library on the same
 # bytes): the validator moves checks, it must not change what the matchers see. 64x64: as test_abi_cpu.py asserts them.
+# (B-32x96 joined emulate.PER_OP_TOPOLOGIES later: what the planner, unchanged since, finds in it -- the figures of B-32x32.)
 GROUPS = {
     ("fp16", "16x16"): 9, ("fp16", "16x48"): 9,
     ("fp16", "80x112"): 9, ("fp16", "96x160"): 9,
     ("fp16", "64x64"): 9, ("fp16", "640x640"): 9,
     ("fp16", "B-32x32"): 9, ("fp16", "B-96x160"): 9,
+    ("fp16", "B-32x96"): 9,
     ("fp16", "lite_p2"): 8, ("fp16", "base16"): 9,
     ("fp16", "classes1"): 9, ("fp16", "classes7"): 9,
     ("fp16", "classes20"): 8, ("fp16", "lite_p2-64x64"): 8,
@@ -107,6 +109,7 @@ GROUPS = {
     ("fp32", "80x112"): 0, ("fp32", "96x160"): 0,
     ("fp32", "64x64"): 0, ("fp32", "640x640"): 0,
     ("fp32", "B-32x32"): 0, ("fp32", "B-96x160"): 0,
+    ("fp32", "B-32x96"): 0,
     ("fp32", "lite_p2"): 0, ("fp32", "base16"): 0,
     ("fp32", "classes1"): 0, ("fp32", "classes7"): 0,
     ("fp32", "classes20"): 0, ("fp32", "lite_p2-64x64"): 0,
@@ -114,6 +117,7 @@ GROUPS = {
     ("int8", "80x112"): 9, ("int8", "96x160"): 9,
     ("int8", "64x64"): 9, ("int8", "640x640"): 9,
     ("int8", "B-32x32"): 9, ("int8", "B-96x160"): 9,
+    ("int8", "B-32x96"): 9,
     ("int8", "lite_p2"): 8, ("int8", "base16"): 9,
     ("int8", "classes1"): 9, ("int8", "classes7"): 9,
     ("int8", "classes20"): 8, ("int8", "lite_p2-64x64"): 8,
@@ -121,6 +125,7 @@ GROUPS = {
     ("strict", "80x112"): 8, ("strict", "96x160"): 8,
     ("strict", "64x64"): 8, ("strict", "640x640"): 8,
     ("strict", "B-32x32"): 7, ("strict", "B-96x160"): 7,
+    ("strict", "B-32x96"): 7,
     ("strict", "lite_p2"): 7, ("strict", "base16"): 8,
     ("strict", "classes1"): 8, ("strict", "classes7"): 8,
     ("strict", "classes20"): 8, ("strict", "lite_p2-64x64"): 7,

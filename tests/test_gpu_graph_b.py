@@ -136,6 +136,24 @@ def test_graph_b_int8_engine_from_a_qat_checkpoint(pkg, sd7b, oracle_mod, torch_
         for bname, (frac, worst) in mm.items():
             i8 = b8.buffers[[bb[0] for bb in b8.buffers].index(bname)][4] == export.BUF_I8
             assert frac < 2e-3 and worst <= (1.0 if i8 else 4.0), (bname, i8, frac, worst)
+        # ... and the exact criterion beside that fraction: every stored element of every op of the file the checkpoint became
+        # within its float64 rounding bound, here and at 96x160 (a 3x5 stride-32 map, partial tiles on every level)
+        from test_gpu_per_op import _hold, _teacher
+        recs = _hold(b8, x, teacher, "int8 engine from a QAT checkpoint, B 128x128")
+        assert {r["buf"] for r in recs} == set(teacher)
+        g96 = pkg.graph.Graph(variant="B", in_h=96, in_w=160)
+        path96 = str(tmp_path / "qat_b_96x160.une")
+        b96 = export.export_qat_checkpoint(_synthetic_qat_checkpoint(pkg, sd7b, g96)[0], path96, in_h=96, in_w=160)
+        assert b96.precision == export.INT8 and sum(b96.op_int8) == sum(b8.op_int8)
+        e96 = Engine(path96)
+        try:
+            assert e96.set_fusion(False) == 0
+            x96 = pkg.rng.frame(1234, 96, 160)
+            t96 = _teacher(b96, e96, torch_cuda.from_numpy(x96).cuda())
+            recs = _hold(b96, x96, t96, "int8 engine from a QAT checkpoint, B 96x160")
+            assert {r["buf"] for r in recs} == set(t96)
+        finally:
+            e96.close()
         ref = oracle_mod.forward(osd, x, variant="B")
         for n in pkg.graph.OUTPUT_NAMES:
             # free-running, the engine and the emulation are two equally valid roundings of the same arithmetic: each

@@ -2,7 +2,8 @@
 (1) the emulator -- fp32 torch convolutions, a summation order of its own -- stays inside the bound on every element of every
 op at every precision, size and topology the GPU test uses (the bound is not too tight for a correct implementation);
 (2) every mutant of one op -- a dropped tap, a replicated border, a shortcut added before the ReLU, an upsample that copies
-the wrong neighbour, a neighbour's bias, half-away rounding, a clamp at 128 -- is flagged (it is not too loose for a wrong one)."""
+the wrong neighbour, a neighbour's bias, half-away rounding, a clamp at 128 -- is flagged (it is not too loose for a wrong one),
+on graph (A) and, in the int8 table, on the ops only graph (B) has."""
 import numpy as np
 import pytest
 import torch
@@ -61,7 +62,7 @@ def test_emulator_stays_within_the_bound(pkg, sd7, precision, size):
     _hold(b, recs, named, f"{precision} {size[0]}x{size[1]}")
 
 
-@pytest.mark.parametrize("precision", ("fp16", "strict"))
+@pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("topology", E.PER_OP_TOPOLOGIES, ids=lambda t: t[0])
 def test_emulator_stays_within_the_bound_on_other_topologies(pkg, precision, topology):
     b, x, named, recs = _free_run(pkg, None, precision, **topology[1])
@@ -140,6 +141,33 @@ def test_int8_conv_mutants_are_flagged(pkg, sd7, kind):
         assert len(ops) == 2
     for oi in ops:
         n, _ = _flagged(b, x, named, recs, oi, kind)
+        assert n > 0, (kind, b.ops[oi].name)
+
+
+@pytest.mark.parametrize("kind", ("drop_tap", "edge_pad", "up2_last_col", "res_before_relu"))
+def test_int8_mutants_on_graph_b_are_flagged(pkg, kind):
+    """The ops graph (A) never instantiates, in the int8 engine of graph (B) at 96x160 (stride-32 map 3x5): the 3x3 int8 conv that
+    writes the stride-32 map, the lateral conv that upsamples FROM it (the third FPN level), and every conv with a shortcut --
+    picked by those properties, not by name."""
+    from unina_yolo_dla_amd import export
+    b, x, named, recs = _free_run(pkg, None, "int8", variant="B", in_h=96, in_w=160)
+    hw = lambda buf: tuple(b.buffers[buf][1:3])
+    s32 = (96 // 32, 160 // 32)
+    q = lambda i: b.ops[i].kind == export.OP_CONV and b.op_int8[i]
+    up2 = [i for i, op in enumerate(b.ops) if q(i) and any(s.flags & export.SEG_UP2 for s in op.segs)]
+    assert len(up2) == 3                                         # graph (A) has two
+    if kind in ("drop_tap", "edge_pad"):
+        ops = [i for i, op in enumerate(b.ops) if q(i) and op.k == 3 and all(hw(s.dst.buf) == s32 for s in op.segs)]
+        assert len(ops) == 1 and b.ops[ops[0]].s == 2, ops       # the stage's stride-2 conv, reading a 6x10 map
+    elif kind == "up2_last_col":
+        ops = [i for i in up2 if hw(b.ops[i].src_buf) == s32]
+        assert len(ops) == 1, ops
+    else:
+        ops = [i for i, op in enumerate(b.ops) if q(i) and op.res is not None]
+        assert ops                                               # every block's bottleneck that runs in int8, the third FPN block's too
+    for oi in ops:
+        n, _ = _flagged(b, x, named, recs, oi, kind)
+        print("int8 B-96x160", kind, b.ops[oi].name, "flagged elements:", n)
         assert n > 0, (kind, b.ops[oi].name)
 
 
