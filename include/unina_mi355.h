@@ -819,8 +819,8 @@ int unina_ground_buffers(unina_ground_t *g, const uint8_t **d_labels, const uint
  * tracking frame. Integer counters, minima, maxima and sums only (no float atomics): two runs give identical bytes, and any
  * permutation of the cloud the same header, table, records and count, and every point its component.
  * NOT covered: bridging of gaps wider than a cell (a cone whose returns leave an empty cell between them is two components),
- * colour and class from the image, association of LiDAR cones with camera records, motion de-skew, 3-D (voxel) connectivity (a
- * branch over a cone joins it). */
+ * colour and class from the image (unina_fuse_async below associates the LiDAR cones with the camera records and hands a
+ * matched cone the detector's class), motion de-skew, 3-D (voxel) connectivity (a branch over a cone joins it). */
 typedef struct { float x_min, y_min, cell; int nx, ny; int min_points, max_points;
                  float min_height, max_height, max_width, confidence; int class_id; } unina_cluster_params;   /* 48 bytes; nx, ny in 1..UNINA_GROUND_MAX_SIDE */
 typedef struct { float x, y, z_lo, z_hi, x_lo, x_hi, y_lo, y_hi; int n_points, n_cells, root, cone; } unina_cluster;   /* 48 bytes */
@@ -851,6 +851,75 @@ int unina_cluster_async(unina_cluster_t *c, const unina_cloud *cloud, const floa
  * A NULL argument is skipped. UNINA_ERR_STATE before the first unina_cluster_async. */
 int unina_cluster_buffers(unina_cluster_t *c, const unina_cluster **d_components, const int **d_point_component,
                           const unina_cluster_header **d_header);
+
+/* ------------------------------------------------------------------ fusion of LiDAR cone candidates with camera records (behind
+ * unina_cluster_async and any of unina_locate_async / unina_locate_stereo_async / unina_locate_lidar_async, in front of ONE
+ * unina_track_update_async)
+ * The camera branch's records (class and box, camera frame) + the clusterer's records (accurate range, no class, level frame) ->
+ * ONE record list in the camera frame and a link per record: a matched record carries the detector's class and box and the
+ * LiDAR's position. One launch (csrc/fuse.hip: one workgroup of 1024 threads) on the caller's stream; nothing is synchronised,
+ * nothing crosses to the host. The call is stateless: no handle, no workspace, everything it leaves is in the caller's buffers.
+ * fusion.fuse_numpy is the definition, decision for decision and bit for bit. Everything is fp32, each operation rounded once in
+ * the order written, never contracted; the divides are correctly rounded; every decision compares integers, or fp32 values where
+ * a NaN fails.
+ *   counts     nc = *d_count, nl = *d_lcount, each clamped to 0..MAX_DETECTIONS on the device
+ *   LiDAR j    (xc, yc, zc) = level_to_cam applied to (x, y, z + lift) of lcones[j] (rows as ((r0 * x + r1 * y) + r2 * z) + t).
+ *              USABLE iff lcones[j].valid != 0 and xc, yc, zc are finite. PROJECTED iff usable and min_depth <= zc <= max_depth;
+ *              then u = (fx * xc) / zc + cx and v = (fy * yc) / zc + cy, kept as floats and not clipped to any image size
+ *   camera i   X1 = x1 * sx, X2 = x2 * sx, Y1 = y1 * sy, Y2 = y2 * sy. BOXED iff the four are finite, X2 >= X1 and Y2 >= Y1; the
+ *              record's own `valid` is ignored, as in every stage. uc = 0.5f * (X1 + X2), vc = 0.5f * (Y1 + Y2),
+ *              hw = (0.5f * grow) * (X2 - X1) + pad, hh = (0.5f * grow) * (Y2 - Y1) + pad
+ *   candidate  (i, j) with i boxed, j projected, du = u - uc, dv = v - vc, fabsf(du) <= hw and fabsf(dv) <= hh, and, where
+ *              cones[i].valid != 0, fabsf(zc - cones[i].z) <= range_abs + range_rel * zc (a camera record without a depth has no
+ *              depth gate). d2 = du * du + dv * dv is never negative, so its bits order as an unsigned integer
+ *   match      greedy over all candidates in ascending (d2 bits, i, j); a pair is taken iff both its members are free
+ *   slot i < nc  belongs to camera record i (the tracker's d_assign stays index-aligned with the camera records). Matched with
+ *              j: the GpuDetection is the camera's, byte for byte; the cone is (xc, yc, zc, u, v, lcones[j].n_valid,
+ *              lcones[j].n_samples, valid = 1); the link {i, j, d2, UNINA_FUSE_BOTH}. Unmatched: both records are the camera's,
+ *              byte for byte (a cone with valid = 0 included); the link {i, -1, 0, UNINA_FUSE_CAMERA}
+ *   slots nc.. the usable unmatched LiDAR cones in ascending j while a slot is left, the others are counted in n_dropped.
+ *              GpuDetection: x1 = x2 = u / sx and y1 = y2 = v / sy where projected (a point box in record coordinates), else the
+ *              four are 0; confidence and class_id are ldets[j]'s; valid = 1, _pad = 0. Cone: (xc, yc, zc, u, v -- or 0, 0 --,
+ *              lcones[j].n_valid, lcones[j].n_samples, valid = 1). Link {-1, j, 0, UNINA_FUSE_LIDAR}
+ *   the rest   *d_out_count = n_written; every slot at and beyond n_written is all-zero bytes in the three arrays: all
+ *              MAX_DETECTIONS entries are defined after every call. d_lidar_slot[j] = the output slot LiDAR cone j went to (its
+ *              match's, or its own appended one), -1 where it is unusable, dropped or j >= nl; all MAX_DETECTIONS words are written
+ *   header     nc, nl, n_projected, n_matched, nc - n_matched, n_lidar_only (usable unmatched), n_written, n_dropped
+ * Integer counters, 64-bit unsigned minima and a fixed order of every fp32 operation: two runs give identical bytes.
+ * LiDAR-only records carry the clusterer's class_id: give it an id the detector does not use, and run the tracker class-blind or
+ * accept that such a track and a coloured one stay apart until the camera sees the cone.
+ * NOT covered: time alignment of sweep and frame, motion de-skew, a globally optimal (Hungarian) assignment, raising the
+ * confidence of a matched record, class from pixels for LiDAR-only cones, lens distortion (the image is rectified). */
+typedef struct {
+  float level_to_cam[12];         /* row-major 3 x 4 [R|t]: level frame (the clusterer's) -> camera OPTICAL frame */
+  unina_pinhole cam;              /* of the image the camera records live on */
+  float sx, sy;                   /* record -> image pixels, as unina_lidar_params */
+  float lift;                     /* metres above the component's lowest point at which a LiDAR cone is represented (e.g. 0.15) */
+  float min_depth, max_depth;     /* zc range in which a LiDAR cone may be matched; min_depth > 0 */
+  float grow, pad;                /* the box a LiDAR pixel must fall into: half extents (0.5*grow)*(X2-X1) + pad, pad in image pixels */
+  float range_abs, range_rel;     /* depth gate where the camera cone has a depth: |zc - cones[i].z| <= range_abs + range_rel * zc */
+} unina_fuse_params;              /* 100 bytes */
+typedef struct { int camera, lidar; float d2; int kind; } unina_fuse_link;      /* 16 bytes, index-aligned with the OUTPUT records */
+typedef struct { int n_camera, n_lidar, n_projected, n_matched, n_camera_only, n_lidar_only, n_written, n_dropped; } unina_fuse_header; /* 32 bytes */
+#define UNINA_FUSE_BOTH 1
+#define UNINA_FUSE_CAMERA 2
+#define UNINA_FUSE_LIDAR 3
+
+/* One launch, enqueued on `stream`; nothing is synchronised.
+ *   d_dets / d_count / d_cones    : device, the camera branch: MAX_DETECTIONS records / one int / MAX_DETECTIONS unina_cone3d
+ *   d_ldets / d_lcount / d_lcones : device, unina_cluster_async's outputs
+ *   d_out_dets / d_out_count / d_out_cones : device, what unina_track_update_async takes
+ *   d_links : device, MAX_DETECTIONS links; d_lidar_slot : device, MAX_DETECTIONS ints, or NULL; d_header : device, one header
+ * Record arrays, d_links and d_header are 16-byte aligned; the counts and d_lidar_slot 4-byte aligned.
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer (d_lidar_slot alone may be NULL); a misaligned pointer; a non-finite
+ * level_to_cam element or pinhole value, fx or fy equal to 0; sx or sy not finite and positive; lift not finite; min_depth not
+ * finite and positive, max_depth not finite or below min_depth; grow, pad, range_abs or range_rel not finite or negative; any
+ * output array (its whole MAX_DETECTIONS extent) overlapping any input array or another output. */
+int unina_fuse_async(const GpuDetection *d_dets,  const int *d_count,  const unina_cone3d *d_cones,
+                     const GpuDetection *d_ldets, const int *d_lcount, const unina_cone3d *d_lcones,
+                     const unina_fuse_params *p,
+                     GpuDetection *d_out_dets, int *d_out_count, unina_cone3d *d_out_cones,
+                     unina_fuse_link *d_links, int *d_lidar_slot, unina_fuse_header *d_header, hipStream_t stream);
 
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the

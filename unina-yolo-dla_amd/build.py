@@ -37,6 +37,7 @@ UNITS = {
     "ground.hip": ["-ffp-contract=off"],        # LiDAR sweep -> the sweep without its ground: transform, cell, envelope and label round as ground.ground_numpy's fp32 arrays do
     "cluster.hip": ["-ffp-contract=off"],       # ground-free sweep -> cone candidates: transform, cell, position and gate round as cluster.cluster_numpy's fp32 arrays do
     "rectify.hip": ["-ffp-contract=off"],       # raw images -> rectified images: the source coordinates round as rectify.rectify_source_numpy's fp32 arrays do
+    "fuse.hip": ["-ffp-contract=off"],          # LiDAR cone candidates + camera records -> one record list: projection, box, gate and keys round as fusion.fuse_numpy's fp32 arrays do
     "track.hip": ["-ffp-contract=off"],         # located cones -> persistent tracks: gate, keys and slot update round as tracking.update_numpy's fp32 scalars do
     "engine.hip": [],
     "stream_probe.hip": [],                     # unina_debug_streams_overlap: do two streams run at the same time?

@@ -4,7 +4,8 @@
 ``cluster_numpy`` is the DEFINITION: fp32 arrays throughout, one rounding per operation in the order the header states, integer
 keys, counters and sums behind the transform; csrc/cluster.hip (through ``DeviceClusterer``) returns its bytes. It is also the
 twin of csrc/cluster_cell.h, which tests/cluster_cell_host.cpp runs on the host. Pure numpy: the components come from a
-min-propagation loop, not from scipy.
+min-propagation loop, not from scipy. The records carry no colour: fusion.DeviceFuser (unina_fuse_async) associates them with the
+camera's records, and a matched cone takes the detector's class.
 """
 from __future__ import annotations
 

@@ -183,6 +183,20 @@ class ClusterParams(C.Structure):
                 ("confidence", C.c_float), ("class_id", C.c_int)]
 
 
+FUSE_BOTH, FUSE_CAMERA, FUSE_LIDAR = 1, 2, 3   # include/unina_mi355.h UNINA_FUSE_*
+FUSE_LINK_DTYPE = np.dtype([("camera", "<i4"), ("lidar", "<i4"), ("d2", "<f4"), ("kind", "<i4")])                       # unina_fuse_link
+FUSE_HEADER_DTYPE = np.dtype([(n, "<i4") for n in ("n_camera", "n_lidar", "n_projected", "n_matched", "n_camera_only", "n_lidar_only",
+                                                   "n_written", "n_dropped")])                                          # unina_fuse_header
+assert FUSE_LINK_DTYPE.itemsize == 16 and FUSE_HEADER_DTYPE.itemsize == 32
+
+
+class FuseParams(C.Structure):
+    """unina_fuse_params: level_to_cam = row-major 3 x 4 [R|t], level frame -> camera optical frame."""
+    _fields_ = [("level_to_cam", C.c_float * 12), ("cam", Pinhole), ("sx", C.c_float), ("sy", C.c_float), ("lift", C.c_float),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("grow", C.c_float), ("pad", C.c_float), ("range_abs", C.c_float),
+                ("range_rel", C.c_float)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -221,6 +235,7 @@ ABI_SYMBOLS = [
     "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
     "unina_ground_create", "unina_ground_destroy", "unina_ground_filter_async", "unina_ground_buffers",
     "unina_cluster_create", "unina_cluster_destroy", "unina_cluster_async", "unina_cluster_buffers",
+    "unina_fuse_async",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -357,6 +372,8 @@ def load_library() -> C.CDLL:
     L.unina_cluster_destroy.restype = None
     L.unina_cluster_async.argtypes = [vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(ClusterParams), vp, vp, vp, vp]
     L.unina_cluster_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    # fusion of LiDAR cone candidates with camera records (csrc/fuse.hip)
+    L.unina_fuse_async.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(FuseParams), vp, vp, vp, vp, vp, vp, vp]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]
