@@ -687,8 +687,9 @@ int unina_rectify_async(const unina_rectify_job *jobs, int n_jobs, hipStream_t s
  *            expressions of unina_locate_async), otherwise x = y = z = 0; u = uc, v = vc always
  * Integer counters only (no float atomics): two runs, and any permutation of the cloud, give identical unina_cone3d bytes.
  * NOT covered: ground removal (unina_ground_filter_async below goes in front of this call and strips the road; without it a
- * ground point inside the window counts as any other), motion de-skew, time alignment of sweep and frame, lens distortion (the
- * pinhole is the rectified image's), clustering -- the median of what falls in the shrunk box is the whole model. */
+ * ground point inside the window counts as any other), lens distortion (the pinhole is the rectified image's), clustering --
+ * the median of what falls in the shrunk box is the whole model. Motion de-skew and the time alignment of sweep and frame are
+ * unina_deskew_async below, which goes in front of this call. */
 #define UNINA_LIDAR_MAX_DIM    16384       /* width, height */
 #define UNINA_LIDAR_MAX_POINTS (1 << 22)
 typedef struct { int n_points, stride; const void *points; } unina_cloud;   /* device; xyz float32 first in each point */
@@ -719,6 +720,84 @@ int unina_locate_lidar_async(unina_lidar_t *l, const GpuDetection *d_dets, const
 /* Device address of the per-point result of the last call (n_points unina_lidar_pixel, in point order), for a consumer that
  * stays on the GPU or a test; read it behind the call on its stream. UNINA_ERR_STATE before the first unina_locate_lidar_async. */
 int unina_lidar_buffers(unina_lidar_t *l, const unina_lidar_pixel **d_pixels);
+
+/* ------------------------------------------------------------------ motion de-skew of a LiDAR sweep (in front of
+ * unina_ground_filter_async, unina_cluster_async or unina_locate_lidar_async: a rotating LiDAR takes about 100 ms per sweep, and
+ * at 15 m/s and 1.5 rad/s of yaw a static cone is displaced by metres between the first and the last column)
+ * A point cloud on the device + a time per point + the LiDAR's poses over the sweep (host memory) + a reference time -> a cloud of
+ * the same length and order with 16-byte points, every point moved to where the LiDAR would have seen it at t_ref. The stages
+ * behind it take {n_points, 16, d_out} unchanged; the caller's lidar_to_level / lidar_to_cam still apply and now describe the
+ * LiDAR at t_ref. With t_ref = the camera frame's exposure time, sweep and frame are aligned as well. The call is stateless: no
+ * handle, no workspace. It enqueues one memset of the header and one kernel (csrc/deskew.hip) on the caller's stream and the
+ * current device; nothing is synchronised. deskew.table_numpy and deskew.deskew_numpy are the definition, decision for decision and
+ * bit for bit.
+ * HOST HALF (unina_deskew_table; float64 throughout, each operation rounded once in the order written; the absolute stamps and
+ * the large odometry coordinates cancel here and never reach the device):
+ *   1 normalise  q_k = q_k / sqrt(((w*w + x*x) + y*y) + z*z), component by component
+ *   2 reference  r = (the number of keys with t_j <= t_ref) - 1, clamped to 0..K-2; s = (t_ref - t_r) / (t_{r+1} - t_r);
+ *                b = q_{r+1}, negated when ((aw*bw + ax*bx) + ay*by) + az*bz < 0 for a = q_r; q_ref = a + s * (b - a) per
+ *                component, normalised as in 1; p_ref = p_r + s * (p_{r+1} - p_r)
+ *   3 relative   with c = conj(q_ref) = (w, -x, -y, -z): D_k = c (x) q_k (Hamilton product: w = ((cw*qw - cx*qx) - cy*qy) - cz*qz,
+ *                x = ((cw*qx + cx*qw) + cy*qz) - cz*qy, y = ((cw*qy - cx*qz) + cy*qw) + cz*qx, z = ((cw*qz + cx*qy) - cy*qx) + cz*qw),
+ *                normalised as in 1; d_k = R(c) (p_k - p_ref), row i as (Ri0 * vx + Ri1 * vy) + Ri2 * vz, with R(q):
+ *                R00 = 1 - 2*(y*y + z*z)  R01 = 2*(x*y - w*z)      R02 = 2*(x*z + w*y)
+ *                R10 = 2*(x*y + w*z)      R11 = 1 - 2*(x*x + z*z)  R12 = 2*(y*z - w*x)
+ *                R20 = 2*(x*z - w*y)      R21 = 2*(y*z + w*x)      R22 = 1 - 2*(x*x + y*y)
+ *   4 hemisphere D_0 is negated when its w < 0; for k >= 1 D_k is negated when dot(D_k, D_{k-1}) < 0 (so keys given as q or
+ *                as -q make the same table)
+ *   5 round      the float32 row {(float)(D_k.w + 0.0), .x, .y, .z, (float)(d_k.x + 0.0), .y, .z, t = (float)(t_k - t_sweep)}:
+ *                the sum turns a -0.0 into +0.0 and changes nothing else
+ * DEVICE HALF (fp32 throughout, each operation rounded once in the order written, never contracted; divide and square root are
+ * correctly rounded), per point i:
+ *   time      tau = the float32 at times.t + i * times.stride (UNINA_TIME_F32_S), or (float)ns * 1e-9f of the uint32 there
+ *             (UNINA_TIME_U32_NS: one conversion, one multiply); seconds after t_sweep
+ *   validity  INVALID iff any of x, y, z is not finite, or tau is not finite. An INVALID point writes four words 0x7fc00000: the
+ *             ground filter's absent entry, which every later stage skips
+ *   segment   k = (the number of keys with t_j <= tau) - 1, clamped to 0..K-2; s = (tau - t_k) / (t_{k+1} - t_k), clamped to
+ *             [0, 1]: tau == t_j belongs to segment j, tau == t_{K-1} gives segment K-2 with s == 1 exactly. BEFORE iff
+ *             tau < t_0, AFTER iff tau > t_{K-1}: such a point takes the first or the last key's pose and is counted
+ *   pose      each of the seven values of the rows k and k+1 as a + s * (b - a); n = sqrt(((qw*qw + qx*qx) + qy*qy) + qz*qz),
+ *             q = q / n per component; the nine elements of R(q) by the expressions of step 3
+ *   point     x' = ((R00 * x + R01 * y) + R02 * z) + px, y' and z' from rows 1 and 2 (the expression of lidar_to_cam)
+ *   output    entry i of d_out = (x', y', z', carry): carry = the 32-bit word at byte carry_offset of the point, verbatim, or
+ *             0x7fc00000 for carry_offset == -1. A NaN result (coordinates so near the fp32 limit that the sums overflow both
+ *             ways) is stored as the word 0x7fc00000
+ *   header    n_points; n_moved = the points that are not INVALID; n_invalid; n_before; n_after; max_shift2_bits = the largest
+ *             bit pattern, as an unsigned integer, of (dx*dx + dy*dy) + dz*dz with dx = x' - x over the moved points (never
+ *             negative, so the patterns order as the values do; a NaN as 0x7fc00000); two reserved words, 0
+ * Integer counters and one integer maximum only (no float atomics): two runs give identical bytes, and any permutation of the
+ * cloud the same header and the permuted points.
+ * The model between two keys is nlerp of the rotation and a linear translation: its error falls with the square of the key
+ * spacing. NOT covered: estimating the poses (odometry / IMU integration is the caller's), per-point times derived
+ * from the azimuth, slerp, more than UNINA_DESKEW_MAX_KEYS keys, rolling-shutter correction of the camera. */
+#define UNINA_DESKEW_MAX_KEYS 64
+#define UNINA_TIME_F32_S  0                /* float32 seconds after t_sweep */
+#define UNINA_TIME_U32_NS 1                /* uint32 nanoseconds after t_sweep */
+typedef struct { const void *t; int stride; int format; } unina_point_times;   /* device; a time inside the point: t = points + offset, stride = the cloud's; a plane: stride = 4 */
+typedef struct { double t; double q[4]; double p[3]; } unina_deskew_pose;       /* 64 bytes, host; q = w, x, y, z; LiDAR frame -> a fixed (odometry) frame at time t */
+typedef struct { float qw, qx, qy, qz, px, py, pz, t; } unina_deskew_key;       /* 32 bytes: the pose of key k relative to the pose at t_ref */
+typedef struct { int n_points, n_moved, n_invalid, n_before, n_after; uint32_t max_shift2_bits; int reserved[2]; } unina_deskew_header;   /* 32 bytes */
+
+/* The host half on its own: no HIP call, no device. out: n_keys rows, written only on UNINA_OK.
+ * UNINA_ERR_ARG: a NULL pointer; n_keys outside 2..UNINA_DESKEW_MAX_KEYS; a non-finite field of a pose, t_sweep or t_ref; a
+ * zero-norm quaternion; the float32 key times (float)(t_k - t_sweep) not finite or not strictly increasing; t_ref outside
+ * [t_0, t_{K-1}]; after step 4 dot(D_k, D_{k-1}) < 0.5 (more than 120 degrees between two keys: nlerp would approach a zero
+ * norm); a relative translation that is not finite as a float32. */
+int unina_deskew_table(const unina_deskew_pose *poses, int n_keys, double t_sweep, double t_ref, unina_deskew_key *out);
+/*   cloud->points : device, n_points * stride bytes, 4-byte aligned (read 16 bytes at a time where the base and the stride allow)
+ *   times->t      : device, 4-byte aligned; times->stride a multiple of 4, at least 4; may be NULL only when n_points == 0
+ *   carry_offset  : -1, or a multiple of 4 in 12 .. stride - 4
+ *   poses         : host, n_keys of them; read before the call returns
+ *   d_out         : device, n_points * 16 bytes, 16-byte aligned; every entry is written exactly once
+ *   d_header      : device, one unina_deskew_header, 4-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: what unina_deskew_table refuses; a NULL cloud, times, d_out or d_header (points may be NULL
+ * only when n_points == 0); n_points outside 0..UNINA_LIDAR_MAX_POINTS; stride < 12 or not a multiple of 4, or points not 4-byte
+ * aligned; times->t not 4-byte aligned, times->stride < 4 or not a multiple of 4, an unknown format; a carry_offset that is not
+ * -1 and not a multiple of 4 in 12 .. stride - 4; d_out not 16-byte or d_header not 4-byte aligned; the n_points * 16 bytes at
+ * d_out overlapping the cloud, the time plane or the header.
+ * n_points == 0 is legal: the header is all-zero and nothing is written to d_out. */
+int unina_deskew_async(const unina_cloud *cloud, const unina_point_times *times, int carry_offset, const unina_deskew_pose *poses,
+                       int n_keys, double t_sweep, double t_ref, void *d_out, unina_deskew_header *d_header, hipStream_t stream);
 
 /* ------------------------------------------------------------------ ground removal from a LiDAR sweep (in front of
  * unina_locate_lidar_async: a road return inside a record's window would otherwise count as any other)
@@ -754,8 +833,8 @@ int unina_lidar_buffers(unina_lidar_t *l, const unina_lidar_pixel **d_pixels);
  * Integer counters and integer minima only (no float atomics): two runs give identical bytes, and any permutation of the cloud
  * gives every point the same label and the same cellmin, g and header.
  * NOT covered: ground steeper than `rise` allows between neighbouring cells (a banked or sloped track beyond it is labelled
- * OBJECT or ABOVE), plane or line fitting, motion de-skew, an estimate of lidar_to_level (the caller's calibration or IMU
- * supplies it). Clustering of what is kept is unina_cluster_async below, which takes {n_points, 16, d_out} as its cloud. */
+ * OBJECT or ABOVE), plane or line fitting, an estimate of lidar_to_level (the caller's calibration or IMU supplies it). Motion
+ * de-skew is unina_deskew_async above, which goes in front of this call. Clustering of what is kept is unina_cluster_async below, which takes {n_points, 16, d_out} as its cloud. */
 #define UNINA_GROUND_MAX_SIDE  1024        /* nx, ny */
 #define UNINA_GROUND_MAX_REACH 4
 typedef struct { float x_min, y_min, cell; int nx, ny;
@@ -820,7 +899,8 @@ int unina_ground_buffers(unina_ground_t *g, const uint8_t **d_labels, const uint
  * permutation of the cloud the same header, table, records and count, and every point its component.
  * NOT covered: bridging of gaps wider than a cell (a cone whose returns leave an empty cell between them is two components),
  * colour and class from the image (unina_fuse_async below associates the LiDAR cones with the camera records and hands a
- * matched cone the detector's class), motion de-skew, 3-D (voxel) connectivity (a branch over a cone joins it). */
+ * matched cone the detector's class), 3-D (voxel) connectivity (a branch over a cone joins it). Motion de-skew is
+ * unina_deskew_async, in front of the ground filter. */
 typedef struct { float x_min, y_min, cell; int nx, ny; int min_points, max_points;
                  float min_height, max_height, max_width, confidence; int class_id; } unina_cluster_params;   /* 48 bytes; nx, ny in 1..UNINA_GROUND_MAX_SIDE */
 typedef struct { float x, y, z_lo, z_hi, x_lo, x_hi, y_lo, y_hi; int n_points, n_cells, root, cone; } unina_cluster;   /* 48 bytes */
@@ -888,7 +968,8 @@ int unina_cluster_buffers(unina_cluster_t *c, const unina_cluster **d_components
  * Integer counters, 64-bit unsigned minima and a fixed order of every fp32 operation: two runs give identical bytes.
  * LiDAR-only records carry the clusterer's class_id: give it an id the detector does not use, and run the tracker class-blind or
  * accept that such a track and a coloured one stay apart until the camera sees the cone.
- * NOT covered: time alignment of sweep and frame, motion de-skew, a globally optimal (Hungarian) assignment, raising the
+ * Time alignment of sweep and frame and motion de-skew are unina_deskew_async, in front of the LiDAR branch, with t_ref = the
+ * frame's exposure time. NOT covered: a globally optimal (Hungarian) assignment, raising the
  * confidence of a matched record, class from pixels for LiDAR-only cones, lens distortion (the image is rectified). */
 typedef struct {
   float level_to_cam[12];         /* row-major 3 x 4 [R|t]: level frame (the clusterer's) -> camera OPTICAL frame */

@@ -34,7 +34,8 @@ UNITS = {
     "locate.hip": ["-ffp-contract=off"],        # detections -> 3-D points: window, validity and back-projection round as localize.locate_numpy's fp32 scalars do
     "stereo.hip": ["-ffp-contract=off"],        # detections -> 3-D points from a stereo pair: range, sub-pixel step and point round as localize.locate_stereo_numpy's fp32 scalars do
     "lidar.hip": ["-ffp-contract=off"],         # detections -> 3-D points from a LiDAR sweep: transform, projection and point round as localize.locate_lidar_numpy's fp32 scalars do
-    "ground.hip": ["-ffp-contract=off"],        # LiDAR sweep -> the sweep without its ground: transform, cell, envelope and label round as ground.ground_numpy's fp32 arrays do
+    "deskew.hip": ["-ffp-contract=off"],        # LiDAR sweep + point times + poses -> the sweep at one reference time: the float64 table and the fp32 pose, point and shift round as deskew.table_numpy's and deskew.deskew_numpy's do
+    "ground.hip": ["-ffp-contract=off"],       # LiDAR sweep -> the sweep without its ground: transform, cell, envelope and label round as ground.ground_numpy's fp32 arrays do
     "cluster.hip": ["-ffp-contract=off"],       # ground-free sweep -> cone candidates: transform, cell, position and gate round as cluster.cluster_numpy's fp32 arrays do
     "rectify.hip": ["-ffp-contract=off"],       # raw images -> rectified images: the source coordinates round as rectify.rectify_source_numpy's fp32 arrays do
     "fuse.hip": ["-ffp-contract=off"],          # LiDAR cone candidates + camera records -> one record list: projection, box, gate and keys round as fusion.fuse_numpy's fp32 arrays do

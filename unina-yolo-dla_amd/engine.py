@@ -157,6 +157,19 @@ class LidarParams(C.Structure):
                 ("min_valid", C.c_int)]
 
 
+DESKEW_MAX_KEYS, TIME_F32_S, TIME_U32_NS = 64, 0, 1   # include/unina_mi355.h UNINA_DESKEW_MAX_KEYS, UNINA_TIME_*
+DESKEW_POSE_DTYPE = np.dtype([("t", "<f8"), ("q", "<f8", (4,)), ("p", "<f8", (3,))])                                    # unina_deskew_pose
+DESKEW_KEY_DTYPE = np.dtype([(n, "<f4") for n in ("qw", "qx", "qy", "qz", "px", "py", "pz", "t")])                      # unina_deskew_key
+DESKEW_HEADER_DTYPE = np.dtype([(n, "<i4") for n in ("n_points", "n_moved", "n_invalid", "n_before", "n_after")] +
+                               [("max_shift2_bits", "<u4"), ("reserved", "<i4", (2,))])                                 # unina_deskew_header
+assert DESKEW_POSE_DTYPE.itemsize == 64 and DESKEW_KEY_DTYPE.itemsize == 32 and DESKEW_HEADER_DTYPE.itemsize == 32
+
+
+class PointTimes(C.Structure):
+    """unina_point_times: a time per point on the device, `stride` bytes apart, TIME_F32_S or TIME_U32_NS."""
+    _fields_ = [("t", C.c_void_p), ("stride", C.c_int), ("format", C.c_int)]
+
+
 GROUND_MAX_SIDE, GROUND_MAX_REACH = 1024, 4   # include/unina_mi355.h UNINA_GROUND_*
 GROUND_HEADER_DTYPE = np.dtype([("n_points", "<i4"), ("n_kept", "<i4"), ("n_label", "<i4", (5,)), ("n_cells_seeded", "<i4")])   # unina_ground_header
 assert GROUND_HEADER_DTYPE.itemsize == 32
@@ -233,6 +246,7 @@ ABI_SYMBOLS = [
     "unina_eval_create", "unina_eval_destroy", "unina_eval_reset_async", "unina_eval_update_async", "unina_eval_read",
     "unina_locate_async", "unina_locate_stereo_async", "unina_rectify_async",
     "unina_lidar_create", "unina_lidar_destroy", "unina_locate_lidar_async", "unina_lidar_buffers",
+    "unina_deskew_table", "unina_deskew_async",
     "unina_ground_create", "unina_ground_destroy", "unina_ground_filter_async", "unina_ground_buffers",
     "unina_cluster_create", "unina_cluster_destroy", "unina_cluster_async", "unina_cluster_buffers",
     "unina_fuse_async",
@@ -372,6 +386,9 @@ def load_library() -> C.CDLL:
     L.unina_cluster_destroy.restype = None
     L.unina_cluster_async.argtypes = [vp, C.POINTER(Cloud), C.POINTER(cf * 12), C.POINTER(ClusterParams), vp, vp, vp, vp]
     L.unina_cluster_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    # motion de-skew of a LiDAR sweep (csrc/deskew.hip)
+    L.unina_deskew_table.argtypes = [vp, ci, C.c_double, C.c_double, vp]
+    L.unina_deskew_async.argtypes = [C.POINTER(Cloud), C.POINTER(PointTimes), ci, vp, ci, C.c_double, C.c_double, vp, vp, vp]
     # fusion of LiDAR cone candidates with camera records (csrc/fuse.hip)
     L.unina_fuse_async.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(FuseParams), vp, vp, vp, vp, vp, vp, vp]
     # tracking (csrc/track.hip)
