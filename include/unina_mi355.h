@@ -966,11 +966,12 @@ int unina_cluster_buffers(unina_cluster_t *c, const unina_cluster **d_components
  *              match's, or its own appended one), -1 where it is unusable, dropped or j >= nl; all MAX_DETECTIONS words are written
  *   header     nc, nl, n_projected, n_matched, nc - n_matched, n_lidar_only (usable unmatched), n_written, n_dropped
  * Integer counters, 64-bit unsigned minima and a fixed order of every fp32 operation: two runs give identical bytes.
- * LiDAR-only records carry the clusterer's class_id: give it an id the detector does not use, and run the tracker class-blind or
- * accept that such a track and a coloured one stay apart until the camera sees the cone.
+ * LiDAR-only records carry the clusterer's class_id: give it an id the detector does not use and put unina_colour_async (below)
+ * behind this call with only_class = that id, which writes the class from the rectified image's pixels; a record it leaves
+ * undecided keeps the unknown id, and such a track and a coloured one stay apart until the camera or the colour stage names it.
  * Time alignment of sweep and frame and motion de-skew are unina_deskew_async, in front of the LiDAR branch, with t_ref = the
  * frame's exposure time. NOT covered: a globally optimal (Hungarian) assignment, raising the
- * confidence of a matched record, class from pixels for LiDAR-only cones, lens distortion (the image is rectified). */
+ * confidence of a matched record, lens distortion (the image is rectified). */
 typedef struct {
   float level_to_cam[12];         /* row-major 3 x 4 [R|t]: level frame (the clusterer's) -> camera OPTICAL frame */
   unina_pinhole cam;              /* of the image the camera records live on */
@@ -1001,6 +1002,107 @@ int unina_fuse_async(const GpuDetection *d_dets,  const int *d_count,  const uni
                      const unina_fuse_params *p,
                      GpuDetection *d_out_dets, int *d_out_count, unina_cone3d *d_out_cones,
                      unina_fuse_link *d_links, int *d_lidar_slot, unina_fuse_header *d_header, hipStream_t stream);
+
+/* ------------------------------------------------------------------ class from pixels (behind unina_fuse_async or any locator,
+ * in front of unina_track_update_async)
+ * A record without a class -- a LiDAR cone the detector missed -- + the rectified colour image (unina_rectify_async's output) ->
+ * the record with the class its pixels show: blue, yellow, orange or large orange. A memset of the header and one launch
+ * (csrc/colour.hip: one workgroup per record slot) on the caller's stream; nothing is synchronised, nothing crosses to the host.
+ * The call is stateless: no handle, no workspace. colour.colour_numpy is the definition, bit for bit. Everything behind the
+ * window is integer arithmetic (divisions are floor divisions of non-negative integers); the window's floats are fp32, each
+ * operation rounded once in the order written, never contracted; the divides are correctly rounded.
+ *   count      n = *d_count clamped to 0..MAX_DETECTIONS on the device. Slots at and beyond n are all-zero bytes in d_out_dets
+ *              and d_colour: all MAX_DETECTIONS entries of both are defined after every call
+ *   selected   record i < n is SELECTED iff only_class < 0 or dets[i].class_id == only_class; the record's own `valid` is
+ *              ignored, as in every stage. A record that is not selected is copied byte for byte, its d_colour entry is zero
+ *   window     BOX: where X1 = x1 * sx, X2 = x2 * sx, Y1 = y1 * sy, Y2 = y2 * sy are finite, X2 > X1 and Y2 > Y1, the window and
+ *              its grid are those of unina_locate_async (csrc/locate_window.h: the covered pixels floorf(c - h) .. floorf(c + h)
+ *              per axis with h = (0.5f * shrink) * (X2 - X1), clipped to the image; stride = ceil(span / max_side)) on
+ *              (x1, y1, x2, y2, sx, sy, shrink, width, height, max_side).
+ *              SIZE: where the BOX conditions fail (the fuser's point box x1 = x2), d_cones != NULL, cones[i].valid != 0 and u, v,
+ *              z of cones[i] are finite with z > 0: hw = (fx * half_width) / z, up = (fy * above) / z, down = (fy * below) / z, and
+ *              the same function on the box (u - hw, v - up, u + hw, v + down) with sx = sy = 1 and the same shrink and max_side.
+ *              half_width, above and below are metres relative to the represented point (the fuser's `lift` above the base); the
+ *              camera is taken to be level: optical y points down.
+ *              Neither case, or a window that covers no pixel: the record is copied byte for byte, its d_colour entry is
+ *              {0, .., status = SELECTED}
+ *   grid       the sampled pixels (u0 + c * stride_x, v0 + k * stride_y), c < cols, k < rows; cols, rows <= max_side <= 64
+ *   silhouette sample (c, k) is INSIDE iff |2c - (cols - 1)| * 256 * rows <= cols * (taper * rows + (256 - taper) * (k + 1)):
+ *              a trapezoid centred on the grid whose top is taper / 256 of its base; taper = 256: every sample.
+ *              mask_k = the inside samples of row k, n_mask their sum
+ *   pixel      bytes 0..2 of the pixel are B, G, R (order == UNINA_COLOUR_BGR) or R, G, B (UNINA_COLOUR_RGB); a fourth channel
+ *              is ignored. mx = max, mn = min, d = mx - mn. The first that holds: BLACK iff mx <= black_max; COLOURED iff
+ *              d * 256 >= sat_min * mx and mx >= val_min (sat_min >= 1: d > 0); WHITE iff mx >= white_min; else OTHER
+ *   hue        of a COLOURED pixel, 0..1535 (256 per sextant):
+ *              mx == R: h = 256 * (G - B) / d where G >= B, else (1536 - 256 * (B - G) / d) % 1536
+ *              else mx == G: h = 512 + 256 * (B - R) / d where B >= R, else 512 - 256 * (R - B) / d
+ *              else: h = 1024 + 256 * (R - G) / d where R >= G, else 1024 - 256 * (G - R) / d
+ *              The pixel votes for the first colour c in the order yellow (0), blue (1), orange (2) whose range holds h:
+ *              hue_lo[c] <= h <= hue_hi[c] where lo <= hi, else h >= lo or h <= hi (a range across 0); no range: OTHER
+ *   rows       per row k six counts over its inside samples: votes_k[3], white_k, black_k, mask_k
+ *   body       votes[c] = the sum of votes_k[c]. best = the colour with the most votes, second = the one with the most of the
+ *              other two; ties go to the earlier colour
+ *   stripes    the stripe colour is BLACK where best is yellow, else WHITE. A row with mask_k > 0 is B iff
+ *              2 * votes_k[best] >= mask_k, else S iff 2 * stripe_k >= mask_k, else it is dropped. n_stripes = the maximal runs
+ *              of S in the string of the remaining rows (top to bottom) with a B somewhere before and a B somewhere after them
+ *   class      the colour index is 3 (large orange) iff best is orange, n_stripes >= 2 and class_of[3] >= 0, else best.
+ *              DECIDED iff n_mask >= min_pixels, votes[best] * 256 >= min_share * n_mask,
+ *              votes[second] * 256 <= max_rival * votes[best], votes[best] > 0, n_stripes >= 1 where require_stripe != 0, and
+ *              class_of[colour index] >= 0. The status bit LARGE: DECIDED with the colour index 3. class_of is a parameter
+ *              because data sets disagree on the ids (yellow 0 and blue 1 in one, blue 0 and yellow 1 in another)
+ *   output     d_out_dets[i] = d_dets[i] byte for byte, except class_id = class_of[colour index] where selected and DECIDED.
+ *              d_colour[i], for a selected record with a window, decided or not: votes[3], n_white, n_black, n_mask, n_stripes,
+ *              status = WINDOW | SELECTED | DECIDED? | LARGE? | SIZE_WINDOW? | best << 8
+ *   header     n_records = n, n_selected, n_window, n_decided, n_class[colour index] over the decided: integer atomics
+ * Every count is an integer: two runs give identical bytes.
+ * NOT covered: cones cut by the image border (the silhouette is centred on the clipped grid), a camera that is not level, white
+ * balance or exposure correction, NV12 or planar colour, raising a record's confidence, learning the thresholds from data. */
+#define UNINA_COLOUR_BGR 0
+#define UNINA_COLOUR_RGB 1
+#define UNINA_COLOUR_YELLOW 0             /* colour indices: votes[], hue_lo[], hue_hi[], class_of[], n_class[] */
+#define UNINA_COLOUR_BLUE 1
+#define UNINA_COLOUR_ORANGE 2
+#define UNINA_COLOUR_LARGE_ORANGE 3       /* class_of[] and n_class[] only */
+#define UNINA_COLOUR_WINDOW 1             /* status bits */
+#define UNINA_COLOUR_SELECTED 2
+#define UNINA_COLOUR_DECIDED 4
+#define UNINA_COLOUR_LARGE 8
+#define UNINA_COLOUR_SIZE_WINDOW 16
+#define UNINA_COLOUR_MAX_SIDE 64
+typedef struct {
+  float sx, sy, shrink;                   /* record -> image pixels; the share of the box (BOX or SIZE) that is sampled, (0, 1] */
+  float half_width, above, below;         /* SIZE window, metres around the represented point (small cone: 0.114, 0.175, 0.15) */
+  int max_side;                           /* 1..UNINA_COLOUR_MAX_SIDE samples per axis */
+  int order;                              /* UNINA_COLOUR_BGR / UNINA_COLOUR_RGB */
+  int only_class;                         /* < 0: every record; else the records with this class_id (the clusterer's unknown id) */
+  int class_of[4];                        /* class_id written for yellow, blue, orange, large orange; < 0: never decided */
+  int black_max, sat_min, val_min, white_min;   /* 0..255, 1..256 (saturation in 1/256), 0..255, 0..255 */
+  int hue_lo[3], hue_hi[3];               /* 0..1535 per colour; lo > hi: a range across 0 */
+  int taper;                              /* 0..256: the silhouette's top width in 1/256 of its base */
+  int min_pixels, min_share, max_rival;   /* >= 1; 0..256: best's share of n_mask, second's share of best, in 1/256 */
+  int require_stripe;                     /* != 0: an undecided record unless n_stripes >= 1 */
+} unina_colour_params;                    /* 112 bytes */
+typedef struct { int votes[3]; int n_white, n_black, n_mask, n_stripes, status; } unina_colour;                 /* 32 bytes, index-aligned with the records */
+typedef struct { int n_records, n_selected, n_window, n_decided, n_class[4]; } unina_colour_header;             /* 32 bytes */
+
+/* A memset of *d_header and one launch, enqueued on `stream`; nothing is synchronised.
+ *   d_dets / d_count : device, MAX_DETECTIONS records / one int, as unina_fuse_async or the _async calls write them
+ *   d_cones    : device, MAX_DETECTIONS unina_cone3d index-aligned with the records, or NULL (then no record has a SIZE window)
+ *   image      : host struct; data on the device, 3 or 4 interleaved 8-bit channels, pitch in bytes. No alignment is required
+ *                of data or of the pitch; no byte behind a pixel's last one is read
+ *   cam        : of that image
+ *   d_out_dets : device, MAX_DETECTIONS records; may be d_dets itself (in place: a workgroup reads and writes its own record only)
+ *   d_colour   : device, MAX_DETECTIONS unina_colour; d_header : device, one header
+ * Record arrays, d_colour and d_header are 16-byte aligned, d_count 4-byte aligned.
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer other than d_cones, or a NULL image->data; a misaligned pointer; channels
+ * not 3 or 4, width or height outside 1..16384, pitch < width * channels; a non-finite pinhole value, fx or fy not positive; sx
+ * or sy not finite and positive, shrink outside (0, 1]; half_width, above or below not finite or negative; max_side outside
+ * 1..64; order not one of the two; black_max, val_min or white_min outside 0..255, sat_min outside 1..256, a hue bound outside
+ * 0..1535, taper, min_share or max_rival outside 0..256, min_pixels < 1; d_out_dets or d_colour overlapping d_dets or each other
+ * over their MAX_DETECTIONS extent, except d_out_dets == d_dets exactly. */
+int unina_colour_async(const GpuDetection *d_dets, const int *d_count, const unina_cone3d *d_cones, const unina_image *image,
+                       const unina_pinhole *cam, const unina_colour_params *p, GpuDetection *d_out_dets, unina_colour *d_colour,
+                       unina_colour_header *d_header, hipStream_t stream);
 
 /* ------------------------------------------------------------------ tracking (cones are static landmarks: no motion model)
  * The frame's records, their unina_cone3d points and the camera's pose in a fixed frame -> a persistent table of tracks on the

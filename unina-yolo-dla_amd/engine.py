@@ -210,6 +210,23 @@ class FuseParams(C.Structure):
                 ("range_rel", C.c_float)]
 
 
+COLOUR_BGR, COLOUR_RGB = 0, 1                                                       # include/unina_mi355.h UNINA_COLOUR_*: pixel orders
+COLOUR_YELLOW, COLOUR_BLUE, COLOUR_ORANGE, COLOUR_LARGE_ORANGE = 0, 1, 2, 3         # colour indices
+COLOUR_WINDOW, COLOUR_SELECTED, COLOUR_DECIDED, COLOUR_LARGE, COLOUR_SIZE_WINDOW = 1, 2, 4, 8, 16   # status bits; best in bits 8..9
+COLOUR_MAX_SIDE = 64
+COLOUR_DTYPE = np.dtype([("votes", "<i4", (3,))] + [(n, "<i4") for n in ("n_white", "n_black", "n_mask", "n_stripes", "status")])   # unina_colour
+COLOUR_HEADER_DTYPE = np.dtype([(n, "<i4") for n in ("n_records", "n_selected", "n_window", "n_decided")] + [("n_class", "<i4", (4,))])   # unina_colour_header
+assert COLOUR_DTYPE.itemsize == 32 and COLOUR_HEADER_DTYPE.itemsize == 32
+
+
+class ColourParams(C.Structure):
+    """unina_colour_params: the window, the pixel thresholds, the hue ranges (yellow, blue, orange), the silhouette and the decision."""
+    _fields_ = [(n, C.c_float) for n in ("sx", "sy", "shrink", "half_width", "above", "below")] + \
+               [("max_side", C.c_int), ("order", C.c_int), ("only_class", C.c_int), ("class_of", C.c_int * 4), ("black_max", C.c_int),
+                ("sat_min", C.c_int), ("val_min", C.c_int), ("white_min", C.c_int), ("hue_lo", C.c_int * 3), ("hue_hi", C.c_int * 3),
+                ("taper", C.c_int), ("min_pixels", C.c_int), ("min_share", C.c_int), ("max_rival", C.c_int), ("require_stripe", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -249,7 +266,7 @@ ABI_SYMBOLS = [
     "unina_deskew_table", "unina_deskew_async",
     "unina_ground_create", "unina_ground_destroy", "unina_ground_filter_async", "unina_ground_buffers",
     "unina_cluster_create", "unina_cluster_destroy", "unina_cluster_async", "unina_cluster_buffers",
-    "unina_fuse_async",
+    "unina_fuse_async", "unina_colour_async",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
@@ -391,6 +408,8 @@ def load_library() -> C.CDLL:
     L.unina_deskew_async.argtypes = [C.POINTER(Cloud), C.POINTER(PointTimes), ci, vp, ci, C.c_double, C.c_double, vp, vp, vp]
     # fusion of LiDAR cone candidates with camera records (csrc/fuse.hip)
     L.unina_fuse_async.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(FuseParams), vp, vp, vp, vp, vp, vp, vp]
+    # class from pixels for records without one (csrc/colour.hip)
+    L.unina_colour_async.argtypes = [vp, vp, vp, C.POINTER(Image), C.POINTER(Pinhole), C.POINTER(ColourParams), vp, vp, vp, vp]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]

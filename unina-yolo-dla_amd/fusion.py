@@ -4,8 +4,9 @@ clusterer and a locator and in front of ONE tracker (include/unina_mi355.h "fusi
 ``fuse_numpy`` is the DEFINITION: fp32 scalars and arrays throughout, one rounding per operation in the order the header states,
 and the association is the plain greedy loop over the sorted candidate pairs; csrc/fuse.hip (through ``DeviceFuser``) returns its
 bytes. It is also the twin of csrc/fuse_math.h, which tests/fuse_math_host.cpp runs on the host.
+Class from pixels for the LiDAR-only records is the stage behind this one (colour.py).
 NOT covered: time alignment of sweep and frame, motion de-skew, a globally optimal (Hungarian) assignment, raising the confidence
-of a matched record, class from pixels for LiDAR-only cones, lens distortion (the image is rectified).
+of a matched record, lens distortion (the image is rectified).
 """
 from __future__ import annotations
 
