@@ -1162,6 +1162,70 @@ int unina_track_buffers(unina_tracker_t *t, const unina_track **d_tracks, const 
 /* Synchronises `stream`, then copies out the header and min(cap, UNINA_TRACK_MAX) slots (tracks may be NULL when cap is 0). */
 int unina_track_read(unina_tracker_t *t, unina_track_header *hdr, unina_track *tracks, size_t cap, hipStream_t stream);
 
+/* ------------------------------------------------------------------ pose from the tracked cones (behind any locator,
+ * unina_fuse_async or unina_colour_async, in front of unina_track_update_async)
+ * The tracker takes the camera's pose on trust, and odometry drifts. The tracker's confirmed tracks are static landmarks with
+ * smoothed positions, resident on the device: this stage aligns the frame's located cones with them by a planar rigid correction
+ * -- a yaw about the tracking frame's z axis (z is up) plus (tx, ty) -- and writes the corrected camera -> tracking pose and the
+ * frame's unina_cone3d records moved into the tracking frame, in place if wanted. The tracker then runs behind it unchanged with
+ * the IDENTITY pose. Stateless: one memset of the 32-byte header and ONE launch (csrc/pose.hip: one workgroup of 1024 threads) on
+ * the caller's stream; nothing is synchronised. pose.pose_numpy is the definition, bit for bit. Every fp32 and float64 operation
+ * is rounded once in the order written, never contracted.
+ *   prior     d_prev == NULL: P = inc, the prior camera -> tracking pose. Else P = d_prev->pose o inc, and inc is this frame's
+ *             camera -> the last frame's camera, which is what odometry gives: the estimate never returns to the host between
+ *             frames. Row-major 3 x 4 [R|t], fp32: P[4r+k] = ((a[4r] * b[k] + a[4r+1] * b[4+k]) + a[4r+2] * b[8+k]), + a[4r+3]
+ *             where k == 3, with a = d_prev->pose and b = inc
+ *   count     n = *d_count clamped to 0..MAX_DETECTIONS, on the device
+ *   point     record j < n: (px, py, pz) as unina_track_update_async's point with the pose P. USABLE iff cones[j].valid != 0, the
+ *             point is finite and |px|, |py| <= 32768
+ *   landmark  a slot with id != 0, hits >= min_hits and |x|, |y| <= 32768 (a NaN fails)
+ *   loop      the correction starts as (c, s, tx, ty) = (1, 0, 0, 0); then `iterations` times:
+ *     move      qx = (c * px - s * py) + tx, qy = (s * px + c * py) + ty, qz = pz
+ *     candidate (landmark k, usable j) iff (class_aware == 0 or track.class_id == dets[j].class_id) and d2 <= gate * gate, d2 as
+ *               the tracker's with q for the point. A NaN d2 fails
+ *     pairs     record j picks the least (d2 bits, k) over its candidates, landmark k the least (d2 bits, j); a PAIR is a mutual
+ *               choice. ONE round, not the tracker's chain of rounds: a record whose landmark prefers another record does not
+ *               vote in this iteration. N = the number of pairs
+ *     too few   N < min_pairs: status = UNINA_POSE_TOO_FEW and the loop ends; the correction of the earlier iterations stays
+ *     sums      over the pairs, in 64-bit integers of 2^-10 m of the UNMOVED point and the landmark (ipx = rint(px * 1024); ipy,
+ *               imx, imy likewise): N, Spx, Spy, Smx, Smy, Sdot = sum(ipx * imx + ipy * imy), Scross = sum(ipx * imy - ipy * imx).
+ *               Exact and free of any order: a term is below 2^51 and 1024 of them below 2^61. Every iteration solves for the
+ *               whole correction, so no error is composed
+ *     rotation  float64: A = Sdot - (Spx * Smx + Spy * Smy) / N, B = Scross - (Spx * Smy - Spy * Smx) / N. fp32: Af = (float)A,
+ *               Bf = (float)B, h = sqrtf(Af * Af + Bf * Bf). h finite and > 0: c = Af / h, s = Bf / h, status = UNINA_POSE_OK.
+ *               Else c = 1, s = 0 and status = UNINA_POSE_DEGENERATE (all pairs at one point); the loop goes on
+ *     translation  float64 with (double)c, (double)s: tx = (float)(((Smx - (c * Spx - s * Spy)) / N) / 1024),
+ *               ty = (float)(((Smy - (s * Spx + c * Spy)) / N) / 1024)
+ *   out cones record j < n: x, y, z = the move of its point under the final correction (for a record that is not usable: of
+ *             whatever the point came out as; a NaN's sign and payload are the processor's), every other field copied. Records
+ *             from n on are copied unchanged
+ *   result    c, s, tx, ty and the corrected pose: pose[k] = (c * P[k] - s * P[4+k]), pose[4+k] = (s * P[k] + c * P[4+k]), + tx
+ *             and + ty where k == 3; row 2 is P's
+ *   header    n_records = n; n_usable; n_landmarks; n_pairs and max_d2_bits (the bits of the largest pair d2, 0 without a pair)
+ *             are of the last pairing made, a too small one included; iterations = those that updated the correction; status =
+ *             that of the last iteration run
+ * Integer sums, integer minima and maxima and a fixed order of every floating operation: two runs give identical bytes, and any
+ * order of the records gives the same result and header wherever no two candidate d2 tie.
+ * NOT covered: roll, pitch and height correction; re-orthonormalising a long d_prev chain (re-seed with d_prev = NULL);
+ * outlier-robust weights; loop closure; feeding the estimate to unina_deskew_table. */
+typedef struct { float inc[12]; float gate; int class_aware, min_hits, iterations, min_pairs; } unina_pose_params;   /* 68 bytes */
+typedef struct { float pose[12]; float c, s, tx, ty; } unina_pose_result;                                             /* 64 bytes, device */
+typedef struct { int n_records, n_usable, n_landmarks, n_pairs, iterations, status; uint32_t max_d2_bits; int reserved; } unina_pose_header;   /* 32 bytes */
+enum { UNINA_POSE_OK = 0, UNINA_POSE_TOO_FEW = 1, UNINA_POSE_DEGENERATE = 2 };
+#define UNINA_POSE_MAX_ITERATIONS 8
+/*   d_dets / d_count / d_cones : device, as unina_track_update_async takes them
+ *   d_tracks    : device, UNINA_TRACK_MAX slots, 16-byte aligned (unina_track_buffers)
+ *   d_prev      : device, 16-byte aligned, or NULL
+ *   d_out_cones : device, MAX_DETECTIONS unina_cone3d, 16-byte aligned; may be d_cones
+ *   d_result    : device, 16-byte aligned; may be d_prev
+ *   d_header    : device, 16-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: a NULL pointer other than d_prev; a misaligned pointer (d_count: 4 bytes); d_out_cones
+ * overlapping d_cones without being equal to it, d_result and d_prev likewise; a non-finite inc element; gate not finite and
+ * positive, or gate * gate not finite; min_hits < 1; iterations outside 1..UNINA_POSE_MAX_ITERATIONS; min_pairs < 2. */
+int unina_pose_async(const GpuDetection *d_dets, const int *d_count, const unina_cone3d *d_cones, const unina_track *d_tracks,
+                     const unina_pose_result *d_prev, const unina_pose_params *p, unina_cone3d *d_out_cones,
+                     unina_pose_result *d_result, unina_pose_header *d_header, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

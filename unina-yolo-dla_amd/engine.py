@@ -227,6 +227,20 @@ class ColourParams(C.Structure):
                 ("taper", C.c_int), ("min_pixels", C.c_int), ("min_share", C.c_int), ("max_rival", C.c_int), ("require_stripe", C.c_int)]
 
 
+POSE_OK, POSE_TOO_FEW, POSE_DEGENERATE = 0, 1, 2                                    # include/unina_mi355.h UNINA_POSE_*: status
+POSE_MAX_ITERATIONS = 8
+POSE_RESULT_DTYPE = np.dtype([("pose", "<f4", (12,))] + [(n, "<f4") for n in ("c", "s", "tx", "ty")])                     # unina_pose_result
+POSE_HEADER_DTYPE = np.dtype([(n, "<i4") for n in ("n_records", "n_usable", "n_landmarks", "n_pairs", "iterations", "status")] +
+                             [("max_d2_bits", "<u4"), ("reserved", "<i4")])                                                # unina_pose_header
+assert POSE_RESULT_DTYPE.itemsize == 64 and POSE_HEADER_DTYPE.itemsize == 32
+
+
+class PoseParams(C.Structure):
+    """unina_pose_params: inc = row-major 3 x 4 [R|t], the prior pose or the odometry increment in front of d_prev's pose."""
+    _fields_ = [("inc", C.c_float * 12), ("gate", C.c_float), ("class_aware", C.c_int), ("min_hits", C.c_int), ("iterations", C.c_int),
+                ("min_pairs", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -269,6 +283,7 @@ ABI_SYMBOLS = [
     "unina_fuse_async", "unina_colour_async",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
+    "unina_pose_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -410,6 +425,8 @@ def load_library() -> C.CDLL:
     L.unina_fuse_async.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(FuseParams), vp, vp, vp, vp, vp, vp, vp]
     # class from pixels for records without one (csrc/colour.hip)
     L.unina_colour_async.argtypes = [vp, vp, vp, C.POINTER(Image), C.POINTER(Pinhole), C.POINTER(ColourParams), vp, vp, vp, vp]
+    # the camera pose from the tracked cones (csrc/pose.hip)
+    L.unina_pose_async.argtypes = [vp, vp, vp, vp, vp, C.POINTER(PoseParams), vp, vp, vp, vp]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]
