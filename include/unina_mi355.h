@@ -1226,6 +1226,58 @@ int unina_pose_async(const GpuDetection *d_dets, const int *d_count, const unina
                      const unina_pose_result *d_prev, const unina_pose_params *p, unina_cone3d *d_out_cones,
                      unina_pose_result *d_result, unina_pose_header *d_header, hipStream_t stream);
 
+/* ------------------------------------------------------------------ track limits and centre line from the tracked cones (behind
+ * unina_track_update_async)
+ * The tracker's table is an unordered set of points; a driverless car needs the left limit and the right limit as ORDERED
+ * polylines and the line between them. This stage reads the table where it lies on the device (unina_track_buffers) and the
+ * camera's pose (unina_pose_async's d_result, or the parameters'), chains the confirmed cones of each side from the vehicle
+ * onwards and walks the two chains as a ladder. Stateless: one memset of the 32-byte header and ONE launch (csrc/boundary.hip:
+ * one workgroup of 1024 threads) on the caller's stream; nothing is synchronised. boundary.boundary_numpy is the definition, bit
+ * for bit. Everything is fp32, each operation rounded once in the order written, never contracted.
+ *   origin    P = d_pose->pose, or p->pose where d_pose == NULL. o = (P[3], P[7]); the heading h: hx = (P[0] * f0 + P[1] * f1) +
+ *             P[2] * f2 with f = forward, hy the same from row 1. Where o is not finite, or hx * hx + hy * hy is not finite and
+ *             > 0: end[0] = end[1] = UNINA_BOUNDARY_NO_HEADING, every other word of the header and every point is zero
+ *   candidate slot s of side k iff id != 0, hits >= min_hits, class_id == class_left (k = 0) or class_right (k = 1), and |x|, |y|
+ *             <= 32768 (a NaN fails). z is carried and never tested. n_candidates[k] counts them
+ *   chain     per side, links m = 0, 1, ...: the current point c is o for m = 0, else the chain's last point; the direction d is h
+ *             for m = 0 and m = 1, else the last point minus the one before, per component. For a candidate not yet in the chain
+ *             dx = x - cx, dy = y - cy, d2 = dx * dx + dy * dy, dot = dx * d.x + dy * d.y. ELIGIBLE for m = 0 iff d2 <= first_gate
+ *             * first_gate and dot >= 0; for m >= 1 iff d2 <= step_gate * step_gate, dot > 0 and dot * dot >= cos2 * (d2 * (d.x *
+ *             d.x + d.y * d.y)), cos2 = cos_turn * cos_turn computed once on the host. A NaN fails every test. The link takes the
+ *             eligible candidate with the least (d2 bits, slot) and writes (x, y, z, ref = the track's id). Without one, end[k] =
+ *             UNINA_BOUNDARY_NO_FIRST (m = 0) or UNINA_BOUNDARY_NO_NEXT; a chain of max_chain points ends UNINA_BOUNDARY_FULL
+ *   centre    a ladder walk over the chains L and R; n_centre = 0 where either is empty. From i = j = 0: w2 = d2(L[i], R[j]) in the
+ *             plane with dx = L.x - R.x; w2 <= width_gate * width_gate: the rung's point ((L.x + R.x) * 0.5f, y and z likewise,
+ *             ref = i | j << 16) is written, else n_wide += 1. The walk stops when neither i + 1 < nL nor j + 1 < nR; it advances i
+ *             if i + 1 < nL and either j + 1 >= nR or d2(L[i+1], R[j]) <= d2(L[i], R[j+1]), else j. At most 127 rungs. A track's z
+ *             is copied as it is; the sign and payload of a NaN that a rung's z sum produces are the processor's
+ *   points    d_points[0, 64) the left chain, [64, 128) the right chain, [128, 256) the centre line. Every call writes all 256
+ *             points and the header; entries behind their count are all-zero bytes
+ * Integer minima and a fixed order of every fp32 operation: two runs give identical bytes, and any order of the slots gives the
+ * same points and header wherever no two eligible candidates tie in d2.
+ * NOT covered: a track seen on one side only (offsetting one chain); orange start / finish cones; closing the loop; smoothing or
+ * splines; curvature and speed; a Delaunay or graph search in place of the greedy chain. */
+#define UNINA_BOUNDARY_MAX_CHAIN 64
+typedef struct {
+  float pose[12];      /* row-major 3 x 4 [R|t], camera -> tracking frame; read only when d_pose == NULL            */
+  float forward[3];    /* the vehicle's forward axis in the camera frame: (0,0,1) pinhole camera, (1,0,0) level frame */
+  float first_gate, step_gate, cos_turn, width_gate;   /* m; m; cosine of the widest turn between two links, [0, 1); m */
+  int class_left, class_right, min_hits, max_chain;    /* class ids differ between data sets, as in unina_colour_params */
+} unina_boundary_params;                                                                  /* 92 bytes */
+typedef struct { float x, y, z; int ref; } unina_boundary_point;                          /* 16 bytes */
+typedef struct { int n_candidates[2], n_chain[2], end[2], n_centre, n_wide; } unina_boundary_header;   /* 32 bytes; [0] left, [1] right */
+enum { UNINA_BOUNDARY_NO_FIRST = 0, UNINA_BOUNDARY_NO_NEXT = 1, UNINA_BOUNDARY_FULL = 2, UNINA_BOUNDARY_NO_HEADING = 3 };
+/*   d_tracks : device, UNINA_TRACK_MAX slots, 16-byte aligned (unina_track_buffers)
+ *   d_pose   : device, 16-byte aligned (unina_pose_async's d_result), or NULL: p->pose is the pose
+ *   d_points : device, 4 * UNINA_BOUNDARY_MAX_CHAIN points, 16-byte aligned
+ *   d_header : device, 16-byte aligned
+ * UNINA_ERR_ARG, before any HIP call: a NULL d_tracks, p, d_points or d_header; a pointer that is not 16-byte aligned, d_pose
+ * included; a non-finite pose element while d_pose == NULL (with d_pose set, pose is not read); a non-finite forward element; a
+ * gate that is not finite and positive, or whose square is not finite; cos_turn NaN or outside [0, 1); min_hits < 1; max_chain
+ * outside 1..UNINA_BOUNDARY_MAX_CHAIN; a negative class id, or class_left == class_right; d_points overlapping d_header. */
+int unina_boundary_async(const unina_track *d_tracks, const unina_pose_result *d_pose, const unina_boundary_params *p,
+                         unina_boundary_point *d_points, unina_boundary_header *d_header, hipStream_t stream);
+
 /* Error text of the last failing call on this handle (never NULL). With e == NULL: last load failure. */
 const char *unina_last_error(const unina_engine_t *e);
 

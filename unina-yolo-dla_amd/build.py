@@ -41,6 +41,7 @@ UNITS = {
     "fuse.hip": ["-ffp-contract=off"],          # LiDAR cone candidates + camera records -> one record list: projection, box, gate and keys round as fusion.fuse_numpy's fp32 arrays do
     "colour.hip": ["-ffp-contract=off"],        # records without a class + the rectified image -> the class the pixels show: the window's floats round as colour.colour_numpy's fp32 scalars do
     "pose.hip": ["-ffp-contract=off"],          # located cones + the tracker's table -> the corrected camera pose: point, gate, keys, the float64 closed form and the pose round as pose.pose_numpy's scalars do
+    "boundary.hip": ["-ffp-contract=off"],      # the tracker's table + the pose -> track limits and centre line: heading, gates, keys and midpoints round as boundary.boundary_numpy's fp32 scalars do
     "track.hip": ["-ffp-contract=off"],         # located cones -> persistent tracks: gate, keys and slot update round as tracking.update_numpy's fp32 scalars do
     "engine.hip": [],
     "stream_probe.hip": [],                     # unina_debug_streams_overlap: do two streams run at the same time?

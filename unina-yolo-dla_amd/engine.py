@@ -241,6 +241,21 @@ class PoseParams(C.Structure):
                 ("min_pairs", C.c_int)]
 
 
+BOUNDARY_NO_FIRST, BOUNDARY_NO_NEXT, BOUNDARY_FULL, BOUNDARY_NO_HEADING = 0, 1, 2, 3   # include/unina_mi355.h UNINA_BOUNDARY_*: end
+BOUNDARY_MAX_CHAIN = 64
+BOUNDARY_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("ref", "<i4")])                              # unina_boundary_point
+BOUNDARY_HEADER_DTYPE = np.dtype([("n_candidates", "<i4", (2,)), ("n_chain", "<i4", (2,)), ("end", "<i4", (2,)), ("n_centre", "<i4"),
+                                  ("n_wide", "<i4")])                                                                      # unina_boundary_header
+assert BOUNDARY_POINT_DTYPE.itemsize == 16 and BOUNDARY_HEADER_DTYPE.itemsize == 32
+
+
+class BoundaryParams(C.Structure):
+    """unina_boundary_params: pose = row-major 3 x 4 [R|t], camera -> tracking frame, read only without a device pose."""
+    _fields_ = [("pose", C.c_float * 12), ("forward", C.c_float * 3), ("first_gate", C.c_float), ("step_gate", C.c_float),
+                ("cos_turn", C.c_float), ("width_gate", C.c_float), ("class_left", C.c_int), ("class_right", C.c_int), ("min_hits", C.c_int),
+                ("max_chain", C.c_int)]
+
+
 class TrackParams(C.Structure):
     """unina_track_params: pose = row-major 3 x 4 [R|t], camera frame -> tracking frame."""
     _fields_ = [("pose", C.c_float * 12), ("gate", C.c_float), ("alpha", C.c_float), ("birth_confidence", C.c_float),
@@ -283,7 +298,7 @@ ABI_SYMBOLS = [
     "unina_fuse_async", "unina_colour_async",
     "unina_track_create", "unina_track_destroy", "unina_track_reset_async", "unina_track_update_async", "unina_track_buffers",
     "unina_track_read",
-    "unina_pose_async",
+    "unina_pose_async", "unina_boundary_async",
     "unina_comm_unique_id", "unina_comm_init", "unina_comm_all_gather", "unina_comm_rank", "unina_comm_world", "unina_comm_destroy",
     "unina_comm_last_error",
     "create_norm_params_imagenet", "create_norm_params", "preprocess_bgra_resize", "preprocess_bgra", "preprocess_nv12",
@@ -427,6 +442,8 @@ def load_library() -> C.CDLL:
     L.unina_colour_async.argtypes = [vp, vp, vp, C.POINTER(Image), C.POINTER(Pinhole), C.POINTER(ColourParams), vp, vp, vp, vp]
     # the camera pose from the tracked cones (csrc/pose.hip)
     L.unina_pose_async.argtypes = [vp, vp, vp, vp, vp, C.POINTER(PoseParams), vp, vp, vp, vp]
+    # track limits and centre line from the tracked cones (csrc/boundary.hip)
+    L.unina_boundary_async.argtypes = [vp, vp, C.POINTER(BoundaryParams), vp, vp, vp]
     # tracking (csrc/track.hip)
     L.unina_track_create.argtypes = [ci, C.POINTER(vp)]
     L.unina_track_destroy.argtypes = [vp]
